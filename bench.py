@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark: Hadamard sweep over every qubit of an n-qubit register
 (BASELINE.json: "amplitude-updates/s (gate*2^n/s) and HBM GB/s vs roofline, n=30 H-sweep").
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1, either form:
       python bench.py --gpus N ...                         (starts its N ranks itself, see self_launch)
       python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -12,7 +12,18 @@ A "step" is one sweep: hadamard_gate(q) for q = 0..n-1, one kernel launch per ga
 (libqcx.so), state resident in HBM.  N = 1: n = 30 (16 GiB).  N > 1 is weak scaling: every rank keeps
 a 2^30-amplitude shard (n = 30 + log2 N); the top log2 N qubits are global and cost all-to-all
 exchanges over RCCL (quantumcomputer_amd/sharded.py).  value = steps * n * 2^n / seconds, where
-seconds is the barrier-to-barrier wall time, max over ranks.
+seconds is the barrier-to-barrier wall time, max over ranks; ms_per_step = seconds / steps.
+
+A plain run sets up, warms up, times the K steps and prints the line: headline, roofline (from the
+events of the timed steps) and total probability before / after.  Everything that takes runs of its
+own -- cpu_baseline, fused_sweep, configs, config4, config5, c_host -- runs only with --full (the
+--no-* switches narrow a --full run).
+
+--dump-outputs DIR: after the timed steps, what they computed -- the state vector after the last step
+(rank 0's shard for N > 1, in the identity layout) -- as a fixed, seeded sample of 64 blocks of 2^14
+amplitudes: DIR/state_sample.npy (float64, (count, 2) = re, im) and DIR/state_sample_index.npy
+(float64, the amplitude index of each row); 24 MiB at n = 30.  The inputs are seeded too, so the
+same arguments give the same arrays from run to run and from build to build.
 
 Extra objects on the JSON line:
   roofline      the dominant kernel (k_h_pair, the pair-form Hadamard used for q >= 3): algorithmic
@@ -20,6 +31,7 @@ Extra objects on the JSON line:
                 with HIP events recorded between the gates of the timed region, vs 8 TB/s HBM peak.
                 `traffic` is NOT measured in this run: it is the per-launch HBM byte count of the committed
                 rocprofv3 --pmc passes of this same command (`traffic_source` names the file).
+  --full adds:
   cpu_baseline  the CPU oracle (oracle/, a port of the reference arithmetic) on bounded samples of the same
                 workload: tier T3 = pairwise in place, OpenMP over the host cores (the headline `value`),
                 T2 = the reference's COO mat-vec alone, T1 = the literal reference algorithm.
@@ -121,6 +133,23 @@ def load_traffic():
     return None, None
 
 
+DUMP_BLOCK_LOG2, DUMP_BLOCKS, DUMP_SEED = 14, 64, 20240611
+
+
+def dump_outputs(path, num_states, read_block):
+    """--dump-outputs: a fixed, seeded sample of the state vector -- DUMP_BLOCKS blocks of 2^DUMP_BLOCK_LOG2 amplitudes
+    (fewer on small registers) at random block-aligned offsets; read_block(first, count) returns 2*count (re, im) doubles"""
+    import numpy as np
+    block = min(1 << DUMP_BLOCK_LOG2, num_states)
+    nblocks = num_states // block
+    starts = np.sort(np.random.default_rng(DUMP_SEED).choice(nblocks, size=min(DUMP_BLOCKS, nblocks), replace=False)) * block
+    amps = np.concatenate([np.asarray(read_block(int(s), block), dtype=np.float64) for s in starts]).reshape(-1, 2)
+    index = (starts[:, None] + np.arange(block)[None, :]).reshape(-1).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "state_sample.npy"), amps)
+    np.save(os.path.join(path, "state_sample_index.npy"), index)
+
+
 def run_c_host(args):
     """rank 0, before it touches a GPU: the C-host leg in a fresh child process; returns its JSON object"""
     cmd = [sys.executable, os.path.abspath(__file__), "--c-host-child", "--gpus", str(args.gpus), "--steps", str(args.steps),
@@ -213,6 +242,9 @@ def main():
     ap.add_argument("--cpu-n", type=int, default=0, help="register size of the CPU sample (0: 30 if the host has the memory, else 28)")
     ap.add_argument("--no-configs", action="store_true", help="N = 1: skip the configs object (BASELINE configs 2, 3, 5)")
     ap.add_argument("--no-c-host", action="store_true", help="N > 1: skip the one-process C-host leg")
+    ap.add_argument("--full", action="store_true", help="also the legs with runs of their own: cpu_baseline, fused_sweep, configs "
+                                                        "(N = 1), config4, config5, c_host (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed sample of the state after the last timed step as DIR/*.npy")
     ap.add_argument("--c-host-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -232,7 +264,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     # N > 1: the one-process C host over the same GPUs, in a fresh child process, before this rank initialises a GPU
     # (the other ranks wait for rank 0 in the rendezvous meanwhile)
-    c_host = run_c_host(args) if (world > 1 and rank == 0 and not args.no_c_host) else None
+    c_host = run_c_host(args) if (args.full and world > 1 and rank == 0 and not args.no_c_host) else None
 
     import torch
     import quantumcomputer_amd as qc
@@ -282,11 +314,13 @@ def main():
 
         per_q_ms = [[reg.event_elapsed(s * (n + 1) + q, s * (n + 1) + q + 1) for s in range(args.steps)] for q in range(n)]
         norm = reg.norm2()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, reg.num_states, reg.read)
 
         # reported separately: the same sweep with gate fusion on -- the 30 gate calls are queued
         # and run as a few fused LDS-tile passes, bit-identical results; bytes are counted once per pass
         fused = None
-        if not args.no_fused:
+        if args.full and not args.no_fused:
             reg.set_fusion(True)
             sweep(); reg.synchronize()
             p0 = reg.fusion_stats()[0]
@@ -310,7 +344,7 @@ def main():
             reg.set_fusion(False)
         reg.close()
         exchanges = 0
-        configs = None if (args.no_configs or args.n_local != 30) else single_gpu_configs(qc)
+        configs = None if (not args.full or args.no_configs or args.n_local != 30) else single_gpu_configs(qc)
     else:
         import datetime
         import torch.distributed as dist
@@ -380,13 +414,19 @@ def main():
         exchanges = reg.exchanges - ex0
         sigma = reg.sigma
         overlapped = reg.overlap and sigma > 0
+        if args.dump_outputs:
+            reg._identity()                                   # collective: every rank restores logical == physical
+            if rank == 0:                                     # rank 0's shard holds amplitudes 0 .. 2^n_local - 1
+                flat = reg.shard.view(-1)
+                dump_outputs(args.dump_outputs, 1 << args.n_local,
+                             lambda first, count: flat[2 * first:2 * (first + count)].cpu().numpy())
         fused = None
         del reg
         torch.cuda.empty_cache()
 
         # BASELINE config 4: n = 32 over 8 GPUs (29 local qubits; the same shard size at other N), H on every global
         # qubit vs a local one.  A global H = pack pass + all-to-all of (W-1)/W of the shard + the local gate.
-        if args.gpus > 1 and not args.no_config4:
+        if args.full and args.gpus > 1 and not args.no_config4:
             nl4 = min(29, args.n_local)
             r4 = make(exchange_mode, nl4 + k)
 
@@ -493,11 +533,9 @@ def main():
             out["config4"] = config4
             out["config5"] = config5
             out["c_host"] = c_host
-        if not args.no_cpu_baseline and args.gpus == 1:
+        if args.full and not args.no_cpu_baseline:
             cpu_n = args.cpu_n or (30 if mem_available_gib() >= 48 else 28)
-            out["cpu_baseline"] = cpu_baseline(cpu_n)
-        elif not args.no_cpu_baseline:
-            out["cpu_baseline"] = None
+            out["cpu_baseline"] = cpu_baseline(cpu_n) if args.gpus == 1 else None
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
 

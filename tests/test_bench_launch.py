@@ -44,7 +44,7 @@ def test_self_launch_happens_before_any_gpu_use():
 
 @pytest.mark.gpu
 def test_two_ranks_on_one_gpu_print_one_json_line():
-    r = run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--n-local", "20", "--no-cpu-baseline"],
+    r = run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--n-local", "20", "--no-cpu-baseline", "--full"],
                   extra_env={"QCX_BENCH_BACKEND": "gloo", "QCX_FORCE_DEVICE": "0"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
