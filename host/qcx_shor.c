@@ -9,7 +9,10 @@
  * launch per gate (qcx_set_fusion(reg, -1)), -F queues every gate call (qcx_set_fusion(reg, 1)); the results are the same
  * bits in all three modes; -T selects the opt-in tolerance mode (qcx_set_fusion(reg, 2): runs of controlled phases merged into
  * one diagonal, rounding-level differences in the amplitudes).  -o file writes the register's state after the LAST period-finding attempt (post-measurement,
- * i.e. collapsed) and -O file the state right after the last circuit, before measuring (qcx_state_save).  Exit code = the reference's ErrorCode (Q:164-170, Q:1340-1347).
+ * i.e. collapsed) and -O file the state right after the last circuit, before measuring (qcx_state_save).  -H shots (with a forced
+ * trial integer) runs reset and the circuit ONCE and draws `shots` measurements from that one state (qcx_sample_states: the same
+ * indices as `shots` rounds of reset, circuit and measurement with the same seed), prints the histogram of x~ (omega = x~/2^L) in
+ * ascending x~ and how many shots the continued-fraction step turns into a period.  Exit code = the reference's ErrorCode (Q:164-170, Q:1340-1347).
  *
  * The quantum part (reset, circuit, measurement) runs on the GPU through include/qcx.h; everything
  * here is host-side control flow written from scratch after the behaviour of find_period
@@ -36,6 +39,7 @@ typedef struct {
     const char *dump_final, *dump_circuit;
     int gpus;                   /* -g N: shard the register over N GPUs (2, 4, 8, 16) from this one process */
     const char *gpu_list;       /* -d "0,0,1,1": HIP device of each shard (default: spread over the visible GPUs) */
+    unsigned long shots;        /* -H shots: a histogram of that many samples of one circuit's state (needs -a / -f) */
 } Options;
 
 typedef struct {
@@ -44,7 +48,7 @@ typedef struct {
 } Stats;
 
 static const char *USAGE =
-    "Usage: qcx_shor -C num -L L_reg_size -M M_reg_size [-a trial_int | -f trial_int] [-v] [-V] [-s seed] [-Q] [-j] [-F | -G | -T] [-g gpus [-d dev,dev,...]] [-o state_file] [-O state_file]\n";
+    "Usage: qcx_shor -C num -L L_reg_size -M M_reg_size [-a trial_int | -f trial_int] [-v] [-V] [-s seed] [-Q] [-j] [-F | -G | -T] [-g gpus [-d dev,dev,...]] [-o state_file] [-O state_file] [-H shots]\n";
 
 static double now_seconds(void)
 {
@@ -58,7 +62,7 @@ static int parse_args(int argc, char **argv, Options *o)
     bool haveC = false, haveL = false, haveM = false;
     int ch;
     memset(o, 0, sizeof *o);
-    while ((ch = getopt(argc, argv, "C:L:M:a:f:s:o:O:g:d:vVQjFGT")) != -1) {
+    while ((ch = getopt(argc, argv, "C:L:M:a:f:s:o:O:g:d:H:vVQjFGT")) != -1) {
         switch (ch) {
         case 'C': o->C = (unsigned)atoi(optarg); haveC = true; break;
         case 'L': o->L = atoi(optarg); haveL = true; break;
@@ -76,6 +80,12 @@ static int parse_args(int argc, char **argv, Options *o)
         case 'd': o->gpu_list = optarg; break;
         case 'o': o->dump_final = optarg; break;
         case 'O': o->dump_circuit = optarg; break;
+        case 'H': {
+            char *end = NULL;
+            o->shots = strtoul(optarg, &end, 10);
+            if (!end || *end || o->shots == 0) { fprintf(stderr, "Error: -H needs a positive number of shots.\n"); fputs(USAGE, stdout); return QCX_BAD_ARGUMENTS; }
+            break;
+        }
         default: fputs(USAGE, stdout); return QCX_BAD_ARGUMENTS;
         }
     }
@@ -85,6 +95,11 @@ static int parse_args(int argc, char **argv, Options *o)
     /* the reference only prints for these (Q:1240-1253); a register cannot be built from them, so stop */
     if (o->C < 2 || o->L <= 0 || o->M <= 0) {
         fprintf(stderr, "Error: C, L and M must be positive (C >= 2).\n");
+        fputs(USAGE, stdout);
+        return QCX_BAD_ARGUMENTS;
+    }
+    if (o->shots && o->forced_a == 0) {
+        fprintf(stderr, "Error: -H samples one circuit's state and needs a trial integer (-a / -f).\n");
         fputs(USAGE, stdout);
         return QCX_BAD_ARGUMENTS;
     }
@@ -146,6 +161,38 @@ static int try_trial_integer(unsigned a, unsigned factors[2], const Options *o, 
     }
     if (verbose)
         printf(" --- A valid period = %u has been found so the factors of C = %u have been found quantum mechanically.\n\n", period, o->C);
+    return QCX_NO_ERROR;
+}
+
+static int cmp_unsigned(const void *a, const void *b)
+{
+    const unsigned x = *(const unsigned *)a, y = *(const unsigned *)b;
+    return x < y ? -1 : (x > y ? 1 : 0);
+}
+
+/* -H: reset and the circuit once, then o->shots samples of that state (not collapsed); x~ of every shot (sorted) and the number of
+ * shots whose omega yields a period */
+static int sample_histogram(const Options *o, qcx_register *reg, qcx_rng *rng, Stats *st, unsigned *xs, unsigned long *valid)
+{
+    const unsigned a = o->forced_a;
+    int s;
+    unsigned long *idx = (unsigned long *)malloc(o->shots * sizeof *idx);
+    if (!idx) return QCX_INSUFFICIENT_MEMORY;
+    if ((s = qcx_reset_register(reg)) != QCX_NO_ERROR ||
+        (s = qcx_quantum_computation(o->C, a, o->ref_quirks ? 1 : 0, reg)) != QCX_NO_ERROR) { free(idx); return s; }
+    st->gates += 3UL * (unsigned long)o->L + (unsigned long)o->L * (unsigned long)(o->L - 1) / 2;
+    st->attempts++;
+    if (o->dump_circuit && (s = qcx_state_save(reg, o->dump_circuit)) != QCX_NO_ERROR) { free(idx); return s; }
+    if ((s = qcx_sample_states(reg, rng, o->shots, idx)) != QCX_NO_ERROR) { free(idx); return s; }
+    for (unsigned long i = 0; i < o->shots; i++) xs[i] = qcx_read_x_tilde(idx[i], o->L, o->M);
+    free(idx);
+    qsort(xs, o->shots, sizeof *xs, cmp_unsigned);
+    *valid = 0;
+    for (unsigned long i = 0, j; i < o->shots; i = j) {
+        for (j = i; j < o->shots && xs[j] == xs[i]; j++) {}
+        const double omega = (double)xs[i] / (double)(1ULL << o->L);      /* = qcx_read_omega of these shots */
+        if (qcx_period_from_omega(omega, a, o->C, o->ref_quirks ? 1 : 0)) *valid += j - i;
+    }
     return QCX_NO_ERROR;
 }
 
@@ -212,8 +259,20 @@ int main(int argc, char **argv)
     if (o.fusion) qcx_set_fusion(reg, 1);        /* -F: every gate call is queued and run as fused passes (same bits) */
     if (o.per_gate) qcx_set_fusion(reg, -1);     /* -G: one kernel launch per gate, also inside the circuit call */
     if (o.tolerance) qcx_set_fusion(reg, 2);     /* -T: opt-in tolerance mode (merged diagonals; amplitudes to ~1e-15, not bit-exact) */
+    unsigned *xs = NULL;
+    unsigned long valid = 0;
+    if (o.shots && !(xs = (unsigned *)malloc(o.shots * sizeof *xs))) {
+        fprintf(stderr, "Error: Insufficient memory.\n");
+        qcx_register_destroy(reg);
+        qcx_rng_free(rng);
+        return QCX_INSUFFICIENT_MEMORY;
+    }
     const double t0 = now_seconds();
-    s = shors_algorithm(factors, &o, reg, rng, &st);
+    if (o.shots) {
+        printf("\n --- Sampling %lu shots of one circuit (a = %u)...\n\n", o.shots, o.forced_a);
+        s = sample_histogram(&o, reg, rng, &st, xs, &valid);
+    } else
+        s = shors_algorithm(factors, &o, reg, rng, &st);
     qcx_synchronize(reg);
     const double dt = now_seconds() - t0;
     if (verbose) printf(" --- Time to run Shor's Algorithm: %.6fs.\n", dt);
@@ -222,17 +281,39 @@ int main(int argc, char **argv)
         const int sd = qcx_state_save(reg, o.dump_final);
         if (sd != QCX_NO_ERROR) fprintf(stderr, "Error: could not write %s: %s.\n", o.dump_final, qcx_last_error());
     }
+    if (o.shots && s == QCX_NO_ERROR) {
+        for (unsigned long i = 0, j; i < o.shots; i = j) {
+            for (j = i; j < o.shots && xs[j] == xs[i]; j++) {}
+            printf(" --- x~ = %u, omega = %.10f: %lu shots\n", xs[i], (double)xs[i] / (double)(1ULL << o.L), j - i);
+        }
+        printf(" --- %lu of %lu shots give a valid period.\n", valid, o.shots);
+    }
     if (o.json) {
         const double dim = (double)qcx_num_states(reg);
         unsigned long exchanges = 0;
         qcx_sharded_stats(reg, &exchanges, NULL);
         printf("{\"C\": %u, \"L\": %d, \"M\": %d, \"qubits\": %d, \"attempts\": %lu, \"gates\": %lu, \"seconds\": %.6f, "
-               "\"amplitude_updates_per_s\": %.6e, \"shards\": %u, \"exchanges\": %lu, \"status\": %d}\n",
+               "\"amplitude_updates_per_s\": %.6e, \"shards\": %u, \"exchanges\": %lu, \"status\": %d",
                o.C, o.L, o.M, o.L + o.M, st.attempts, st.gates, dt, dt > 0 ? (double)st.gates * dim / dt : 0.0,
                qcx_register_shards(reg), exchanges, s);
+        if (o.shots && s == QCX_NO_ERROR) {          /* the histogram: x~ -> shots, ascending */
+            printf(", \"shots\": %lu, \"valid_period_shots\": %lu, \"histogram\": {", o.shots, valid);
+            for (unsigned long i = 0, j; i < o.shots; i = j) {
+                for (j = i; j < o.shots && xs[j] == xs[i]; j++) {}
+                printf("%s\"%u\": %lu", i ? ", " : "", xs[i], j - i);
+            }
+            printf("}");
+        }
+        printf("}\n");
     }
     qcx_register_destroy(reg);                                                   /* Q:1330-1333 */
     qcx_rng_free(rng);
+    free(xs);
+    if (o.shots) {
+        if (s == QCX_NO_ERROR) return QCX_NO_ERROR;
+        fprintf(stderr, "Error: %s.\n", qcx_status_string(s));
+        return QCX_UNKNOWN_ERROR;
+    }
 
     if (s == QCX_NO_ERROR) {
         printf(" --- Factors of %u found: (%u, %u).\n", o.C, factors[0], factors[1]);

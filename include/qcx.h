@@ -144,6 +144,22 @@ int  qcx_fusion_stats(qcx_register *reg, unsigned long *passes_launched, unsigne
 /* ---- measurement: Q:272-306 ----------------------------------------------- */
 int  qcx_measure_state(qcx_register *reg, qcx_rng *rng, unsigned long *state_num);
 int  qcx_measure_state_r(qcx_register *reg, double r, unsigned long *state_num);   /* r supplied */
+/* K shots from the current state, NOT collapsed (no reference counterpart: Q:298-300 notes that the collapse could be left out to
+ * measure one state repeatedly).  state_nums[i] is the index qcx_measure_state_r(reg, r_i) would return on this state, with r_i
+ * the i-th draw qcx_rng_uniform(rng) makes (the _r form takes the r_i from the caller, in any order, repeats allowed): the
+ * first index in 0 .. dim-2 whose sequential running sum fl(cum + |a|^2) reaches r_i, else dim-1; r_i <= 0 gives 0, NaN and
+ * r_i above the total give dim-1.  So K shots of one state give, in order, the indices of K rounds of reset + circuit +
+ * qcx_measure_state with the same rng.  The state is read once for all shots (DESIGN s4.5c).
+ * The state, and every lazy form of it, is left exactly as it was: a pending basis state stays pending, a circuit's compact
+ * result stays compact (a call that scanned it counts in qcx_compact_measure_stats, as a measurement does), a register written
+ * with non-finite amplitudes keeps its strict gates.  Queued gates are flushed first.  shots = 0 does nothing (no draw);
+ * NULL state_nums with shots > 0: QCX_BAD_ARGUMENTS; a sharded register: QCX_UNSUPPORTED, and no draw is made. */
+int  qcx_sample_states(qcx_register *reg, qcx_rng *rng, unsigned long shots, unsigned long *state_nums);
+int  qcx_sample_states_r(qcx_register *reg, const double *r, unsigned long shots, unsigned long *state_nums);
+/* the last sample call on this register: whole-state scans launched (1 on the fast path, plus one per fallback shot; 0 for a
+ * pending basis state), and shots a per-shot scan answered (shots the fast path could not vouch for, or every shot of a
+ * register holding non-finite amplitudes) */
+int  qcx_sample_last_stats(qcx_register *reg, unsigned long *state_scans, unsigned long *fallback_shots);
 
 /* ---- state access (replaces gsl_vector_complex_get/set uses, T:7-37) ------- */
 int  qcx_state_read(qcx_register *reg, unsigned long first, unsigned long count, double *out_re_im);

@@ -60,6 +60,9 @@ SIGNATURES = {
     "qcx_fusion_stats": (_i, [_p, C.POINTER(_ul), C.POINTER(_ul)]),
     "qcx_measure_state": (_i, [_p, _p, C.POINTER(_ul)]),
     "qcx_measure_state_r": (_i, [_p, _d, C.POINTER(_ul)]),
+    "qcx_sample_states": (_i, [_p, _p, _ul, _p]),
+    "qcx_sample_states_r": (_i, [_p, _p, _ul, _p]),
+    "qcx_sample_last_stats": (_i, [_p, C.POINTER(_ul), C.POINTER(_ul)]),
     "qcx_state_read": (_i, [_p, _ul, _ul, _p]),
     "qcx_state_write": (_i, [_p, _ul, _ul, _p]),
     "qcx_norm2": (_i, [_p, C.POINTER(_d)]),

@@ -216,6 +216,13 @@ struct Workspace {
     meas_slot_t *meas_look = nullptr;   // K4c: look-back area (one allocation): agg, incl per workgroup, gincl per group (filled with ones), then
                                         // gsum, gcount per group and the ticket (zeroed)
     MeasBlock  *meas_up = nullptr;      // K4c: the levels above the records (sums of 64, 64^2, ... records), back to back
+    double     *samp_ends = nullptr;    // K4d (sampling): the exact running sum at the end of every record
+    SampCarry  *samp_aux = nullptr;     // K4d: chunk totals, chunk prefixes, then the `bad` word
+    uint64_t    samp_cap = 0;           // records samp_ends / samp_aux are sized for
+    double     *samp_r = nullptr;       // K4d: one batch of draws ...
+    uint64_t   *samp_out = nullptr;     // ... and their answers
+    size_t      samp_shot_cap = 0;
+    uint64_t samp_nch_cap() const { return (samp_cap + QCX_SAMP_CHUNK - 1) / QCX_SAMP_CHUNK; }
 };
 static const unsigned NORM_BLOCKS = 2048;
 static std::mutex g_ws_mutex;
@@ -738,26 +745,39 @@ extern "C" int qcx_shard_norm2(const void *amp, unsigned n_local, double *out, v
     return QCX_NO_ERROR;
 }
 
-extern "C" int qcx_shard_measure_scan(const void *amp, unsigned n_local, uint64_t first_global,
-                                      uint64_t last_excluded, double cum_in, double r,
-                                      int *found, uint64_t *index, double *cum_out, void *stream)
+// the sampling scan's buffers (K4d): the record ends, the chunk carries of the segmented scan and its `bad` word
+static int samp_reserve(Workspace *w, uint64_t nrec)
 {
-    if (!amp || !found || !index || !cum_out || n_local > 40) return QCX_BAD_ARGUMENTS;
-    Workspace *w;
-    QCX_TRY(workspace(&w));
-    std::lock_guard<std::mutex> use(g_ws_use[w - g_ws]);
-    hipStream_t st = (hipStream_t)stream;
-    uint64_t count = (uint64_t)1 << n_local;
-    if (first_global >= last_excluded) count = 0;
-    else if (last_excluded - first_global < count) count = last_excluded - first_global;
-    if (count == 0) { *found = 0; *index = 0; *cum_out = cum_in; return QCX_NO_ERROR; }
+    std::lock_guard<std::mutex> lock(g_ws_mutex);
+    if (w->samp_cap >= nrec) return QCX_NO_ERROR;
+    if (w->samp_ends) { HIP_TRY(hipFree(w->samp_ends)); HIP_TRY(hipFree(w->samp_aux)); }
+    w->samp_ends = nullptr; w->samp_aux = nullptr; w->samp_cap = 0;
+    const uint64_t nch = (nrec + QCX_SAMP_CHUNK - 1) / QCX_SAMP_CHUNK;
+    HIP_TRY(hipMalloc(&w->samp_ends, ((size_t)nrec + 1) * sizeof(double)));
+    HIP_TRY(hipMalloc(&w->samp_aux, (2 * (size_t)nch + 2) * sizeof(SampCarry)));
+    w->samp_cap = nrec;
+    return QCX_NO_ERROR;
+}
+
+// The launches of one measurement scan of `count` amplitudes on stream st; the caller holds the device's scratch.  ends = true (the
+// sampling scan, K4d): they also leave the exact running sum at the end of every record in w->samp_ends (2^*elog_out amplitudes per
+// record, *nrec_out records) -- k_sample_seq where the single-wave scan would run, the ENDS forms of k_meas_fast / k_meas_walk
+// otherwise, and then only the events' ends are there (*need_fill: the plain records' are still to be assembled).
+static int meas_launch(Workspace *w, const void *amp, uint64_t count, double cum_in, double r, MeasureOut *res, hipStream_t st,
+                       bool *parallel_out, bool ends, unsigned *elog_out, uint64_t *nrec_out, bool *need_fill)
+{
     const Tune tn = tune_now();
     const bool parallel = tn.meas_parallel != 0 && count >= ((uint64_t)1 << tn.meas_min_log2);
-    // The scan's last kernel writes its result (a MeasureOut, 32 bytes) STRAIGHT into pinned host memory (meas_host_out, round 5): the
-    // copy back used to be one more operation on the stream -- a blit kernel, 6-10 us of an attempt that takes 27 us at n = 7 and
-    // 100 us at n = 20.  The kernels only write it (what the fast scan leaves for the walk travels in MeasResume, device memory).
-    MeasureOut *const res = tn.meas_host_out ? w->h_mout : w->mout;
-    if (!parallel) {
+    *parallel_out = parallel;
+    if (!parallel && ends) {
+        // (the sampling scan) the single-wave chain stores the sum at the end of every amplitude -- or of every 2^11 of a large register
+        // scanned this way (meas_parallel = 0)
+        const unsigned elog = count > ((uint64_t)1 << 16) ? 11u : 0u;
+        const uint64_t nrec = (count + (((uint64_t)1 << elog) - 1)) >> elog;
+        QCX_TRY(samp_reserve(w, nrec));
+        hipLaunchKernelGGL(k_sample_seq, dim3(1), dim3(64), 0, st, (const amp_t *)amp, count, cum_in, elog, w->samp_ends);
+        *elog_out = elog; *nrec_out = nrec; *need_fill = false;
+    } else if (!parallel) {
         // small shards: the strictly sequential single-wave scan
         hipLaunchKernelGGL(k_measure_scan, dim3(1), dim3(64), 0, st, (const amp_t *)amp, count, cum_in, r, res);
     } else {
@@ -788,6 +808,12 @@ extern "C" int qcx_shard_measure_scan(const void *amp, unsigned n_local, uint64_
                 w->meas_cap = nblocks;
             }
         }
+        if (ends) {                                                 // every record "not redone yet" (all ones) before the scan
+            QCX_TRY(samp_reserve(w, nblocks));
+            HIP_TRY(hipMemsetAsync(w->samp_ends, 0xff, (size_t)nblocks * sizeof(double), st));
+            *elog_out = blog; *nrec_out = nblocks; *need_fill = true;
+        }
+        double *const ends_p = ends ? w->samp_ends : nullptr;
         {
             const unsigned nwg = (nblocks + 3u) / 4u, ngrp = (nwg + 63u) / 64u;
             MeasLookback LB;
@@ -820,15 +846,48 @@ extern "C" int qcx_shard_measure_scan(const void *amp, unsigned n_local, uint64_
                 T.lv[T.top] = up; T.n[T.top] = nout;
                 up += nout;
             }
-            if (fast)
-                hipLaunchKernelGGL(k_meas_fast, dim3(1), dim3(512), 0, st, (const amp_t *)amp, count, T, cum_in, r, res, res->stats, blog,
-                                   (const MeasCands *)w->meas_cands, w->meas_resume, (unsigned)tn.meas_dbg);
-            hipLaunchKernelGGL(k_meas_walk, dim3(1), dim3(64), 0, st, (const amp_t *)amp, count, T, cum_in, r, res, res->stats, blog,
-                               fast ? (const MeasResume *)w->meas_resume : (const MeasResume *)nullptr, w->meas_cands,
-                               T.top == 0 ? w->meas_look : (meas_slot_t *)nullptr, (unsigned)nslots);
+            if (fast) {
+                if (ends)
+                    hipLaunchKernelGGL(k_meas_fast<true>, dim3(1), dim3(512), 0, st, (const amp_t *)amp, count, T, cum_in, r, res, res->stats, blog,
+                                       (const MeasCands *)w->meas_cands, w->meas_resume, (unsigned)tn.meas_dbg, ends_p);
+                else
+                    hipLaunchKernelGGL(k_meas_fast<false>, dim3(1), dim3(512), 0, st, (const amp_t *)amp, count, T, cum_in, r, res, res->stats, blog,
+                                       (const MeasCands *)w->meas_cands, w->meas_resume, (unsigned)tn.meas_dbg, ends_p);
+            }
+            if (ends)
+                hipLaunchKernelGGL(k_meas_walk<true>, dim3(1), dim3(64), 0, st, (const amp_t *)amp, count, T, cum_in, r, res, res->stats, blog,
+                                   fast ? (const MeasResume *)w->meas_resume : (const MeasResume *)nullptr, w->meas_cands,
+                                   T.top == 0 ? w->meas_look : (meas_slot_t *)nullptr, (unsigned)nslots, ends_p);
+            else
+                hipLaunchKernelGGL(k_meas_walk<false>, dim3(1), dim3(64), 0, st, (const amp_t *)amp, count, T, cum_in, r, res, res->stats, blog,
+                                   fast ? (const MeasResume *)w->meas_resume : (const MeasResume *)nullptr, w->meas_cands,
+                                   T.top == 0 ? w->meas_look : (meas_slot_t *)nullptr, (unsigned)nslots, ends_p);
             w->meas_slots_pending = slots_after;
         }
     }
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_shard_measure_scan(const void *amp, unsigned n_local, uint64_t first_global,
+                                      uint64_t last_excluded, double cum_in, double r,
+                                      int *found, uint64_t *index, double *cum_out, void *stream)
+{
+    if (!amp || !found || !index || !cum_out || n_local > 40) return QCX_BAD_ARGUMENTS;
+    Workspace *w;
+    QCX_TRY(workspace(&w));
+    std::lock_guard<std::mutex> use(g_ws_use[w - g_ws]);
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t count = (uint64_t)1 << n_local;
+    if (first_global >= last_excluded) count = 0;
+    else if (last_excluded - first_global < count) count = last_excluded - first_global;
+    if (count == 0) { *found = 0; *index = 0; *cum_out = cum_in; return QCX_NO_ERROR; }
+    // The scan's last kernel writes its result (a MeasureOut, 32 bytes) STRAIGHT into pinned host memory (meas_host_out, round 5): the
+    // copy back used to be one more operation on the stream -- a blit kernel, 6-10 us of an attempt that takes 27 us at n = 7 and
+    // 100 us at n = 20.  The kernels only write it (what the fast scan leaves for the walk travels in MeasResume, device memory).
+    MeasureOut *const res = tune_now().meas_host_out ? w->h_mout : w->mout;
+    bool parallel = false, fill = false;
+    unsigned elog = 0; uint64_t nrec = 0;
+    QCX_TRY(meas_launch(w, amp, count, cum_in, r, res, st, &parallel, false, &elog, &nrec, &fill));
     HIP_TRY(hipGetLastError());
     if (res != w->h_mout) HIP_TRY(hipMemcpyAsync(w->h_mout, w->mout, sizeof(MeasureOut), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -836,6 +895,57 @@ extern "C" int qcx_shard_measure_scan(const void *amp, unsigned n_local, uint64_
     *found = w->h_mout->found;
     *index = first_global + w->h_mout->index;
     *cum_out = w->h_mout->cum;
+    return QCX_NO_ERROR;
+}
+
+// K4d: the answers of the measurement scan for `shots` draws r[] on the 2^n_local amplitudes at amp, from ONE scan of them, nothing
+// written to the state.  out[i] (host) = the index (< last_excluded), QCX_SAMP_NOTFOUND or QCX_SAMP_FALLBACK (qcx_kernels.h)
+static int sample_scan(const void *amp, unsigned n_local, uint64_t last_excluded, const double *r, size_t shots, uint64_t *out,
+                       hipStream_t st)
+{
+    Workspace *w;
+    QCX_TRY(workspace(&w));
+    std::lock_guard<std::mutex> use(g_ws_use[w - g_ws]);
+    const uint64_t count = (uint64_t)1 << n_local;
+    MeasureOut *const res = tune_now().meas_host_out ? w->h_mout : w->mout;
+    bool parallel = false, fill = false;
+    unsigned elog = 0; uint64_t nrec = 0;
+    QCX_TRY(meas_launch(w, amp, count, 0.0, INFINITY, res, st, &parallel, true, &elog, &nrec, &fill));
+    SampCarry *const chunk_tot = w->samp_aux, *const chunk_pre = w->samp_aux + w->samp_nch_cap(), *const badw = chunk_pre + w->samp_nch_cap();
+    unsigned *const bad = (unsigned *)badw;
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(unsigned), st));
+    if (fill) {
+        const uint64_t nch = (nrec + QCX_SAMP_CHUNK - 1) / QCX_SAMP_CHUNK;
+        hipLaunchKernelGGL(k_samp_chunks, dim3((unsigned)nch), dim3(256), 0, st, (const MeasBlock *)w->meas_blocks, (const double *)w->samp_ends, nrec, chunk_tot);
+        hipLaunchKernelGGL(k_samp_chunk_scan, dim3(1), dim3(256), 0, st, (const SampCarry *)chunk_tot, (unsigned)nch, chunk_pre);
+        hipLaunchKernelGGL(k_samp_fill, dim3((unsigned)nch), dim3(256), 0, st, (const MeasBlock *)w->meas_blocks, w->samp_ends, nrec,
+                           (const SampCarry *)chunk_pre, 0.0, bad);
+    }
+    HIP_TRY(hipGetLastError());
+    // the shots, in batches (the draws in, the answers out: 16 bytes a shot)
+    const size_t BATCH = (size_t)1 << 20;
+    for (size_t s0 = 0; s0 < shots; s0 += BATCH) {
+        const size_t k = std::min(BATCH, shots - s0);
+        {
+            std::lock_guard<std::mutex> lock(g_ws_mutex);
+            if (w->samp_shot_cap < k) {
+                if (w->samp_r) { HIP_TRY(hipFree(w->samp_r)); HIP_TRY(hipFree(w->samp_out)); }
+                w->samp_r = nullptr; w->samp_out = nullptr; w->samp_shot_cap = 0;
+                const size_t cap = std::max<size_t>(k, 1024);
+                HIP_TRY(hipMalloc(&w->samp_r, cap * sizeof(double)));
+                HIP_TRY(hipMalloc(&w->samp_out, cap * sizeof(uint64_t)));
+                w->samp_shot_cap = cap;
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(w->samp_r, r + s0, k * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_sample_shots, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, (const amp_t *)amp, count, (const double *)w->samp_ends, nrec,
+                           elog, 0.0, (const double *)w->samp_r, (uint64_t)k, last_excluded, (const unsigned *)bad, w->samp_out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out + s0, w->samp_out, k * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (parallel) { w->h_meas_stats[0] = w->h_mout->stats[0]; w->h_meas_stats[1] = w->h_mout->stats[1]; w->meas_clean = true; w->meas_clean_slots = w->meas_slots_pending; }
     return QCX_NO_ERROR;
 }
 
@@ -880,6 +990,7 @@ struct qcx_register {
     amp_t     *compact_amp;     // inside r->scratch
     unsigned   compact_cb, compact_ncols;
     uint16_t   compact_orbit[16];
+    unsigned long samp_scans, samp_fallback;   // the last qcx_sample_states call: whole-state scans launched / shots a per-shot scan answered
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
 };
 
@@ -1693,6 +1804,91 @@ extern "C" int qcx_measure_state(qcx_register *r, qcx_rng *rng, unsigned long *s
 {
     if (!rng) return QCX_BAD_ARGUMENTS;
     return qcx_measure_state_r(r, qcx_rng_uniform(rng), state_num);         // Q:281
+}
+
+// K4d: many shots from the current state, which stays exactly as it is (include/qcx.h).  out[i] = what qcx_measure_state_r(r, rs[i])
+// would return: the same scan on the same form of the state -- the register, or the compact form of a circuit's result --, one
+// scan for all shots; a shot the fast path cannot vouch for is answered by that very scan of its own (no collapse).
+static int sample_fallback_shot(qcx_register *r, double rnd, unsigned long *out)
+{
+    int found = 0; uint64_t idx = 0; double cum = 0.0;
+    r->samp_scans++; r->samp_fallback++;
+    if (r->compact_pending) {
+        const unsigned M = (unsigned)r->M, cb = r->compact_cb, nv = r->n - M + cb;
+        uint64_t last_excl = (uint64_t)1 << nv, cidx = 0;
+        if (r->compact_orbit[r->compact_ncols - 1] == (1u << M) - 1u) last_excl = ((((uint64_t)1 << (r->n - M)) - 1) << cb) | (r->compact_ncols - 1);
+        QCX_TRY(qcx_shard_measure_scan(r->compact_amp, nv, 0, last_excl, 0.0, rnd, &found, &cidx, &cum, r->stream));
+        const unsigned col = (unsigned)(cidx & ((1u << cb) - 1u));
+        if (!found || col < r->compact_ncols) { *out = found ? (unsigned long)(((cidx >> cb) << M) | r->compact_orbit[col]) : (unsigned long)(r->dim - 1); return QCX_NO_ERROR; }
+        // a hit in a padding column: the compact premise broke -- as qcx_measure_state_r, expand (same bits) and scan the register
+        QCX_TRY(expand_pending(r));
+        found = 0;
+    }
+    QCX_TRY(qcx_shard_measure_scan(r->amp, r->n, 0, r->dim - 1, 0.0, rnd, &found, &idx, &cum, r->stream));
+    *out = found ? (unsigned long)idx : (unsigned long)(r->dim - 1);
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_sample_states_r(qcx_register *r, const double *rs, unsigned long shots, unsigned long *state_nums)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (shots == 0) return QCX_NO_ERROR;
+    if (!rs || !state_nums) return QCX_BAD_ARGUMENTS;
+    if (r->sh) return QCX_UNSUPPORTED;
+    r->samp_scans = 0; r->samp_fallback = 0;
+    if (r->basis_pending && (!r->queue || r->queue->gates.empty())) {
+        // the lazily pending basis state k (amplitude 1, no gate queued behind it): the running sum is 0 before k and 1 from k on --
+        // nothing to scan, and the state stays unwritten
+        const unsigned long k = (unsigned long)r->basis_index;
+        for (unsigned long i = 0; i < shots; i++) state_nums[i] = rs[i] <= 0.0 ? 0ul : (rs[i] <= 1.0 ? k : (unsigned long)(r->dim - 1));
+        return QCX_NO_ERROR;
+    }
+    QCX_TRY(fuse_flush(r, true));                                           // (a compact chain's result stays compact)
+    if (r->nonfinite) {                                                     // the fast path's arithmetic wants finite sums: every shot its own scan
+        for (unsigned long i = 0; i < shots; i++) QCX_TRY(sample_fallback_shot(r, rs[i], &state_nums[i]));
+        return QCX_NO_ERROR;
+    }
+    if (r->compact_pending == 2) QCX_TRY(compact_finish_last(r, false));   // (the chain's deferred last pass, as measure_state runs it)
+    std::vector<uint64_t> res(shots);
+    const bool compact = r->compact_pending != 0;
+    const unsigned M = (unsigned)r->M, cb = compact ? r->compact_cb : 0u;
+    if (compact) {
+        const unsigned nv = r->n - M + cb;
+        uint64_t last_excl = (uint64_t)1 << nv;                             // as qcx_measure_state_r bounds the compact scan
+        if (r->compact_orbit[r->compact_ncols - 1] == (1u << M) - 1u) last_excl = ((((uint64_t)1 << (r->n - M)) - 1) << cb) | (r->compact_ncols - 1);
+        QCX_TRY(sample_scan(r->compact_amp, nv, last_excl, rs, shots, res.data(), r->stream));
+        r->compact_measures++;
+    } else
+        QCX_TRY(sample_scan(r->amp, r->n, r->dim - 1, rs, shots, res.data(), r->stream));
+    r->samp_scans = 1;
+    for (unsigned long i = 0; i < shots; i++) {
+        const uint64_t v = res[i];
+        if (rs[i] <= 0.0) state_nums[i] = 0;                                // Q:289 (the compact scan's element 0 need not be index 0)
+        else if (v == QCX_SAMP_NOTFOUND) state_nums[i] = (unsigned long)(r->dim - 1);
+        else if (v == QCX_SAMP_FALLBACK || (compact && (unsigned)(v & ((1u << cb) - 1u)) >= r->compact_ncols))
+            QCX_TRY(sample_fallback_shot(r, rs[i], &state_nums[i]));
+        else state_nums[i] = compact ? (unsigned long)(((v >> cb) << M) | r->compact_orbit[v & ((1u << cb) - 1u)]) : (unsigned long)v;
+    }
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_sample_states(qcx_register *r, qcx_rng *rng, unsigned long shots, unsigned long *state_nums)
+{
+    if (!r || (!rng && shots)) return QCX_BAD_ARGUMENTS;
+    if (shots == 0) return QCX_NO_ERROR;
+    if (!state_nums) return QCX_BAD_ARGUMENTS;
+    if (r->sh) return QCX_UNSUPPORTED;
+    std::vector<double> rs(shots);
+    for (unsigned long i = 0; i < shots; i++) rs[i] = qcx_rng_uniform(rng);  // Q:281, one draw a shot
+    return qcx_sample_states_r(r, rs.data(), shots, state_nums);
+}
+
+extern "C" int qcx_sample_last_stats(qcx_register *r, unsigned long *state_scans, unsigned long *fallback_shots)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (state_scans) *state_scans = r->samp_scans;
+    if (fallback_shots) *fallback_shots = r->samp_fallback;
+    return QCX_NO_ERROR;
 }
 
 extern "C" int qcx_state_read(qcx_register *r, unsigned long first, unsigned long count, double *out)

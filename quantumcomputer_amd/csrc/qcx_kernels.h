@@ -962,9 +962,11 @@ struct MeasLevels {
 // the whole scan is this kernel's
 struct MeasResume { uint32_t state, slow; uint64_t b; double cum; };
 
+// ENDS (the sampling scan, K4d): every record this kernel redoes exactly leaves its exact running sum at its end in ends[record]
+template <bool ENDS>
 __global__ __launch_bounds__(64) void k_meas_walk(const amp_t *__restrict__ amp, uint64_t count, MeasLevels T,
                                                   double cum_in, double r, MeasureOut *out, unsigned *stats, unsigned rlog, const MeasResume *resume,
-                                                  MeasCands *cands, meas_slot_t *look, unsigned nslots)
+                                                  MeasCands *cands, meas_slot_t *look, unsigned nslots, double *ends)
 {
     const unsigned lane = threadIdx.x;
     const unsigned n0 = T.n[0];
@@ -989,6 +991,7 @@ __global__ __launch_bounds__(64) void k_meas_walk(const amp_t *__restrict__ amp,
             if (lane == 0) { out->found = 1; out->index = hi; out->cum = hc; if (stats) { stats[0] = slow; stats[1] = n0; } }
             return;
         }
+        if (ENDS && lane == 0) ends[0] = cum;
         b = 1;
     }
     while (b < n0) {
@@ -1035,6 +1038,7 @@ __global__ __launch_bounds__(64) void k_meas_walk(const amp_t *__restrict__ amp,
             if (lane == 0) { out->found = 1; out->index = hi; out->cum = hc; if (stats) { stats[0] = slow; stats[1] = n0; } }
             return;
         }
+        if (ENDS && lane == 0) ends[b] = cum;
         b++;
         cap = T.top;
     }
@@ -1182,9 +1186,10 @@ __device__ __forceinline__ bool meas_record_exact(const double (&p)[32], unsigne
     return false;
 }
 
+template <bool ENDS>      // ENDS: as in k_meas_walk, the exact running sum at the end of every candidate record goes to ends[record]
 __global__ __launch_bounds__(512) void k_meas_fast(const amp_t *__restrict__ amp, uint64_t count, MeasLevels T, double cum_in, double r,
                                                    MeasureOut *out, unsigned *stats, unsigned rlog, const MeasCands *cands,
-                                                   MeasResume *resume, unsigned dbg)
+                                                   MeasResume *resume, unsigned dbg, double *ends)
 {
     __shared__ unsigned s_raw[QCX_MEAS_CAND_CAP], s_sorted[QCX_MEAS_CAND_CAP + 1];
     __shared__ unsigned long long s_cum[QCX_MEAS_CAND_CAP + 1];
@@ -1278,6 +1283,7 @@ __global__ __launch_bounds__(512) void k_meas_fast(const amp_t *__restrict__ amp
                 return;
             }
             if (lane == 0) {
+                if (ENDS) ends[b] = cum;
                 __hip_atomic_store(&s_cum[k], (unsigned long long)__double_as_longlong(cum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 __hip_atomic_store(&s_flag[k], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
@@ -1287,6 +1293,193 @@ __global__ __launch_bounds__(512) void k_meas_fast(const amp_t *__restrict__ amp
             resume->state = 0u;
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// K4d  many shots from ONE state, not collapsed (qcx_sample_states, DESIGN s4.5c).  The running sum is monotone (fl(x + p) with
+// p >= 0 never decreases), so the reference's answer for a draw r lies in the first RECORD whose exact end sum reaches r, and
+// that record alone, redone from its exact start, gives the index.  So the state is read once for all shots:
+//   1. the K4c scan run to the end (r = +inf, as qcx_total_probability runs it) with ENDS: every record k_meas_fast / k_meas_walk
+//      redo exactly (an EVENT: binade crossing, tie, oversized element, wrong guess, start of the sum) leaves its exact end
+//      sum in ends[];  every other record is PLAIN: the scan validated it as "all zero, or no flag and guessed in the binade
+//      the exact running sum is in, with no overflow", so its increment S (MeasBlock) is an exact integer count of that
+//      binade's ulp -- the K4 argument above;
+//   2. k_samp_chunks / k_samp_chunk_scan / k_samp_fill: a segmented scan over the records gives every plain record its exact end
+//      = (exact end of the last event before it) + (integer sum of the plain S since) x ulp, assembled in the bits (the
+//      integer significand + the sum, the exponent kept).  What cannot be assembled so (no event before a non-zero plain
+//      record, a carry out of the binade, a non-finite end) raises `bad`, and every shot then falls back;
+//   3. k_sample_shots: one wave per shot: a 64-way search of ends[] (3-4 steps at 2^19 records), then wave_exact_block over that
+//      one record from its exact start, with r -- the reference's own additions where something happens.  A record that does
+//      not reach r after all (it cannot: the ends are exact) is reported as QCX_SAMP_FALLBACK, never guessed.
+// k_sample_seq is step 1 for registers the single-wave scan takes (below meas_min_log2): it stores the exact running sum at the
+// end of every record of 2^elog amplitudes (elog = 0: every amplitude), step 2 is then empty.
+// ---------------------------------------------------------------------------
+#define QCX_SAMP_NOTFOUND (~0ULL)               // the sum never reaches r before the bound: the reference's fall-through index
+#define QCX_SAMP_FALLBACK (~0ULL - 1ULL)        // the fast path cannot vouch for this shot: the host runs the exact scan for it
+#define QCX_SAMP_PER 16u                        // records per thread in the segmented scan; 256 threads: 4096 records per chunk
+#define QCX_SAMP_CHUNK (256u * QCX_SAMP_PER)
+
+__global__ __launch_bounds__(64) void k_sample_seq(const amp_t *__restrict__ amp, uint64_t count, double cum_in, unsigned elog, double *ends)
+{
+    const unsigned lane = threadIdx.x;
+    const uint64_t emask = ((uint64_t)1 << elog) - 1;
+    double cum = cum_in;
+    for (uint64_t base = 0; base < count; base += 64) {
+        const uint64_t i = base + lane;
+        const double p = i < count ? prob_of(amp[i]) : 0.0;
+        double run = cum;
+#pragma unroll
+        for (int j = 0; j < 64; j++) {                       // the chain of k_measure_scan: lane k ends holding the sum through element k
+            const double pj = readlane_f64(p, j);
+            run = run + ((int)lane >= j ? pj : 0.0);
+        }
+        if (i < count && (((i + 1) & emask) == 0 || i + 1 == count)) ends[i >> elog] = run;
+        cum = readlane_f64(run, 63);
+    }
+}
+
+struct SampCarry { uint64_t E, s, ev; };       // ev: a record with an exact end E (bits) lies behind; s: plain increments since (saturated)
+
+__device__ __forceinline__ SampCarry samp_combine(const SampCarry &a, const SampCarry &b)
+{
+    if (b.ev) return b;
+    SampCarry c = a;
+    c.s = a.s + b.s;                                        // both <= 2^60: no overflow
+    if (c.s > ((uint64_t)1 << 60)) c.s = (uint64_t)1 << 60;
+    return c;
+}
+
+__device__ __forceinline__ SampCarry samp_item(const MeasBlock *__restrict__ blk, const double *ends, uint64_t b)
+{
+    SampCarry c;
+    const uint64_t eb = (uint64_t)__double_as_longlong(ends[b]);
+    if (eb != ~0ULL) { c.ev = 1; c.E = eb; c.s = 0; }      // (all ones: not redone by the scan, a plain record)
+    else {
+        const MeasBlock m = blk[b];
+        c.ev = 0; c.E = 0; c.s = (m.meta & MEAS_ALLZERO) ? 0 : (m.S > ((uint64_t)1 << 60) ? (uint64_t)1 << 60 : m.S);
+    }
+    return c;
+}
+
+// the exact running sum a carry stands for; false: it cannot be assembled (the fast path must not answer)
+__device__ __forceinline__ bool samp_value(const SampCarry &c, double cum_in, double &v)
+{
+    if (c.s == 0) {
+        v = c.ev ? __longlong_as_double((long long)c.E) : cum_in;
+        return v >= 0.0 && v < __builtin_inf();
+    }
+    if (!c.ev || (c.E >> 63)) return false;
+    const uint64_t ex = (c.E >> 52) & 0x7ff;
+    if (ex == 0 || ex == 0x7ff) return false;
+    const uint64_t K = ((c.E & 0xfffffffffffffULL) | ((uint64_t)1 << 52)) + c.s;
+    if (K >= ((uint64_t)1 << 53)) return false;
+    v = __longlong_as_double((long long)((ex << 52) | (K & 0xfffffffffffffULL)));
+    return true;
+}
+
+// this thread's QCX_SAMP_PER records folded into one carry
+__device__ __forceinline__ SampCarry samp_thread_fold(const MeasBlock *__restrict__ blk, const double *ends, uint64_t b0, uint64_t nrec)
+{
+    SampCarry c; c.E = 0; c.s = 0; c.ev = 0;
+    for (unsigned k = 0; k < QCX_SAMP_PER; k++) if (b0 + k < nrec) c = samp_combine(c, samp_item(blk, ends, b0 + k));
+    return c;
+}
+
+// exclusive scan of one carry per thread over a workgroup of 256 (Hillis-Steele in LDS); *total = the whole workgroup's
+__device__ __forceinline__ SampCarry samp_block_excl(SampCarry mine, SampCarry *sh, SampCarry *total)
+{
+    const unsigned t = threadIdx.x;
+    sh[t] = mine;
+    __syncthreads();
+    for (unsigned o = 1; o < 256u; o <<= 1) {
+        SampCarry v = sh[t];
+        if (t >= o) v = samp_combine(sh[t - o], v);
+        __syncthreads();
+        sh[t] = v;
+        __syncthreads();
+    }
+    SampCarry ex; ex.E = 0; ex.s = 0; ex.ev = 0;
+    if (t) ex = sh[t - 1];
+    *total = sh[255];
+    return ex;
+}
+
+__global__ __launch_bounds__(256) void k_samp_chunks(const MeasBlock *__restrict__ blk, const double *ends, uint64_t nrec, SampCarry *chunk_tot)
+{
+    __shared__ SampCarry sh[256];
+    const uint64_t b0 = (uint64_t)blockIdx.x * QCX_SAMP_CHUNK + (uint64_t)threadIdx.x * QCX_SAMP_PER;
+    SampCarry tot;
+    samp_block_excl(samp_thread_fold(blk, ends, b0, nrec), sh, &tot);
+    if (threadIdx.x == 0) chunk_tot[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void k_samp_chunk_scan(const SampCarry *chunk_tot, unsigned nch, SampCarry *chunk_pre)
+{
+    __shared__ SampCarry sh[256];
+    const unsigned per = (nch + 255u) / 256u, c0 = threadIdx.x * per;
+    SampCarry mine; mine.E = 0; mine.s = 0; mine.ev = 0;
+    for (unsigned k = 0; k < per; k++) if (c0 + k < nch) mine = samp_combine(mine, chunk_tot[c0 + k]);
+    SampCarry tot;
+    SampCarry run = samp_block_excl(mine, sh, &tot);
+    for (unsigned k = 0; k < per; k++) if (c0 + k < nch) { chunk_pre[c0 + k] = run; run = samp_combine(run, chunk_tot[c0 + k]); }
+}
+
+__global__ __launch_bounds__(256) void k_samp_fill(const MeasBlock *__restrict__ blk, double *ends, uint64_t nrec, const SampCarry *chunk_pre,
+                                                   double cum_in, unsigned *bad)
+{
+    __shared__ SampCarry sh[256];
+    const uint64_t b0 = (uint64_t)blockIdx.x * QCX_SAMP_CHUNK + (uint64_t)threadIdx.x * QCX_SAMP_PER;
+    SampCarry tot;
+    const SampCarry ex = samp_block_excl(samp_thread_fold(blk, ends, b0, nrec), sh, &tot);
+    SampCarry carry = samp_combine(chunk_pre[blockIdx.x], ex);
+    bool ok = true;
+    for (unsigned k = 0; k < QCX_SAMP_PER; k++) {
+        const uint64_t b = b0 + k;
+        if (b >= nrec) break;
+        const SampCarry it = samp_item(blk, ends, b);
+        carry = samp_combine(carry, it);
+        double v;
+        const bool good = samp_value(carry, cum_in, v);
+        ok = ok && good;
+        if (!it.ev && good) ends[b] = v;
+    }
+    if (!ok) atomicOr(bad, 1u);
+}
+
+// one wave per shot.  out[s]: the index (< last_excl), QCX_SAMP_NOTFOUND or QCX_SAMP_FALLBACK
+__global__ __launch_bounds__(256) void k_sample_shots(const amp_t *__restrict__ amp, uint64_t count, const double *__restrict__ ends, uint64_t nrec,
+                                                      unsigned rlog, double cum_in, const double *__restrict__ rs, uint64_t nshots,
+                                                      uint64_t last_excl, const unsigned *bad, uint64_t *out)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const uint64_t s = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (s >= nshots) return;                                        // (uniform per wave)
+    const double r = rs[s];
+    uint64_t res;
+    if (*bad) res = QCX_SAMP_FALLBACK;
+    else if (r <= 0.0) res = 0;                                     // Q:289: cum after element 0 is >= 0 >= r
+    else {
+        // the first record whose exact end reaches r (NaN r: none).  Invariant: the answer lies in [lo, hi], hi = nrec = none
+        uint64_t lo = 0, hi = nrec;
+        while (lo < hi) {
+            const uint64_t step = (hi - lo + 63u) / 64u, cnt = (hi - lo) / step;     // probes lo + (l+1) step - 1, l < cnt (<= 64)
+            const uint64_t pi = lo + (uint64_t)(lane + 1u) * step - 1u;
+            const bool ge = lane < cnt && ends[pi] >= r;
+            const unsigned long long m = __ballot(ge);
+            if (m) { const uint64_t f = (uint64_t)__builtin_ctzll(m); hi = lo + (f + 1u) * step - 1u; lo += f * step; }
+            else lo += cnt * step;
+        }
+        if (lo >= nrec) res = QCX_SAMP_NOTFOUND;
+        else {
+            double cum = lo ? ends[lo - 1] : cum_in;                // < r
+            const uint64_t first = lo << rlog;
+            const uint64_t len = min((uint64_t)1 << rlog, count - first);
+            uint64_t hit = 0; double hc = 0.0;
+            if (wave_exact_block(amp, first, len, cum, r, &hit, &hc)) res = hit >= last_excl ? QCX_SAMP_NOTFOUND : hit;
+            else res = QCX_SAMP_FALLBACK;
+        }
+    }
+    if (lane == 0) out[s] = res;
 }
 
 // ---------------------------------------------------------------------------

@@ -189,6 +189,12 @@ class Register:
         check(lib().qcx_total_probability(self._h, C.byref(out)), "qcx_total_probability")
         return out.value
 
+    def sample_stats(self):
+        """(whole-state scans launched, shots answered by a per-shot scan) of the last sample_states call on this register"""
+        scans, fb = C.c_ulong(0), C.c_ulong(0)
+        check(lib().qcx_sample_last_stats(self._h, C.byref(scans), C.byref(fb)), "qcx_sample_last_stats")
+        return scans.value, fb.value
+
     def set_fusion(self, enable=True):
         """Fused LDS-tile passes (bit-identical results).  True/1: every gate call is queued; False/0 (default): only
         the whole-circuit calls (inverse_QFT, quantum_computation) run as fused passes; -1: strictly one kernel launch
@@ -276,6 +282,27 @@ def measure_state(reg, rng):
     else:
         check(lib().qcx_measure_state_r(reg._h, float(rng), C.byref(out)), "measure_state")
     return int(out.value)
+
+
+def sample_states(reg, rng_or_rs, shots=None):
+    """Many measurement shots from the current state WITHOUT collapsing it, from one read of the state (include/qcx.h:
+    qcx_sample_states).  `rng_or_rs` is an Rng -- `shots` draws are made, shot i gets the i-th: the indices K rounds of
+    reset + circuit + measure_state would give with the same Rng --, or a sequence of draws r (any order, repeats allowed).
+    Returns a numpy.uint64 array; the register's state is left exactly as it was."""
+    if isinstance(rng_or_rs, Rng):
+        if shots is None:
+            raise ValueError("sample_states: an Rng needs the number of shots")
+        k = int(shots)
+        out = np.zeros(k, dtype=np.uint64)
+        check(lib().qcx_sample_states(reg._h, rng_or_rs._h, k, out.ctypes.data_as(C.c_void_p)), "sample_states")
+        return out
+    rs = np.ascontiguousarray(np.asarray(rng_or_rs, dtype=np.float64).reshape(-1))
+    if shots is not None and int(shots) != rs.size:
+        raise ValueError(f"sample_states: {rs.size} draws given for {shots} shots")
+    out = np.zeros(rs.size, dtype=np.uint64)
+    check(lib().qcx_sample_states_r(reg._h, rs.ctypes.data_as(C.c_void_p), rs.size, out.ctypes.data_as(C.c_void_p)),
+          "sample_states")
+    return out
 
 
 def read_omega(state_num, reg):
