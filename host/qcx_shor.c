@@ -12,7 +12,10 @@
  * i.e. collapsed) and -O file the state right after the last circuit, before measuring (qcx_state_save).  -H shots (with a forced
  * trial integer) runs reset and the circuit ONCE and draws `shots` measurements from that one state (qcx_sample_states: the same
  * indices as `shots` rounds of reset, circuit and measurement with the same seed), prints the histogram of x~ (omega = x~/2^L) in
- * ascending x~ and how many shots the continued-fraction step turns into a period.  Exit code = the reference's ErrorCode (Q:164-170, Q:1340-1347).
+ * ascending x~ and how many shots the continued-fraction step turns into a period.  -P (with a forced trial integer) runs reset and
+ * the circuit once and takes the EXACT distribution of x~ from one marginal of the L register (qcx_marginal_probabilities): it
+ * prints P(x~) of the most probable x~ and the exact probabilities that one attempt yields a period and non-trivial factors (with
+ * -H, next to the sampled histogram of the same state).  Exit code = the reference's ErrorCode (Q:164-170, Q:1340-1347).
  *
  * The quantum part (reset, circuit, measurement) runs on the GPU through include/qcx.h; everything
  * here is host-side control flow written from scratch after the behaviour of find_period
@@ -40,6 +43,7 @@ typedef struct {
     int gpus;                   /* -g N: shard the register over N GPUs (2, 4, 8, 16) from this one process */
     const char *gpu_list;       /* -d "0,0,1,1": HIP device of each shard (default: spread over the visible GPUs) */
     unsigned long shots;        /* -H shots: a histogram of that many samples of one circuit's state (needs -a / -f) */
+    bool exact;                 /* -P: the exact x~ distribution of one circuit's state (needs -a / -f) */
 } Options;
 
 typedef struct {
@@ -48,7 +52,7 @@ typedef struct {
 } Stats;
 
 static const char *USAGE =
-    "Usage: qcx_shor -C num -L L_reg_size -M M_reg_size [-a trial_int | -f trial_int] [-v] [-V] [-s seed] [-Q] [-j] [-F | -G | -T] [-g gpus [-d dev,dev,...]] [-o state_file] [-O state_file] [-H shots]\n";
+    "Usage: qcx_shor -C num -L L_reg_size -M M_reg_size [-a trial_int | -f trial_int] [-v] [-V] [-s seed] [-Q] [-j] [-F | -G | -T] [-g gpus [-d dev,dev,...]] [-o state_file] [-O state_file] [-H shots] [-P]\n";
 
 static double now_seconds(void)
 {
@@ -62,7 +66,7 @@ static int parse_args(int argc, char **argv, Options *o)
     bool haveC = false, haveL = false, haveM = false;
     int ch;
     memset(o, 0, sizeof *o);
-    while ((ch = getopt(argc, argv, "C:L:M:a:f:s:o:O:g:d:H:vVQjFGT")) != -1) {
+    while ((ch = getopt(argc, argv, "C:L:M:a:f:s:o:O:g:d:H:PvVQjFGT")) != -1) {
         switch (ch) {
         case 'C': o->C = (unsigned)atoi(optarg); haveC = true; break;
         case 'L': o->L = atoi(optarg); haveL = true; break;
@@ -80,6 +84,7 @@ static int parse_args(int argc, char **argv, Options *o)
         case 'd': o->gpu_list = optarg; break;
         case 'o': o->dump_final = optarg; break;
         case 'O': o->dump_circuit = optarg; break;
+        case 'P': o->exact = true; break;
         case 'H': {
             char *end = NULL;
             o->shots = strtoul(optarg, &end, 10);
@@ -95,6 +100,16 @@ static int parse_args(int argc, char **argv, Options *o)
     /* the reference only prints for these (Q:1240-1253); a register cannot be built from them, so stop */
     if (o->C < 2 || o->L <= 0 || o->M <= 0) {
         fprintf(stderr, "Error: C, L and M must be positive (C >= 2).\n");
+        fputs(USAGE, stdout);
+        return QCX_BAD_ARGUMENTS;
+    }
+    if (o->exact && o->forced_a == 0) {
+        fprintf(stderr, "Error: -P takes the distribution of one circuit's state and needs a trial integer (-a / -f).\n");
+        fputs(USAGE, stdout);
+        return QCX_BAD_ARGUMENTS;
+    }
+    if (o->exact && o->gpus > 1) {
+        fprintf(stderr, "Error: -P is not available on a sharded register (-g).\n");
         fputs(USAGE, stdout);
         return QCX_BAD_ARGUMENTS;
     }
@@ -170,19 +185,26 @@ static int cmp_unsigned(const void *a, const void *b)
     return x < y ? -1 : (x > y ? 1 : 0);
 }
 
-/* -H: reset and the circuit once, then o->shots samples of that state (not collapsed); x~ of every shot (sorted) and the number of
- * shots whose omega yields a period */
-static int sample_histogram(const Options *o, qcx_register *reg, qcx_rng *rng, Stats *st, unsigned *xs, unsigned long *valid)
+/* -H / -P: reset and the circuit once (the state they read) */
+static int one_circuit(const Options *o, qcx_register *reg, Stats *st)
+{
+    int s;
+    if ((s = qcx_reset_register(reg)) != QCX_NO_ERROR ||
+        (s = qcx_quantum_computation(o->C, o->forced_a, o->ref_quirks ? 1 : 0, reg)) != QCX_NO_ERROR) return s;
+    st->gates += 3UL * (unsigned long)o->L + (unsigned long)o->L * (unsigned long)(o->L - 1) / 2;
+    st->attempts++;
+    if (o->dump_circuit && (s = qcx_state_save(reg, o->dump_circuit)) != QCX_NO_ERROR) return s;
+    return QCX_NO_ERROR;
+}
+
+/* -H: o->shots samples of the circuit's state (not collapsed); x~ of every shot (sorted) and the number of shots whose omega
+ * yields a period */
+static int sample_histogram(const Options *o, qcx_register *reg, qcx_rng *rng, unsigned *xs, unsigned long *valid)
 {
     const unsigned a = o->forced_a;
     int s;
     unsigned long *idx = (unsigned long *)malloc(o->shots * sizeof *idx);
     if (!idx) return QCX_INSUFFICIENT_MEMORY;
-    if ((s = qcx_reset_register(reg)) != QCX_NO_ERROR ||
-        (s = qcx_quantum_computation(o->C, a, o->ref_quirks ? 1 : 0, reg)) != QCX_NO_ERROR) { free(idx); return s; }
-    st->gates += 3UL * (unsigned long)o->L + (unsigned long)o->L * (unsigned long)(o->L - 1) / 2;
-    st->attempts++;
-    if (o->dump_circuit && (s = qcx_state_save(reg, o->dump_circuit)) != QCX_NO_ERROR) { free(idx); return s; }
     if ((s = qcx_sample_states(reg, rng, o->shots, idx)) != QCX_NO_ERROR) { free(idx); return s; }
     for (unsigned long i = 0; i < o->shots; i++) xs[i] = qcx_read_x_tilde(idx[i], o->L, o->M);
     free(idx);
@@ -194,6 +216,58 @@ static int sample_histogram(const Options *o, qcx_register *reg, qcx_rng *rng, S
         if (qcx_period_from_omega(omega, a, o->C, o->ref_quirks ? 1 : 0)) *valid += j - i;
     }
     return QCX_NO_ERROR;
+}
+
+/* -P: the exact distribution of x~ from one marginal of the L register (qubits M .. M+L-1); x~ reads them in reversed bit order
+ * (qcx_read_x_tilde).  p_period / p_factors = the sums of P(x~), x~ ascending, over the x~ whose omega = x~/2^L yields a period /
+ * a period with valid, non-trivial factors -- exactly what one attempt of find_period / try_trial_integer would conclude. */
+#define EXACT_TOP 16
+typedef struct {
+    double p_period, p_factors;
+    unsigned ntop, top_x[EXACT_TOP];
+    double top_p[EXACT_TOP];
+} Exact;
+
+static int exact_distribution(const Options *o, qcx_register *reg, Exact *ex)
+{
+    const unsigned L = (unsigned)o->L, a = o->forced_a;
+    const int quirks = o->ref_quirks ? 1 : 0;
+    if (L > 30) return QCX_UNSUPPORTED;
+    const unsigned long nx = 1UL << L;
+    double *probs = (double *)malloc(nx * sizeof *probs), *P = (double *)malloc(nx * sizeof *P);
+    int s = QCX_INSUFFICIENT_MEMORY;
+    if (!probs || !P) goto done;
+    if ((s = qcx_marginal_probabilities(reg, (unsigned)o->M, L, probs)) != QCX_NO_ERROR) goto done;
+    for (unsigned long v = 0; v < nx; v++) {
+        unsigned long x = 0;
+        for (unsigned p = 0; p < L; p++) x |= ((v >> (L - 1 - p)) & 1UL) << p;
+        P[x] = probs[v];
+    }
+    memset(ex, 0, sizeof *ex);
+    for (unsigned long x = 0; x < nx; x++) {
+        const double px = P[x];
+        if (ex->ntop < EXACT_TOP || px > ex->top_p[ex->ntop - 1]) {        /* the most probable x~, by P descending then x~ */
+            unsigned k = ex->ntop < EXACT_TOP ? ex->ntop++ : EXACT_TOP - 1;
+            for (; k > 0 && !(px <= ex->top_p[k - 1]); k--) { ex->top_p[k] = ex->top_p[k - 1]; ex->top_x[k] = ex->top_x[k - 1]; }
+            ex->top_p[k] = px; ex->top_x[k] = (unsigned)x;
+        }
+        if (px == 0.0) continue;                                             /* +0: adds nothing, and no continued fractions */
+        const unsigned period = qcx_period_from_omega((double)x / (double)nx, a, o->C, quirks);
+        if (!period) continue;
+        ex->p_period += px;
+        unsigned f[2];
+        if (qcx_factors_from_period(a, period, o->C, quirks, f) == 0 && f[0] != 1 && f[1] != 1) ex->p_factors += px;
+    }
+    for (unsigned i = 1; i < ex->ntop; i++)                                 /* printed in ascending x~ */
+        for (unsigned k = i; k > 0 && ex->top_x[k] < ex->top_x[k - 1]; k--) {
+            const unsigned tx = ex->top_x[k]; ex->top_x[k] = ex->top_x[k - 1]; ex->top_x[k - 1] = tx;
+            const double tp = ex->top_p[k]; ex->top_p[k] = ex->top_p[k - 1]; ex->top_p[k - 1] = tp;
+        }
+    s = QCX_NO_ERROR;
+done:
+    free(probs);
+    free(P);
+    return s;
 }
 
 /* Q:1003-1134: one forced trial integer, or a = 2 .. C-2 until non-trivial factors appear */
@@ -267,10 +341,19 @@ int main(int argc, char **argv)
         qcx_rng_free(rng);
         return QCX_INSUFFICIENT_MEMORY;
     }
+    Exact ex;
+    memset(&ex, 0, sizeof ex);
     const double t0 = now_seconds();
-    if (o.shots) {
-        printf("\n --- Sampling %lu shots of one circuit (a = %u)...\n\n", o.shots, o.forced_a);
-        s = sample_histogram(&o, reg, rng, &st, xs, &valid);
+    if (o.shots || o.exact) {
+        s = one_circuit(&o, reg, &st);
+        if (s == QCX_NO_ERROR && o.shots) {
+            printf("\n --- Sampling %lu shots of one circuit (a = %u)...\n\n", o.shots, o.forced_a);
+            s = sample_histogram(&o, reg, rng, xs, &valid);
+        }
+        if (s == QCX_NO_ERROR && o.exact) {
+            printf("\n --- Exact distribution of x~ for one circuit (a = %u)...\n\n", o.forced_a);
+            s = exact_distribution(&o, reg, &ex);
+        }
     } else
         s = shors_algorithm(factors, &o, reg, rng, &st);
     qcx_synchronize(reg);
@@ -288,6 +371,12 @@ int main(int argc, char **argv)
         }
         printf(" --- %lu of %lu shots give a valid period.\n", valid, o.shots);
     }
+    if (o.exact && s == QCX_NO_ERROR) {
+        for (unsigned i = 0; i < ex.ntop; i++)
+            printf(" --- P(x~ = %u, omega = %.10f) = %.17g\n", ex.top_x[i], (double)ex.top_x[i] / (double)(1ULL << o.L), ex.top_p[i]);
+        printf(" --- Exact probability that one attempt yields a period: %.17g\n", ex.p_period);
+        printf(" --- Exact probability that one attempt yields non-trivial factors: %.17g\n", ex.p_factors);
+    }
     if (o.json) {
         const double dim = (double)qcx_num_states(reg);
         unsigned long exchanges = 0;
@@ -304,12 +393,17 @@ int main(int argc, char **argv)
             }
             printf("}");
         }
+        if (o.exact && s == QCX_NO_ERROR) {          /* the exact distribution: the most probable x~ -> P, ascending */
+            printf(", \"p_period\": %.17g, \"p_factors\": %.17g, \"top\": {", ex.p_period, ex.p_factors);
+            for (unsigned i = 0; i < ex.ntop; i++) printf("%s\"%u\": %.17g", i ? ", " : "", ex.top_x[i], ex.top_p[i]);
+            printf("}");
+        }
         printf("}\n");
     }
     qcx_register_destroy(reg);                                                   /* Q:1330-1333 */
     qcx_rng_free(rng);
     free(xs);
-    if (o.shots) {
+    if (o.shots || o.exact) {
         if (s == QCX_NO_ERROR) return QCX_NO_ERROR;
         fprintf(stderr, "Error: %s.\n", qcx_status_string(s));
         return QCX_UNKNOWN_ERROR;

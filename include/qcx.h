@@ -160,6 +160,21 @@ int  qcx_sample_states_r(qcx_register *reg, const double *r, unsigned long shots
  * pending basis state), and shots a per-shot scan answered (shots the fast path could not vouch for, or every shot of a
  * register holding non-finite amplitudes) */
 int  qcx_sample_last_stats(qcx_register *reg, unsigned long *state_scans, unsigned long *fallback_shots);
+/* The exact outcome distribution of the qubits [first_qubit, first_qubit + num_qubits), the others summed out (no reference
+ * counterpart; Table I of the reference's report estimates it from 100 shots).  probs[v], v < 2^num_qubits, is the sum of
+ * p_i = fl(fl(re_i*re_i) + fl(im_i*im_i)) (Q:286, no FMA) over the indices i whose bits [first_qubit, first_qubit + num_qubits)
+ * equal v, summed as ONE PAIRWISE TREE over the summed bits s_0 < s_1 < ...: level h adds the pairs of partial sums that differ
+ * only in bit s_(h-1), lower bits reduced completely before higher ones (tests/marginal_ref.py restates it in numpy).  Inf and
+ * NaN propagate by IEEE rules; +-0 give +0.  The state is read once (K10, DESIGN s4.5d; stage plan: qcx_plan.h).
+ * The state, and every lazy form of it, is left as it was: a pending basis state with no gate queued is answered on the host
+ * (no kernel); a circuit's compact result stays compact -- a range above the M register is read there in place (the call
+ * counts in qcx_compact_measure_stats), a range that reaches into it is read from the expanded state.  Queued gates are flushed
+ * first.  first_qubit + num_qubits > n: QCX_BAD_QUBIT; num_qubits > 30: QCX_UNSUPPORTED; NULL probs: QCX_BAD_ARGUMENTS; a
+ * sharded register: QCX_UNSUPPORTED, nothing touched. */
+int  qcx_marginal_probabilities(qcx_register *reg, unsigned first_qubit, unsigned num_qubits, double *probs);
+/* the last marginal call on this register: source 0 = the register, 1 = the compact form in place, 2 = a pending basis state
+ * (no kernel), 3 = the compact form expanded first; state_reads = the passes that read amplitudes (0 for a basis state) */
+int  qcx_marginal_last_stats(qcx_register *reg, unsigned *source, unsigned long *state_reads);
 
 /* ---- state access (replaces gsl_vector_complex_get/set uses, T:7-37) ------- */
 int  qcx_state_read(qcx_register *reg, unsigned long first, unsigned long count, double *out_re_im);

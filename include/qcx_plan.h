@@ -54,6 +54,31 @@ int  qcx_fusion_plan(unsigned n_local, unsigned M, unsigned count, const qcx_gat
 int  qcx_fusion_plan_mode(int mode, unsigned n_local, unsigned M, unsigned count, const qcx_gate_desc *gates,
                           qcx_plan_action *actions, unsigned max_actions, unsigned *n_actions,
                           qcx_fuse_record *records, size_t max_records, size_t *n_records);
+
+/* The stage plan of qcx_marginal_probabilities (include/qcx.h; K10, DESIGN s4.5d), on the host.  The marginal sums the bits
+ * outside [first, first + num) as one pairwise tree, lowest summed bit first; each stage reduces the lowest summed bits that
+ * are left, inside tiles of 2^T elements of its input: the c lowest index bits (whole 128-B runs: 8 amplitudes, 16 partials),
+ * then summed bits above them, then -- once no summed bit is left outside the tile -- the lowest other bits, up to 2^12
+ * elements (2^8 compact blocks).  A stage's output is indexed by its input's bits that it does not sum, in ascending order,
+ * so the last stage's output is the marginal itself.  Non-final outputs lie back to back in the call's device scratch: at
+ * most 1/512 of the state's bytes.  stages[] must hold QCX_MARGINAL_MAX_STAGES entries.  first + num > n: QCX_BAD_QUBIT;
+ * num > 30: QCX_UNSUPPORTED. */
+#define QCX_MARGINAL_MAX_STAGES 8
+typedef struct {
+    unsigned kind;              /* 0: reads the amplitudes; 1: reads the partials of the stage before; 2: reads a circuit's compact
+                                 * result in place, one element per L-register block (its 2^M leaves summed first) */
+    unsigned in_bits;           /* the input holds 2^in_bits elements */
+    unsigned T, c;              /* a tile: 2^T elements, input index bits 0 .. c-1 among them */
+    uint64_t tile_mask;         /* the input index bits of a tile */
+    uint64_t sum_mask;          /* the input index bits this stage sums out (inside tile_mask) */
+    uint64_t qubits;            /* the same bits as qubit numbers (kind 2: the M register's bits as well) */
+    unsigned out_bits;          /* the output: 2^out_bits doubles */
+    unsigned final_stage;       /* 1: the output is the marginal */
+    uint64_t out_offset;        /* a non-final stage's output in the scratch, in doubles from its start */
+} qcx_marginal_stage;
+int  qcx_marginal_plan(unsigned n, unsigned first, unsigned num, qcx_marginal_stage *stages, unsigned *n_stages);
+/* the same for a compact circuit result (M-register bits = the orbit residues, include/qcx.h): needs first >= M */
+int  qcx_marginal_plan_compact(unsigned n, unsigned M, unsigned first, unsigned num, qcx_marginal_stage *stages, unsigned *n_stages);
 #ifdef __cplusplus
 }
 #endif

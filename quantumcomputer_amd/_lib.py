@@ -63,6 +63,10 @@ SIGNATURES = {
     "qcx_sample_states": (_i, [_p, _p, _ul, _p]),
     "qcx_sample_states_r": (_i, [_p, _p, _ul, _p]),
     "qcx_sample_last_stats": (_i, [_p, C.POINTER(_ul), C.POINTER(_ul)]),
+    "qcx_marginal_probabilities": (_i, [_p, _u, _u, _p]),
+    "qcx_marginal_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
+    "qcx_marginal_plan": (_i, [_u, _u, _u, _p, C.POINTER(_u)]),
+    "qcx_marginal_plan_compact": (_i, [_u, _u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_state_read": (_i, [_p, _ul, _ul, _p]),
     "qcx_state_write": (_i, [_p, _ul, _ul, _p]),
     "qcx_norm2": (_i, [_p, C.POINTER(_d)]),
@@ -159,6 +163,28 @@ class PlanAction(C.Structure):
                 ("chained", C.c_uint), ("tl", C.c_ubyte * 16), ("in_pos", C.c_ubyte * 16), ("st_loc", C.c_ubyte * 16),
                 ("st_pos", C.c_ubyte * 16), ("nseg_in", C.c_ubyte), ("nseg_out", C.c_ubyte), ("nseg_lg", C.c_ubyte), ("pad_", C.c_ubyte),
                 ("seg_in", C.c_ubyte * 64), ("seg_out", C.c_ubyte * 64), ("seg_lg", C.c_ubyte * 64)]      # segments: (src, dst, len, pad) x 16
+
+
+MARGINAL_MAX_STAGES = 8     # QCX_MARGINAL_MAX_STAGES (include/qcx_plan.h)
+
+
+class MarginalStage(C.Structure):
+    """qcx_marginal_stage (include/qcx_plan.h): one stage of a marginal's plan"""
+    _fields_ = [("kind", _u), ("in_bits", _u), ("T", _u), ("c", _u), ("tile_mask", _u64), ("sum_mask", _u64),
+                ("qubits", _u64), ("out_bits", _u), ("final_stage", _u), ("out_offset", _u64)]
+
+
+def marginal_plan(n, first, num, M=None):
+    """The stage plan of qcx_marginal_probabilities (host code, no GPU needed): a list of MarginalStage.  M: the plan for a
+    compact circuit result with that M register (first >= M)."""
+    arr = (MarginalStage * MARGINAL_MAX_STAGES)()
+    ns = C.c_uint(0)
+    if M is None:
+        st = lib().qcx_marginal_plan(n, first, num, C.cast(arr, C.c_void_p), C.byref(ns))
+    else:
+        st = lib().qcx_marginal_plan_compact(n, M, first, num, C.cast(arr, C.c_void_p), C.byref(ns))
+    check(st, "qcx_marginal_plan")
+    return [arr[i] for i in range(ns.value)]
 
 
 def fusion_plan(n_local, M, descs, mode=1):

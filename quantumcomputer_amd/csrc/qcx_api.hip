@@ -949,6 +949,95 @@ static int sample_scan(const void *amp, unsigned n_local, uint64_t last_excluded
     return QCX_NO_ERROR;
 }
 
+// ---- K10: the stage plan of a marginal (include/qcx_plan.h, DESIGN s4.5d) ----------------------------------------------
+// labels[b] = the register qubit that input index bit b stands for; a qubit in [first, first + num) is kept, the others summed.
+// kind 0 / 1: tiles of up to 2^12 elements, the c = 3 (amplitudes) / 4 (partials) lowest bits first; kind 2 (compact blocks,
+// >= 64 B each): up to 2^8 elements, c = 1.
+static int marginal_plan_from(unsigned kind0, std::vector<unsigned> labels, uint64_t qubits0, unsigned first, unsigned num,
+                              qcx_marginal_stage *stages, unsigned *n_stages)
+{
+    auto summed = [&](unsigned q) { return q < first || q >= first + num; };
+    unsigned ns = 0;
+    uint64_t off = 0;
+    for (unsigned kind = kind0;; kind = 1) {
+        if (ns >= QCX_MARGINAL_MAX_STAGES) return QCX_UNKNOWN_ERROR;
+        const unsigned m = (unsigned)labels.size();
+        const unsigned Tmax = kind == 2 ? 8u : 12u, cmin = kind == 0 ? 3u : (kind == 1 ? 4u : 1u);
+        const unsigned c = std::min(cmin, m);
+        uint64_t tile = c ? ((((uint64_t)1) << c) - 1u) : 0u;
+        unsigned T = c;
+        for (unsigned b = c; b < m && T < Tmax; b++)
+            if (summed(labels[b])) { tile |= (uint64_t)1 << b; T++; }
+        for (unsigned b = c; b < m && T < Tmax; b++)          // (no summed bit left outside the tile: fill it with kept bits)
+            if (!(tile >> b & 1u)) { tile |= (uint64_t)1 << b; T++; }
+        uint64_t sum = 0, qb = ns == 0 ? qubits0 : 0;
+        for (unsigned b = 0; b < m; b++)
+            if ((tile >> b & 1u) && summed(labels[b])) { sum |= (uint64_t)1 << b; qb |= (uint64_t)1 << labels[b]; }
+        std::vector<unsigned> rest;
+        bool more = false;
+        for (unsigned b = 0; b < m; b++)
+            if (!(sum >> b & 1u)) { rest.push_back(labels[b]); more |= summed(labels[b]); }
+        qcx_marginal_stage &S = stages[ns++];
+        memset(&S, 0, sizeof S);
+        S.kind = kind; S.in_bits = m; S.T = T; S.c = c; S.tile_mask = tile; S.sum_mask = sum; S.qubits = qb;
+        S.out_bits = (unsigned)rest.size();
+        S.final_stage = more ? 0u : 1u;
+        S.out_offset = more ? off : 0u;
+        if (more) off += (uint64_t)1 << S.out_bits;
+        labels.swap(rest);
+        if (!more) break;
+    }
+    *n_stages = ns;
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_marginal_plan(unsigned n, unsigned first, unsigned num, qcx_marginal_stage *stages, unsigned *n_stages)
+{
+    if (!stages || !n_stages) return QCX_BAD_ARGUMENTS;
+    if (n < 1 || n > 40 || (uint64_t)first + num > n) return QCX_BAD_QUBIT;
+    if (num > 30) return QCX_UNSUPPORTED;
+    std::vector<unsigned> labels(n);
+    for (unsigned b = 0; b < n; b++) labels[b] = b;
+    return marginal_plan_from(0, labels, 0, first, num, stages, n_stages);
+}
+
+extern "C" int qcx_marginal_plan_compact(unsigned n, unsigned M, unsigned first, unsigned num, qcx_marginal_stage *stages, unsigned *n_stages)
+{
+    if (!stages || !n_stages) return QCX_BAD_ARGUMENTS;
+    if (n < 1 || n > 40 || (uint64_t)first + num > n) return QCX_BAD_QUBIT;
+    if (num > 30) return QCX_UNSUPPORTED;
+    if (M < 1 || M >= n || first < M) return QCX_BAD_ARGUMENTS;
+    std::vector<unsigned> labels(n - M);
+    for (unsigned b = 0; b < n - M; b++) labels[b] = M + b;
+    return marginal_plan_from(2, labels, (((uint64_t)1) << M) - 1u, first, num, stages, n_stages);
+}
+
+// the kernel's parameters of one planned stage (tile-local bits, tree levels, output bits, tile-number segments)
+static void marginal_params(const qcx_marginal_stage &S, MargParams *P)
+{
+    memset(P, 0, sizeof *P);
+    const uint64_t all = S.in_bits >= 64 ? ~(uint64_t)0 : ((((uint64_t)1) << S.in_bits) - 1u);
+    auto out_pos = [&](unsigned b) { return (unsigned)__builtin_popcountll(~S.sum_mask & all & ((((uint64_t)1) << b) - 1u)); };
+    unsigned j = 0, kept = 0;
+    for (unsigned b = 0; b < S.in_bits; b++) {
+        if (!(S.tile_mask >> b & 1u)) continue;
+        P->tpos[j++] = (uint8_t)b;
+        if (S.sum_mask >> b & 1u) P->lvl_q[P->nlvl++] = (uint8_t)kept;
+        else P->kpos[kept++] = (uint8_t)out_pos(b);
+    }
+    P->T = j; P->nkeep = kept;
+    unsigned i = 0;                                     // bit i of the tile number = the i-th input bit outside the tile
+    for (unsigned b = 0; b < S.in_bits; b++) {
+        if (S.tile_mask >> b & 1u) continue;
+        const unsigned o = out_pos(b);
+        MargSeg *g = P->nseg ? &P->seg[P->nseg - 1] : nullptr;
+        if (g && g->src + g->len == i && g->dst_in + g->len == b && g->dst_out + g->len == o) g->len++;
+        else P->seg[P->nseg++] = MargSeg{(uint8_t)i, (uint8_t)b, (uint8_t)o, 1};
+        i++;
+    }
+    P->ntiles = ((uint64_t)1) << (S.in_bits - S.T);
+}
+
 // diagnostics of the last parallel measurement scan on the current device: blocks redone sequentially / blocks
 extern "C" int qcx_measure_last_stats(unsigned *slow_blocks, unsigned *blocks)
 {
@@ -991,6 +1080,10 @@ struct qcx_register {
     unsigned   compact_cb, compact_ncols;
     uint16_t   compact_orbit[16];
     unsigned long samp_scans, samp_fallback;   // the last qcx_sample_states call: whole-state scans launched / shots a per-shot scan answered
+    double    *marg_buf;        // K10 (qcx_marginal_probabilities): the stages' partials, the output and the `bad` word; its own buffer
+    size_t     marg_cap;        // doubles marg_buf holds
+    unsigned   marg_source;     // the last marginal call: 0 register, 1 compact in place, 2 basis (no kernel), 3 compact expanded first
+    unsigned long marg_reads;   // ... and the passes of it that read amplitudes
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
 };
 
@@ -1184,6 +1277,7 @@ extern "C" int qcx_register_destroy(qcx_register *r)
     (void)hipStreamDestroy(r->own_stream);
     (void)hipFree(r->amp);
     if (r->scratch) (void)hipFree(r->scratch);
+    if (r->marg_buf) (void)hipFree(r->marg_buf);
     free(r);
     return QCX_NO_ERROR;
 }
@@ -1888,6 +1982,123 @@ extern "C" int qcx_sample_last_stats(qcx_register *r, unsigned long *state_scans
     if (!r) return QCX_BAD_ARGUMENTS;
     if (state_scans) *state_scans = r->samp_scans;
     if (fallback_shots) *fallback_shots = r->samp_fallback;
+    return QCX_NO_ERROR;
+}
+
+// K10: the marginal of bits [first, first + num) (include/qcx.h, DESIGN s4.5d).  The planned stages run on r->stream: the first
+// reads the state (the register, or the compact form in place), the others only the partials; then one copy of the output.
+static int marginal_launch(qcx_register *r, const void *src, bool compact, unsigned first, unsigned num, double *probs, bool *bad_out)
+{
+    qcx_marginal_stage st[QCX_MARGINAL_MAX_STAGES];
+    unsigned ns = 0;
+    if (compact) QCX_TRY(qcx_marginal_plan_compact(r->n, (unsigned)r->M, first, num, st, &ns));
+    else QCX_TRY(qcx_marginal_plan(r->n, first, num, st, &ns));
+    size_t scratch = 0;
+    for (unsigned i = 0; i < ns; i++)
+        if (!st[i].final_stage) scratch = std::max<size_t>(scratch, (size_t)(st[i].out_offset + (((uint64_t)1) << st[i].out_bits)));
+    const size_t nout = (size_t)1 << num, need = scratch + nout + 1;
+    if (r->marg_cap < need) {
+        if (r->marg_buf) HIP_TRY(hipFree(r->marg_buf));
+        r->marg_buf = nullptr; r->marg_cap = 0;
+        HIP_TRY(hipMalloc(&r->marg_buf, need * sizeof(double)));
+        r->marg_cap = need;
+    }
+    double *const out = r->marg_buf + scratch;
+    unsigned *const bad = (unsigned *)(out + nout);
+    if (compact) HIP_TRY(hipMemsetAsync(bad, 0, sizeof(unsigned), r->stream));
+    for (unsigned i = 0; i < ns; i++) {
+        MargParams P;
+        marginal_params(st[i], &P);
+        P.src = i == 0 ? src : (const void *)(r->marg_buf + st[i - 1].out_offset);
+        P.dst = st[i].final_stage ? out : r->marg_buf + st[i].out_offset;
+        P.bad = bad;
+        const unsigned grid = (unsigned)std::min<uint64_t>(P.ntiles, 2048);
+        if (st[i].kind == 2) {
+            // the sparse tree of one block's 2^M leaves: +0 everywhere but at the orbit residues (columns, ascending)
+            const unsigned M = (unsigned)r->M;
+            std::vector<std::pair<unsigned, unsigned>> nodes;          // (position at this level, slot)
+            for (unsigned j = 0; j < r->compact_ncols; j++) nodes.push_back({r->compact_orbit[j], j});
+            std::sort(nodes.begin(), nodes.end());
+            for (unsigned h = 0; h < M; h++) {
+                std::vector<std::pair<unsigned, unsigned>> up;
+                for (size_t k = 0; k < nodes.size(); k++) {
+                    if (k + 1 < nodes.size() && (nodes[k].first >> 1) == (nodes[k + 1].first >> 1)) {
+                        P.prog_a[P.nprog] = (uint8_t)nodes[k].second; P.prog_b[P.nprog] = (uint8_t)nodes[k + 1].second; P.nprog++;
+                        up.push_back({nodes[k].first >> 1, nodes[k].second});
+                        k++;
+                    } else
+                        up.push_back({nodes[k].first >> 1, nodes[k].second});
+                }
+                nodes.swap(up);
+            }
+            if (nodes.size() != 1 || nodes[0].second != 0) {         // the root sits in the slot of the lowest residue: column 0
+                snprintf(g_last_error, sizeof g_last_error, "compact orbit is not ascending");
+                return QCX_UNKNOWN_ERROR;
+            }
+            P.cb = r->compact_cb; P.ncols = r->compact_ncols;
+            hipLaunchKernelGGL(k_marginal<MARG_COMPACT>, dim3(grid), dim3(256), 0, r->stream, P);
+        } else if (st[i].kind == 0)
+            hipLaunchKernelGGL(k_marginal<MARG_AMP>, dim3(grid), dim3(256), 0, r->stream, P);
+        else
+            hipLaunchKernelGGL(k_marginal<MARG_DBL>, dim3(grid), dim3(256), 0, r->stream, P);
+        HIP_TRY(hipGetLastError());
+    }
+    unsigned hbad = 0;
+    HIP_TRY(hipMemcpyAsync(probs, out, nout * sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    if (compact) HIP_TRY(hipMemcpyAsync(&hbad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    *bad_out = hbad != 0;
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_marginal_probabilities(qcx_register *r, unsigned first, unsigned num, double *probs)
+{
+    if (!r || !probs) return QCX_BAD_ARGUMENTS;
+    if (r->sh) return QCX_UNSUPPORTED;
+    if ((uint64_t)first + num > r->n) return QCX_BAD_QUBIT;
+    if (num > 30) return QCX_UNSUPPORTED;
+    r->marg_source = 0; r->marg_reads = 0;
+    const uint64_t nout = (uint64_t)1 << num;
+    if (r->basis_pending && (!r->queue || r->queue->gates.empty())) {
+        // the lazily pending basis state k: 1 at k's range value, +0 everywhere else -- no kernel, the state stays unwritten
+        const uint64_t v = (r->basis_index >> first) & (nout - 1u);
+        for (uint64_t i = 0; i < nout; i++) probs[i] = i == v ? 1.0 : 0.0;
+        r->marg_source = 2;
+        return QCX_NO_ERROR;
+    }
+    QCX_TRY(fuse_flush(r, true));                                           // (a compact chain's result stays compact)
+    if (r->compact_pending == 2) QCX_TRY(compact_finish_last(r, false));   // (the chain's deferred last pass, as measure_state runs it)
+    bool bad = false;
+    if (r->compact_pending && first >= (unsigned)r->M) {
+        QCX_TRY(marginal_launch(r, r->compact_amp, true, first, num, probs, &bad));
+        r->marg_source = 1; r->marg_reads = 1;
+        r->compact_measures++;
+        if (!bad) return QCX_NO_ERROR;
+        // a padding column that is not +0: the compact premise broke -- as qcx_measure_state_r, expand (same bits) and read the
+        // register
+        QCX_TRY(expand_pending(r));
+    } else if (r->compact_pending) {
+        // a range inside the M register: the register's buffer (stale while the state is compact) gets the expanded state, and
+        // the compact form stays what later calls see
+        ExpandParams E;
+        memset(&E, 0, sizeof E);
+        E.M = (unsigned)r->M; E.cb = r->compact_cb; E.ncols = r->compact_ncols;
+        for (unsigned j = 0; j < r->compact_ncols; j++) E.orbit[j] = r->compact_orbit[j];
+        const uint64_t nchunks = ((uint64_t)1 << (r->n - (unsigned)r->M)) >> 6;
+        hipLaunchKernelGGL(k_expand_compact, dim3(grid_for(nchunks, 1, 65536)), dim3(256), 0, r->stream, (const amp_t *)r->compact_amp, r->amp, nchunks, E, (int)tune_now().fuse_expand_direct);
+        HIP_TRY(hipGetLastError());
+    }
+    QCX_TRY(marginal_launch(r, r->amp, false, first, num, probs, &bad));
+    r->marg_reads += 1;
+    if (r->marg_source == 1 || r->compact_pending) r->marg_source = 3;
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_marginal_last_stats(qcx_register *r, unsigned *source, unsigned long *state_reads)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (source) *source = r->marg_source;
+    if (state_reads) *state_reads = r->marg_reads;
     return QCX_NO_ERROR;
 }
 

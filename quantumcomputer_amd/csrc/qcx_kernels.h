@@ -3908,4 +3908,161 @@ __global__ __launch_bounds__(256) void k_cam_big_scatter(amp_t *__restrict__ amp
     }
 }
 
+// ---------------------------------------------------------------------------
+// K10  marginal probabilities of a contiguous qubit range (qcx_marginal_probabilities, DESIGN s4.5d).  probs[v] = the PAIRWISE
+// TREE, over the summed bits (every bit outside the range) in ascending order, of p_i = fl(fl(re*re) + fl(im*im)): level h adds
+// the pairs of partial sums that differ only in the h-th lowest summed bit.  The planner (qcx_api.hip, marginal_plan) cuts the
+// tree into stages; a stage reduces the lowest summed bits that are left, inside TILES of 2^T elements of its input array (the
+// c lowest index bits -- whole 128-B runs -- plus summed bits above them, then kept bits to fill the tile), and writes the
+// partial sums indexed by its input's remaining bits in ascending order.  Every summed bit below a tile's highest summed bit
+// lies inside the tile, so the in-tile tree is a prefix of the whole tree, and the stages compose to exactly that tree.
+//   MARG_AMP      the stage reads amplitudes (leaf = |a|^2, no FMA)
+//   MARG_DBL      the stage reads the double partials of the stage before
+//   MARG_COMPACT  the stage reads a circuit's compact result in place: element = one L-register block, whose 2^M-leaf tree has
+//                 +0 leaves everywhere except at the orbit residues (x + 0 = x: the sparse tree P.prog is the same bits); a
+//                 padding column that is not +0 sets *P.bad (the caller then falls back to the expanded register)
+// Nothing is written but the stage's output (and *P.bad).
+// ---------------------------------------------------------------------------
+enum { MARG_AMP = 0, MARG_DBL = 1, MARG_COMPACT = 2 };
+struct MargSeg { uint8_t src, dst_in, dst_out, len; };
+struct MargParams {
+    const void *src;
+    double *dst;
+    unsigned *bad;                  // MARG_COMPACT: set to 1 when a padding column holds anything but +0
+    uint64_t ntiles;
+    uint32_t T, nlvl, nkeep, nseg;
+    uint8_t tpos[16];               // input index bit of tile-local bit j
+    uint8_t lvl_q[16];              // level h sums the partials that differ in bit lvl_q[h] of the compacted tile index
+    uint8_t kpos[16];               // output index bit of the i-th bit left in the tile (ascending)
+    MargSeg seg[40];                // tile number bits [src, src + len) -> input bits dst_in.. / output bits dst_out..
+    uint32_t cb, ncols, nprog;      // MARG_COMPACT: 2^cb columns per block, the first ncols hold the orbit; the sparse tree:
+    uint8_t prog_a[16], prog_b[16]; //   slot[prog_a[k]] += slot[prog_b[k]], k < nprog (slot j = column j; the root is slot 0)
+};
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_marginal(MargParams P)
+{
+    // a thread loads 16 elements of the tile (MARG_COMPACT: 16 amplitudes of its 2^8 blocks, 2^cb <= 16 columns each, in
+    // index order: a wave reads whole runs of blocks)
+    constexpr unsigned EPT = 16u;
+    constexpr unsigned CROW = 17u;                                   // (padded row of a block's columns: fewer bank conflicts)
+    __shared__ double buf[KIND == MARG_COMPACT ? 256u * (CROW + 1u) : 4096u];
+    // the parameters indexed at run time, in LDS: read from the kernel arguments they would be vector loads, and every wait for
+    // one of them would also wait for the next tile's amplitude loads in flight
+    __shared__ uint8_t s_tpos[16], s_lvlq[16], s_kpos[16];
+    __shared__ MargSeg s_seg[40];
+    double *red = KIND == MARG_COMPACT ? buf + 256u * CROW : buf;
+    const unsigned tid = threadIdx.x, nel = 1u << P.T;
+    const unsigned cb = KIND == MARG_COMPACT ? P.cb : 0u, ncb = 1u << cb;
+    if (tid < 16) { s_tpos[tid] = P.tpos[tid]; s_lvlq[tid] = P.lvl_q[tid]; s_kpos[tid] = P.kpos[tid]; }
+    if (tid < 40) s_seg[tid] = P.seg[tid];
+    __syncthreads();
+    // element j of this thread: tile-local element e = (tid + 256 j) >> cb, column (tid + 256 j) mod 2^cb; off[j] = its offset
+    uint64_t off[EPT];
+    unsigned nld = 0;                                                // elements this thread loads (the first nld j)
+#pragma unroll
+    for (unsigned j = 0; j < EPT; j++) {
+        const unsigned i = tid + 256u * j, e = i >> cb;
+        uint64_t o = 0;
+        for (unsigned b = 0; b < P.T; b++) o |= (uint64_t)((e >> b) & 1u) << s_tpos[b];
+        off[j] = (o << cb) | (i & (ncb - 1u));
+        if (e < nel && (KIND != MARG_COMPACT || j < ncb)) nld = j + 1;
+    }
+    auto base_of = [&](uint64_t t, bool out) {
+        uint64_t b = 0;
+        for (unsigned s = 0; s < P.nseg; s++)
+            b |= ((t >> s_seg[s].src) & ((((uint64_t)1) << s_seg[s].len) - 1u)) << (out ? s_seg[s].dst_out : s_seg[s].dst_in);
+        return b;
+    };
+    // the next tile's loads are issued before this tile's tree levels run (they are in flight meanwhile); a whole tile of loads
+    // without a guard, so that each use waits for its own load only
+    typedef typename std::conditional<KIND == MARG_DBL, double, amp_t>::type ld_t;
+    ld_t a[EPT];
+    const bool full = nld == EPT;
+    auto load = [&](uint64_t t) {
+        const uint64_t base = base_of(t, false) << cb;
+        if (full) {
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++) {
+                if constexpr (KIND == MARG_DBL) a[j] = ((const double *)P.src)[base | off[j]];
+                else a[j] = __builtin_nontemporal_load((const amp_t *)P.src + (base | off[j]));
+            }
+        } else {
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (j < nld) {
+                    if constexpr (KIND == MARG_DBL) a[j] = ((const double *)P.src)[base | off[j]];
+                    else a[j] = __builtin_nontemporal_load((const amp_t *)P.src + (base | off[j]));
+                }
+        }
+    };
+    auto leaf = [&](unsigned j) {
+        if constexpr (KIND == MARG_DBL) return a[j];
+        else return a[j].x * a[j].x + a[j].y * a[j].y;
+    };
+    if (blockIdx.x < P.ntiles) load(blockIdx.x);
+    for (uint64_t t = blockIdx.x; t < P.ntiles; t += gridDim.x) {
+        const uint64_t base_out = base_of(t, true);
+        if constexpr (KIND != MARG_COMPACT) {
+            if (full) {
+#pragma unroll
+                for (unsigned j = 0; j < EPT; j++) red[tid + 256u * j] = leaf(j);
+            } else {
+#pragma unroll
+                for (unsigned j = 0; j < EPT; j++)
+                    if (j < nld) red[tid + 256u * j] = leaf(j);
+            }
+            if (t + gridDim.x < P.ntiles) load(t + gridDim.x);
+        } else {
+            // the leaves of block e's orbit columns into its LDS row; a padding column must hold +0
+            bool bad = false;
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (j < nld) {
+                    const unsigned i = tid + 256u * j, e = i >> cb, col = i & (ncb - 1u);
+                    if (col < P.ncols) buf[e * CROW + col] = leaf(j);
+                    else bad |= (__double_as_longlong(a[j].x) | __double_as_longlong(a[j].y)) != 0;
+                }
+            if (bad) *P.bad = 1u;                                    // (a plain store: every writer stores the same value)
+            if (t + gridDim.x < P.ntiles) load(t + gridDim.x);
+            __syncthreads();
+            // each block's sparse tree over its 2^M leaves (+0 but at the orbit residues)
+            if (tid < nel) {
+                double *row = buf + tid * CROW;
+                for (unsigned k = 0; k < P.nprog; k++) row[P.prog_a[k]] = row[P.prog_a[k]] + row[P.prog_b[k]];
+                red[tid] = row[0];
+            }
+        }
+        __syncthreads();
+        // the tree levels inside the tile, lowest summed bit first; in place (read all, barrier, write all)
+        unsigned sz = nel;
+        for (unsigned h = 0; h < P.nlvl; h++) {
+            const unsigned half = sz >> 1, q = s_lvlq[h], lo = (1u << q) - 1u;
+            double v[EPT > 8 ? 8 : 1];
+#pragma unroll
+            for (unsigned m = 0; m < (EPT > 8 ? 8u : 1u); m++) {
+                const unsigned k = tid + 256u * m;
+                if (k < half) {
+                    const unsigned i0 = ((k & ~lo) << 1) | (k & lo);
+                    v[m] = red[i0] + red[i0 | (1u << q)];
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (unsigned m = 0; m < (EPT > 8 ? 8u : 1u); m++) {
+                const unsigned k = tid + 256u * m;
+                if (k < half) red[k] = v[m];
+            }
+            __syncthreads();
+            sz = half;
+        }
+        for (unsigned k = tid; k < sz; k += 256u) {
+            uint64_t o = base_out;
+            for (unsigned b = 0; b < P.nkeep; b++) o |= (uint64_t)((k >> b) & 1u) << s_kpos[b];
+            P.dst[o] = red[k];
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace qcx

@@ -195,6 +195,23 @@ class Register:
         check(lib().qcx_sample_last_stats(self._h, C.byref(scans), C.byref(fb)), "qcx_sample_last_stats")
         return scans.value, fb.value
 
+    def marginal(self, first, num):
+        """The exact outcome distribution of qubits [first, first + num), the others summed out: a float64 array of 2^num
+        (include/qcx.h: qcx_marginal_probabilities; one pinned pairwise summation order, tests/marginal_ref.py)."""
+        first, num = int(first), int(num)
+        if first < 0 or num < 0:
+            raise ValueError("marginal: first and num must be >= 0")
+        out = np.empty(1 << num if num <= 30 else 1, dtype=np.float64)      # (num > 30: the call refuses, QCX_UNSUPPORTED)
+        check(lib().qcx_marginal_probabilities(self._h, first, num, out.ctypes.data_as(C.c_void_p)), "qcx_marginal_probabilities")
+        return out
+
+    def marginal_stats(self):
+        """(source, state reads) of the last marginal call on this register: source 0 = the register, 1 = the compact form in
+        place, 2 = a pending basis state (no kernel), 3 = the compact form expanded first"""
+        src, reads = C.c_uint(0), C.c_ulong(0)
+        check(lib().qcx_marginal_last_stats(self._h, C.byref(src), C.byref(reads)), "qcx_marginal_last_stats")
+        return src.value, reads.value
+
     def set_fusion(self, enable=True):
         """Fused LDS-tile passes (bit-identical results).  True/1: every gate call is queued; False/0 (default): only
         the whole-circuit calls (inverse_QFT, quantum_computation) run as fused passes; -1: strictly one kernel launch
@@ -302,6 +319,20 @@ def sample_states(reg, rng_or_rs, shots=None):
     out = np.zeros(rs.size, dtype=np.uint64)
     check(lib().qcx_sample_states_r(reg._h, rs.ctypes.data_as(C.c_void_p), rs.size, out.ctypes.data_as(C.c_void_p)),
           "sample_states")
+    return out
+
+
+def omega_distribution(reg):
+    """P[x~] for x~ = 0 .. 2^L - 1: the exact probability that measuring the register gives x~ (the L register read in
+    reversed bit order, as read_omega reads it), from one marginal of the L register (Register.marginal)."""
+    L, M = reg.L_size, reg.M_size
+    probs = reg.marginal(M, L)
+    v = np.arange(1 << L, dtype=np.uint64)
+    xt = np.zeros_like(v)
+    for p in range(L):
+        xt |= ((v >> np.uint64(L - 1 - p)) & np.uint64(1)) << np.uint64(p)
+    out = np.empty_like(probs)
+    out[xt] = probs
     return out
 
 
