@@ -1077,8 +1077,7 @@ struct qcx_register {
     int        compact_pending;
     unsigned long compact_measures;            // measurements that scanned the compact form
     amp_t     *compact_amp;     // inside r->scratch
-    unsigned   compact_cb, compact_ncols;
-    uint16_t   compact_orbit[16];
+    ExpandParams compact_E;     // ... and its layout: M, column bits, orbit (compact_params)
     unsigned long samp_scans, samp_fallback;   // the last qcx_sample_states call: whole-state scans launched / shots a per-shot scan answered
     double    *marg_buf;        // K10 (qcx_marginal_probabilities): the stages' partials, the output and the `bad` word; its own buffer
     size_t     marg_cap;        // doubles marg_buf holds
@@ -1384,10 +1383,7 @@ extern "C" int qcx_shard_compact_front(void *compact, unsigned n_local_compact, 
     BasisFront B;
     if (front_plan(n, M, basis, tune_now(), q, &B) != count) return QCX_BAD_ARGUMENTS;
     B.first = first_global;
-    ExpandParams E;
-    memset(&E, 0, sizeof E);
-    E.M = M; E.cb = cb; E.ncols = ncols;
-    for (unsigned j = 0; j < ncols; j++) E.orbit[j] = orbit16[j];
+    const ExpandParams E = compact_params(M, cb, orbit16, ncols);
     const uint64_t nblocks = (uint64_t)1 << (n_local_compact - cb);
     hipLaunchKernelGGL(k_basis_front_compact, dim3(grid_for(nblocks, 256, 65536)), dim3(256), 0, (hipStream_t)stream, (amp_t *)compact, n_local_compact, B, E);
     HIP_TRY(hipGetLastError());
@@ -1399,14 +1395,7 @@ extern "C" int qcx_shard_expand_compact(const void *compact, void *real, unsigne
                                         const uint16_t *orbit16, void *stream)
 {
     if (!compact || !real || !orbit16 || n_local > 40 || M > 12 || n_local < M + 6 || ncols == 0 || ncols > 16 || cb < 2 || cb > 4 || (1u << cb) < ncols) return QCX_BAD_ARGUMENTS;
-    ExpandParams E;
-    memset(&E, 0, sizeof E);
-    E.M = M; E.cb = cb; E.ncols = ncols;
-    for (unsigned j = 0; j < ncols; j++) E.orbit[j] = orbit16[j];
-    const uint64_t nchunks = ((uint64_t)1 << (n_local - M)) >> 6;
-    hipLaunchKernelGGL(k_expand_compact, dim3(grid_for(nchunks, 1, 65536)), dim3(256), 0, (hipStream_t)stream, (const amp_t *)compact, (amp_t *)real, nchunks, E, (int)tune_now().fuse_expand_direct);
-    HIP_TRY(hipGetLastError());
-    return QCX_NO_ERROR;
+    return launch_expand_compact((const amp_t *)compact, (amp_t *)real, n_local, compact_params(M, cb, orbit16, ncols), (hipStream_t)stream);
 }
 
 extern "C" int qcx_shard_run_fused_mode(int mode, void *amp, unsigned n_local, unsigned M, unsigned count, const qcx_gate_desc *gates, void *stream);
@@ -1853,39 +1842,50 @@ static int quantum_computation_body(unsigned C, unsigned a, int intpow_mode, qcx
     return inverse_qft_body(r);
 }
 
+// the observers' prologue: the queue flushed, a compact chain's result kept compact -- its deferred last pass run as an ordinary
+// pass, since the observers read the compact form
+static int settle_for_read(qcx_register *r)
+{
+    QCX_TRY(fuse_flush(r, true));
+    return compact_finish_last(r, false);
+}
+
+// the state is the lazily pending basis state (amplitude 1 at basis_index) with no gate queued behind it: answered on the host
+static bool basis_only(const qcx_register *r)
+{
+    return r->basis_pending && (!r->queue || r->queue->gates.empty());
+}
+
+// The scan of Q:283-292 on whichever form holds the state (after settle_for_read).  On the compact form the amplitudes left out
+// are +0 and add exactly nothing to the running sum, and the compact order IS the index order (orbit ascending), so the first
+// compact element with cum >= r is the first real one -- except for r <= 0, where the reference stops at index 0 whatever it
+// holds.  A hit in a padding column is not mapped through stale orbit slots: the state is expanded (same bits) and the register
+// scanned.
+static int scan_state(qcx_register *r, double rnd, uint64_t *idx)
+{
+    int found = 0; uint64_t i = 0; double cum = 0.0;
+    *idx = r->dim - 1;                                                      // Q:283 fall-through
+    if (r->compact_pending) {
+        const ExpandParams &E = r->compact_E;
+        if (rnd <= 0.0) { *idx = 0; return QCX_NO_ERROR; }
+        QCX_TRY(qcx_shard_measure_scan(r->compact_amp, r->n - E.M + E.cb, 0, compact_scan_end(r->n, E), 0.0, rnd, &found, &i, &cum, r->stream));
+        if (!found || compact_real_index(E, i, idx)) return QCX_NO_ERROR;
+        QCX_TRY(expand_pending(r));
+    }
+    QCX_TRY(qcx_shard_measure_scan(r->amp, r->n, 0, r->dim - 1, 0.0, rnd, &found, &i, &cum, r->stream));
+    if (found) *idx = i;
+    return QCX_NO_ERROR;
+}
+
 extern "C" int qcx_measure_state_r(qcx_register *r, double rnd, unsigned long *state_num)
 {
     if (!r || !state_num) return QCX_BAD_ARGUMENTS;
     if (r->sh) return sh_measure(r->sh, rnd, state_num);
-    QCX_TRY(fuse_flush(r, true));                                           // (a compact chain's result may stay compact)
-    int found = 0; uint64_t idx = 0; double cum = 0.0;
-    if (r->compact_pending == 2) QCX_TRY(compact_finish_last(r, false));   // (the chain's deferred last pass, as an ordinary pass: the scan wants the compact form)
-    if (r->compact_pending) {
-        // The scan of Q:283-292 on the compact form: the amplitudes it leaves out are +0 and add exactly nothing to the running
-        // sum, and the compact order IS the index order (orbit ascending), so the first compact element with cum >= r is the
-        // first real one -- except for r <= 0, where the reference stops at index 0 whatever it holds.
-        const unsigned M = (unsigned)r->M, cb = r->compact_cb, nv = r->n - M + cb;
-        if (rnd <= 0.0) { found = 1; idx = 0; }
-        else {
-            uint64_t last_excl = (uint64_t)1 << nv;                         // compact elements whose real index is below dim - 1
-            if (r->compact_orbit[r->compact_ncols - 1] == (1u << M) - 1u) last_excl = ((((uint64_t)1 << (r->n - M)) - 1) << cb) | (r->compact_ncols - 1);
-            uint64_t cidx = 0;
-            QCX_TRY(qcx_shard_measure_scan(r->compact_amp, nv, 0, last_excl, 0.0, rnd, &found, &cidx, &cum, r->stream));
-            const unsigned col = (unsigned)(cidx & ((1u << cb) - 1u));
-            if (found && col >= r->compact_ncols) {
-                // a hit in a PADDING column: those hold +0 through every gate and add nothing to the sum, so the scan cannot
-                // stop there -- unless the premise broke.  Do not map it through stale orbit slots: expand and scan the register.
-                QCX_TRY(expand_pending(r));
-                found = 0;
-                QCX_TRY(qcx_shard_measure_scan(r->amp, r->n, 0, r->dim - 1, 0.0, rnd, &found, &idx, &cum, r->stream));
-            }
-            else if (found) idx = ((cidx >> cb) << M) | r->compact_orbit[col];
-        }
-        r->compact_pending = 0;                                             // the collapse below replaces the whole state
-        r->compact_measures++;
-    } else
-    QCX_TRY(qcx_shard_measure_scan(r->amp, r->n, 0, r->dim - 1, 0.0, rnd, &found, &idx, &cum, r->stream));
-    if (!found) idx = r->dim - 1;                                           // Q:283 fall-through
+    QCX_TRY(settle_for_read(r));
+    const bool compact = r->compact_pending != 0;
+    uint64_t idx = 0;
+    QCX_TRY(scan_state(r, rnd, &idx));
+    if (compact) { r->compact_pending = 0; r->compact_measures++; }
     r->zeros_dirty = 0;                                                     // (the collapse replaces the whole state)
     r->nonfinite = 0;
     if (r->fusion >= 0) { r->basis_pending = 1; r->basis_index = idx; }     // Q:302-303, written at the next flush (or never: a reset may follow)
@@ -1905,21 +1905,10 @@ extern "C" int qcx_measure_state(qcx_register *r, qcx_rng *rng, unsigned long *s
 // scan for all shots; a shot the fast path cannot vouch for is answered by that very scan of its own (no collapse).
 static int sample_fallback_shot(qcx_register *r, double rnd, unsigned long *out)
 {
-    int found = 0; uint64_t idx = 0; double cum = 0.0;
+    uint64_t idx = 0;
     r->samp_scans++; r->samp_fallback++;
-    if (r->compact_pending) {
-        const unsigned M = (unsigned)r->M, cb = r->compact_cb, nv = r->n - M + cb;
-        uint64_t last_excl = (uint64_t)1 << nv, cidx = 0;
-        if (r->compact_orbit[r->compact_ncols - 1] == (1u << M) - 1u) last_excl = ((((uint64_t)1 << (r->n - M)) - 1) << cb) | (r->compact_ncols - 1);
-        QCX_TRY(qcx_shard_measure_scan(r->compact_amp, nv, 0, last_excl, 0.0, rnd, &found, &cidx, &cum, r->stream));
-        const unsigned col = (unsigned)(cidx & ((1u << cb) - 1u));
-        if (!found || col < r->compact_ncols) { *out = found ? (unsigned long)(((cidx >> cb) << M) | r->compact_orbit[col]) : (unsigned long)(r->dim - 1); return QCX_NO_ERROR; }
-        // a hit in a padding column: the compact premise broke -- as qcx_measure_state_r, expand (same bits) and scan the register
-        QCX_TRY(expand_pending(r));
-        found = 0;
-    }
-    QCX_TRY(qcx_shard_measure_scan(r->amp, r->n, 0, r->dim - 1, 0.0, rnd, &found, &idx, &cum, r->stream));
-    *out = found ? (unsigned long)idx : (unsigned long)(r->dim - 1);
+    QCX_TRY(scan_state(r, rnd, &idx));
+    *out = (unsigned long)idx;
     return QCX_NO_ERROR;
 }
 
@@ -1930,38 +1919,34 @@ extern "C" int qcx_sample_states_r(qcx_register *r, const double *rs, unsigned l
     if (!rs || !state_nums) return QCX_BAD_ARGUMENTS;
     if (r->sh) return QCX_UNSUPPORTED;
     r->samp_scans = 0; r->samp_fallback = 0;
-    if (r->basis_pending && (!r->queue || r->queue->gates.empty())) {
-        // the lazily pending basis state k (amplitude 1, no gate queued behind it): the running sum is 0 before k and 1 from k on --
-        // nothing to scan, and the state stays unwritten
+    if (basis_only(r)) {
+        // the running sum is 0 before the basis state k and 1 from k on -- nothing to scan, and the state stays unwritten
         const unsigned long k = (unsigned long)r->basis_index;
         for (unsigned long i = 0; i < shots; i++) state_nums[i] = rs[i] <= 0.0 ? 0ul : (rs[i] <= 1.0 ? k : (unsigned long)(r->dim - 1));
         return QCX_NO_ERROR;
     }
-    QCX_TRY(fuse_flush(r, true));                                           // (a compact chain's result stays compact)
+    QCX_TRY(settle_for_read(r));
     if (r->nonfinite) {                                                     // the fast path's arithmetic wants finite sums: every shot its own scan
         for (unsigned long i = 0; i < shots; i++) QCX_TRY(sample_fallback_shot(r, rs[i], &state_nums[i]));
         return QCX_NO_ERROR;
     }
-    if (r->compact_pending == 2) QCX_TRY(compact_finish_last(r, false));   // (the chain's deferred last pass, as measure_state runs it)
     std::vector<uint64_t> res(shots);
     const bool compact = r->compact_pending != 0;
-    const unsigned M = (unsigned)r->M, cb = compact ? r->compact_cb : 0u;
+    const ExpandParams &E = r->compact_E;
     if (compact) {
-        const unsigned nv = r->n - M + cb;
-        uint64_t last_excl = (uint64_t)1 << nv;                             // as qcx_measure_state_r bounds the compact scan
-        if (r->compact_orbit[r->compact_ncols - 1] == (1u << M) - 1u) last_excl = ((((uint64_t)1 << (r->n - M)) - 1) << cb) | (r->compact_ncols - 1);
-        QCX_TRY(sample_scan(r->compact_amp, nv, last_excl, rs, shots, res.data(), r->stream));
+        QCX_TRY(sample_scan(r->compact_amp, r->n - E.M + E.cb, compact_scan_end(r->n, E), rs, shots, res.data(), r->stream));
         r->compact_measures++;
     } else
         QCX_TRY(sample_scan(r->amp, r->n, r->dim - 1, rs, shots, res.data(), r->stream));
     r->samp_scans = 1;
     for (unsigned long i = 0; i < shots; i++) {
         const uint64_t v = res[i];
+        uint64_t idx = v;
         if (rs[i] <= 0.0) state_nums[i] = 0;                                // Q:289 (the compact scan's element 0 need not be index 0)
         else if (v == QCX_SAMP_NOTFOUND) state_nums[i] = (unsigned long)(r->dim - 1);
-        else if (v == QCX_SAMP_FALLBACK || (compact && (unsigned)(v & ((1u << cb) - 1u)) >= r->compact_ncols))
+        else if (v == QCX_SAMP_FALLBACK || (compact && !compact_real_index(E, v, &idx)))
             QCX_TRY(sample_fallback_shot(r, rs[i], &state_nums[i]));
-        else state_nums[i] = compact ? (unsigned long)(((v >> cb) << M) | r->compact_orbit[v & ((1u << cb) - 1u)]) : (unsigned long)v;
+        else state_nums[i] = (unsigned long)idx;
     }
     return QCX_NO_ERROR;
 }
@@ -2017,7 +2002,7 @@ static int marginal_launch(qcx_register *r, const void *src, bool compact, unsig
             // the sparse tree of one block's 2^M leaves: +0 everywhere but at the orbit residues (columns, ascending)
             const unsigned M = (unsigned)r->M;
             std::vector<std::pair<unsigned, unsigned>> nodes;          // (position at this level, slot)
-            for (unsigned j = 0; j < r->compact_ncols; j++) nodes.push_back({r->compact_orbit[j], j});
+            for (unsigned j = 0; j < r->compact_E.ncols; j++) nodes.push_back({r->compact_E.orbit[j], j});
             std::sort(nodes.begin(), nodes.end());
             for (unsigned h = 0; h < M; h++) {
                 std::vector<std::pair<unsigned, unsigned>> up;
@@ -2035,7 +2020,7 @@ static int marginal_launch(qcx_register *r, const void *src, bool compact, unsig
                 snprintf(g_last_error, sizeof g_last_error, "compact orbit is not ascending");
                 return QCX_UNKNOWN_ERROR;
             }
-            P.cb = r->compact_cb; P.ncols = r->compact_ncols;
+            P.cb = r->compact_E.cb; P.ncols = r->compact_E.ncols;
             hipLaunchKernelGGL(k_marginal<MARG_COMPACT>, dim3(grid), dim3(256), 0, r->stream, P);
         } else if (st[i].kind == 0)
             hipLaunchKernelGGL(k_marginal<MARG_AMP>, dim3(grid), dim3(256), 0, r->stream, P);
@@ -2059,15 +2044,14 @@ extern "C" int qcx_marginal_probabilities(qcx_register *r, unsigned first, unsig
     if (num > 30) return QCX_UNSUPPORTED;
     r->marg_source = 0; r->marg_reads = 0;
     const uint64_t nout = (uint64_t)1 << num;
-    if (r->basis_pending && (!r->queue || r->queue->gates.empty())) {
-        // the lazily pending basis state k: 1 at k's range value, +0 everywhere else -- no kernel, the state stays unwritten
+    if (basis_only(r)) {
+        // 1 at the basis state's range value, +0 everywhere else -- no kernel, the state stays unwritten
         const uint64_t v = (r->basis_index >> first) & (nout - 1u);
         for (uint64_t i = 0; i < nout; i++) probs[i] = i == v ? 1.0 : 0.0;
         r->marg_source = 2;
         return QCX_NO_ERROR;
     }
-    QCX_TRY(fuse_flush(r, true));                                           // (a compact chain's result stays compact)
-    if (r->compact_pending == 2) QCX_TRY(compact_finish_last(r, false));   // (the chain's deferred last pass, as measure_state runs it)
+    QCX_TRY(settle_for_read(r));
     bool bad = false;
     if (r->compact_pending && first >= (unsigned)r->M) {
         QCX_TRY(marginal_launch(r, r->compact_amp, true, first, num, probs, &bad));
@@ -2080,13 +2064,7 @@ extern "C" int qcx_marginal_probabilities(qcx_register *r, unsigned first, unsig
     } else if (r->compact_pending) {
         // a range inside the M register: the register's buffer (stale while the state is compact) gets the expanded state, and
         // the compact form stays what later calls see
-        ExpandParams E;
-        memset(&E, 0, sizeof E);
-        E.M = (unsigned)r->M; E.cb = r->compact_cb; E.ncols = r->compact_ncols;
-        for (unsigned j = 0; j < r->compact_ncols; j++) E.orbit[j] = r->compact_orbit[j];
-        const uint64_t nchunks = ((uint64_t)1 << (r->n - (unsigned)r->M)) >> 6;
-        hipLaunchKernelGGL(k_expand_compact, dim3(grid_for(nchunks, 1, 65536)), dim3(256), 0, r->stream, (const amp_t *)r->compact_amp, r->amp, nchunks, E, (int)tune_now().fuse_expand_direct);
-        HIP_TRY(hipGetLastError());
+        QCX_TRY(launch_expand_compact(r->compact_amp, r->amp, r->n, r->compact_E, r->stream));
     }
     QCX_TRY(marginal_launch(r, r->amp, false, first, num, probs, &bad));
     r->marg_reads += 1;

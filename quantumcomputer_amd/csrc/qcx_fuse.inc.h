@@ -1530,6 +1530,46 @@ static bool compact_orbit(const BasisFront &B, unsigned M, std::vector<uint16_t>
     return true;
 }
 
+// ---- the compact form, read and written by these helpers only (DESIGN s4.4).  Every host that keeps a compact result -- the
+// register (compact_chain), the C sharded host (sh_compact) and the one-process-per-GPU host (qcx_shard_*_compact; sharded.py
+// restates compact_scan_end / compact_real_index) -- describes it by one ExpandParams.
+static ExpandParams compact_params(unsigned M, unsigned cb, const uint16_t *orbit, unsigned ncols)
+{
+    ExpandParams E;
+    memset(&E, 0, sizeof E);
+    E.M = M; E.cb = cb; E.ncols = ncols;
+    for (unsigned j = 0; j < ncols; j++) E.orbit[j] = orbit[j];
+    return E;
+}
+
+// the real register (2^n_local amplitudes, n_local - M >= 6) from its compact form.  Only launches: the caller owns the state's bookkeeping
+static int launch_expand_compact(const amp_t *compact, amp_t *real, unsigned n_local, const ExpandParams &E, hipStream_t stream)
+{
+    const uint64_t nchunks = ((uint64_t)1 << (n_local - E.M)) >> 6;        // 64 blocks per workgroup iteration
+    hipLaunchKernelGGL(k_expand_compact, dim3(grid_for(nchunks, 1, 65536)), dim3(256), 0, stream, compact, real, nchunks, E, (int)tune_now().fuse_expand_direct);
+    HIP_TRY(hipGetLastError());
+    return QCX_NO_ERROR;
+}
+
+// the last_excluded of a scan (Q:283-292) of the compact form of an n-qubit register: compact elements whose real index is
+// below 2^n - 1 -- all of them, unless the orbit's last residue is 2^M - 1
+static uint64_t compact_scan_end(unsigned n, const ExpandParams &E)
+{
+    const unsigned top = E.ncols - 1;
+    if (E.orbit[top] != (1u << E.M) - 1u) return (uint64_t)1 << (n - E.M + E.cb);
+    return ((((uint64_t)1 << (n - E.M)) - 1) << E.cb) | top;
+}
+
+// the real index of compact index cidx; false for a padding column (those hold +0 through every gate and add nothing to a
+// running sum, so a scan that stops there means the compact premise broke: the caller expands and reads the register)
+static bool compact_real_index(const ExpandParams &E, uint64_t cidx, uint64_t *idx)
+{
+    const unsigned col = (unsigned)(cidx & ((1u << E.cb) - 1u));
+    if (col >= E.ncols) return false;
+    *idx = ((cidx >> E.cb) << E.M) | E.orbit[col];
+    return true;
+}
+
 // the deferred last pass of a compact chain (compact_pending == 2, GateQueue::last): into_register: with the expanding store,
 // the state is then in r->amp (compact_pending = 0); otherwise as planned, the compact form is complete (compact_pending = 1)
 static int launch_pass(qcx_register *r, const Tune &tn, const FusePass &P_in, const FuseOp *d_ops, bool nopipe, amp_t *amp_in, amp_t *amp_out);
@@ -1565,13 +1605,7 @@ static int expand_pending(qcx_register *r)
 {
     if (r->compact_pending == 2) QCX_TRY(compact_finish_last(r, true));
     if (!r->compact_pending) return QCX_NO_ERROR;
-    ExpandParams E;
-    memset(&E, 0, sizeof E);
-    E.M = (unsigned)r->M; E.cb = r->compact_cb; E.ncols = r->compact_ncols;
-    for (unsigned j = 0; j < r->compact_ncols; j++) E.orbit[j] = r->compact_orbit[j];
-    const uint64_t nchunks = ((uint64_t)1 << (r->n - (unsigned)r->M)) >> 6;  // 64 blocks per workgroup iteration (L >= 8)
-    hipLaunchKernelGGL(k_expand_compact, dim3(grid_for(nchunks, 1, 65536)), dim3(256), 0, r->stream, (const amp_t *)r->compact_amp, r->amp, nchunks, E, (int)tune_now().fuse_expand_direct);
-    HIP_TRY(hipGetLastError());
+    QCX_TRY(launch_expand_compact(r->compact_amp, r->amp, r->n, r->compact_E, r->stream));   // (L >= 8)
     r->compact_pending = 0;
     return QCX_NO_ERROR;
 }
@@ -1743,8 +1777,7 @@ static int compact_chain(qcx_register *r, GateQueue *gq, const Tune &tn, const B
     if (expanded) { r->compact_pending = 0; gq->expanding_stores++; }
     else {
         r->compact_pending = deferred ? 2 : 1;
-        r->compact_amp = v.amp; r->compact_cb = cb; r->compact_ncols = (unsigned)orbit.size();
-        for (size_t j = 0; j < orbit.size(); j++) r->compact_orbit[j] = orbit[j];
+        r->compact_amp = v.amp; r->compact_E = compact_params(M, cb, orbit.data(), (unsigned)orbit.size());
         if (!keep) QCX_TRY(expand_pending(r));
     }
     r->basis_pending = 0;

@@ -652,10 +652,7 @@ static int sh_compact(ShardSet *sh, bool *done)
     c->fusion = sh->fusion;
     c->queue.clear(); c->basis_pending = false; c->zeros_dirty = false;
     sh_identity_perm(c);
-    ExpandParams E;
-    memset(&E, 0, sizeof E);
-    E.M = M; E.cb = cb; E.ncols = (unsigned)orbit.size();
-    for (size_t j = 0; j < orbit.size(); j++) E.orbit[j] = orbit[j];
+    const ExpandParams E = compact_params(M, cb, orbit.data(), (unsigned)orbit.size());
     const unsigned long ex0 = c->exchanges, pp0 = c->pack_passes, rb0 = c->relayed_bytes, og0 = c->overlapped_gates;
     for (unsigned r = 0; r < sh->W; r++) {
         SH_DEV(c, r);
@@ -697,12 +694,9 @@ static int sh_expand_pending(ShardSet *sh)
     sh->comp_pending = false;
     ShardSet *c = sh->comp;
     if (!c) { set_error("sharded register: a compact result without its companion"); return QCX_UNKNOWN_ERROR; }
-    const Tune tn = tune_now();
-    const uint64_t nchunks = ((uint64_t)1 << (sh->n_local - sh->M)) >> 6;
     for (unsigned r = 0; r < sh->W; r++) {
         SH_DEV(sh, r);
-        hipLaunchKernelGGL(k_expand_compact, dim3(grid_for(nchunks, 1, 65536)), dim3(256), 0, sh->st[r], (const amp_t *)c->buf[c->cur][r], sh->buf[sh->cur][r], nchunks, sh->comp_E, (int)tn.fuse_expand_direct);
-        HIP_TRY(hipGetLastError());
+        QCX_TRY(launch_expand_compact(c->buf[c->cur][r], sh->buf[sh->cur][r], sh->n_local, sh->comp_E, sh->st[r]));
         // the expansion READS the companion's buffer on the register's stream: whatever the companion's own streams do next
         // (the front of the next compact circuit overwrites that buffer) has to wait for it
         if (r < c->ev_a.size() && c->ev_a[r]) {
@@ -941,45 +935,51 @@ static int sh_norm2(ShardSet *sh, double *out)
     return QCX_NO_ERROR;
 }
 
-// Q:272-306 over the shards: the sequential cumulative sum is handed from shard to shard in index order
+// the scan of Q:283-292 over a set's shards in index order: the running sum is handed from shard to shard.  *idx is written
+// only when an element is found
+static int sh_scan(ShardSet *s, uint64_t last_excl, double rnd, bool *found, uint64_t *idx)
+{
+    double cum = 0.0;
+    *found = false;
+    for (unsigned r = 0; r < s->W && !*found; r++) {
+        SH_DEV(s, r);
+        int f = 0; uint64_t i = 0; double c2 = cum;
+        QCX_TRY(qcx_shard_measure_scan(s->buf[s->cur][r], s->n_local, (uint64_t)r << s->n_local, last_excl, cum, rnd, &f, &i, &c2, s->st[r]));
+        cum = c2;
+        if (f) { *found = true; *idx = i; }
+    }
+    return QCX_NO_ERROR;
+}
+
+// Q:302-303: the owner's shard gets the basis state, every other shard +0
+static int sh_collapse(ShardSet *sh, uint64_t idx)
+{
+    const unsigned owner = (unsigned)(idx >> sh->n_local);
+    for (unsigned r = 0; r < sh->W; r++) {
+        SH_DEV(sh, r);
+        QCX_TRY(qcx_shard_collapse(sh->buf[sh->cur][r], sh->n_local, r == owner ? (int64_t)(idx & ((((uint64_t)1) << sh->n_local) - 1)) : -1, sh->st[r]));
+    }
+    return QCX_NO_ERROR;
+}
+
+// Q:272-306 over the shards
 static int sh_measure(ShardSet *sh, double rnd, unsigned long *state_num)
 {
     QCX_TRY(sh_flush(sh, true));                                                // (a compact circuit's result may stay on the companion)
+    const uint64_t dim = (uint64_t)1 << sh->n;
+    uint64_t idx = dim - 1;                                                     // Q:283 fall-through
+    bool found = false;
     if (sh->comp_pending && !sh->dry) {
-        // the scan of Q:283-292 on the compact form, shard by shard (qcx_measure_state_r does the same on one GPU): the amplitudes it
-        // leaves out are +0, the compact order is the index order; r <= 0 stops at index 0 whatever it holds; the register's last
-        // index stays unexamined also when it lies on the orbit
-        ShardSet *c = sh->comp;
+        // the scan on the compact form, shard by shard, as scan_state does it on one GPU: r <= 0 stops at index 0 whatever it
+        // holds; a hit in a padding column means the premise broke -- expand and scan the register
         const ExpandParams &E = sh->comp_E;
-        const uint64_t dim = (uint64_t)1 << sh->n;
-        uint64_t idx = dim - 1;
-        bool have = false, rescan = false;
-        if (rnd <= 0.0) { idx = 0; have = true; }
-        else {
-            uint64_t last_excl = (uint64_t)1 << c->n;
-            if (E.orbit[E.ncols - 1] == (1u << E.M) - 1u) last_excl = ((((uint64_t)1 << (sh->n - E.M)) - 1) << E.cb) | (E.ncols - 1);
-            double cum = 0.0;
-            for (unsigned r = 0; r < c->W && !have && !rescan; r++) {
-                SH_DEV(c, r);
-                int found = 0; uint64_t ci = 0; double c2 = cum;
-                QCX_TRY(qcx_shard_measure_scan(c->buf[c->cur][r], c->n_local, (uint64_t)r << c->n_local, last_excl, cum, rnd, &found, &ci, &c2, c->st[r]));
-                cum = c2;
-                if (found) {
-                    const unsigned col = (unsigned)(ci & ((1u << E.cb) - 1u));
-                    if (col >= E.ncols) rescan = true;                        // a hit in a padding column: the premise broke -- expand and scan the register
-                    else { idx = ((ci >> E.cb) << E.M) | E.orbit[col]; have = true; }
-                }
-            }
-            if (!rescan) have = true;                                           // (nothing found: Q:283 fall-through to the last index)
-        }
-        if (have && !rescan) {
+        uint64_t ci = 0;
+        if (rnd <= 0.0) idx = 0;
+        else QCX_TRY(sh_scan(sh->comp, compact_scan_end(sh->n, E), rnd, &found, &ci));
+        if (!found || compact_real_index(E, ci, &idx)) {
             sh->comp_pending = false;                                           // the collapse below replaces the whole state
             sh->compact_measures++;
-            const unsigned owner = (unsigned)(idx >> sh->n_local);
-            for (unsigned r = 0; r < sh->W; r++) {
-                SH_DEV(sh, r);
-                QCX_TRY(qcx_shard_collapse(sh->buf[sh->cur][r], sh->n_local, r == owner ? (int64_t)(idx & ((((uint64_t)1) << sh->n_local) - 1)) : -1, sh->st[r]));
-            }
+            QCX_TRY(sh_collapse(sh, idx));
             *state_num = (unsigned long)idx;
             return QCX_NO_ERROR;
         }
@@ -988,22 +988,8 @@ static int sh_measure(ShardSet *sh, double rnd, unsigned long *state_num)
     QCX_TRY(sh_identity(sh));
     if (sh->dry) return QCX_UNSUPPORTED;
     QCX_TRY(sh_sync(sh));
-    const uint64_t dim = (uint64_t)1 << sh->n, last_excluded = dim - 1;
-    double cum = 0.0;
-    uint64_t idx = last_excluded;                                               // Q:283 fall-through
-    for (unsigned r = 0; r < sh->W; r++) {
-        SH_DEV(sh, r);
-        int found = 0; uint64_t i = 0; double c2 = cum;
-        QCX_TRY(qcx_shard_measure_scan(sh->buf[sh->cur][r], sh->n_local, (uint64_t)r << sh->n_local, last_excluded, cum, rnd,
-                                       &found, &i, &c2, sh->st[r]));
-        cum = c2;
-        if (found) { idx = i; break; }
-    }
-    const unsigned owner = (unsigned)(idx >> sh->n_local);
-    for (unsigned r = 0; r < sh->W; r++) {
-        SH_DEV(sh, r);
-        QCX_TRY(qcx_shard_collapse(sh->buf[sh->cur][r], sh->n_local, r == owner ? (int64_t)(idx & ((((uint64_t)1) << sh->n_local) - 1)) : -1, sh->st[r]));
-    }
+    QCX_TRY(sh_scan(sh, dim - 1, rnd, &found, &idx));
+    QCX_TRY(sh_collapse(sh, idx));
     *state_num = (unsigned long)idx;
     return QCX_NO_ERROR;
 }

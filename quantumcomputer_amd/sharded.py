@@ -794,30 +794,36 @@ class ShardedRegister:
             if idx is not None:
                 self._compact = None
                 self.compact_measures += 1
-                owner = idx >> self.n_local
-                self.engine.collapse(self.shard, self.n_local, idx & ((1 << self.n_local) - 1) if owner == self.rank else -1)
-                return idx
+                return self._collapse(idx)
             self._expand_compact()               # (a hit in a padding column: the premise broke -- scan the expanded register)
         self._identity()
-        last_excluded = self.num_states - 1
+        idx = self._chained_scan(self.shard, self.n_local, self.num_states - 1, float(r))
+        return self._collapse(self.num_states - 1 if idx is None else idx)        # (None: Q:283 fall-through)
+
+    def _chained_scan(self, t, n_local, last_excl, r):
+        """Q:283-292 over every rank's tensor t in index order, the running sum broadcast from rank to rank: the first global
+        index whose sum reaches r, or None"""
         msg = torch.zeros(3, dtype=torch.float64, device=self.device)
-        cum, idx = 0.0, last_excluded
+        cum = 0.0
         for rk in range(self.world):
             if self.rank == rk:
-                f, i, cum_out = self.engine.measure_scan(self.shard, self.n_local, rk << self.n_local, last_excluded, cum, float(r))
+                f, i, cum_out = self.engine.measure_scan(t, n_local, rk << n_local, last_excl, cum, r)
                 msg[0], msg[1], msg[2] = float(f), float(i), cum_out        # indices < 2^53: exact in a double
             dist.broadcast(msg, src=rk if self.group is None else dist.get_global_rank(self.group, rk), group=self.group)
             m = msg.tolist()
             cum = m[2]
             if m[0] != 0.0:
-                idx = int(m[1])
-                break
+                return int(m[1])
+        return None
+
+    def _collapse(self, idx):
         owner = idx >> self.n_local
         self.engine.collapse(self.shard, self.n_local, idx & ((1 << self.n_local) - 1) if owner == self.rank else -1)
         return idx
 
     def _measure_compact(self, r):
-        """Q:283-292 on the companion register; the real index, or None when the compact premise does not hold"""
+        """Q:283-292 on the companion register; the real index, or None when the compact premise does not hold.  The scan end
+        and the index decode are the C hosts' compact_scan_end and compact_real_index (qcx_fuse.inc.h)"""
         comp = self._comp
         cb, orbit = self._compact
         M, n = self.M_size, self.num_qubits
@@ -826,18 +832,7 @@ class ShardedRegister:
         last_excl = 1 << comp.num_qubits         # compact elements whose real index is below 2^n - 1
         if orbit[-1] == (1 << M) - 1:
             last_excl = (((1 << (n - M)) - 1) << cb) | (len(orbit) - 1)
-        msg = torch.zeros(3, dtype=torch.float64, device=self.device)
-        cum, cidx = 0.0, None
-        for rk in range(self.world):
-            if self.rank == rk:
-                f, i, cum_out = self.engine.measure_scan(comp.shard, comp.n_local, rk << comp.n_local, last_excl, cum, r)
-                msg[0], msg[1], msg[2] = float(f), float(i), cum_out
-            dist.broadcast(msg, src=rk if self.group is None else dist.get_global_rank(self.group, rk), group=self.group)
-            m = msg.tolist()
-            cum = m[2]
-            if m[0] != 0.0:
-                cidx = int(m[1])
-                break
+        cidx = self._chained_scan(comp.shard, comp.n_local, last_excl, r)
         if cidx is None:
             return self.num_states - 1           # Q:283 fall-through
         col = cidx & ((1 << cb) - 1)
