@@ -15,7 +15,9 @@
  * ascending x~ and how many shots the continued-fraction step turns into a period.  -P (with a forced trial integer) runs reset and
  * the circuit once and takes the EXACT distribution of x~ from one marginal of the L register (qcx_marginal_probabilities): it
  * prints P(x~) of the most probable x~ and the exact probabilities that one attempt yields a period and non-trivial factors (with
- * -H, next to the sampled histogram of the same state).  Exit code = the reference's ErrorCode (Q:164-170, Q:1340-1347).
+ * -H, next to the sampled histogram of the same state).  -p value (only with -P) first post-selects the M register on `value`
+ * (qcx_postselect_qubits: the state collapses onto it), prints P(M = value) and then gives the same -P report for the conditional
+ * state; a value the state never holds reports the zero-probability error and exits non-zero.  Exit code = the reference's ErrorCode (Q:164-170, Q:1340-1347).
  *
  * The quantum part (reset, circuit, measurement) runs on the GPU through include/qcx.h; everything
  * here is host-side control flow written from scratch after the behaviour of find_period
@@ -44,6 +46,8 @@ typedef struct {
     const char *gpu_list;       /* -d "0,0,1,1": HIP device of each shard (default: spread over the visible GPUs) */
     unsigned long shots;        /* -H shots: a histogram of that many samples of one circuit's state (needs -a / -f) */
     bool exact;                 /* -P: the exact x~ distribution of one circuit's state (needs -a / -f) */
+    bool postselect;            /* -p value (with -P): the M register is post-selected on `value` before the distribution is taken */
+    unsigned long post_value;
 } Options;
 
 typedef struct {
@@ -52,7 +56,7 @@ typedef struct {
 } Stats;
 
 static const char *USAGE =
-    "Usage: qcx_shor -C num -L L_reg_size -M M_reg_size [-a trial_int | -f trial_int] [-v] [-V] [-s seed] [-Q] [-j] [-F | -G | -T] [-g gpus [-d dev,dev,...]] [-o state_file] [-O state_file] [-H shots] [-P]\n";
+    "Usage: qcx_shor -C num -L L_reg_size -M M_reg_size [-a trial_int | -f trial_int] [-v] [-V] [-s seed] [-Q] [-j] [-F | -G | -T] [-g gpus [-d dev,dev,...]] [-o state_file] [-O state_file] [-H shots] [-P [-p M_value]]\n";
 
 static double now_seconds(void)
 {
@@ -66,7 +70,7 @@ static int parse_args(int argc, char **argv, Options *o)
     bool haveC = false, haveL = false, haveM = false;
     int ch;
     memset(o, 0, sizeof *o);
-    while ((ch = getopt(argc, argv, "C:L:M:a:f:s:o:O:g:d:H:PvVQjFGT")) != -1) {
+    while ((ch = getopt(argc, argv, "C:L:M:a:f:s:o:O:g:d:H:p:PvVQjFGT")) != -1) {
         switch (ch) {
         case 'C': o->C = (unsigned)atoi(optarg); haveC = true; break;
         case 'L': o->L = atoi(optarg); haveL = true; break;
@@ -85,6 +89,13 @@ static int parse_args(int argc, char **argv, Options *o)
         case 'o': o->dump_final = optarg; break;
         case 'O': o->dump_circuit = optarg; break;
         case 'P': o->exact = true; break;
+        case 'p': {
+            char *end = NULL;
+            o->post_value = strtoul(optarg, &end, 10);
+            if (!end || *end || end == optarg) { fprintf(stderr, "Error: -p needs a value of the M register.\n"); fputs(USAGE, stdout); return QCX_BAD_ARGUMENTS; }
+            o->postselect = true;
+            break;
+        }
         case 'H': {
             char *end = NULL;
             o->shots = strtoul(optarg, &end, 10);
@@ -110,6 +121,11 @@ static int parse_args(int argc, char **argv, Options *o)
     }
     if (o->exact && o->gpus > 1) {
         fprintf(stderr, "Error: -P is not available on a sharded register (-g).\n");
+        fputs(USAGE, stdout);
+        return QCX_BAD_ARGUMENTS;
+    }
+    if (o->postselect && !o->exact) {
+        fprintf(stderr, "Error: -p post-selects the state that -P reads and needs -P.\n");
         fputs(USAGE, stdout);
         return QCX_BAD_ARGUMENTS;
     }
@@ -342,10 +358,16 @@ int main(int argc, char **argv)
         return QCX_INSUFFICIENT_MEMORY;
     }
     Exact ex;
+    double post_p = 0.0;
     memset(&ex, 0, sizeof ex);
     const double t0 = now_seconds();
     if (o.shots || o.exact) {
         s = one_circuit(&o, reg, &st);
+        if (s == QCX_NO_ERROR && o.postselect) {     /* -p: collapse onto M = value; -H and -P then read the conditional state */
+            s = qcx_postselect_qubits(reg, 0, (unsigned)o.M, o.post_value, &post_p);
+            if (s == QCX_NO_ERROR) printf("\n --- P(M = %lu) = %.17g; post-selected on it.\n", o.post_value, post_p);
+            else fprintf(stderr, "Error: cannot post-select M = %lu: %s.\n", o.post_value, qcx_last_error());
+        }
         if (s == QCX_NO_ERROR && o.shots) {
             printf("\n --- Sampling %lu shots of one circuit (a = %u)...\n\n", o.shots, o.forced_a);
             s = sample_histogram(&o, reg, rng, xs, &valid);
@@ -393,6 +415,7 @@ int main(int argc, char **argv)
             }
             printf("}");
         }
+        if (o.postselect && s == QCX_NO_ERROR) printf(", \"postselect_M\": %lu, \"p_postselect\": %.17g", o.post_value, post_p);
         if (o.exact && s == QCX_NO_ERROR) {          /* the exact distribution: the most probable x~ -> P, ascending */
             printf(", \"p_period\": %.17g, \"p_factors\": %.17g, \"top\": {", ex.p_period, ex.p_factors);
             for (unsigned i = 0; i < ex.ntop; i++) printf("%s\"%u\": %.17g", i ? ", " : "", ex.top_x[i], ex.top_p[i]);

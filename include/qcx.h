@@ -175,6 +175,38 @@ int  qcx_marginal_probabilities(qcx_register *reg, unsigned first_qubit, unsigne
 /* the last marginal call on this register: source 0 = the register, 1 = the compact form in place, 2 = a pending basis state
  * (no kernel), 3 = the compact form expanded first; state_reads = the passes that read amplitudes (0 for a basis state) */
 int  qcx_marginal_last_stats(qcx_register *reg, unsigned *source, unsigned long *state_reads);
+/* Measure the qubits [first_qubit, first_qubit + num_qubits), keep the others, and collapse the state (no reference counterpart:
+ * Q:272-306 measures the whole register).  Two passes over the state: the marginal above, then one collapse pass (DESIGN s4.5e;
+ * tests/collapse_ref.py restates all of it in numpy).
+ *   P[v], v < 2^num_qubits, is exactly what qcx_marginal_probabilities(reg, first_qubit, num_qubits, P) returns on this state.
+ *   The outcome is the scan of Q:283-292 on P: cum = 0; for v = 0 .. 2^num_qubits - 2 in order cum = fl(cum + P[v]), the first
+ *   v with cum >= r wins, none: 2^num_qubits - 1.  So r <= 0 gives 0, NaN and an r above the total give the last value;
+ *   num_qubits = 0 has the single outcome 0.  qcx_measure_qubits takes r from one qcx_rng_uniform(rng) draw;
+ *   qcx_postselect_qubits takes the outcome from the caller (outcome >= 2^num_qubits: QCX_BAD_ARGUMENTS).
+ *   *probability (may be NULL) receives P[outcome], bit for bit, whether or not the collapse then happens.
+ *   Collapse: with s = fl(1 / fl(sqrt(P[outcome]))) (binary64, on the host) every amplitude whose bits [first_qubit,
+ *   first_qubit + num_qubits) equal the outcome becomes (fl(re * s), fl(im * s)) -- two separately rounded products, no FMA,
+ *   IEEE signs: a -0 stays -0 -- and every other amplitude (+0, +0); those are written without being read.  If P[outcome] is
+ *   not a finite number > 0 (or s is not finite) nothing is written, the state and its lazy forms stay as they were, and the call
+ *   returns QCX_BAD_ARGUMENTS with a qcx_last_error() that names the outcome and its probability; *outcome and *probability are
+ *   still set.
+ * Queued gates are flushed first.  A pending basis state with no gate queued is answered on the host (P = 1 at its range value,
+ * s = 1: it stays pending, no kernel; any other post-selected value is the P = 0 error).  A circuit's compact result is read by
+ * the marginal as described there, then expanded into the register and collapsed there.  A register flagged non-finite keeps its
+ * flag.  Afterwards the state is an ordinary one in the register's buffer, and every following call behaves as if it had been
+ * written with qcx_state_write (it may hold -0: the next gate canonicalises it as it does caller data).
+ * first_qubit + num_qubits > n: QCX_BAD_QUBIT; num_qubits > 30: QCX_UNSUPPORTED; NULL reg, outcome (measure forms) or rng:
+ * QCX_BAD_ARGUMENTS; a sharded register: QCX_UNSUPPORTED, nothing touched, no draw made. */
+int  qcx_measure_qubits_r(qcx_register *reg, unsigned first_qubit, unsigned num_qubits, double r,
+                          unsigned long *outcome, double *probability);
+int  qcx_measure_qubits(qcx_register *reg, qcx_rng *rng, unsigned first_qubit, unsigned num_qubits,
+                        unsigned long *outcome, double *probability);
+int  qcx_postselect_qubits(qcx_register *reg, unsigned first_qubit, unsigned num_qubits, unsigned long outcome,
+                           double *probability);
+/* the last measure_qubits / postselect_qubits call on this register: source 0 = the register, 2 = a pending basis state (no
+ * kernel), 3 = a compact result expanded first; state_reads = the passes that read amplitudes for the probabilities (the
+ * marginal's count); state_writes = collapse passes launched (0 or 1) */
+int  qcx_collapse_last_stats(qcx_register *reg, unsigned *source, unsigned long *state_reads, unsigned long *state_writes);
 
 /* ---- state access (replaces gsl_vector_complex_get/set uses, T:7-37) ------- */
 int  qcx_state_read(qcx_register *reg, unsigned long first, unsigned long count, double *out_re_im);

@@ -65,6 +65,10 @@ SIGNATURES = {
     "qcx_sample_last_stats": (_i, [_p, C.POINTER(_ul), C.POINTER(_ul)]),
     "qcx_marginal_probabilities": (_i, [_p, _u, _u, _p]),
     "qcx_marginal_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
+    "qcx_measure_qubits_r": (_i, [_p, _u, _u, _d, C.POINTER(_ul), C.POINTER(_d)]),
+    "qcx_measure_qubits": (_i, [_p, _p, _u, _u, C.POINTER(_ul), C.POINTER(_d)]),
+    "qcx_postselect_qubits": (_i, [_p, _u, _u, _ul, C.POINTER(_d)]),
+    "qcx_collapse_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul), C.POINTER(_ul)]),
     "qcx_marginal_plan": (_i, [_u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_marginal_plan_compact": (_i, [_u, _u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_state_read": (_i, [_p, _ul, _ul, _p]),
@@ -123,6 +127,7 @@ _EXTRA = {
     "qcx_compact_measure_stats": (_i, [_p, C.POINTER(_ul)]),
     "qcx_expanding_store_stats": (_i, [_p, C.POINTER(_ul)]),
     "qcx_plan_cache_stats": (_i, [_p, C.POINTER(_ul)]),
+    "qcx_collapse_pass": (_i, [_p, _u, _u, _ul, _d]),
     "qcx_expand_store_plan": (_i, [_u, _p, _p, _u, _u, _p, _p, _p, C.POINTER(_i)]),
 }
 

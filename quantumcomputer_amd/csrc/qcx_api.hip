@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <string>
@@ -160,6 +161,9 @@ struct Tune {
     long meas_host_out = 1;    // the scan's result is written straight into pinned host memory (no copy back on the stream)
     long meas_fast = 1;        // K4c: the scan's events by k_meas_fast (list of candidate records, 8 waves) with k_meas_walk as the fallback; 0: the walk alone
     long meas_spin_limit = 4000000;   // K4c: polls a look-back may spend on one window before it gives up (the block is then scanned exactly)
+    long collapse_grid_cap = 65536;   // K11 (k_collapse_range): workgroups, each walks 16-KiB steps
+    long collapse_upt = 4;     // K11: amplitudes per lane and step (4 or 8)
+    long collapse_perm = 1;    // K11: ranges starting at qubit 3 .. 5 take the wave-uniform index map (0: the plain map, divergent there)
 };
 static Tune g_tune;
 static std::mutex g_tune_mutex;
@@ -169,7 +173,7 @@ static Tune tune_now() { std::lock_guard<std::mutex> lock(g_tune_mutex); return 
 extern "C" int qcx_tune_set(const char *key, long value)
 {
 #define K(name) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); g_tune.name = value; return QCX_NO_ERROR; }
-    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos)
+    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt)
 #undef K
     return QCX_BAD_ARGUMENTS;
 }
@@ -177,7 +181,7 @@ extern "C" int qcx_tune_set(const char *key, long value)
 extern "C" long qcx_tune_get(const char *key)
 {
 #define K(name) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); return g_tune.name; }
-    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos)
+    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt)
 #undef K
     return -1;
 }
@@ -1083,6 +1087,8 @@ struct qcx_register {
     size_t     marg_cap;        // doubles marg_buf holds
     unsigned   marg_source;     // the last marginal call: 0 register, 1 compact in place, 2 basis (no kernel), 3 compact expanded first
     unsigned long marg_reads;   // ... and the passes of it that read amplitudes
+    unsigned   coll_source;     // the last measure_qubits / postselect call: 0 register, 2 basis (no kernel), 3 compact expanded first
+    unsigned long coll_reads, coll_writes;   // ... the marginal's reads behind its probabilities, and collapse passes launched (0 or 1)
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
 };
 
@@ -2077,6 +2083,108 @@ extern "C" int qcx_marginal_last_stats(qcx_register *r, unsigned *source, unsign
     if (!r) return QCX_BAD_ARGUMENTS;
     if (source) *source = r->marg_source;
     if (state_reads) *state_reads = r->marg_reads;
+    return QCX_NO_ERROR;
+}
+
+// K11: measure or post-select the qubits [first, first + num) and collapse the state (include/qcx.h, DESIGN s4.5e).  Two passes:
+// the marginal above gives P (its code path, its summation order), the host picks the outcome by the scan of Q:283-292 on P, then
+// k_collapse_range rewrites the state in the register's current buffer.
+static int launch_collapse(qcx_register *r, unsigned first, unsigned num, uint64_t outcome, double s)
+{
+    const Tune tn = tune_now();
+    const bool perm = tn.collapse_perm && first >= 3 && first < 6 && num >= 1 && r->n >= num + 6;
+    const unsigned U = tn.collapse_upt == 8 ? 8u : 4u;
+    const unsigned grid = grid_for(r->dim, 256 * U, tn.collapse_grid_cap, 256);
+#define QCX_COLLAPSE(PERM, UPT) hipLaunchKernelGGL((k_collapse_range<PERM, UPT>), dim3(grid), dim3(256), 0, r->stream, r->amp, r->dim, first, num, outcome, s)
+    if (perm) { if (U == 8) QCX_COLLAPSE(true, 8); else QCX_COLLAPSE(true, 4); }
+    else { if (U == 8) QCX_COLLAPSE(false, 8); else QCX_COLLAPSE(false, 4); }
+#undef QCX_COLLAPSE
+    HIP_TRY(hipGetLastError());
+    return QCX_NO_ERROR;
+}
+
+// rnd is used when `given` is null (the measure forms), else *given is the caller's outcome (post-selection)
+static int collapse_range(qcx_register *r, unsigned first, unsigned num, double rnd, const unsigned long *given,
+                          unsigned long *outcome_out, double *prob_out)
+{
+    if ((uint64_t)first + num > r->n) return QCX_BAD_QUBIT;
+    if (num > 30) return QCX_UNSUPPORTED;
+    const uint64_t nout = (uint64_t)1 << num;
+    if (given && (uint64_t)*given >= nout) {
+        set_error("qcx_postselect_qubits: outcome %lu does not fit %u qubits", *given, num);
+        return QCX_BAD_ARGUMENTS;
+    }
+    r->coll_source = 0; r->coll_reads = 0; r->coll_writes = 0;
+    const bool was_basis = basis_only(r);
+    std::vector<double> P(nout);
+    QCX_TRY(qcx_marginal_probabilities(r, first, num, P.data()));
+    r->coll_reads = r->marg_reads;
+    r->coll_source = was_basis ? 2u : (r->marg_source == 1 || r->marg_source == 3) ? 3u : 0u;
+    uint64_t v = nout - 1;                                                  // Q:283 fall-through
+    if (given) v = *given;
+    else {
+        double cum = 0.0;
+        for (uint64_t k = 0; k + 1 < nout; k++) {
+            cum += P[k];                                                    // Q:286-287 on the range's values
+            if (cum >= rnd) { v = k; break; }
+        }
+    }
+    const double p = P[v];
+    if (outcome_out) *outcome_out = (unsigned long)v;
+    if (prob_out) *prob_out = p;
+    const double s = 1.0 / sqrt(p);
+    if (!(p > 0.0) || !std::isfinite(p) || !std::isfinite(s)) {
+        set_error("qubits [%u, %u): outcome %lu has probability %.17g: the state cannot be collapsed onto it", first, first + num,
+                  (unsigned long)v, p);
+        return QCX_BAD_ARGUMENTS;
+    }
+    if (was_basis) return QCX_NO_ERROR;                                     // P = 1, s = 1: the pending basis state is the result
+    QCX_TRY(expand_pending(r));                                             // (a compact result: collapsed in the register)
+    QCX_TRY(launch_collapse(r, first, num, v, s));
+    r->coll_writes = 1;
+    r->zeros_dirty = 1;                                                     // kept -0 stay -0, products may underflow to -0: as caller data
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_measure_qubits_r(qcx_register *r, unsigned first, unsigned num, double rnd, unsigned long *outcome, double *probability)
+{
+    if (!r || !outcome) return QCX_BAD_ARGUMENTS;
+    if (r->sh) return QCX_UNSUPPORTED;
+    return collapse_range(r, first, num, rnd, nullptr, outcome, probability);
+}
+
+extern "C" int qcx_measure_qubits(qcx_register *r, qcx_rng *rng, unsigned first, unsigned num, unsigned long *outcome, double *probability)
+{
+    if (!r || !rng || !outcome) return QCX_BAD_ARGUMENTS;
+    if (r->sh) return QCX_UNSUPPORTED;
+    if ((uint64_t)first + num > r->n) return QCX_BAD_QUBIT;                 // (no draw for a call that cannot run)
+    if (num > 30) return QCX_UNSUPPORTED;
+    return collapse_range(r, first, num, qcx_rng_uniform(rng), nullptr, outcome, probability);   // Q:281
+}
+
+extern "C" int qcx_postselect_qubits(qcx_register *r, unsigned first, unsigned num, unsigned long outcome, double *probability)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (r->sh) return QCX_UNSUPPORTED;
+    return collapse_range(r, first, num, 0.0, &outcome, nullptr, probability);
+}
+
+// diagnostics (tools/time_measure_qubits.py): the collapse pass alone, on the register's current state
+extern "C" int qcx_collapse_pass(qcx_register *r, unsigned first, unsigned num, unsigned long outcome, double s)
+{
+    if (!r || r->sh) return QCX_BAD_ARGUMENTS;
+    if ((uint64_t)first + num > r->n || num > 30 || (uint64_t)outcome >= ((uint64_t)1 << num)) return QCX_BAD_ARGUMENTS;
+    FLUSH(r);
+    r->zeros_dirty = 1;
+    return launch_collapse(r, first, num, outcome, s);
+}
+
+extern "C" int qcx_collapse_last_stats(qcx_register *r, unsigned *source, unsigned long *state_reads, unsigned long *state_writes)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (source) *source = r->coll_source;
+    if (state_reads) *state_reads = r->coll_reads;
+    if (state_writes) *state_writes = r->coll_writes;
     return QCX_NO_ERROR;
 }
 

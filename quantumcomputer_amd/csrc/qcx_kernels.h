@@ -4065,4 +4065,47 @@ __global__ __launch_bounds__(256) void k_marginal(MargParams P)
     }
 }
 
+// ---------------------------------------------------------------------------
+// K11  collapse of the qubit range [first, first + num) onto `outcome` (qcx_measure_qubits, DESIGN s4.5e).  An amplitude whose
+// range bits equal `outcome` becomes (fl(re * s), fl(im * s)) -- two products, nothing to contract into an FMA --, every other
+// one (+0, +0) and is NEVER READ: its lane only stores.  A wave takes 64 amplitudes per step, lane l the element e = 64 t + l of
+// wave-tile t; a workgroup takes 256 U consecutive elements a step, U per lane (all U loads are issued before the first store).
+//   PERM = false: index = e.  Kept-or-dropped is the same for a whole wave when first >= 6 (and lines are mixed when first < 3:
+//                 a lane's load is predicated, the line comes in whole either way).
+//   PERM = true (3 <= first < 6, n >= num + 6): the 6 - first lane bits that would fall into the range are moved ABOVE it, the
+//                 range takes tile-number bits instead: index = e[0, first) | e[6, 6 + num) << first | e[first, 6) << (first + num)
+//                 | e[6 + num, ..) << (6 + num).  A wave instruction then covers 2^(6 - first) runs of 2^first amplitudes (whole
+//                 128-B lines) that share their range bits: the branch is wave-uniform again.
+// ---------------------------------------------------------------------------
+template <bool PERM, int U>
+__global__ __launch_bounds__(256) void k_collapse_range(amp_t *__restrict__ amp, uint64_t count, unsigned first, unsigned num,
+                                                        uint64_t outcome, double s)
+{
+    const uint64_t rmask = ((uint64_t)1 << num) - 1u;
+    const uint64_t lowmask = ((uint64_t)1 << first) - 1u;
+    for (uint64_t e0 = (uint64_t)blockIdx.x * (256u * U) + threadIdx.x; e0 < count; e0 += (uint64_t)gridDim.x * (256u * U)) {
+        uint64_t idx[U];
+        bool keep[U];
+        amp_t v[U];
+#pragma unroll
+        for (unsigned u = 0; u < (unsigned)U; u++) {
+            const uint64_t e = e0 + u * 256u;
+            uint64_t i = e;
+            if (PERM) {
+                const uint64_t up = e >> 6;                                  // tile number: range bits, then the bits above the moved ones
+                i = (e & lowmask) | ((up & rmask) << first) | (((e & 63u) >> first) << (first + num)) | ((up >> num) << (6u + num));
+            }
+            idx[u] = i;
+            keep[u] = e < count && ((i >> first) & rmask) == outcome;
+            v[u].x = 0.0; v[u].y = 0.0;
+            if (keep[u]) v[u] = __builtin_nontemporal_load(amp + i);
+        }
+#pragma unroll
+        for (unsigned u = 0; u < (unsigned)U; u++) {
+            if (keep[u]) { v[u].x = v[u].x * s; v[u].y = v[u].y * s; }
+            if (e0 + u * 256u < count) __builtin_nontemporal_store(v[u], amp + idx[u]);
+        }
+    }
+}
+
 }  // namespace qcx

@@ -212,6 +212,38 @@ class Register:
         check(lib().qcx_marginal_last_stats(self._h, C.byref(src), C.byref(reads)), "qcx_marginal_last_stats")
         return src.value, reads.value
 
+    def measure_qubits(self, first, num, rng_or_r, strict=True):
+        """Measure the qubits [first, first + num), keep the others and collapse the state (include/qcx.h: qcx_measure_qubits).
+        `rng_or_r` is an Rng (one uniform draw is made) or a float r.  Returns (outcome, probability of that outcome).  An
+        outcome the state cannot be collapsed onto (probability not a finite number > 0) raises QcxError, which then carries
+        .outcome and .probability; strict=False returns (outcome, probability, status) instead and raises nothing for it."""
+        first, num = int(first), int(num)
+        if first < 0 or num < 0:
+            raise ValueError("measure_qubits: first and num must be >= 0")
+        out, p = C.c_ulong(0), C.c_double(float("nan"))
+        if isinstance(rng_or_r, Rng):
+            st = lib().qcx_measure_qubits(self._h, rng_or_r._h, first, num, C.byref(out), C.byref(p))
+        else:
+            st = lib().qcx_measure_qubits_r(self._h, first, num, float(rng_or_r), C.byref(out), C.byref(p))
+        return _collapse_result(st, "measure_qubits", strict, int(out.value), p.value, True)
+
+    def postselect(self, first, num, outcome, strict=True):
+        """Collapse the state onto `outcome` of the qubits [first, first + num) (include/qcx.h: qcx_postselect_qubits).  Returns
+        the probability the outcome had.  Errors as in measure_qubits; strict=False returns (probability, status)."""
+        first, num, outcome = int(first), int(num), int(outcome)
+        if first < 0 or num < 0 or outcome < 0:
+            raise ValueError("postselect: first, num and outcome must be >= 0")
+        p = C.c_double(float("nan"))
+        st = lib().qcx_postselect_qubits(self._h, first, num, outcome, C.byref(p))
+        return _collapse_result(st, "postselect_qubits", strict, outcome, p.value, False)
+
+    def collapse_stats(self):
+        """(source, state reads, state writes) of the last measure_qubits / postselect call on this register: source 0 = the
+        register, 2 = a pending basis state (no kernel), 3 = a compact circuit result expanded first"""
+        src, reads, writes = C.c_uint(0), C.c_ulong(0), C.c_ulong(0)
+        check(lib().qcx_collapse_last_stats(self._h, C.byref(src), C.byref(reads), C.byref(writes)), "qcx_collapse_last_stats")
+        return src.value, reads.value, writes.value
+
     def set_fusion(self, enable=True):
         """Fused LDS-tile passes (bit-identical results).  True/1: every gate call is queued; False/0 (default): only
         the whole-circuit calls (inverse_QFT, quantum_computation) run as fused passes; -1: strictly one kernel launch
@@ -258,6 +290,17 @@ class Register:
         ms = C.c_double(0.0)
         check(lib().qcx_timer_stop(self._h, C.byref(ms)), "qcx_timer_stop")
         return ms.value
+
+
+def _collapse_result(status, where, strict, outcome, probability, with_outcome):
+    if strict and status != _lib.NO_ERROR:
+        err = _lib.QcxError(status, where)
+        err.outcome, err.probability = outcome, probability        # (set by the library before it refused the collapse)
+        raise err
+    res = (outcome, probability) if with_outcome else (probability,)
+    if not strict:
+        return res + (status,)
+    return res if with_outcome else probability
 
 
 # ---- the reference's free functions ----------------------------------------------------------
@@ -320,6 +363,17 @@ def sample_states(reg, rng_or_rs, shots=None):
     check(lib().qcx_sample_states_r(reg._h, rs.ctypes.data_as(C.c_void_p), rs.size, out.ctypes.data_as(C.c_void_p)),
           "sample_states")
     return out
+
+
+def measure_qubits(reg, first, num, rng_or_r, strict=True):
+    """Measure the qubits [first, first + num) of `reg` and collapse it: (outcome, probability) (Register.measure_qubits).
+    `rng_or_r` is an Rng or a float r, as for measure_state."""
+    return reg.measure_qubits(first, num, rng_or_r, strict=strict)
+
+
+def postselect_qubits(reg, first, num, outcome, strict=True):
+    """Collapse `reg` onto `outcome` of the qubits [first, first + num): the probability it had (Register.postselect)."""
+    return reg.postselect(first, num, outcome, strict=strict)
 
 
 def omega_distribution(reg):
