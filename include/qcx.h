@@ -80,7 +80,7 @@ int  qcx_M_size(const qcx_register *reg);
  * check; qcx_sharded_set_relays runs it again through the relays).
  * M_size > 12 works like on one GPU (the modular multiply then runs in place through a per-device staging buffer instead of
  * LDS tiles; M_size <= 26).  Not available on a sharded register: qcx_register_set_stream, qcx_device_pointer (NULL),
- * the event pool. */
+ * the event pool, qcx_one_qubit_gate / qcx_c_one_qubit_gate (QCX_UNSUPPORTED). */
 int  qcx_register_create_sharded(int L_size, int M_size, unsigned nshards, const int *devices, qcx_register **out);
 int  qcx_spread_devices(unsigned nshards, int visible_devices /* <= 0: ask HIP */, int *devices_out /* [nshards] */);
 int  qcx_sharded_selfcheck(qcx_register *reg);             /* the pre-flight exchange check on demand */
@@ -103,6 +103,32 @@ int  qcx_c_phase_shift_gate(unsigned c_qubit_num, unsigned qubit_num, double the
                             qcx_register *reg);                                    /* Q:513-565 */
 int  qcx_c_amodc_gate(unsigned C, unsigned long long atox, unsigned c_qubit_num,
                       qcx_register *reg);                                          /* Q:595-660 */
+/* Any one-qubit gate, plain or controlled by qubit c_qubit_num (no reference counterpart; the construction of hadamard_gate
+ * and c_phase_shift_gate, Q:456-481 / Q:529-562, with four free complex entries, applied as the reference's mat-vec applies
+ * every gate, Q:393-413; tests/one_qubit_ref.py restates it in numpy).
+ *   u = 8 doubles, row-major: u00r, u00i, u01r, u01i, u10r, u10i, u11r, u11i.  For every index pair (i0, i1 = i0 | 2^qubit_num)
+ *   with bit qubit_num of i0 clear, a = amp[i0], b = amp[i1], every fl() one binary64 rounding, no FMA, the triplets in column
+ *   order (Q:396-413):
+ *     lo.re = fl( fl(0.0 + fl(fl(u00r*a.re) - fl(u00i*a.im))) + fl(fl(u01r*b.re) - fl(u01i*b.im)) )
+ *     lo.im = fl( fl(0.0 + fl(fl(u00r*a.im) + fl(u00i*a.re))) + fl(fl(u01r*b.im) + fl(u01i*b.re)) )
+ *     hi.*  = the same with u10 for u00 and u11 for u01;   amp[i0] = lo, amp[i1] = hi.
+ *   All four entries count as stored triplets, entries that are exactly zero included (0 * Inf = NaN, as in the reference).
+ *   The controlled form does this to the pairs whose bit c_qubit_num is set; every other amplitude takes the reference's
+ *   identity row (fl(0.0 + fl(fl(1*x) - fl(0*y))), fl(0.0 + fl(fl(1*y) + fl(0*x)))) -- on a finite state without -0 the value
+ *   unchanged, so those amplitudes are not touched; a register flagged non-finite has them rewritten by a strict pass (K9).
+ *   With H's entries (M_SQRT1_2) the plain gate gives qcx_hadamard_gate's bits, controlled with diag(1, qcx_polar(theta))
+ *   qcx_c_phase_shift_gate's.
+ * The matrix is applied as given and NOT checked for unitarity; each of the 8 components must be finite with absolute value
+ * <= 1, which every unitary satisfies (else QCX_BAD_ARGUMENTS).  The 2^500 bound behind the non-finite flag (qcx_state_write)
+ * covers any sane sequence of such gates; a caller who keeps applying norm-growing matrices is outside the overflow guarantee.
+ * Asynchronous like the other gates.  In every fusion mode the call flushes what is pending (queued gates, a pending basis
+ * state, a circuit's compact result) and launches its own kernel: it never enters the queue, qcx_fusion_stats does not count
+ * it (the statistics move by what qcx_flush alone would have counted there: the queued gates' passes, a front, the deferred
+ * last pass of a circuit's compact chain), and in mode 2 the gate itself stays exact.
+ * NULL reg or u: QCX_BAD_ARGUMENTS; a qubit >= n or c_qubit_num == qubit_num: QCX_BAD_QUBIT; a sharded register:
+ * QCX_UNSUPPORTED, nothing touched. */
+int  qcx_one_qubit_gate(unsigned qubit_num, const double *u, qcx_register *reg);
+int  qcx_c_one_qubit_gate(unsigned c_qubit_num, unsigned qubit_num, const double *u, qcx_register *reg);
 int  qcx_swap_states(qcx_register *reg);                                           /* Q:242-249: no-op */
 /* host-side gate schedules */
 int  qcx_inverse_QFT(qcx_register *reg);                                           /* Q:678-690 */

@@ -524,6 +524,102 @@ extern "C" int qcx_shard_phase(void *amp, unsigned n_local, uint64_t mask, doubl
     return QCX_NO_ERROR;
 }
 
+// ---- K12: any one-qubit gate, plain or controlled --------------------------------------------------------------------------
+template <int PPT, bool NT, bool CTL>
+static void launch_u_pair(amp_t *a, unsigned q, unsigned c, const UMat &U, uint64_t npairs, long want_slog, hipStream_t st)
+{
+    constexpr int BLOCK = 64;                            // the smallest work item wins everywhere (h_plan)
+    const unsigned grid = grid_for(npairs, BLOCK * PPT, 0, BLOCK);
+    unsigned glog, slog;
+    stream_map(grid, (uint64_t)grid * (BLOCK * PPT), npairs, want_slog, &glog, &slog);
+    hipLaunchKernelGGL((k_u_pair<PPT, NT, CTL, BLOCK>), dim3(grid), dim3(BLOCK), 0, st, a, q, c, U, npairs, glog, slog);
+}
+
+template <int Q, int R, bool NT>
+static void launch_u_wave_q(amp_t *a, const UMat &U, uint64_t namps, long want_slog, hipStream_t st)
+{
+    const uint64_t ntiles = namps / (64 * R);
+    const unsigned grid = grid_for(ntiles, 4 /* waves per 256-thread block */, 0, 256);
+    unsigned glog, slog;
+    stream_map(grid, (uint64_t)grid * 4, ntiles, want_slog, &glog, &slog);
+    hipLaunchKernelGGL((k_u_wave<Q, R, NT, 256>), dim3(grid), dim3(256), 0, st, a, U, ntiles, glog, slog);
+}
+
+template <int R, bool NT>
+static bool launch_u_wave(amp_t *a, unsigned q, const UMat &U, uint64_t namps, long want_slog, hipStream_t st)
+{
+    switch (q) {
+    case 0: launch_u_wave_q<0, R, NT>(a, U, namps, want_slog, st); return true;
+    case 1: launch_u_wave_q<1, R, NT>(a, U, namps, want_slog, st); return true;
+    case 2: launch_u_wave_q<2, R, NT>(a, U, namps, want_slog, st); return true;
+    case 3: launch_u_wave_q<3, R, NT>(a, U, namps, want_slog, st); return true;
+    case 4: launch_u_wave_q<4, R, NT>(a, U, namps, want_slog, st); return true;
+    case 5: launch_u_wave_q<5, R, NT>(a, U, namps, want_slog, st); return true;
+    case 6: launch_u_wave_q<6, R, NT>(a, U, namps, want_slog, st); return true;
+    case 7: if constexpr (R >= 4) { launch_u_wave_q<7, R, NT>(a, U, namps, want_slog, st); return true; } return false;
+    case 8: if constexpr (R >= 8) { launch_u_wave_q<8, R, NT>(a, U, namps, want_slog, st); return true; } return false;
+    default: return false;
+    }
+}
+
+// The plain gate moves the bytes the Hadamard moves, so it takes the Hadamard's measured plan (h_plan) and listens to its knobs:
+// h_variant (0 = the plan, 1 = pair form for every q, 2 = wave-tile form for q < 6 + log2 h_wave_r), h_wave_r, h_ppt (1 or 2),
+// h_streams_log2, h_nt (pair form only).  The controlled gate touches the control-set half: the pair form with the control as a second
+// squeezed-out bit (streams as for a phase: ph_streams_log2, ph_nt), or, with the control or the target inside a 128-B line
+// and n_local >= 9, the whole-line form (ph_lines = 0: the pair form for every pair of qubits).
+extern "C" int qcx_shard_one_qubit(void *amp, unsigned n_local, unsigned q, int ctl, const double *u, void *stream)
+{
+    if (!amp || !u || n_local == 0 || n_local > 40) return QCX_BAD_ARGUMENTS;
+    if (q >= n_local || (ctl >= 0 && ((unsigned)ctl >= n_local || (unsigned)ctl == q))) return QCX_BAD_QUBIT;
+    hipStream_t st = (hipStream_t)stream;
+    amp_t *a = (amp_t *)amp;
+    const UMat U = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]};
+    const uint64_t namps = (uint64_t)1 << n_local;
+    const Tune t = tune_now();
+    if (ctl < 0) {
+        const HPlan pl = h_plan(q);
+        const bool autop = t.h_variant == 0;
+        const bool wave = autop ? pl.wave_form != 0 : t.h_variant == 2;
+        const int R = autop ? 2 : (t.h_wave_r >= 8 ? 8 : (t.h_wave_r >= 4 ? 4 : 2));
+        const unsigned tile_bits = (R == 8) ? 9 : (R == 4 ? 8 : 7);
+        const long slog = autop ? pl.slog : t.h_streams_log2;
+        const bool nt = autop || (t.h_nt & 3) == 3;
+        bool launched = false;
+        if (wave && q < tile_bits && n_local >= tile_bits + 2) {      // whole 64*R tiles and the partner inside the tile
+            // (whole-line accesses: always nontemporal, as in the Hadamard's plan)
+            launched = (R == 8) ? launch_u_wave<8, true>(a, q, U, namps, slog, st) : (R == 4) ? launch_u_wave<4, true>(a, q, U, namps, slog, st) : launch_u_wave<2, true>(a, q, U, namps, slog, st);
+        }
+        if (!launched) {
+            const uint64_t npairs = namps >> 1;
+            long ppt = autop ? pl.ppt : t.h_ppt;
+            if (ppt > 1 && npairs < 1024) ppt = 1;
+            const bool ntp = nt && q >= 3;                            // nontemporal only where a wave instruction covers whole 128-B lines
+            if (ppt >= 2) { if (ntp) launch_u_pair<2, true, false>(a, q, 0, U, npairs, slog, st); else launch_u_pair<2, false, false>(a, q, 0, U, npairs, slog, st); }
+            else          { if (ntp) launch_u_pair<1, true, false>(a, q, 0, U, npairs, slog, st); else launch_u_pair<1, false, false>(a, q, 0, U, npairs, slog, st); }
+        }
+    } else {
+        const unsigned c = (unsigned)ctl, lowest = c < q ? c : q;
+        if (lowest < 3 && t.ph_lines && n_local >= 9) {
+            const bool lowq = q < 3;
+            const uint64_t count = (lowq && c < 3) ? namps : namps >> 1;
+            const int store_all = c < 2 ? 1 : 0;
+            const unsigned grid = grid_for(count, 64, 0, 64);
+            unsigned glog, slog;
+            stream_map(grid, (uint64_t)grid * 64, count, 2, &glog, &slog);
+            if (lowq) hipLaunchKernelGGL((k_cu_lines<true>), dim3(grid), dim3(64), 0, st, a, q, c, store_all, U, count, glog, slog);
+            else      hipLaunchKernelGGL((k_cu_lines<false>), dim3(grid), dim3(64), 0, st, a, q, c, store_all, U, count, glog, slog);
+        } else {
+            long slog = t.ph_streams_log2;
+            if (slog < 0) slog = lowest >= 8 ? 1 : 2;
+            if (t.ph_nt != 0 && lowest >= 3) launch_u_pair<1, true, true>(a, q, c, U, namps >> 2, slog, st);
+            else                             launch_u_pair<1, false, true>(a, q, c, U, namps >> 2, slog, st);
+        }
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "one-qubit gate launch: %s", hipGetErrorString(e)); return QCX_HIP_ERROR; }
+    return QCX_NO_ERROR;
+}
+
 static unsigned gcd_u32(unsigned a, unsigned b) { while (b) { unsigned t = a % b; a = b; b = t; } return a; }
 
 // modular inverse of a mod m (gcd(a, m) == 1, m >= 1); 0 when m == 1
@@ -1758,6 +1854,39 @@ extern "C" int qcx_c_phase_shift_gate(unsigned c, unsigned t, double theta, qcx_
     FLUSH(r);
     QCX_TRY(canon_if_dirty(r));
     return qcx_shard_phase(r->amp, r->n, ((uint64_t)1 << c) | ((uint64_t)1 << t), er, ei, r->stream);
+}
+
+// Any one-qubit gate (ctl < 0: plain).  Never queued, in any fusion mode: the fused passes know H and phase only, so the call
+// flushes what is pending and launches its own kernel (K12); the fusion statistics do not count it.
+static int one_qubit_gate(int ctl, unsigned q, const double *u, qcx_register *r, const char *who)
+{
+    if (!r || !u) return QCX_BAD_ARGUMENTS;
+    for (int k = 0; k < 8; k++)
+        if (!(fabs(u[k]) <= 1.0)) { set_error("%s: matrix component %d is %g (each must be finite with |.| <= 1)", who, k, u[k]); return QCX_BAD_ARGUMENTS; }
+    if (q >= r->n || (ctl >= 0 && ((unsigned)ctl >= r->n || (unsigned)ctl == q))) return QCX_BAD_QUBIT;
+    if (r->sh) { set_error("%s: not available on a sharded register", who); return QCX_UNSUPPORTED; }
+    FLUSH(r);                                         // queued gates, a pending basis state, a compact circuit result
+    if (r->nonfinite) {                               // strict pass: every amplitude rewritten with the mat-vec's own products
+        r->zeros_dirty = 0;
+        if (ctl < 0) return qcx_shard_one_qubit(r->amp, r->n, q, -1, u, r->stream);      // (the plain kernels already are strict)
+        const UMat U = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]};
+        hipLaunchKernelGGL(k_strict_cu, dim3(grid_for(r->dim >> 1, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, q, (unsigned)ctl, U, 1.0, 0.0);
+        HIP_TRY(hipGetLastError());
+        return QCX_NO_ERROR;
+    }
+    QCX_TRY(canon_if_dirty(r));
+    return qcx_shard_one_qubit(r->amp, r->n, q, ctl, u, r->stream);
+}
+
+extern "C" int qcx_one_qubit_gate(unsigned q, const double *u, qcx_register *r)
+{
+    return one_qubit_gate(-1, q, u, r, "one_qubit_gate");
+}
+
+extern "C" int qcx_c_one_qubit_gate(unsigned c, unsigned q, const double *u, qcx_register *r)
+{
+    if (r && c >= r->n) return QCX_BAD_QUBIT;         // (before the cast: a control >= 2^31 is a bad qubit, not "no control")
+    return one_qubit_gate((int)c, q, u, r, "c_one_qubit_gate");
 }
 
 extern "C" int qcx_c_amodc_gate(unsigned C, unsigned long long atox, unsigned c, qcx_register *r)

@@ -4108,4 +4108,171 @@ __global__ __launch_bounds__(256) void k_collapse_range(amp_t *__restrict__ amp,
     }
 }
 
+// ---------------------------------------------------------------------------
+// K12  any one-qubit gate, plain or controlled (qcx_one_qubit_gate / qcx_c_one_qubit_gate, DESIGN s4.5f): the 2x2 matrix
+// u = (u00 u01; u10 u11) on the pairs (i0, i1 = i0 | 2^q), as the reference's mat-vec would apply it from four stored
+// triplets per pair taken in column order (Q:396-413; the construction of Q:456-481 / Q:529-562 with free entries):
+//     lo = (0 + u00 * a) + u01 * b,   hi = (0 + u10 * a) + u11 * b,    complex products spelled out as Q:409 / Q:412,
+// every product and sum rounded on its own (no FMA), all four entries multiplied out even where they are zero.  The "0 +"
+// is the accumulator's start: it turns a -0 first product into +0 and nothing else, and IEEE rules do not let a compiler
+// drop it.  The eight components are kernel arguments (SGPRs); no LDS, no table, one arithmetic path for every matrix.
+// The kernels are k_h_pair / k_h_wave / k_phase / k_phase_lines with this butterfly in place of theirs.  A result is never
+// -0 (the second addend meets a first sum that is not -0), so the invariant of K0c holds behind them.
+// ---------------------------------------------------------------------------
+struct UMat { double r00, i00, r01, i01, r10, i10, r11, i11; };
+
+// one row: (0 + m0 * a) + m1 * b; a = the pair's amplitude with the target bit clear, b = with it set
+__device__ __forceinline__ amp_t u_row(double m0r, double m0i, double m1r, double m1i, amp_t a, amp_t b)
+{
+    amp_t o;
+    o.x = (0.0 + ((m0r * a.x) - (m0i * a.y))) + ((m1r * b.x) - (m1i * b.y));      // Q:409, columns i0 then i1
+    o.y = (0.0 + ((m0r * a.y) + (m0i * a.x))) + ((m1r * b.y) + (m1i * b.x));      // Q:412
+    return o;
+}
+
+__device__ __forceinline__ void u_butterfly(const UMat &U, amp_t &a, amp_t &b)
+{
+    const amp_t lo = u_row(U.r00, U.i00, U.r01, U.i01, a, b);
+    const amp_t hi = u_row(U.r10, U.i10, U.r11, U.i11, a, b);
+    a = lo; b = hi;
+}
+
+// K12a  pair form, any target qubit (k_h_pair's shape).  CTL: only the pairs whose control bit c is set are read and
+// written -- c is a second squeezed-out index bit (as in k_phase<NB>), npairs = 2^(n-2).  PPT pairs per lane are loaded
+// before any is stored; stream-interleaved tile order as in k_phase.
+template <int PPT, bool NT, bool CTL, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_u_pair(amp_t *__restrict__ amp, unsigned q, unsigned c, UMat U, uint64_t npairs,
+                                                    unsigned glog, unsigned slog)
+{
+    const uint64_t bit = (uint64_t)1 << q, cbit = (uint64_t)1 << c;
+    const unsigned b0 = (CTL && c < q) ? c : q, b1 = (c < q) ? q : c;      // the squeezed-out bits, ascending
+    const uint64_t step = (uint64_t)gridDim.x * (BLOCK * PPT);
+    uint64_t tile0 = blockIdx.x;
+    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    for (uint64_t base = tile0 * (BLOCK * PPT); base < npairs; base += step) {
+        amp_t a[PPT], b[PPT];
+        uint64_t i0[PPT];
+#pragma unroll
+        for (int k = 0; k < PPT; k++) {
+            const uint64_t p = base + (uint64_t)k * BLOCK + threadIdx.x;
+            uint64_t i = insert_zero(p, b0);
+            if (CTL) i = insert_zero(i, b1) | cbit;
+            i0[k] = i;
+            if (p < npairs) { a[k] = ld<NT>(amp + i); b[k] = ld<NT>(amp + i + bit); }
+        }
+#pragma unroll
+        for (int k = 0; k < PPT; k++) {
+            const uint64_t p = base + (uint64_t)k * BLOCK + threadIdx.x;
+            if (p < npairs) {
+                u_butterfly(U, a[k], b[k]);
+                st<NT>(amp + i0[k], a[k]);
+                st<NT>(amp + i0[k] + bit, b[k]);
+            }
+        }
+    }
+}
+
+// K12b  wave-tile form for low targets (k_h_wave's shape: 64 * R consecutive amplitudes as R registers x 64 lanes).
+// Q < 6: the partner arrives by xor-shuffle and every lane computes its OWN row -- the lower lane (0 + u00 * own) + u01 * other,
+// the upper lane (0 + u10 * other) + u11 * own: the column order of the definition, the partner's product first up there.
+// Q >= 6: the partner is another register of the same lane.
+template <int Q, int R>
+__device__ __forceinline__ void u_wave_tile(const UMat &U, amp_t (&r)[R], unsigned lane)
+{
+    if constexpr (Q < 6) {
+        const bool upper = (lane >> Q) & 1u;
+        const double m0r = upper ? U.r10 : U.r00, m0i = upper ? U.i10 : U.i00;
+        const double m1r = upper ? U.r11 : U.r01, m1i = upper ? U.i11 : U.i01;
+#pragma unroll
+        for (int k = 0; k < R; k++) {
+            const amp_t o = shfl_xor_amp(r[k], 1 << Q);
+            r[k] = u_row(m0r, m0i, m1r, m1i, upper ? o : r[k], upper ? r[k] : o);
+        }
+    } else {
+        constexpr int D = 1 << (Q - 6);
+#pragma unroll
+        for (int k = 0; k < R; k++)
+            if ((k & D) == 0) u_butterfly(U, r[k], r[k + D]);
+    }
+}
+
+template <int Q, int R, bool NT, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_u_wave(amp_t *__restrict__ amp, UMat U, uint64_t ntiles, unsigned glog, unsigned slog)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    uint64_t blk = blockIdx.x;
+    if (slog) blk = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    const uint64_t wave = (blk * BLOCK + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * BLOCK) >> 6;
+    for (uint64_t t = wave; t < ntiles; t += nwaves) {
+        amp_t *base = amp + t * (64 * R) + lane;
+        amp_t r[R];
+#pragma unroll
+        for (int k = 0; k < R; k++) r[k] = ld<NT>(base + k * 64);
+        u_wave_tile<Q, R>(U, r, lane);
+#pragma unroll
+        for (int k = 0; k < R; k++) st<NT>(base + k * 64, r[k]);
+    }
+}
+
+// K12c  controlled form with the control or the target below bit 3, i.e. inside a 128-B line (k_phase_lines' reason: one
+// touched amplitude per lane would fetch 16 B out of every 32 or 64).  A lane owns one amplitude of every touched line:
+//   LOWQ (q < 3, any c):  the partner sits in the same line and arrives by xor-shuffle, every lane computes its own row as in
+//         K12b.  A control >= 3 is squeezed out of the numbering (count = 2^(n-1), only control-set lines are read, every lane
+//         hits); a control < 3 leaves every line touched (count = 2^n) and the lanes with their control bit clear keep their value.
+//   !LOWQ (c < 3 <= q):   a lane owns the pair (i0, i0 | 2^q), count = 2^(n-1); both lines are loaded whole, the lanes with bit c
+//         set rotate.
+// store_all: control at 16- or 32-B granularity -- whole lines are stored back, the untouched amplitudes with the bits they had
+// (k_phase_lines measured masked 32-B stores at 4.0 ms against 2.6); a control at bit 2 stores its 64-B halves only.
+// count is a multiple of 64 (the host asks for n >= 9), so a wave never diverges at the loop's end and the shuffle sees every lane.
+template <bool LOWQ>
+__global__ __launch_bounds__(64) void k_cu_lines(amp_t *__restrict__ amp, unsigned q, unsigned c, int store_all, UMat U,
+                                                 uint64_t count, unsigned glog, unsigned slog)
+{
+    const uint64_t step = (uint64_t)gridDim.x * 64u;
+    uint64_t tile0 = blockIdx.x;
+    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    for (uint64_t p = tile0 * 64u + threadIdx.x; p < count; p += step) {
+        if (LOWQ) {
+            uint64_t i = p;
+            if (c >= 3) i = insert_zero(p, c) | ((uint64_t)1 << c);      // (bits below c keep their place: lane ^ 2^q holds the partner)
+            const amp_t v = __builtin_nontemporal_load(amp + i);
+            const amp_t o = shfl_xor_amp(v, 1 << q);
+            const bool upper = (i >> q) & 1u, hit = (i >> c) & 1u;
+            if (hit) {
+                const amp_t w = u_row(upper ? U.r10 : U.r00, upper ? U.i10 : U.i00, upper ? U.r11 : U.r01, upper ? U.i11 : U.i01,
+                                      upper ? o : v, upper ? v : o);
+                __builtin_nontemporal_store(w, amp + i);
+            } else if (store_all) __builtin_nontemporal_store(v, amp + i);
+        } else {
+            const uint64_t i0 = insert_zero(p, q), i1 = i0 | ((uint64_t)1 << q);
+            amp_t a = __builtin_nontemporal_load(amp + i0), b = __builtin_nontemporal_load(amp + i1);
+            const bool hit = (i0 >> c) & 1u;
+            if (hit) u_butterfly(U, a, b);
+            if (hit || store_all) { __builtin_nontemporal_store(a, amp + i0); __builtin_nontemporal_store(b, amp + i1); }
+        }
+    }
+}
+
+// K12s  the controlled gate as a STRICT pass (K9's reason: a register that holds non-finite amplitudes): the same rows on the
+// control-set pairs, and every control-clear amplitude rewritten through the reference's identity row 0 + (1 * x - 0 * y),
+// 0 + (1 * y + 0 * x); `one` and `z` are kernel arguments so that no product is folded.  (The plain gate needs no strict
+// twin: K12a / K12b already multiply every stored triplet out and rewrite every amplitude.)
+__global__ __launch_bounds__(256) void k_strict_cu(amp_t *__restrict__ amp, unsigned n, unsigned q, unsigned c, UMat U, double one, double z)
+{
+    const uint64_t half = (uint64_t)1 << (n - 1);
+    for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < half; p += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i0 = insert_zero(p, q), i1 = i0 | ((uint64_t)1 << q);
+        amp_t a = amp[i0], b = amp[i1];
+        if ((i0 >> c) & 1u) u_butterfly(U, a, b);
+        else {
+            amp_t lo, hi;
+            lo.x = 0.0 + ((one * a.x) - (z * a.y));   lo.y = 0.0 + ((one * a.y) + (z * a.x));
+            hi.x = 0.0 + ((one * b.x) - (z * b.y));   hi.y = 0.0 + ((one * b.y) + (z * b.x));
+            a = lo; b = hi;
+        }
+        amp[i0] = a; amp[i1] = b;
+    }
+}
+
 }  // namespace qcx

@@ -320,6 +320,58 @@ def c_amodc_gate(C_, atox, c_qubit_num, reg, matrix=None):
     check(lib().qcx_c_amodc_gate(C_, int(atox), c_qubit_num, reg._h), "c_amodc_gate")
 
 
+def _matrix8(U):
+    """U as the 8 doubles qcx_one_qubit_gate takes: row-major (re, im)"""
+    m = np.asarray(U, dtype=complex)
+    if m.shape != (2, 2):
+        raise ValueError(f"a one-qubit gate is a 2x2 matrix, not shape {m.shape}")
+    return np.ascontiguousarray(m.reshape(4)).view(np.float64)
+
+
+def one_qubit_gate(qubit_num, U, reg):
+    """Apply the 2x2 matrix U (anything numpy.asarray(U, complex) turns into shape (2, 2)) to qubit `qubit_num`, with the
+    reference's mat-vec arithmetic (include/qcx.h: qcx_one_qubit_gate).  U is applied as given, not checked for unitarity."""
+    u = _matrix8(U)
+    check(lib().qcx_one_qubit_gate(int(qubit_num), u.ctypes.data_as(C.c_void_p), reg._h), "one_qubit_gate")
+
+
+def c_one_qubit_gate(c_qubit_num, qubit_num, U, reg):
+    """one_qubit_gate on the amplitudes whose qubit `c_qubit_num` reads 1 (include/qcx.h: qcx_c_one_qubit_gate)"""
+    u = _matrix8(U)
+    check(lib().qcx_c_one_qubit_gate(int(c_qubit_num), int(qubit_num), u.ctypes.data_as(C.c_void_p), reg._h), "c_one_qubit_gate")
+
+
+def phase(theta):
+    """diag(1, e^{i theta}) with the factor c_phase_shift_gate uses (qcx_polar)"""
+    c, s = _lib.polar(theta)
+    return np.array([[1.0, 0.0], [0.0, complex(c, s)]], dtype=complex)
+
+
+def rz(theta):
+    """diag(e^{-i theta/2}, e^{+i theta/2}), both factors from qcx_polar"""
+    cm, sm = _lib.polar(-0.5 * float(theta))
+    cp, sp = _lib.polar(0.5 * float(theta))
+    return np.array([[complex(cm, sm), 0.0], [0.0, complex(cp, sp)]], dtype=complex)
+
+
+def __getattr__(name):
+    """GATES: the exact matrices X, Y, Z, S, T, H.  Built on first use (PEP 562), because T's factor is the library's
+    qcx_polar(pi/4) and importing the package must not load the library."""
+    if name != "GATES":
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+    s = 0.70710678118654752440          # M_SQRT1_2 (qc_shor.c:210-213): hadamard_gate's entry
+    gates = {
+        "X": np.array([[0, 1], [1, 0]], dtype=complex),
+        "Y": np.array([[0, -1j], [1j, 0]], dtype=complex),
+        "Z": np.array([[1, 0], [0, -1]], dtype=complex),
+        "S": np.array([[1, 0], [0, 1j]], dtype=complex),
+        "T": phase(np.pi / 4),
+        "H": np.array([[s, s], [s, -s]], dtype=complex),
+    }
+    globals()["GATES"] = gates
+    return gates
+
+
 def swap_states(reg):
     check(lib().qcx_swap_states(reg._h), "swap_states")
 
