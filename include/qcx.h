@@ -80,7 +80,7 @@ int  qcx_M_size(const qcx_register *reg);
  * check; qcx_sharded_set_relays runs it again through the relays).
  * M_size > 12 works like on one GPU (the modular multiply then runs in place through a per-device staging buffer instead of
  * LDS tiles; M_size <= 26).  Not available on a sharded register: qcx_register_set_stream, qcx_device_pointer (NULL),
- * the event pool, qcx_one_qubit_gate / qcx_c_one_qubit_gate (QCX_UNSUPPORTED). */
+ * the event pool, qcx_one_qubit_gate / qcx_c_one_qubit_gate, qcx_two_qubit_gate / qcx_c_two_qubit_gate (QCX_UNSUPPORTED). */
 int  qcx_register_create_sharded(int L_size, int M_size, unsigned nshards, const int *devices, qcx_register **out);
 int  qcx_spread_devices(unsigned nshards, int visible_devices /* <= 0: ask HIP */, int *devices_out /* [nshards] */);
 int  qcx_sharded_selfcheck(qcx_register *reg);             /* the pre-flight exchange check on demand */
@@ -129,6 +129,33 @@ int  qcx_c_amodc_gate(unsigned C, unsigned long long atox, unsigned c_qubit_num,
  * QCX_UNSUPPORTED, nothing touched. */
 int  qcx_one_qubit_gate(unsigned qubit_num, const double *u, qcx_register *reg);
 int  qcx_c_one_qubit_gate(unsigned c_qubit_num, unsigned qubit_num, const double *u, qcx_register *reg);
+/* Any two-qubit gate, plain or controlled by qubit c_qubit_num (no reference counterpart; a general 4x4 complex matrix applied
+ * as the reference's mat-vec applies every gate, Q:393-413; tests/two_qubit_ref.py restates it in numpy and IS the definition).
+ *   u = 32 doubles, a 4x4 complex matrix, row-major, (re, im) per entry.  The matrix index is k = bit(qubit0) + 2 * bit(qubit1):
+ *   qubit0 is bit 0 of the matrix index (the LSB convention of this library); "A on qubit0, B on qubit1" is kron(B, A).
+ *   The reference accumulates a row's triplets in ascending state index, so with lo = min(qubit0, qubit1), hi = max(...):
+ *   if qubit0 > qubit1 the matrix is first permuted to m = P u P (P = the index swap 1 <-> 2), else m = u.  For every i with
+ *   bits lo and hi clear, x0 = amp[i], x1 = amp[i | 2^lo], x2 = amp[i | 2^hi], x3 = amp[i | 2^lo | 2^hi], and with every fl()
+ *   one binary64 rounding, no FMA, for each row r = 0 .. 3:
+ *     out_r.re = fl(fl(fl(fl(0.0 + P(r,0).re) + P(r,1).re) + P(r,2).re) + P(r,3).re),   out_r.im the same with .im,
+ *     P(r,k).re = fl(fl(m[r][k].re * x_k.re) - fl(m[r][k].im * x_k.im))                                        (Q:409)
+ *     P(r,k).im = fl(fl(m[r][k].re * x_k.im) + fl(m[r][k].im * x_k.re))                                        (Q:412)
+ *   then x_r = out_r.  All 16 entries count as stored triplets, exact zeros included (0 * Inf = NaN, as in the reference); no
+ *   special case for permutation, diagonal or tensor-product matrices.  A result is never -0.
+ *   The controlled form does this to the quads whose bit c_qubit_num is set; every other amplitude takes the reference's
+ *   identity row, exactly as for qcx_c_one_qubit_gate -- on a finite state without -0 the value unchanged, so those amplitudes
+ *   are not touched; a register flagged non-finite has them rewritten by a strict pass.  Two controls: a Toffoli is the
+ *   controlled CNOT matrix, a Fredkin the controlled SWAP.
+ *   On finite states without -0: kron(I, U) gives qcx_one_qubit_gate(qubit0, U)'s bits, kron(U, I) those of qubit1,
+ *   diag(1, 1, 1, e^{i theta}) qcx_c_phase_shift_gate's, and (qubit0, qubit1, V) the bits of (qubit1, qubit0, P V P).
+ * The matrix is applied as given and NOT checked for unitarity; each of the 32 components must be finite with absolute value
+ * <= 1 (else QCX_BAD_ARGUMENTS, the message names the component).  Asynchronous; flushes what is pending in every fusion mode
+ * and launches its own kernel, never enters the queue, is not counted by qcx_fusion_stats, stays exact in mode 2 -- all as
+ * qcx_one_qubit_gate.
+ * NULL reg or u: QCX_BAD_ARGUMENTS; a qubit >= n or two of the qubits equal: QCX_BAD_QUBIT (so also every register too small to
+ * name distinct qubits); a sharded register: QCX_UNSUPPORTED, nothing touched. */
+int  qcx_two_qubit_gate(unsigned qubit0, unsigned qubit1, const double *u, qcx_register *reg);
+int  qcx_c_two_qubit_gate(unsigned c_qubit_num, unsigned qubit0, unsigned qubit1, const double *u, qcx_register *reg);
 int  qcx_swap_states(qcx_register *reg);                                           /* Q:242-249: no-op */
 /* host-side gate schedules */
 int  qcx_inverse_QFT(qcx_register *reg);                                           /* Q:678-690 */

@@ -28,6 +28,10 @@ int  qcx_shard_hadamard(void *amp, unsigned n_local, unsigned q_local, void *str
 /* the 2x2 matrix u (8 doubles, row-major (re, im); qcx.h: qcx_one_qubit_gate) on local bit q_local, on the pairs whose local
  * bit ctl_local is set (ctl_local < 0: on every pair).  u is read before the call returns.  Not used by the sharded hosts. */
 int  qcx_shard_one_qubit(void *amp, unsigned n_local, unsigned q_local, int ctl_local, const double *u, void *stream);
+/* the 4x4 matrix u (32 doubles, row-major (re, im), matrix index = bit(q0) + 2 * bit(q1); qcx.h: qcx_two_qubit_gate) on local
+ * bits q0, q1, on the quads whose local bit ctl_local is set (ctl_local < 0: on every quad).  u is read before the call
+ * returns.  Not used by the sharded hosts. */
+int  qcx_shard_two_qubit(void *amp, unsigned n_local, unsigned q0, unsigned q1, int ctl_local, const double *u, void *stream);
 /* multiply by (cos_t + i sin_t) every amplitude whose local index has all bits of
  * `mask_local` set; mask_local has 0, 1 or 2 bits (global control bits that are 1
  * simply drop out of the mask; a global bit that is 0 means: do not call). */

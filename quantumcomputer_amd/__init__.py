@@ -5,9 +5,9 @@ the ctypes loader and the host-side mirror of the reference's gate interface.
 """
 from ._lib import LIB_PATH, QcxError, front_plan, fusion_plan, idle_devices, lib, marginal_plan, polar, spread_devices, tune  # noqa: F401
 from .register import (Register, Rng, load_state_file, c_amodc_gate, c_one_qubit_gate, c_phase_shift_gate,  # noqa: F401
-                       check_normalisation, display_state, hadamard_gate,
+                       c_two_qubit_gate, check_normalisation, controlled, display_state, hadamard_gate,
                        inverse_QFT, measure_qubits, measure_state, omega_distribution, one_qubit_gate, phase, postselect_qubits,
-                       quantum_computation, read_omega, reset_register, rz, sample_states, swap_states)
+                       quantum_computation, read_omega, reset_register, rz, sample_states, swap_states, two_qubit_gate)
 
 FUSION_TOLERANCE = 2      # qcx_set_fusion(reg, 2): the opt-in tolerance mode (include/qcx.h)
 
@@ -16,10 +16,14 @@ def __getattr__(name):
     if name == "GATES":       # register.GATES: X, Y, Z, S, T, H (built on first use: T's factor comes from the library)
         from . import register
         return register.GATES
+    if name == "GATES2":      # register.GATES2: SWAP, ISWAP, CNOT, CZ
+        from . import register
+        return register.GATES2
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = ["FUSION_TOLERANCE", "Register", "Rng", "reset_register", "hadamard_gate", "c_phase_shift_gate", "c_amodc_gate",
            "one_qubit_gate", "c_one_qubit_gate", "GATES", "rz", "phase",
+           "two_qubit_gate", "c_two_qubit_gate", "GATES2", "controlled",
            "swap_states", "inverse_QFT", "quantum_computation", "measure_state", "measure_qubits", "postselect_qubits", "sample_states", "omega_distribution", "read_omega",
            "display_state", "check_normalisation", "lib", "tune", "polar", "QcxError", "LIB_PATH", "spread_devices", "idle_devices"]

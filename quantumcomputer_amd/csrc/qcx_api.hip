@@ -164,6 +164,10 @@ struct Tune {
     long collapse_grid_cap = 65536;   // K11 (k_collapse_range): workgroups, each walks 16-KiB steps
     long collapse_upt = 4;     // K11: amplitudes per lane and step (4 or 8)
     long collapse_perm = 1;    // K11: ranges starting at qubit 3 .. 5 take the wave-uniform index map (0: the plain map, divergent there)
+    long u2_variant  = 0;      // K13 (two-qubit gate): 0 = the plan (line forms from n = 9 when lo or the control is below bit 3), 1 = quad form for every qubit pair
+    long u2_nt       = 1;      // K13: nontemporal accesses (only where a wave instruction covers whole 128-B lines, as in K12)
+    long u2_streams_log2 = -1; // K13: -1 = plain gate: the Hadamard plan's streams for hi; controlled: the phase gate's rule.  Both are guesses taken
+                               // over from kernels with two address streams, not four; tools/time_two_qubit_gate.py is there to measure them
 };
 static Tune g_tune;
 static std::mutex g_tune_mutex;
@@ -173,7 +177,7 @@ static Tune tune_now() { std::lock_guard<std::mutex> lock(g_tune_mutex); return 
 extern "C" int qcx_tune_set(const char *key, long value)
 {
 #define K(name) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); g_tune.name = value; return QCX_NO_ERROR; }
-    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt)
+    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt) K(u2_variant) K(u2_nt) K(u2_streams_log2)
 #undef K
     return QCX_BAD_ARGUMENTS;
 }
@@ -181,7 +185,7 @@ extern "C" int qcx_tune_set(const char *key, long value)
 extern "C" long qcx_tune_get(const char *key)
 {
 #define K(name) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); return g_tune.name; }
-    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt)
+    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt) K(u2_variant) K(u2_nt) K(u2_streams_log2)
 #undef K
     return -1;
 }
@@ -617,6 +621,82 @@ extern "C" int qcx_shard_one_qubit(void *amp, unsigned n_local, unsigned q, int 
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "one-qubit gate launch: %s", hipGetErrorString(e)); return QCX_HIP_ERROR; }
+    return QCX_NO_ERROR;
+}
+
+// ---- K13: any two-qubit gate, plain or controlled --------------------------------------------------------------------------
+template <bool NT, bool CTL>
+static void launch_u2_quad(amp_t *a, unsigned lo, unsigned hi, unsigned c, const U4Mat &U, uint64_t count, long want_slog, hipStream_t st)
+{
+    constexpr int BLOCK = 64;
+    unsigned s[3] = {lo, hi, c};                           // the squeezed-out bits, ascending (lo < hi already)
+    if (CTL) { if (s[2] < s[1]) std::swap(s[1], s[2]); if (s[1] < s[0]) std::swap(s[0], s[1]); }
+    const unsigned grid = grid_for(count, BLOCK, 0, BLOCK);
+    unsigned glog, slog;
+    stream_map(grid, (uint64_t)grid * BLOCK, count, want_slog, &glog, &slog);
+    hipLaunchKernelGGL((k_u2_quad<NT, CTL, BLOCK>), dim3(grid), dim3(BLOCK), 0, st, a, lo, hi, c, s[0], s[1], s[2], U, count, glog, slog);
+}
+
+// The reference sums a row's triplets in ascending state index: with qubit0 above qubit1 the matrix is taken as P u P (P = the
+// index swap 1 <-> 2), so that the kernels' matrix index is k = bit(lo) + 2 * bit(hi).
+static U4Mat u4_ascending(unsigned q0, unsigned q1, const double *u)
+{
+    static const int swap12[4] = {0, 2, 1, 3};
+    U4Mat U;
+    for (int r = 0; r < 4; r++)
+        for (int k = 0; k < 4; k++) {
+            const int sr = q0 > q1 ? swap12[r] : r, sk = q0 > q1 ? swap12[k] : k;
+            U.m[(4 * r + k) * 2] = u[(4 * sr + sk) * 2]; U.m[(4 * r + k) * 2 + 1] = u[(4 * sr + sk) * 2 + 1];
+        }
+    return U;
+}
+
+// Form selection (DESIGN s4.5g).  Knobs: u2_variant (0 = the plan, 1 = quad form for every qubit pair), u2_nt, u2_streams_log2
+// (-1: the plain gate takes the Hadamard plan's streams for hi, the controlled gate the phase gate's rule -- both taken over
+// from kernels that walk two address streams, as guesses until tools/time_two_qubit_gate.py has measured the four-stream walk).
+extern "C" int qcx_shard_two_qubit(void *amp, unsigned n_local, unsigned q0, unsigned q1, int ctl, const double *u, void *stream)
+{
+    if (!amp || !u || n_local == 0 || n_local > 40) return QCX_BAD_ARGUMENTS;
+    if (q0 >= n_local || q1 >= n_local || q0 == q1) return QCX_BAD_QUBIT;
+    if (ctl >= 0 && ((unsigned)ctl >= n_local || (unsigned)ctl == q0 || (unsigned)ctl == q1)) return QCX_BAD_QUBIT;
+    hipStream_t st = (hipStream_t)stream;
+    amp_t *a = (amp_t *)amp;
+    const U4Mat U = u4_ascending(q0, q1, u);
+    const unsigned lo = q0 < q1 ? q0 : q1, hi = q0 < q1 ? q1 : q0, c = ctl >= 0 ? (unsigned)ctl : 0u;
+    const unsigned lowest = (ctl >= 0 && c < lo) ? c : lo;
+    const uint64_t namps = (uint64_t)1 << n_local;
+    const Tune t = tune_now();
+    long want = t.u2_streams_log2;
+    if (want < 0) want = ctl < 0 ? h_plan(hi).slog : (lowest >= 8 ? 1 : 2);
+    const bool nt = t.u2_nt != 0;
+    if (t.u2_variant == 0 && n_local >= 9 && lowest < 3) {
+        // line forms: where each target sits in the lane numbering once a control >= 3 is squeezed out
+        const bool csq = ctl >= 3;
+        const unsigned plo = lo - ((csq && c < lo) ? 1u : 0u), phi = hi - ((csq && c < hi) ? 1u : 0u);
+        const int ns = (plo < 6 ? 1 : 0) + (phi < 6 ? 1 : 0);
+        unsigned s[2] = {0, 0}, nsq = 0;                       // (csq means lo < 3, so ns >= 1: never more than two bits)
+        if (plo >= 6) s[nsq++] = lo;
+        if (phi >= 6) s[nsq++] = hi;
+        if (csq) s[nsq++] = c;
+        if (nsq == 2 && s[1] < s[0]) std::swap(s[0], s[1]);
+        const uint64_t count = namps >> nsq, cset = csq ? (uint64_t)1 << c : 0;
+        const unsigned clow = (ctl >= 0 && !csq) ? 1u << c : 0u, mlo = 1u << (plo & 31u), mhi = 1u << (phi & 31u);
+        const int store_all = (ctl >= 0 && c < 2) ? 1 : 0;
+        const unsigned grid = grid_for(count, 64, 0, 64);
+        unsigned glog, slog;
+        stream_map(grid, (uint64_t)grid * 64, count, want, &glog, &slog);
+#define QCX_U2_LINES(NS, NT) hipLaunchKernelGGL((k_u2_lines<NS, NT>), dim3(grid), dim3(64), 0, st, a, lo, hi, mlo, mhi, nsq, s[0], s[1], cset, clow, store_all, U, count, glog, slog)
+        if (ns == 2)      { if (nt) QCX_U2_LINES(2, true); else QCX_U2_LINES(2, false); }
+        else if (ns == 1) { if (nt) QCX_U2_LINES(1, true); else QCX_U2_LINES(1, false); }
+        else              { if (nt) QCX_U2_LINES(0, true); else QCX_U2_LINES(0, false); }
+#undef QCX_U2_LINES
+    } else {
+        const bool ntq = nt && lowest >= 3;                    // nontemporal only where a wave instruction covers whole 128-B lines
+        if (ctl < 0) { if (ntq) launch_u2_quad<true, false>(a, lo, hi, 0, U, namps >> 2, want, st); else launch_u2_quad<false, false>(a, lo, hi, 0, U, namps >> 2, want, st); }
+        else         { if (ntq) launch_u2_quad<true, true>(a, lo, hi, c, U, namps >> 3, want, st);  else launch_u2_quad<false, true>(a, lo, hi, c, U, namps >> 3, want, st); }
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "two-qubit gate launch: %s", hipGetErrorString(e)); return QCX_HIP_ERROR; }
     return QCX_NO_ERROR;
 }
 
@@ -1887,6 +1967,41 @@ extern "C" int qcx_c_one_qubit_gate(unsigned c, unsigned q, const double *u, qcx
 {
     if (r && c >= r->n) return QCX_BAD_QUBIT;         // (before the cast: a control >= 2^31 is a bad qubit, not "no control")
     return one_qubit_gate((int)c, q, u, r, "c_one_qubit_gate");
+}
+
+// Any two-qubit gate (ctl < 0: plain).  one_qubit_gate()'s sequence: never queued, in any fusion mode; the call flushes what
+// is pending and launches its own kernel (K13); the fusion statistics do not count it.
+static int two_qubit_gate(int ctl, unsigned q0, unsigned q1, const double *u, qcx_register *r, const char *who)
+{
+    if (!r || !u) return QCX_BAD_ARGUMENTS;
+    for (int k = 0; k < 32; k++)
+        if (!(fabs(u[k]) <= 1.0)) { set_error("%s: matrix component %d is %g (each must be finite with |.| <= 1)", who, k, u[k]); return QCX_BAD_ARGUMENTS; }
+    if (q0 >= r->n || q1 >= r->n || q0 == q1) return QCX_BAD_QUBIT;
+    if (ctl >= 0 && ((unsigned)ctl >= r->n || (unsigned)ctl == q0 || (unsigned)ctl == q1)) return QCX_BAD_QUBIT;
+    if (r->sh) { set_error("%s: not available on a sharded register", who); return QCX_UNSUPPORTED; }
+    FLUSH(r);                                         // queued gates, a pending basis state, a compact circuit result
+    if (r->nonfinite) {                               // strict pass: every amplitude rewritten with the mat-vec's own products
+        r->zeros_dirty = 0;
+        if (ctl < 0) return qcx_shard_two_qubit(r->amp, r->n, q0, q1, -1, u, r->stream);      // (the plain kernels already are strict)
+        const U4Mat U = u4_ascending(q0, q1, u);
+        const unsigned lo = q0 < q1 ? q0 : q1, hi = q0 < q1 ? q1 : q0;
+        hipLaunchKernelGGL(k_strict_cu2, dim3(grid_for(r->dim >> 2, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, lo, hi, (unsigned)ctl, U, 1.0, 0.0);
+        HIP_TRY(hipGetLastError());
+        return QCX_NO_ERROR;
+    }
+    QCX_TRY(canon_if_dirty(r));
+    return qcx_shard_two_qubit(r->amp, r->n, q0, q1, ctl, u, r->stream);
+}
+
+extern "C" int qcx_two_qubit_gate(unsigned q0, unsigned q1, const double *u, qcx_register *r)
+{
+    return two_qubit_gate(-1, q0, q1, u, r, "two_qubit_gate");
+}
+
+extern "C" int qcx_c_two_qubit_gate(unsigned c, unsigned q0, unsigned q1, const double *u, qcx_register *r)
+{
+    if (r && c >= r->n) return QCX_BAD_QUBIT;         // (before the cast: a control >= 2^31 is a bad qubit, not "no control")
+    return two_qubit_gate((int)c, q0, q1, u, r, "c_two_qubit_gate");
 }
 
 extern "C" int qcx_c_amodc_gate(unsigned C, unsigned long long atox, unsigned c, qcx_register *r)

@@ -4275,4 +4275,149 @@ __global__ __launch_bounds__(256) void k_strict_cu(amp_t *__restrict__ amp, unsi
     }
 }
 
+// ---------------------------------------------------------------------------
+// K13  any two-qubit gate, plain or controlled (qcx_two_qubit_gate / qcx_c_two_qubit_gate, DESIGN s4.5g): the 4x4 matrix m on
+// the quads (i, i | 2^lo, i | 2^hi, i | 2^lo | 2^hi), lo < hi, as the reference's mat-vec would apply it from sixteen stored
+// triplets per quad taken in ascending state index (Q:396-413):
+//     out_r = (((0 + m[r][0] * x0) + m[r][1] * x1) + m[r][2] * x2) + m[r][3] * x3,   complex products as Q:409 / Q:412,
+// every product and sum rounded on its own (no FMA), all sixteen entries multiplied out even where they are zero.  The host
+// has already permuted the caller's matrix when qubit0 > qubit1 (P u P, P = the index swap 1 <-> 2): a kernel only sees
+// lo < hi and matrix index k = bit(lo) + 2 * bit(hi).  The 32 components are kernel arguments (SGPRs), read with constant
+// indices only -- a lane that needs "its own" row picks it with selects, never with a run-time index, so nothing goes to
+// scratch.  No LDS, no table, one arithmetic path for every matrix.  A result is never -0 (as in K12), so K0c's invariant
+// holds behind these kernels.
+// ---------------------------------------------------------------------------
+struct U4Mat { double m[32]; };                          // m[(4 * r + k) * 2 + (0: re, 1: im)]
+struct U4Row { double r0, i0, r1, i1, r2, i2, r3, i3; };
+
+template <int ROW> __device__ __forceinline__ U4Row u4_row_of(const U4Mat &U)
+{
+    return {U.m[8 * ROW], U.m[8 * ROW + 1], U.m[8 * ROW + 2], U.m[8 * ROW + 3], U.m[8 * ROW + 4], U.m[8 * ROW + 5], U.m[8 * ROW + 6], U.m[8 * ROW + 7]};
+}
+
+// the row of the lane's own amplitude: row = lb + 2 * hb (its bits lo and hi)
+__device__ __forceinline__ U4Row u4_row_sel(const U4Mat &U, bool lb, bool hb)
+{
+#define QCX_U4_SEL(k) (hb ? (lb ? U.m[24 + k] : U.m[16 + k]) : (lb ? U.m[8 + k] : U.m[k]))
+    return {QCX_U4_SEL(0), QCX_U4_SEL(1), QCX_U4_SEL(2), QCX_U4_SEL(3), QCX_U4_SEL(4), QCX_U4_SEL(5), QCX_U4_SEL(6), QCX_U4_SEL(7)};
+#undef QCX_U4_SEL
+}
+
+// one row, the 4-column extension of u_row: x0 .. x3 = the quad's amplitudes in ascending index order
+__device__ __forceinline__ amp_t u4_row(const U4Row &m, amp_t x0, amp_t x1, amp_t x2, amp_t x3)
+{
+    amp_t o;
+    o.x = (((0.0 + ((m.r0 * x0.x) - (m.i0 * x0.y))) + ((m.r1 * x1.x) - (m.i1 * x1.y))) + ((m.r2 * x2.x) - (m.i2 * x2.y))) + ((m.r3 * x3.x) - (m.i3 * x3.y));      // Q:409
+    o.y = (((0.0 + ((m.r0 * x0.y) + (m.i0 * x0.x))) + ((m.r1 * x1.y) + (m.i1 * x1.x))) + ((m.r2 * x2.y) + (m.i2 * x2.x))) + ((m.r3 * x3.y) + (m.i3 * x3.x));      // Q:412
+    return o;
+}
+
+__device__ __forceinline__ void u4_quad(const U4Mat &U, amp_t &x0, amp_t &x1, amp_t &x2, amp_t &x3)
+{
+    const amp_t o0 = u4_row(u4_row_of<0>(U), x0, x1, x2, x3), o1 = u4_row(u4_row_of<1>(U), x0, x1, x2, x3);
+    const amp_t o2 = u4_row(u4_row_of<2>(U), x0, x1, x2, x3), o3 = u4_row(u4_row_of<3>(U), x0, x1, x2, x3);
+    x0 = o0; x1 = o1; x2 = o2; x3 = o3;
+}
+
+// K13a  quad form, any pair of targets (K12a's shape).  A lane owns one quad: four 16-B loads before the first store.  s0 < s1
+// (< s2) are the squeezed-out index bits in ascending order: lo and hi, and with CTL the control, which is then set -- only
+// the 2^(n-3) control-set quads are read or written.  count = 2^(n-2) (CTL: 2^(n-3)); stream-interleaved tile order as in
+// k_phase; a partial last tile (count < BLOCK) is guarded by p < count.
+template <bool NT, bool CTL, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_u2_quad(amp_t *__restrict__ amp, unsigned lo, unsigned hi, unsigned c, unsigned s0, unsigned s1,
+                                                     unsigned s2, U4Mat U, uint64_t count, unsigned glog, unsigned slog)
+{
+    const uint64_t lob = (uint64_t)1 << lo, hib = (uint64_t)1 << hi;
+    const uint64_t step = (uint64_t)gridDim.x * BLOCK;
+    uint64_t tile0 = blockIdx.x;
+    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    for (uint64_t base = tile0 * BLOCK; base < count; base += step) {
+        const uint64_t p = base + threadIdx.x;
+        if (p < count) {
+            uint64_t i = insert_zero(insert_zero(p, s0), s1);
+            if (CTL) i = insert_zero(i, s2) | ((uint64_t)1 << c);
+            amp_t x0 = ld<NT>(amp + i), x1 = ld<NT>(amp + (i | lob)), x2 = ld<NT>(amp + (i | hib)), x3 = ld<NT>(amp + (i | lob | hib));
+            u4_quad(U, x0, x1, x2, x3);
+            st<NT>(amp + i, x0); st<NT>(amp + (i | lob), x1); st<NT>(amp + (i | hib), x2); st<NT>(amp + (i | lob | hib), x3);
+        }
+    }
+}
+
+// K13b  line forms: lo, or the control, below bit 3, i.e. inside a 128-B line (K12b / K12c's reason: a wave memory instruction
+// must cover whole lines).  A lane owns ONE amplitude of every touched line, and the four amplitudes of its quad reach it
+//   - by xor-shuffle where the target sits below bit 6 of the lane numbering (NS of the two targets: lo first, lo < hi),
+//   - as further registers of the same lane, loaded from the lines 2^hi (and 2^lo) away, where it sits above.
+// Squeezed out of the numbering p (in ascending order s0 < s1, nsq of them): a control >= 3, which is then set (cset: only
+// control-set lines are read), and the targets that live in registers.  Squeezing a control in 3 .. 5 moves the targets above
+// it down by one lane bit: mlo / mhi are the shuffle masks in LANE numbering, the lane's own row comes from the bits of its
+// INDEX.  Every lane computes its OWN row (NS = 2), its own two rows (NS = 1) or all four (NS = 0), the row's eight components
+// chosen by its bits lo and hi, the four amplitudes fed in ascending index order -- so the sums are those of the definition.
+// A control < 3 (clow = its bit, else 0) leaves every line touched: lanes whose control bit is clear keep their bits and, with
+// store_all (control at 16- or 32-B granularity, as in k_cu_lines), whole lines are stored back.
+// count is a multiple of 64 (the host asks for n >= 9 and squeezes at most two bits), so no wave diverges around a shuffle.
+template <int NS, bool NT>
+__global__ __launch_bounds__(64) void k_u2_lines(amp_t *__restrict__ amp, unsigned lo, unsigned hi, unsigned mlo, unsigned mhi, unsigned nsq,
+                                                 unsigned s0, unsigned s1, uint64_t cset, unsigned clow, int store_all, U4Mat U,
+                                                 uint64_t count, unsigned glog, unsigned slog)
+{
+    const uint64_t lob = (uint64_t)1 << lo, hib = (uint64_t)1 << hi;
+    const uint64_t step = (uint64_t)gridDim.x * 64u;
+    uint64_t tile0 = blockIdx.x;
+    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    for (uint64_t p = tile0 * 64u + threadIdx.x; p < count; p += step) {
+        uint64_t i = p;
+        if constexpr (NS == 0) i = insert_zero(insert_zero(p, lo), hi);      // (only with a control < 3: nothing else is squeezed out)
+        else {
+            if (nsq > 0) i = insert_zero(i, s0);
+            if (nsq > 1) i = insert_zero(i, s1);
+            i |= cset;
+        }
+        const bool hit = clow == 0 || (i & clow) != 0;
+        const bool lb = (i & lob) != 0, hb = (i & hib) != 0;
+        if constexpr (NS == 2) {
+            const amp_t v = ld<NT>(amp + i);
+            const amp_t ol = shfl_xor_amp(v, (int)mlo), oh = shfl_xor_amp(v, (int)mhi), olh = shfl_xor_amp(ol, (int)mhi);
+            // a_j: bit lo = j & 1, bit hi = (own) ^ (j >> 1); then ascending order
+            const amp_t a0 = lb ? ol : v, a1 = lb ? v : ol, a2 = lb ? olh : oh, a3 = lb ? oh : olh;
+            if (hit) st<NT>(amp + i, u4_row(u4_row_sel(U, lb, hb), hb ? a2 : a0, hb ? a3 : a1, hb ? a0 : a2, hb ? a1 : a3));
+            else if (store_all) st<NT>(amp + i, v);
+        } else if constexpr (NS == 1) {                        // (i has bit hi clear: squeezed out)
+            const amp_t v0 = ld<NT>(amp + i), v1 = ld<NT>(amp + (i | hib));
+            const amp_t o0 = shfl_xor_amp(v0, (int)mlo), o1 = shfl_xor_amp(v1, (int)mlo);
+            const amp_t x0 = lb ? o0 : v0, x1 = lb ? v0 : o0, x2 = lb ? o1 : v1, x3 = lb ? v1 : o1;
+            if (hit) {
+                st<NT>(amp + i, u4_row(u4_row_sel(U, lb, false), x0, x1, x2, x3));
+                st<NT>(amp + (i | hib), u4_row(u4_row_sel(U, lb, true), x0, x1, x2, x3));
+            } else if (store_all) { st<NT>(amp + i, v0); st<NT>(amp + (i | hib), v1); }
+        } else {                                               // (bits lo and hi clear: both squeezed out)
+            amp_t x0 = ld<NT>(amp + i), x1 = ld<NT>(amp + (i | lob)), x2 = ld<NT>(amp + (i | hib)), x3 = ld<NT>(amp + (i | lob | hib));
+            if (hit) u4_quad(U, x0, x1, x2, x3);
+            if (hit || store_all) { st<NT>(amp + i, x0); st<NT>(amp + (i | lob), x1); st<NT>(amp + (i | hib), x2); st<NT>(amp + (i | lob | hib), x3); }
+        }
+    }
+}
+
+// K13s  the controlled gate as a STRICT pass (K9's reason: a register that holds non-finite amplitudes): one plain pass over all
+// 2^(n-2) quads, the defined rows on the control-set quads, and every control-clear amplitude rewritten through the reference's
+// identity row; `one` and `z` are kernel arguments so that no product is folded, as in k_strict_cu.  (The plain gate needs no
+// strict twin: every form of K13 rewrites every amplitude from all sixteen products; the non-finite tests prove it.)
+__global__ __launch_bounds__(256) void k_strict_cu2(amp_t *__restrict__ amp, unsigned n, unsigned lo, unsigned hi, unsigned c, U4Mat U, double one, double z)
+{
+    const uint64_t quads = (uint64_t)1 << (n - 2), lob = (uint64_t)1 << lo, hib = (uint64_t)1 << hi;
+    for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < quads; p += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i = insert_zero(insert_zero(p, lo), hi);
+        amp_t x[4] = {amp[i], amp[i | lob], amp[i | hib], amp[i | lob | hib]};
+        if ((i >> c) & 1u) u4_quad(U, x[0], x[1], x[2], x[3]);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                amp_t o;
+                o.x = 0.0 + ((one * x[k].x) - (z * x[k].y));   o.y = 0.0 + ((one * x[k].y) + (z * x[k].x));
+                x[k] = o;
+            }
+        }
+        amp[i] = x[0]; amp[i | lob] = x[1]; amp[i | hib] = x[2]; amp[i | lob | hib] = x[3];
+    }
+}
+
 }  // namespace qcx

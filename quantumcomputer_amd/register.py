@@ -341,6 +341,42 @@ def c_one_qubit_gate(c_qubit_num, qubit_num, U, reg):
     check(lib().qcx_c_one_qubit_gate(int(c_qubit_num), int(qubit_num), u.ctypes.data_as(C.c_void_p), reg._h), "c_one_qubit_gate")
 
 
+def _matrix32(U):
+    """U as the 32 doubles qcx_two_qubit_gate takes: row-major (re, im); U is a 4x4 matrix or those 32 doubles themselves"""
+    m = np.asarray(U)
+    if m.shape == (32,) and not np.iscomplexobj(m):
+        return np.ascontiguousarray(m, dtype=np.float64)
+    m = np.asarray(U, dtype=complex)
+    if m.shape != (4, 4):
+        raise ValueError(f"a two-qubit gate is a 4x4 matrix, not shape {m.shape}")
+    return np.ascontiguousarray(m.reshape(16)).view(np.float64)
+
+
+def two_qubit_gate(qubit0, qubit1, U, reg):
+    """Apply the 4x4 matrix U (anything numpy.asarray(U, complex) turns into shape (4, 4), or the 32 doubles) to two qubits, with
+    the reference's mat-vec arithmetic (include/qcx.h: qcx_two_qubit_gate).  Matrix index = bit(qubit0) + 2 * bit(qubit1): "A on
+    qubit0, B on qubit1" is numpy.kron(B, A).  U is applied as given, not checked for unitarity."""
+    u = _matrix32(U)
+    check(lib().qcx_two_qubit_gate(int(qubit0), int(qubit1), u.ctypes.data_as(C.c_void_p), reg._h), "two_qubit_gate")
+
+
+def c_two_qubit_gate(c_qubit_num, qubit0, qubit1, U, reg):
+    """two_qubit_gate on the amplitudes whose qubit `c_qubit_num` reads 1 (include/qcx.h: qcx_c_two_qubit_gate)"""
+    u = _matrix32(U)
+    check(lib().qcx_c_two_qubit_gate(int(c_qubit_num), int(qubit0), int(qubit1), u.ctypes.data_as(C.c_void_p), reg._h), "c_two_qubit_gate")
+
+
+def controlled(U2):
+    """the 4x4 matrix "U2 on qubit1 where qubit0 reads 1": the identity with U2 in rows and columns {1, 3}, so that
+    c_two_qubit_gate(c, a, b, controlled(X)) is a Toffoli with controls c and a"""
+    m = np.asarray(U2, dtype=complex)
+    if m.shape != (2, 2):
+        raise ValueError(f"controlled() takes a 2x2 matrix, not shape {m.shape}")
+    out = np.eye(4, dtype=complex)
+    out[np.ix_([1, 3], [1, 3])] = m
+    return out
+
+
 def phase(theta):
     """diag(1, e^{i theta}) with the factor c_phase_shift_gate uses (qcx_polar)"""
     c, s = _lib.polar(theta)
@@ -357,6 +393,16 @@ def rz(theta):
 def __getattr__(name):
     """GATES: the exact matrices X, Y, Z, S, T, H.  Built on first use (PEP 562), because T's factor is the library's
     qcx_polar(pi/4) and importing the package must not load the library."""
+    if name == "GATES2":
+        # the exact two-qubit matrices, matrix index = bit(qubit0) + 2 * bit(qubit1); CNOT: control qubit0, target qubit1
+        gates2 = {
+            "SWAP": np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], dtype=complex),
+            "ISWAP": np.array([[1, 0, 0, 0], [0, 0, 1j, 0], [0, 1j, 0, 0], [0, 0, 0, 1]], dtype=complex),
+            "CNOT": np.array([[1, 0, 0, 0], [0, 0, 0, 1], [0, 0, 1, 0], [0, 1, 0, 0]], dtype=complex),
+            "CZ": np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, -1]], dtype=complex),
+        }
+        globals()["GATES2"] = gates2
+        return gates2
     if name != "GATES":
         raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
     s = 0.70710678118654752440          # M_SQRT1_2 (qc_shor.c:210-213): hadamard_gate's entry
