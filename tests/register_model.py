@@ -1,0 +1,667 @@
+"""The host model of an unsharded register, and the generator of random call sequences over the whole register API
+(tests/test_register_model.py pins both on the CPU, tests/test_gpu_api_sequences.py runs them against the GPU).
+
+The model holds the state as interleaved float64 and has one method per public call; every method does what the project already
+defines for that call -- the oracle (oracle/binding.py) for reset, fill, the reference's gates, the circuits and measure_state,
+tests/one_qubit_ref.py / two_qubit_ref.py for the matrix gates, tests/marginal_ref.py / collapse_ref.py for the marginal and the
+range collapse -- so a sequence of calls on the model is the bit-for-bit expectation for the same calls on the GPU, whatever lazy
+form (queue, pending basis state, compact result, owed zero pass, strict mode) the library keeps the state in between them.
+
+An op is a tuple of a name and plain numbers / strings, so that a failing sequence prints as a Python literal and replays:
+written data and matrices are regenerated from the seed inside the op (window_data, matrix_data).  Host only."""
+import numpy as np
+
+import one_qubit_ref
+import two_qubit_ref
+from collapse_ref import collapse_ref, measure_ref
+from marginal_ref import marginal_ref
+
+NO_ERROR, BAD_ARGUMENTS, BAD_QUBIT = 0, 2, 6
+THREADS = 8
+
+
+# ---- data an op names by seed -----------------------------------------------------------------------------------------------
+
+def window_data(dim, count, seed, flavour):
+    """`count` amplitudes a write op stores: components U(-0.5, 0.5) at the scale of a normalised state of `dim` amplitudes;
+    "negzero": a quarter of the components are zeros of either sign; "inf" / "nan": one component is not finite; "subnormal": four
+    times the scale (a whole state of norm^2 about 16) with a quarter of the components the smallest subnormal of either sign -- a
+    collapse onto an outcome of probability > 4 scales by s < 1/2, and the negative ones underflow to -0"""
+    rs = np.random.RandomState(seed)
+    a = rs.uniform(-0.5, 0.5, 2 * count) * np.sqrt(6.0 / dim)
+    if flavour == "subnormal":
+        a *= 4.0
+        k = max(2, (2 * count) // 4)
+        a[rs.randint(0, 2 * count, k)] = -5e-324
+        a[rs.randint(0, 2 * count, k // 3)] = 5e-324
+        return a
+    if flavour == "negzero":
+        k = max(2, (2 * count) // 4)
+        a[rs.randint(0, 2 * count, k)] = -0.0
+        a[rs.randint(0, 2 * count, k // 2)] = 0.0
+        a[int(rs.randint(0, 2 * count))] = -0.0
+    elif flavour in ("inf", "nan"):
+        a[int(rs.randint(0, 2 * count))] = {"inf": [np.inf, -np.inf][int(rs.randint(0, 2))], "nan": np.nan}[flavour]
+    else:
+        assert flavour == "plain", flavour
+    return a
+
+
+_S = 0.70710678118654752440
+_NAMED2 = [np.array(m, dtype=complex) for m in (
+    [[_S, _S], [_S, -_S]], [[0, 1], [1, 0]], [[0, -1j], [1j, 0]], [[1, 0], [0, -1]], [[1, 0], [0, 1j]])]
+_NAMED4 = [np.array(m, dtype=complex) for m in (
+    [[1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], [[1, 0, 0, 0], [0, 0, 1j, 0], [0, 1j, 0, 0], [0, 0, 0, 1]],
+    [[1, 0, 0, 0], [0, 0, 0, 1], [0, 0, 1, 0], [0, 1, 0, 0]], [[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, -1]])]
+
+
+def matrix_data(k, seed, ulp=False):
+    """the k x k complex matrix a gate op applies (k = 2, 4): one of the exact named gates or a random unitary, every component
+    within [-1, 1]; ulp: one component is 1 + 1 ulp, which the library must refuse"""
+    rs = np.random.RandomState(seed)
+    if rs.randint(0, 3) == 0:
+        named = _NAMED2 if k == 2 else _NAMED4
+        m = named[int(rs.randint(0, len(named)))].copy()
+    else:
+        m, _ = np.linalg.qr(rs.standard_normal((k, k)) + 1j * rs.standard_normal((k, k)))
+    d = np.ascontiguousarray(m.reshape(-1)).view(np.float64).copy()
+    d /= max(1.0, float(np.max(np.abs(d))))
+    if ulp:
+        d[int(rs.randint(0, d.size))] = np.nextafter(1.0, 2.0) * [1.0, -1.0][int(rs.randint(0, 2))]
+    return d.view(np.complex128).reshape(k, k)
+
+
+def sample_draws(seed, shots):
+    """the draws of a sample op: uniform, with the reference's edge values mixed in"""
+    rs = np.random.RandomState(seed)
+    r = rs.uniform(0.0, 1.0, shots)
+    if shots > 2 and rs.randint(0, 2):
+        r[int(rs.randint(0, shots))] = float(rs.choice([0.0, 1.0, 1.5, -0.25, 1e-300]))
+    return r
+
+
+# ---- the model --------------------------------------------------------------------------------------------------------------
+
+class RegisterModel:
+    def __init__(self, ob, L, M):
+        self.ob, self.L, self.M, self.n = ob, L, M, L + M
+        self.dim = 1 << self.n
+        self.a = np.zeros(2 * self.dim)
+        self.saved = {}
+
+    def holds_nonfinite(self):
+        return not bool(np.all(np.isfinite(self.a)))
+
+    # state access
+    def reset_register(self):
+        self.a = np.zeros(2 * self.dim)
+        self.ob.reset(self.a, self.n)
+
+    def fill_random(self, seed):
+        self.a = self.ob.fill_random(self.n, seed)
+
+    def write(self, amps, first=0):
+        amps = np.ascontiguousarray(amps, dtype=np.float64)
+        self.a[2 * first:2 * first + amps.size] = amps                   # (a -0 stays until a gate canonicalises it)
+
+    def read(self, first=0, count=None):
+        count = self.dim - first if count is None else count
+        return self.a[2 * first:2 * (first + count)].copy()
+
+    def save(self, key):
+        self.saved[key] = self.a.copy()
+
+    def load(self, key):
+        self.a = self.saved[key].copy()
+
+    def flush(self): pass
+    def synchronize(self): pass
+    def set_fusion(self, mode): pass
+
+    # the reference's gates and circuits
+    def hadamard_gate(self, q): self.ob.hadamard(self.a, self.n, q, THREADS)
+    def c_phase_shift_gate(self, c, t, theta): self.ob.cphase(self.a, self.n, c, t, theta, THREADS)
+    def c_amodc_gate(self, Cn, atox, ctl): self.ob.camodc(self.a, self.n, self.M, Cn, atox, ctl, THREADS)
+    def inverse_QFT(self): self.ob.iqft(self.a, self.n, self.M, THREADS)
+    def quantum_computation(self, Cn, a): self.ob.quantum_computation(self.a, self.n, self.M, Cn, a, threads=THREADS)
+
+    # the matrix gates
+    def one_qubit_gate(self, q, U): self.a = one_qubit_ref.apply(self.a, self.n, q, U)
+    def c_one_qubit_gate(self, c, q, U): self.a = one_qubit_ref.apply(self.a, self.n, q, U, control=c)
+    def two_qubit_gate(self, q0, q1, U): self.a = two_qubit_ref.apply(self.a, self.n, q0, q1, U)
+    def c_two_qubit_gate(self, c, q0, q1, U): self.a = two_qubit_ref.apply(self.a, self.n, q0, q1, U, control=c)
+
+    # observers and collapses
+    def measure_state(self, r):
+        return self.ob.measure(self.a, self.n, float(r))                  # (collapses self.a)
+
+    def sample_states(self, rs):
+        return np.array([self.ob.measure(self.a.copy(), self.n, float(r)) for r in rs], dtype=np.uint64)
+
+    def marginal(self, first, num):
+        return marginal_ref(self.a, self.n, first, num)
+
+    def measure_qubits(self, first, num, r):
+        """(outcome, probability, status); BAD_ARGUMENTS leaves the state as it was"""
+        v, p, out = measure_ref(self.a, self.n, first, num, r)
+        if out is None:
+            return v, p, BAD_ARGUMENTS
+        self.a = out
+        return v, p, NO_ERROR
+
+    def postselect(self, first, num, outcome):
+        p, out = collapse_ref(self.a, self.n, first, num, outcome)
+        if out is None:
+            return p, BAD_ARGUMENTS
+        self.a = out
+        return p, NO_ERROR
+
+    def total_probability(self):
+        with np.errstate(over="ignore", invalid="ignore"):
+            return self.ob.norm2(self.a, self.n)                          # the sequential sum (testing_and_debug.c:28-37)
+
+    def norm2(self):
+        """not bit-defined (the GPU sums a tree): compare within 1e-9, and not at all on a non-finite state"""
+        return self.ob.norm2(self.a, self.n)
+
+
+# ---- ops ---------------------------------------------------------------------------------------------------------------------
+
+FOLLOWING = ("reset", "fill", "write", "read", "h", "cphase", "camodc", "iqft", "qcomp", "u1", "cu1", "u2", "cu2", "measure",
+             "sample", "marginal", "measure_qubits", "postselect", "total", "norm2", "save", "load", "flush", "sync", "fusion")
+SETTING = ("reset", "measure_state", "fill", "write_full_negzero", "write_partial", "write_nonfinite", "collapse", "compact",
+           "queued_mode1", "queued_behind_basis", "load")
+QUEUED = ("h", "cphase", "camodc", "iqft", "qcomp")
+
+
+def apply_to_model(m, op):
+    """one op on the model; returns what the call returns, in the form apply_to_register (test_gpu_api_sequences.py) gives"""
+    k = op[0]
+    if k == "reset": m.reset_register()
+    elif k == "fill": m.fill_random(op[1])
+    elif k == "write": m.write(window_data(m.dim, op[2], op[3], op[4]), op[1])
+    elif k == "read": return m.read(op[1], op[2])
+    elif k == "h": m.hadamard_gate(op[1])
+    elif k == "cphase": m.c_phase_shift_gate(op[1], op[2], op[3])
+    elif k == "camodc": m.c_amodc_gate(op[1], op[2], op[3])
+    elif k == "iqft": m.inverse_QFT()
+    elif k == "qcomp": m.quantum_computation(op[1], op[2])
+    elif k == "u1": m.one_qubit_gate(op[1], matrix_data(2, op[2]))
+    elif k == "cu1": m.c_one_qubit_gate(op[1], op[2], matrix_data(2, op[3]))
+    elif k == "u2": m.two_qubit_gate(op[1], op[2], matrix_data(4, op[3]))
+    elif k == "cu2": m.c_two_qubit_gate(op[1], op[2], op[3], matrix_data(4, op[4]))
+    elif k == "measure": return m.measure_state(op[1])
+    elif k == "sample": return m.sample_states(sample_draws(op[1], op[2]))
+    elif k == "marginal": return m.marginal(op[1], op[2])
+    elif k == "measure_qubits": return m.measure_qubits(op[1], op[2], op[3])
+    elif k == "postselect": return m.postselect(op[1], op[2], op[3])
+    elif k == "total": return m.total_probability()
+    elif k == "norm2": return None if m.holds_nonfinite() else m.norm2()
+    elif k == "save": m.save(op[1])
+    elif k == "load": m.load(op[1])
+    elif k == "flush": m.flush()
+    elif k == "sync": m.synchronize()
+    elif k == "fusion": m.set_fusion(op[1])
+    elif k == "stats": pass
+    elif k == "refused":
+        inner, status = op[1], op[2]
+        if inner[0] == "postselect" and inner[3] < (1 << inner[2]) and inner[1] + inner[2] <= m.n:
+            p, out = collapse_ref(m.a, m.n, inner[1], inner[2], inner[3])
+            assert out is None, ("the generator drew an outcome the state CAN be collapsed onto", op)
+            return (p, status)
+        return status                                                       # the state stays as it was
+    else:
+        raise ValueError(f"unknown op {op!r}")
+    return None
+
+
+# ---- the generator -----------------------------------------------------------------------------------------------------------
+
+NSEEDS = 64
+# (L, M, C, a); n = 6 .. 14, M = 0 and n < 9 (partial tiles in several kernels) included
+SHAPES = [(8, 4, 15, 7), (9, 5, 21, 2), (8, 5, 21, 2), (6, 0, 1, 1), (10, 0, 1, 1), (2, 4, 15, 7), (3, 4, 15, 7), (4, 4, 15, 7),
+          (5, 5, 21, 2), (13, 0, 1, 1), (7, 6, 35, 2), (10, 4, 15, 7), (4, 5, 21, 2), (8, 0, 1, 1)]
+# compact_chain (csrc/qcx_fuse.inc.h) runs a circuit on the compact copy when L + cb >= 14 with cb = the orbit's column bits
+# (2 for the four residues of C = 15, 3 for the six of C = 21): the smallest registers that reach it have n = 16
+COMPACT_SHAPES = [(11, 5, 21, 2), (12, 4, 15, 7)]
+SMALL_SHAPES = [(2, 2, 3, 2), (3, 3, 7, 3), (2, 4, 15, 7), (5, 0, 1, 1), (6, 0, 1, 1), (3, 0, 1, 1), (1, 4, 15, 7), (3, 2, 3, 2)]
+# launch knobs: values the forced-form tests of K1 / K2 / K12 / K13 use (registers of n >= 9 only), and K11's
+KNOBS_N9 = [dict(h_variant=1, h_ppt=2, h_streams_log2=3), dict(h_variant=2, h_wave_r=4, h_nt=0, h_streams_log2=0), dict(ph_lines=0),
+            dict(ph_lines=0, ph_nt=0, ph_streams_log2=0), dict(u2_variant=1), dict(u2_streams_log2=3), dict(u2_variant=1, u2_nt=0)]
+KNOBS_ANY = [dict(collapse_upt=8), dict(collapse_perm=0), dict(collapse_grid_cap=1), dict(collapse_grid_cap=3, collapse_upt=8)]
+
+
+class Config:
+    def __init__(self, seed, small=False):
+        rs = np.random.RandomState(7919 * seed + 13)
+        self.seed, self.small = seed, small
+        self.compact = (not small) and seed % 8 == 5
+        if small:
+            shapes = [SMALL_SHAPES[seed % len(SMALL_SHAPES)]]
+        elif self.compact:
+            shapes = [COMPACT_SHAPES[(seed // 8) % 2]]
+        else:
+            shapes = [SHAPES[seed % len(SHAPES)]]
+            if seed % 4 == 2:                                              # two registers of different sizes, interleaved
+                shapes.append(SHAPES[(seed + 5) % len(SHAPES)])
+        self.shapes = shapes
+        self.mode = int(rs.choice([-1, 0, 1]))
+        self.modes = [self.mode] + [int(rs.choice([-1, 0, 1])) for _ in shapes[1:]]      # the start mode of every register
+        self.knobs = {}
+        if not small and seed % 3 == 1:
+            pool = KNOBS_ANY + (KNOBS_N9 if min(s[0] + s[1] for s in shapes) >= 9 else [])
+            for i in rs.choice(len(pool), 3, replace=False):
+                self.knobs.update(pool[int(i)])
+
+    def __repr__(self):
+        return f"seed {self.seed}: shapes (L, M, C, a) {self.shapes} start mode {self.mode} knobs {self.knobs}"
+
+
+def pair_is_legal(s, f, shape, compact):
+    L, M, Cn, a = shape
+    if (s == "compact") != compact:
+        return False
+    if f in ("camodc", "qcomp") and M == 0:
+        return False
+    if s == "write_nonfinite" and f == "norm2":                            # (norm2 is not compared on a non-finite state)
+        return False
+    return True
+
+
+def _schedule():
+    """every legal (state-setting kind, following kind) pair three times, dealt round-robin to the seeds whose register allows it"""
+    cfgs = [Config(s) for s in range(NSEEDS)]
+    out = [[] for _ in range(NSEEDS)]
+    at = 0
+    for _ in range(3):
+        for s in SETTING:
+            for f in FOLLOWING:
+                for k in range(NSEEDS):
+                    c = cfgs[(at + k) % NSEEDS]
+                    if pair_is_legal(s, f, c.shapes[0], c.compact):
+                        out[c.seed].append((s, f))
+                        at = (at + k + 1) % NSEEDS
+                        break
+    return out
+
+
+_SCHEDULE = None
+
+
+class _Gen:
+    """the ops of ONE register: scheduled (setting, following) probes with random parameters, random ops between them"""
+
+    def __init__(self, ob, shape, mode, rs, allow_nonfinite=True, tag=0):
+        self.ob, self.rs, self.tag = ob, rs, tag
+        self.L, self.M, self.Cn, self.a0 = shape
+        self.n = self.L + self.M
+        self.dim = 1 << self.n
+        self.m = RegisterModel(ob, self.L, self.M)
+        self.mode = mode
+        self.pending = False                    # the library would hold a lazily pending basis state
+        self.strict = False                     # ... would run strict passes (a non-finite write since the last reset / fill / measurement)
+        self.slots = {}                         # saved slot -> the state in it was finite
+        self.allow_nonfinite = allow_nonfinite
+        self.ops = []
+        self.emit(("reset",) if rs.randint(0, 2) else ("fill", int(rs.randint(1, 1 << 20))))
+
+    # bookkeeping -----------------------------------------------------------------------------------------------------------
+    def emit(self, op):
+        self.ops.append(op)
+        apply_to_model(self.m, op)
+        k = op[0]
+        if k == "fusion":
+            self.mode = op[1]
+        if k in ("reset", "measure"):
+            self.pending = self.mode >= 0
+        elif k in ("sample", "marginal", "stats", "measure_qubits", "postselect", "refused") or (k in QUEUED and self.mode == 1):
+            pass
+        else:
+            self.pending = False
+        if k == "write" and op[4] in ("inf", "nan"):
+            self.strict = True
+        elif k in ("reset", "measure", "fill"):
+            self.strict = False
+        if k == "save":
+            self.slots[op[1]] = not self.m.holds_nonfinite()
+
+    def r(self):
+        rs = self.rs
+        return float(rs.uniform(0, 1)) if rs.randint(0, 5) else float(rs.choice([0.0, 1.0, 1e-9, 0.999999999]))
+
+    def seed(self):
+        return int(self.rs.randint(1, 1 << 30))
+
+    def qubits(self, k):
+        return [int(v) for v in self.rs.choice(self.n, k, replace=False)]
+
+    def a_range(self, lo=0):
+        first = int(self.rs.randint(lo, self.n + 1))
+        num = int(self.rs.randint(0, min(self.n - first, 6) + 1))
+        if self.rs.randint(0, 4) == 0 and first < self.n:
+            num = max(num, 1)
+        return first, num
+
+    def cleanse(self):
+        """a finite state again (any way the API offers)"""
+        if self.m.holds_nonfinite():
+            c = int(self.rs.randint(0, 4))
+            self.emit([("reset",), ("fill", self.seed()), ("measure", self.r()), ("write", 0, self.dim, self.seed(), "plain")][c])
+
+    def dense(self):
+        """a state with more than a few populated amplitudes (a collapse of a basis state says little)"""
+        if np.count_nonzero(self.m.a) < 8 and self.rs.randint(0, 4):
+            if self.rs.randint(0, 2):
+                self.emit(("fill", self.seed()))
+            else:
+                for q in self.qubits(min(self.n, 4)):
+                    self.emit(("h", q))
+
+    def gate(self):
+        rs = self.rs
+        k = int(rs.randint(0, 3)) if self.M else int(rs.randint(0, 2))
+        if k == 0 or self.n < 2:
+            return ("h", int(rs.randint(0, self.n)))
+        if k == 1:
+            c, t = self.qubits(2)
+            th = float(rs.uniform(-3.2, 3.2)) if rs.randint(0, 2) else float(np.pi / (1 << int(rs.randint(1, 12))))
+            return ("cphase", c, t, th)
+        return ("camodc", self.Cn, int(rs.randint(1, 4 * self.Cn)), int(rs.randint(0, self.n)))
+
+    def good_outcome(self, first, num):
+        P = self.m.marginal(first, num)
+        ok = [v for v in range(P.size) if np.isfinite(P[v]) and P[v] > 0 and np.isfinite(1.0 / np.sqrt(P[v]))]
+        return int(ok[int(self.rs.randint(0, len(ok)))]) if ok else None
+
+    # ops by following kind ---------------------------------------------------------------------------------------------------
+    def op_of(self, f):
+        rs, n = self.rs, self.n
+        if f == "reset": return ("reset",)
+        if f == "fill": return ("fill", self.seed())
+        if f == "write":
+            finite = ("plain", "negzero")
+            fl = str(rs.choice(finite + (("inf", "nan") if self.allow_nonfinite and rs.randint(0, 4) == 0 else ())))
+            if rs.randint(0, 3) == 0:
+                return ("write", 0, self.dim, self.seed(), fl)
+            first = int(rs.randint(0, self.dim))
+            return ("write", first, int(rs.randint(1, min(self.dim - first, 600) + 1)), self.seed(), fl)
+        if f == "read":
+            if rs.randint(0, 3) == 0:
+                return ("read", 0, self.dim)
+            first = int(rs.randint(0, self.dim))
+            return ("read", first, int(rs.randint(1, min(self.dim - first, 2000) + 1)))
+        if f in ("h", "cphase", "camodc"):
+            while True:
+                g = self.gate()
+                if g[0] == f or (f == "cphase" and n < 2):
+                    return g
+        if f == "iqft": return ("iqft",)
+        if f == "qcomp": return ("qcomp", self.Cn, self.a0)
+        if f == "u1": return ("u1", int(rs.randint(0, n)), self.seed())
+        if f == "cu1" and n >= 2: return ("cu1", *self.qubits(2), self.seed())
+        if f == "u2" and n >= 2: return ("u2", *self.qubits(2), self.seed())
+        if f == "cu2" and n >= 3: return ("cu2", *self.qubits(3), self.seed())
+        if f in ("cu1", "u2", "cu2"): return ("u1", int(rs.randint(0, n)), self.seed())
+        if f == "measure": return ("measure", self.r())
+        if f == "sample": return ("sample", self.seed(), int(rs.choice([1, 3, 8, 17])))
+        if f == "marginal": return ("marginal", *self.a_range())
+        if f == "measure_qubits": return ("measure_qubits", *self.a_range(), self.r())
+        if f == "postselect":
+            first, num = self.a_range()
+            v = self.good_outcome(first, num)
+            return ("postselect", first, num, v if v is not None else int(rs.randint(0, 1 << num)))
+        if f in ("total", "norm2", "flush", "sync"): return (f,)
+        if f == "save": return ("save", int(rs.randint(0, 2)))
+        if f == "load":
+            if not self.slots:
+                return ("save", 0)
+            return ("load", int(rs.choice(sorted(self.slots))))
+        if f == "fusion": return ("fusion", int(rs.choice([-1, 0, 1])))
+        raise ValueError(f)
+
+    def quiet(self):
+        """a call that leaves every lazy form as it is (the issue's "non-flushing" calls)"""
+        c = int(self.rs.randint(0, 3))
+        if c == 0: return ("sample", self.seed(), int(self.rs.choice([1, 4, 9])))
+        if c == 1: return ("marginal", *self.a_range(self.M))
+        return ("stats",)
+
+    def refused(self):
+        """a call the library must refuse with the state untouched: (inner op, status)"""
+        rs, n = self.rs, self.n
+        c = int(rs.randint(0, 4))
+        if c == 0:                                                           # bad qubit
+            k = int(rs.randint(0, 4))
+            if k == 0: return ("h", n), BAD_QUBIT
+            if k == 1: return ("marginal", n - 1, 2), BAD_QUBIT
+            if k == 2: return ("u1", n + 3, self.seed()), BAD_QUBIT
+            q = int(rs.randint(0, n))
+            return ("cphase", q, q, 0.5), BAD_QUBIT
+        if c == 1:                                                           # a matrix component of 1 + 1 ulp
+            if n >= 2 and rs.randint(0, 2):
+                return ("u2x", *self.qubits(2), self.seed()), BAD_ARGUMENTS
+            return ("u1x", int(rs.randint(0, n)), self.seed()), BAD_ARGUMENTS
+        first, num = self.a_range()
+        if c == 2:                                                           # an outcome that does not fit
+            return ("postselect", first, num, 1 << num), BAD_ARGUMENTS
+        for first, num in [self.a_range() for _ in range(6)]:                # an outcome of probability +0
+            P = self.m.marginal(first, num)
+            zero = np.flatnonzero((P == 0) & ~np.signbit(P))
+            if zero.size:
+                return ("postselect", first, num, int(zero[int(rs.randint(0, zero.size))])), BAD_ARGUMENTS
+        return ("postselect", first, num, 1 << num), BAD_ARGUMENTS
+
+    # state-setting kinds -----------------------------------------------------------------------------------------------------
+    def finite_slot(self):
+        good = [k for k, fin in self.slots.items() if fin]
+        if not good:
+            self.cleanse()
+            self.emit(("save", int(self.rs.randint(0, 2))))
+            good = [k for k, fin in self.slots.items() if fin]
+        return int(self.rs.choice(good))
+
+    def want_mode(self, modes):
+        if self.mode not in modes:
+            self.emit(("fusion", int(self.rs.choice(modes))))
+
+    def setting(self, s, f):
+        rs = self.rs
+        if f == "load" and not self.slots:
+            self.emit(("save", int(rs.randint(0, 2))))
+        if s == "reset": self.emit(("reset",))
+        elif s == "measure_state": self.emit(("measure", self.r()))
+        elif s == "fill": self.emit(("fill", self.seed()))
+        elif s == "write_full_negzero": self.emit(("write", 0, self.dim, self.seed(), "negzero"))
+        elif s == "write_partial":
+            self.cleanse()
+            first = int(rs.randint(0, self.dim - 1))
+            self.emit(("write", first, int(rs.randint(1, min(self.dim - first, 600, self.dim - 1) + 1)), self.seed(), str(rs.choice(["plain", "negzero"]))))
+        elif s == "write_nonfinite":
+            first = int(rs.randint(0, self.dim)) if rs.randint(0, 4) else 0
+            count = self.dim - first if rs.randint(0, 4) == 0 else int(rs.randint(1, min(self.dim - first, 600) + 1))
+            self.emit(("write", first, count, self.seed(), str(rs.choice(["inf", "nan"]))))
+        elif s == "collapse":
+            self.cleanse()
+            self.dense()
+            first, num = self.a_range()
+            v = self.good_outcome(first, num)
+            if v is None or rs.randint(0, 2):
+                self.emit(("measure_qubits", first, num, float(rs.uniform(0.02, 0.98))))
+            else:
+                self.emit(("postselect", first, num, v))
+        elif s == "compact":
+            self.want_mode([0, 1])
+            self.emit(("reset",))
+            self.emit(("qcomp", self.Cn, self.a0))
+        elif s == "queued_mode1":
+            self.want_mode([1])
+            self.cleanse()
+            if self.strict:                                                  # (strict passes are not queued)
+                self.emit(("fill", self.seed()))
+            if self.pending:
+                self.emit(("fill", self.seed()) if rs.randint(0, 2) else ("flush",))
+            for _ in range(int(rs.randint(1, 6))):
+                self.emit(self.gate())
+        elif s == "queued_behind_basis":
+            self.want_mode([1])
+            self.emit(("reset",) if rs.randint(0, 2) else ("measure", self.r()))
+            if self.M and rs.randint(0, 2):                                  # a circuit front: the H layer, then part of the multiply ladder
+                for l in range(self.M, self.n):
+                    self.emit(("h", l))
+                x = self.a0 % self.Cn
+                for l in range(self.M, self.M + int(rs.randint(0, min(self.L, 3) + 1))):
+                    self.emit(("camodc", self.Cn, x, l))
+                    x = (x * x) % self.Cn
+                if rs.randint(0, 2):
+                    self.emit(self.gate())
+            else:
+                for _ in range(int(rs.randint(1, 5))):
+                    self.emit(self.gate())
+        elif s == "load":
+            slot = self.finite_slot()
+            if rs.randint(0, 2):
+                self.emit(self.op_of(str(rs.choice(["h", "fill", "reset", "u1"]))))   # (so that the load changes something)
+            self.emit(("load", slot))
+        else:
+            raise ValueError(s)
+
+    def probe(self, s, f):
+        self.setting(s, f)
+        for _ in range(int(self.rs.choice([0, 0, 1, 2]))):
+            self.emit(self.quiet())
+        if f == "norm2" and self.m.holds_nonfinite():
+            f = "total"
+        self.emit(self.op_of(f))
+
+    def refuse(self):
+        """a refused call, then a window that shows the state untouched"""
+        inner, status = self.refused()
+        self.emit(("refused", inner, status))
+        first = int(self.rs.randint(0, self.dim))
+        self.emit(("read", first, int(self.rs.randint(1, min(self.dim - first, 2000) + 1))))
+
+    def underflow(self):
+        """a collapse that itself makes -0 out of negative subnormals, on a state whose zero pass was NOT owed before it; then a
+        gate that leaves most amplitudes alone (the reference turns their -0 into +0 all the same) and a read"""
+        rs = self.rs
+        self.emit(("write", 0, self.dim, self.seed(), "subnormal"))
+        c, t = self.qubits(2)
+        self.emit(("cphase", c, t, float(rs.uniform(-3, 3))))               # runs the pass the write owes
+        if self.mode == 1:
+            self.emit(("flush",))
+        first = int(rs.randint(0, self.n))
+        self.emit(("postselect", first, 1, int(np.argmax(self.m.marginal(first, 1)))))
+        if rs.randint(0, 2) or self.n < 3:
+            self.emit(("cphase", c, t, float(rs.uniform(-3, 3))))
+        else:
+            self.emit(("cu2", *self.qubits(3), self.seed()))
+        self.emit(("read", 0, self.dim))
+
+    def extra(self):
+        rs = self.rs
+        if rs.randint(0, 7) == 0:
+            self.refuse()
+            return
+        if rs.randint(0, 12) == 0:
+            self.underflow()
+            return
+        f = FOLLOWING[int(rs.randint(0, len(FOLLOWING)))]
+        if (f in ("camodc", "qcomp") and self.M == 0) or (f == "norm2" and self.m.holds_nonfinite()):
+            f = "h"
+        if f == "write" and not self.allow_nonfinite:
+            self.cleanse()
+        self.emit(self.op_of(f))
+
+
+def generate(ob, seed, small=False, length=None):
+    """(Config, ops) of one seed; an op of the list is (register number, op tuple).  small: registers of n <= 6, no non-finite
+    values, `length` ops (the sequences test_register_model.py replays in long double)"""
+    global _SCHEDULE
+    cfg = Config(seed, small)
+    rs = np.random.RandomState(104729 * seed + 71)
+    g = _Gen(ob, cfg.shapes[0], cfg.mode, rs, allow_nonfinite=not small)
+    if small:
+        while len(g.ops) < length:
+            s, f = SETTING[int(rs.randint(0, len(SETTING)))], FOLLOWING[int(rs.randint(0, len(FOLLOWING)))]
+            if pair_is_legal(s, f, cfg.shapes[0], False) and s != "write_nonfinite" and rs.randint(0, 2):
+                g.probe(s, f)
+            else:
+                g.extra()
+        return cfg, [(0, op) for op in g.ops[:length]]
+    if _SCHEDULE is None:
+        _SCHEDULE = _schedule()
+    probes = list(_SCHEDULE[seed])
+    rs.shuffle(probes)
+    for s, f in probes:
+        g.probe(s, f)
+        if rs.randint(0, 6) == 0:
+            g.emit(("read", 0, g.dim))
+        if rs.randint(0, 5) == 0:                                            # about one op in twenty is a refused call
+            g.refuse()
+        if rs.randint(0, 10) < 2:
+            g.extra()
+    while len(g.ops) < 40:
+        g.extra()
+    g.emit(("read", 0, g.dim))
+    ops = [(0, op) for op in g.ops]
+    if len(cfg.shapes) > 1:                                                  # the second register: random ops, dealt in between
+        h = _Gen(ob, cfg.shapes[1], cfg.modes[1], rs, tag=1)
+        while len(h.ops) < max(12, len(g.ops) // 3):
+            h.extra()
+        h.emit(("read", 0, h.dim))
+        where = np.sort(rs.randint(0, len(ops) + 1, len(h.ops)))
+        for k in range(len(h.ops) - 1, -1, -1):
+            ops.insert(int(where[k]), (1, h.ops[k]))
+    return cfg, ops
+
+
+# ---- what a list of ops reaches (judged on the list alone) ---------------------------------------------------------------------
+
+def is_quiet(op, M):
+    return op[0] in ("sample", "stats") or (op[0] == "marginal" and op[1] >= M)
+
+
+def compact_shape(shape):
+    L, M, Cn, a = shape
+    cb = {15: 2, 21: 3}.get(Cn)
+    return M in (4, 5) and L >= 8 and L + M >= 12 and cb is not None and L + cb >= 14
+
+
+def pairs_reached(shape, start_mode, ops):
+    """{(setting kind, following kind): count} over the ops of one register: a pair counts when nothing but quiet calls stand
+    between the two"""
+    L, M, Cn, a = shape
+    dim = 1 << (L + M)
+    mode, pending, strict = start_mode, False, False
+    kinds = []
+    for i, op in enumerate(ops):
+        k, s = op[0], None
+        if k == "reset": s = "reset"
+        elif k == "measure": s = "measure_state"
+        elif k == "fill": s = "fill"
+        elif k == "load": s = "load"
+        elif k == "write":
+            if op[4] in ("inf", "nan"): s = "write_nonfinite"
+            elif op[2] < dim: s = "write_partial"
+            elif op[4] == "negzero": s = "write_full_negzero"
+        elif k in ("measure_qubits", "postselect"): s = "collapse"
+        elif k == "qcomp" and i and ops[i - 1][0] == "reset" and mode in (0, 1) and compact_shape(shape): s = "compact"
+        elif k in QUEUED and mode == 1 and not strict:
+            s = "queued_behind_basis" if pending else "queued_mode1"
+        kinds.append(s)
+        if k == "fusion": mode = op[1]
+        if k in ("reset", "measure"): pending = mode >= 0
+        elif k in ("sample", "marginal", "stats", "measure_qubits", "postselect", "refused") or (k in QUEUED and mode == 1 and not strict): pass
+        else: pending = False
+        if k == "write" and op[4] in ("inf", "nan"): strict = True
+        elif k in ("reset", "measure", "fill"): strict = False
+    out = {}
+    for i, s in enumerate(kinds):
+        if s is None:
+            continue
+        for op in ops[i + 1:]:
+            if op[0] in FOLLOWING:
+                out[(s, op[0])] = out.get((s, op[0]), 0) + 1
+            if not is_quiet(op, M):
+                break
+    return out

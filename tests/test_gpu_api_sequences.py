@@ -1,0 +1,484 @@
+"""GPU: random call sequences over the whole API of an unsharded register, and a dozen named chains, against the host model of
+tests/register_model.py.  A register carries lazy state between calls (the strict flag, the owed zero pass, the gate queue, a
+pending basis state, a compact circuit result, the fusion mode) and every entry point settles it in its own way; the files of
+the single features check each call next to a few hand-picked neighbours, this one checks chains of them.  Everything a call
+returns is compared bit for bit (NaN matching NaN) with the model; full reads are rare, so that the lazy forms live long.
+
+One seed alone:  QCX_SEQ_CASE=<seed> [QCX_SEQ_OPS=<k>] python -m pytest tests/test_gpu_api_sequences.py -m gpu -q -s -k random
+(a failure prints the seed, the index of the failing op and the ops up to it as a Python literal)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import register_model as rm
+
+pytestmark = pytest.mark.gpu
+
+KNOB_KEYS = sorted({k for d in rm.KNOBS_N9 + rm.KNOBS_ANY for k in d})
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def same(got, want, what):
+    """bitwise, NaN matching NaN"""
+    got, want = np.asarray(got, dtype=np.float64).reshape(-1), np.asarray(want, dtype=np.float64).reshape(-1)
+    assert got.shape == want.shape, what
+    gn, wn = np.isnan(got), np.isnan(want)
+    assert np.array_equal(gn, wn), f"{what}: NaN positions differ at {np.flatnonzero(gn != wn)[:6]}"
+    bad = np.flatnonzero(bits(got[~gn]) != bits(want[~wn]))
+    assert bad.size == 0, f"{what}: {bad.size} values differ, first at {bad[:4]}: {got[~gn][bad[:4]]} vs {want[~wn][bad[:4]]}"
+
+
+def compact_measures(qc, reg):
+    v = C.c_ulong(0)
+    assert qc.lib().qcx_compact_measure_stats(reg._h, C.byref(v)) == 0
+    return int(v.value)
+
+
+def compact_chains(qc, reg):
+    v = C.c_ulong(0)
+    assert qc.lib().qcx_compact_stats(reg._h, C.byref(v)) == 0
+    return int(v.value)
+
+
+def measure_last_stats(qc):
+    s, b = C.c_uint(0), C.c_uint(0)
+    qc.lib().qcx_measure_last_stats(C.byref(s), C.byref(b))
+    return s.value, b.value
+
+
+def status_of(qc, call):
+    try:
+        call()
+    except qc.QcxError as e:
+        return e.status
+    return rm.NO_ERROR
+
+
+def apply_to_register(qc, reg, op, path_of):
+    """one op on the GPU register; returns what the call returns, in the form register_model.apply_to_model gives"""
+    k = op[0]
+    if k == "reset": qc.reset_register(reg)
+    elif k == "fill": reg.fill_random(op[1])
+    elif k == "write": reg.write(rm.window_data(reg.num_states, op[2], op[3], op[4]), op[1])
+    elif k == "read": return reg.read(op[1], op[2])
+    elif k == "h": qc.hadamard_gate(op[1], reg)
+    elif k == "cphase": qc.c_phase_shift_gate(op[1], op[2], op[3], reg)
+    elif k == "camodc": qc.c_amodc_gate(op[1], op[2], op[3], reg)
+    elif k == "iqft": qc.inverse_QFT(reg)
+    elif k == "qcomp": qc.quantum_computation(op[1], op[2], reg)
+    elif k == "u1": qc.one_qubit_gate(op[1], rm.matrix_data(2, op[2]), reg)
+    elif k == "cu1": qc.c_one_qubit_gate(op[1], op[2], rm.matrix_data(2, op[3]), reg)
+    elif k == "u2": qc.two_qubit_gate(op[1], op[2], rm.matrix_data(4, op[3]), reg)
+    elif k == "cu2": qc.c_two_qubit_gate(op[1], op[2], op[3], rm.matrix_data(4, op[4]), reg)
+    elif k == "measure": return qc.measure_state(reg, op[1])
+    elif k == "sample": return qc.sample_states(reg, rm.sample_draws(op[1], op[2]))
+    elif k == "marginal": return reg.marginal(op[1], op[2])
+    elif k == "measure_qubits": return reg.measure_qubits(op[1], op[2], op[3], strict=False)
+    elif k == "postselect": return reg.postselect(op[1], op[2], op[3], strict=False)
+    elif k == "total": return reg.total_probability()
+    elif k == "norm2": return reg.norm2()
+    elif k == "save": reg.save(path_of(op[1]))
+    elif k == "load": reg.load(path_of(op[1]))
+    elif k == "flush": reg.flush()
+    elif k == "sync": reg.synchronize()
+    elif k == "fusion": reg.set_fusion(op[1])
+    elif k == "stats":
+        reg.fusion_stats(); reg.marginal_stats(); reg.sample_stats(); reg.collapse_stats(); compact_measures(qc, reg)
+    elif k == "refused":
+        inner = op[1]
+        j = inner[0]
+        if j == "postselect":
+            p, st = reg.postselect(inner[1], inner[2], inner[3], strict=False)
+            return (p, st) if inner[3] < (1 << inner[2]) and inner[1] + inner[2] <= reg.num_qubits else st
+        if j == "h": return status_of(qc, lambda: qc.hadamard_gate(inner[1], reg))
+        if j == "marginal": return status_of(qc, lambda: reg.marginal(inner[1], inner[2]))
+        if j == "cphase": return status_of(qc, lambda: qc.c_phase_shift_gate(inner[1], inner[2], inner[3], reg))
+        if j == "u1": return status_of(qc, lambda: qc.one_qubit_gate(inner[1], rm.matrix_data(2, inner[2]), reg))
+        if j == "u1x": return status_of(qc, lambda: qc.one_qubit_gate(inner[1], rm.matrix_data(2, inner[2], ulp=True), reg))
+        if j == "u2x": return status_of(qc, lambda: qc.two_qubit_gate(inner[1], inner[2], rm.matrix_data(4, inner[3], ulp=True), reg))
+        raise ValueError(f"unknown refused op {op!r}")
+    else:
+        raise ValueError(f"unknown op {op!r}")
+    return None
+
+
+def compare(op, got, want):
+    k = op[0]
+    if k in ("read", "marginal"):
+        same(got, want, k)
+    elif k in ("measure",):
+        assert got == want, f"index {got} != {want}"
+    elif k == "sample":
+        assert np.array_equal(got, want), f"indices {got.tolist()} != {want.tolist()}"
+    elif k == "measure_qubits":
+        assert (got[0], got[2]) == (want[0], want[2]), f"(outcome, status) {(got[0], got[2])} != {(want[0], want[2])}"
+        same([got[1]], [want[1]], "probability")
+    elif k == "postselect":
+        assert got[1] == want[1], f"status {got[1]} != {want[1]}"
+        same([got[0]], [want[0]], "probability")
+    elif k == "total":
+        same([got], [want], "total_probability")
+    elif k == "norm2":
+        if want is not None:                                               # (a tree sum: not bit-defined; skipped on a non-finite state)
+            assert abs(got - want) < 1e-9, f"norm2 {got!r} vs {want!r}"
+    elif k == "refused":
+        if isinstance(want, tuple):
+            assert got[1] == want[1], f"status {got[1]} != {want[1]}"
+            same([got[0]], [want[0]], "probability")
+        else:
+            assert got == want, f"status {got} != {want}"
+    else:
+        assert got is None and want is None
+
+
+FLUSHES_NOTHING = ("reset", "fill", "stats", "refused") + rm.QUEUED      # (in mode 1: these leave a queued circuit queued, or drop it)
+
+
+def run_ops(qc, ob, shapes, modes, ops, tmp_path, header, compact=False):
+    """the ops on fresh registers and fresh models, everything returned compared; ends with a full read of every register.
+    compact: register 0 has a shape at which reset + quantum_computation must run as a compact chain (qcx_compact_stats moves:
+    with the call in mode 0, with the first call that flushes the queue in mode 1)"""
+    regs, models = [], []
+    done = []
+    modes = list(modes)
+    owed = None                                 # the compact-chain count register 0 must show after its next flushing call
+    try:
+        for (L, M, Cn, a), mode in zip(shapes, modes):
+            reg = qc.Register(L, M)
+            reg.set_fusion(mode)
+            regs.append(reg)
+            models.append(rm.RegisterModel(ob, L, M))
+        for i, (which, op) in enumerate(ops):
+            done.append((which, op))
+            try:
+                chains = compact_chains(qc, regs[0]) if compact and which == 0 else 0
+                got = apply_to_register(qc, regs[which], op, lambda slot: str(tmp_path / f"reg{which}_slot{slot}.qcx"))
+                want = rm.apply_to_model(models[which], op)
+                compare(op, got, want)
+                if op[0] == "fusion":
+                    modes[which] = op[1]
+                if compact and which == 0:
+                    if owed is not None and op[0] not in FLUSHES_NOTHING:
+                        assert compact_chains(qc, regs[0]) == owed, f"the queued circuit did not run as a compact chain ({chains} chains before, {compact_chains(qc, regs[0])} now)"
+                    if owed is not None and op[0] != "stats":
+                        owed = None
+                    if op[0] == "qcomp" and len(done) > 1 and [o for w, o in done[:-1] if w == 0][-1:] == [("reset",)]:
+                        if modes[0] == 0:
+                            assert compact_chains(qc, regs[0]) == chains + 1, "reset + quantum_computation did not run as a compact chain"
+                        elif modes[0] == 1:
+                            owed = chains + 1
+                if i + 1 == len(ops):
+                    for w in range(len(regs)):
+                        same(regs[w].read(), models[w].a, f"the final state of register {w}")
+            except Exception as e:
+                raise AssertionError(f"{header}\nop {i} on register {which}: {op!r}\n{type(e).__name__}: {e}\nops = {done!r}") from e
+    finally:
+        for reg in regs:
+            reg.close()
+
+
+# ---- random sequences ----------------------------------------------------------------------------------------------------------
+
+def one_seed(qc, ob, seed, tmp_path):
+    cfg, ops = rm.generate(ob, seed)
+    limit = os.environ.get("QCX_SEQ_OPS")
+    if limit:
+        ops = ops[:int(limit)]
+    old = {k: qc.lib().qcx_tune_get(k.encode()) for k in KNOB_KEYS}
+    try:
+        qc.tune(**cfg.knobs)
+        run_ops(qc, ob, cfg.shapes, cfg.modes, ops, tmp_path, f"{cfg!r} ({len(ops)} ops)", compact=cfg.compact)
+    finally:
+        qc.tune(**old)
+
+
+ONLY = os.environ.get("QCX_SEQ_CASE")
+
+
+@pytest.mark.parametrize("seed", [int(ONLY)] if ONLY else range(rm.NSEEDS))
+def test_random_sequences_against_the_model(qc, ob, tmp_path, seed):
+    one_seed(qc, ob, seed, tmp_path)
+
+
+# ---- named chains ----------------------------------------------------------------------------------------------------------------
+
+class Chain:
+    """one register and its model, op by op; do() compares what the call returns and hands it back"""
+
+    def __init__(self, qc, ob, L, M, mode, tmp_path, tag="a"):
+        self.qc, self.ob, self.tmp, self.tag = qc, ob, tmp_path, tag
+        self.reg = qc.Register(L, M)
+        self.reg.set_fusion(mode)
+        self.m = rm.RegisterModel(ob, L, M)
+        self.n, self.dim = L + M, 1 << (L + M)
+        self.done = []
+
+    def do(self, *op):
+        self.done.append(op)
+        try:
+            got = apply_to_register(self.qc, self.reg, op, lambda slot: str(self.tmp / f"{self.tag}_slot{slot}.qcx"))
+            compare(op, got, rm.apply_to_model(self.m, op))
+        except Exception as e:
+            raise AssertionError(f"op {len(self.done) - 1}: {op!r}\n{type(e).__name__}: {e}\nops = {self.done!r}") from e
+        return got
+
+    def state(self):
+        return self.do("read", 0, self.dim)
+
+    def close(self):
+        self.reg.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def test_chain_postselect_queue_sample_partial_write_controlled_gate(qc, ob, tmp_path):
+    with Chain(qc, ob, 9, 5, 1, tmp_path) as c:
+        c.do("fill", 11)
+        c.do("postselect", 2, 3, 5)                                       # leaves the zero pass owed
+        assert c.reg.collapse_stats() == (0, 1, 1)
+        p0, g0 = c.reg.fusion_stats()
+        c.do("h", 3); c.do("cphase", 4, 9, 0.3); c.do("h", 13); c.do("cphase", 0, 13, -1.2)
+        assert c.reg.fusion_stats() == (p0, g0), "mode 1 queues the gates"
+        c.do("sample", 5, 9)                                              # settles the queue
+        assert c.reg.sample_stats()[0] >= 1
+        c.do("write", 1000, 300, 6, "negzero")
+        c.do("cu2", 1, 6, 2, 7)
+        c.state()
+
+
+@pytest.fixture(scope="module")
+def shor_20(ob):
+    """the Shor circuit's result at L = 15, M = 5 (the compact chain runs there), computed once; tests copy it"""
+    n = 20
+    w = np.zeros(2 << n)
+    ob.reset(w, n)
+    ob.quantum_computation(w, n, 5, 21, 2, threads=8)
+    return w
+
+
+def compact_start(c, shor_20):
+    """reset + quantum_computation on the GPU, the shared oracle result into the model"""
+    c.qc.reset_register(c.reg)
+    c.qc.quantum_computation(21, 2, c.reg)
+    c.m.a = shor_20.copy()
+    c.done += [("reset",), ("qcomp", 21, 2)]
+
+
+def test_chain_compact_marginal_inside_m_keeps_the_compact_form(qc, ob, tmp_path, shor_20):
+    with Chain(qc, ob, 15, 5, 0, tmp_path) as c:
+        k0 = compact_chains(qc, c.reg)
+        compact_start(c, shor_20)
+        assert compact_chains(qc, c.reg) == k0 + 1
+        m0 = compact_measures(qc, c.reg)
+        c.do("marginal", 1, 3)                                            # inside the M register: expanded into the buffer ...
+        assert c.reg.marginal_stats() == (3, 1)
+        c.do("sample", 3, 8)                                              # ... and the compact form is still what is scanned
+        assert compact_measures(qc, c.reg) == m0 + 1 and c.reg.sample_stats()[0] >= 1
+        c.do("marginal", 7, 4)
+        assert c.reg.marginal_stats() == (1, 1) and compact_measures(qc, c.reg) == m0 + 2
+        c.do("u1", 2, 3)
+        c.do("marginal", 0, 6)
+        assert c.reg.marginal_stats() == (0, 1)
+        c.do("read", 12345, 4096)
+
+
+def test_chain_compact_postselect_iqft_measure_marginal_two_qubit_gate(qc, ob, tmp_path, shor_20):
+    with Chain(qc, ob, 15, 5, 0, tmp_path) as c:
+        compact_start(c, shor_20)
+        v = int(np.argmax(c.m.marginal(5, 4)))
+        c.do("postselect", 5, 4, v)
+        assert c.reg.collapse_stats() == (3, 1, 1)
+        c.do("iqft")
+        c.do("measure", 0.61)
+        c.do("marginal", 3, 6)                                            # the pending basis state: no kernel
+        assert c.reg.marginal_stats() == (2, 0)
+        c.do("u2", 4, 17, 9)
+        c.do("marginal", 3, 6)
+        assert c.reg.marginal_stats() == (0, 1)
+        c.do("read", 0, 1 << 14)
+        c.do("total")
+
+
+def test_chain_inf_window_error_keeps_state_then_finite_overwrite(qc, ob, tmp_path):
+    with Chain(qc, ob, 8, 4, 0, tmp_path) as c:
+        c.do("fill", 3)
+        c.do("write", 700, 64, 21, "inf")
+        c.do("cu1", 5, 1, 4)                                              # strict pass
+        got = c.do("measure_qubits", 0, 0, 0.5)                           # the total is not finite: refused, state kept
+        assert got[2] == rm.BAD_ARGUMENTS
+        c.do("read", 600, 300)
+        c.do("h", 7)                                                      # still strict
+        c.do("write", 0, c.dim, 22, "negzero")                            # finite data over everything
+        c.do("h", 0)
+        c.do("postselect", 3, 2, 1)
+        c.state()
+
+
+def test_chain_measure_mode_switches_save_load(qc, ob, tmp_path):
+    with Chain(qc, ob, 9, 5, 0, tmp_path) as c:
+        c.do("fill", 8)
+        c.do("measure", 0.37)
+        c.do("fusion", -1)                                                # the flush writes the pending basis state
+        c.do("u2", 0, 13, 5)
+        c.do("fusion", 1)
+        c.do("h", 6); c.do("cphase", 6, 2, 0.8); c.do("camodc", 21, 4, 9)
+        c.do("save", 0)
+        c.do("h", 1); c.do("u1", 3, 12); c.do("cphase", 1, 12, 2.0)
+        c.do("load", 0)
+        c.do("marginal", 4, 5)
+        assert c.reg.marginal_stats() == (0, 1)
+        c.state()
+
+
+def test_chain_front_queued_behind_reset_then_postselect_is_not_basis_only(qc, ob, tmp_path):
+    L, M = 9, 5
+    with Chain(qc, ob, L, M, 1, tmp_path) as c:
+        c.do("reset")
+        for l in range(M, M + L):
+            c.do("h", l)
+        x = 2
+        for l in range(M, M + L):
+            c.do("camodc", 21, x, l)
+            x = (x * x) % 21
+        v = int(np.flatnonzero(c.m.marginal(0, M) > 0)[1])
+        c.do("postselect", 0, M, v)
+        assert c.reg.collapse_stats() == (0, 1, 1), "gates were queued: the basis-state shortcut does not apply"
+        c.do("sample", 2, 17)
+        assert c.reg.sample_stats()[0] >= 1
+        c.do("iqft")
+        c.state()
+
+
+def test_chain_fill_over_a_compact_result(qc, ob, tmp_path):
+    with Chain(qc, ob, 15, 5, 0, tmp_path) as c:
+        k0 = compact_chains(qc, c.reg)
+        qc.reset_register(c.reg); qc.quantum_computation(21, 2, c.reg)
+        assert compact_chains(qc, c.reg) == k0 + 1
+        c.do("fill", 4)
+        c.do("marginal", 8, 3)
+        assert c.reg.marginal_stats() == (0, 1)
+        c.do("measure_qubits", 3, 4, 0.42)
+        assert c.reg.collapse_stats() == (0, 1, 1)
+        c.do("read", 99, 5000)
+        c.do("total")
+
+
+def test_chain_two_registers_nan_write_between_the_others_measurements(qc, ob, tmp_path):
+    def run_b(with_a):
+        out = []
+        with Chain(qc, ob, 10, 4, 0, tmp_path, "b") as b, Chain(qc, ob, 7, 4, 1, tmp_path, "a") as a:
+            b.do("fill", 5)
+            b.do("h", 3)
+            if with_a:
+                a.do("fill", 1); a.do("h", 2)
+            # (the first word of the scan's statistics counts records looked at closely, which depends on timing: it is compared
+            #  across A's write, which borrows that word, and only the record count between the two runs)
+            out.append(b.do("sample", 7, 17).tolist()); out.append(measure_last_stats(qc)[1])
+            if with_a:
+                before = measure_last_stats(qc)
+                a.do("write", 100, 50, 3, "nan")
+                a.do("h", 4)
+                assert measure_last_stats(qc) == before, "a write into A changed the statistics of B's last scan"
+            out.append(b.do("sample", 8, 8).tolist()); out.append(measure_last_stats(qc)[1])
+            if with_a:
+                a.do("read", 0, a.dim)
+            out.append(b.do("measure", 0.77)); out.append(measure_last_stats(qc)[1])
+            out.append(bits(b.state()).tolist())
+            if with_a:
+                a.do("cu1", 1, 5, 2)
+                a.state()
+        return out
+
+    assert run_b(True) == run_b(False)
+
+
+def test_chain_circuit_queued_in_mode_1_sample_then_partial_write(qc, ob, tmp_path, shor_20):
+    with Chain(qc, ob, 15, 5, 1, tmp_path) as c:
+        k0, m0 = compact_chains(qc, c.reg), compact_measures(qc, c.reg)
+        compact_start(c, shor_20)                                          # mode 1: everything is still queued
+        assert compact_chains(qc, c.reg) == k0
+        c.do("sample", 9, 4)                                              # the observer's flush keeps the result compact
+        assert compact_chains(qc, c.reg) == k0 + 1 and compact_measures(qc, c.reg) == m0 + 1
+        c.do("write", 4000, 128, 5, "negzero")                            # into the expanded register
+        c.do("marginal", 0, 5)
+        assert c.reg.marginal_stats() == (0, 1)
+        c.do("h", 0)
+        c.do("read", 3900, 400)
+
+
+def test_chain_gates_queued_behind_a_pending_basis_state_are_seen(qc, ob, tmp_path):
+    with Chain(qc, ob, 10, 0, 1, tmp_path) as c:
+        c.do("reset")
+        c.do("marginal", 0, 3)
+        assert c.reg.marginal_stats() == (2, 0)
+        c.do("h", 0); c.do("h", 9)
+        c.do("marginal", 0, 3)                                            # gates are queued: not the host shortcut
+        assert c.reg.marginal_stats() == (0, 1)
+        c.do("measure", 0.3)
+        c.do("h", 4)
+        c.do("sample", 3, 9)
+        assert c.reg.sample_stats()[0] >= 1
+        c.do("measure", 0.9)
+        c.do("postselect", 2, 4, (c.m.measure_state(0.5) >> 2) & 15)      # (the model's state is that basis state already)
+        assert c.reg.collapse_stats() == (2, 0, 0)
+        c.state()
+
+
+def test_chain_negative_zeros_wait_for_the_first_gate(qc, ob, tmp_path):
+    with Chain(qc, ob, 7, 4, 0, tmp_path) as c:
+        c.do("write", 0, c.dim, 31, "negzero")
+        c.do("marginal", 2, 5); c.do("sample", 1, 8); c.do("total")
+        c.do("read", 0, c.dim)                                            # the -0 are still there
+        c.do("save", 1)
+        c.do("cphase", 10, 0, 0.4)                                        # canonicalises every amplitude, touched or not
+        c.state()
+        c.do("load", 1)
+        c.do("fusion", 1)
+        c.do("cphase", 10, 0, 0.4)
+        c.do("cu2", 3, 0, 8, 2)
+        c.state()
+
+
+def test_chain_collapse_that_underflows_to_negative_zero_owes_the_zero_pass(qc, ob, tmp_path):
+    """the collapse itself makes -0 (negative subnormals times s < 1/2) on a register whose zero pass was not owed: the next gate
+    must still canonicalise every amplitude, also those it does not act on"""
+    for follow in (("cphase", 9, 10, 0.7), ("cu1", 10, 9, 6), ("cu2", 10, 9, 8, 7), ("h", 10)):
+        with Chain(qc, ob, 7, 4, 0, tmp_path) as c:
+            c.do("write", 0, c.dim, 77, "subnormal")
+            c.do("cphase", 9, 10, 0.4)                                    # runs the pass the write owes; touches a quarter of the state
+            v = int(np.argmax(c.m.marginal(0, 1)))
+            p, st = c.do("postselect", 0, 1, v)
+            assert st == 0 and p > 4.0
+            made = (c.m.a == 0) & np.signbit(c.m.a)
+            idx = np.arange(c.dim)
+            alone = np.repeat((idx & 1 == v) & ((idx >> 10) & 1 == 0), 2)   # kept, and outside what the gates below act on (but H)
+            assert np.count_nonzero(made & alone) > 50, "the chain must make -0 where the next gate does not act"
+            c.do("read", 0, 64)                                           # the -0 are the state until a gate runs
+            c.do(*follow)
+            c.state()
+
+
+def test_chain_pending_basis_state_through_the_flushing_observers(qc, ob, tmp_path):
+    with Chain(qc, ob, 8, 4, 0, tmp_path) as c:
+        c.do("fill", 2)
+        c.do("measure", 0.52)
+        c.do("total")
+        c.do("measure", 0.1)
+        c.do("norm2")
+        c.do("measure", 0.99)
+        c.do("save", 0)
+        c.do("fill", 3)
+        c.do("load", 0)
+        c.do("iqft")
+        c.do("measure_qubits", 4, 8, 0.35)
+        c.do("qcomp", 15, 7)
+        c.state()

@@ -67,6 +67,81 @@ def test_hadamard_all_kernel_variants(qc, ob, variant):
         qc.tune(**defaults)
 
 
+@pytest.mark.parametrize("variant", [dict(h_variant=1, h_ppt=1, h_block=64, h_streams_log2=2, h_skew=1),
+                                     dict(h_variant=1, h_ppt=2, h_block=128, h_streams_log2=3, h_skew=3),
+                                     dict(h_variant=1, h_ppt=1, h_block=256, h_streams_log2=1, h_skew=5)])
+def test_hadamard_skewed_streams(qc, ob, variant):
+    """h_skew: stream j of the pair form walks its segment rotated by j * skew tiles.  The launcher honours it with h_variant = 1
+    and streams on, i.e. when the grid has at least 2^h_streams_log2 tiles: at n = 13 for all three variants, at n = 10 for the
+    first and the third only (the second has 4 tiles for 8 streams there and runs unskewed)"""
+    keys = ("h_variant", "h_ppt", "h_block", "h_streams_log2", "h_skew")
+    defaults = {k: qc.lib().qcx_tune_get(k.encode()) for k in keys}
+    try:
+        qc.tune(**variant)
+        for n in (10, 13):
+            for q in range(n):
+                a = ob.random_state(n, 200 + q)
+                with qc.Register(n, 0) as reg:
+                    reg.write(a); qc.hadamard_gate(q, reg); got = reg.read()
+                want = a.copy(); ob.hadamard(want, n, q)
+                assert_bits_equal(got, want, f"H {variant} n={n} q={q}")
+    finally:
+        qc.tune(**defaults)
+
+
+PHASE_FORMS = [dict(ph_grid_cap=1), dict(ph_grid_cap=3, ph_apt=2), dict(ph_apt=4, ph_block=256), dict(ph_apt=2, ph_block=256, ph_grid_cap=3),
+               dict(ph_block=256, ph_lines=0), dict(ph_apt=4, ph_grid_cap=1, ph_lines=0), dict(ph_apt=2, ph_grid_cap=3, ph_nt=0, ph_lines=0)]
+
+
+@pytest.mark.parametrize("variant", PHASE_FORMS, ids=[",".join(f"{k}={v}" for k, v in d.items()) for d in PHASE_FORMS])
+def test_cphase_forced_launch_forms(qc, ob, variant):
+    """k_phase with 1, 2 and 4 amplitudes per lane, 64 and 256 threads, and grids capped at 1 and 3 workgroups, so that the
+    grid-stride loop iterates.  n = 13: 2048 touched amplitudes, every ph_apt honoured, up to 32 steps.  n = 10: 256 touched
+    amplitudes, where the launcher lowers ph_apt to 1 (it wants 256 * apt of them) -- there only ph_block and the caps are
+    cases: 4 steps of a single 64-thread workgroup, or one full step of 256 threads.  ph_lines = 0 sends the masks with a bit
+    below 3 to k_phase too"""
+    keys = ("ph_grid_cap", "ph_apt", "ph_block", "ph_lines", "ph_nt")
+    defaults = {k: qc.lib().qcx_tune_get(k.encode()) for k in keys}
+    try:
+        qc.tune(**variant)
+        for n in (10, 13):
+            for k, (c, t) in enumerate([(0, 1), (2, n - 1), (n - 1, 3), (4, 7), (n - 2, n - 1), (5, 0), (9, 6)]):
+                theta = math.pi / (1 << (1 + k)) if k % 2 else 0.3 + k
+                a = ob.random_state(n, 400 + k)
+                with qc.Register(n, 0) as reg:
+                    reg.write(a); qc.c_phase_shift_gate(c, t, theta, reg); got = reg.read()
+                want = a.copy(); ob.cphase(want, n, c, t, theta)
+                assert_bits_equal(got, want, f"CPHASE {variant} n={n} c={c} t={t}")
+    finally:
+        qc.tune(**defaults)
+
+
+CAM_FORMS = [dict(cam_grid_cap=1), dict(cam_grid_cap=3, cam_logT=9), dict(cam_logT=10, cam_block=512), dict(cam_logT=12, cam_block=1024, cam_grid_cap=3),
+             dict(cam_logT=11, cam_block=512, cam_grid_cap=1), dict(cam_block=1024)]
+
+
+@pytest.mark.parametrize("variant", CAM_FORMS, ids=[",".join(f"{k}={v}" for k, v in d.items()) for d in CAM_FORMS])
+def test_camodc_forced_launch_forms(qc, ob, variant):
+    """k_camodc / k_camodc_table with tiles of 2^8 .. 2^12 amplitudes, 256, 512 and 1024 threads (the closed form; the table
+    form always takes 256) and grids capped at 1 and 3 workgroups, so that a workgroup walks many tiles: permutations,
+    many-to-one multipliers, C > 2^M (table form), controls inside the M register, inside the tile and above it"""
+    keys = ("cam_grid_cap", "cam_logT", "cam_block")
+    defaults = {k: qc.lib().qcx_tune_get(k.encode()) for k in keys}
+    try:
+        qc.tune(**variant)
+        for (L, M, C, atox, ctl) in [(8, 5, 21, 2, 9), (6, 5, 21, 16, 5), (7, 6, 33, 7, 6), (9, 4, 15, 10, 12), (8, 3, 15, 7, 4),
+                                     (7, 5, 21, 10, 0), (5, 7, 100, 30, 11), (3, 7, 127, 3, 8)]:
+            n = L + M
+            a = ob.random_state(n, 700 + ctl)
+            want = a.copy(); ob.camodc(want, n, M, C, atox, ctl)
+            with qc.Register(L, M) as reg:
+                reg.write(a); reg.set_fusion(-1)
+                qc.c_amodc_gate(C, atox, ctl, reg)
+                assert_bits_equal(reg.read(), want, f"C_AMODC {variant} L={L} M={M} C={C} atox={atox} ctl={ctl}")
+    finally:
+        qc.tune(**defaults)
+
+
 @pytest.mark.parametrize("n", [2, 3, 6, 10, 12, 15])
 def test_cphase_bit_exact(qc, ob, n):
     rs = np.random.RandomState(n)

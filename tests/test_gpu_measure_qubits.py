@@ -69,15 +69,16 @@ def draws(P, rs):
     return out
 
 
-def check_call(reg, a, n, first, num, r=None, outcome=None, reads=1):
-    """one measure (r) or postselect (outcome) on a register that holds `a`; returns the state it holds afterwards"""
+def check_call(reg, a, n, first, num, r=None, outcome=None, reads=1, ref=None):
+    """one measure (r) or postselect (outcome) on a register that holds `a`; returns the state it holds afterwards
+    (ref: collapse_ref's answer for a postselect, where the caller has it already)"""
     if outcome is None:
         v, p, want = measure_ref(a, n, first, num, r)
         gv, gp, st = reg.measure_qubits(first, num, r, strict=False)
         assert gv == v, (n, first, num, r, gv, v)
     else:
         v = outcome
-        p, want = collapse_ref(a, n, first, num, v)
+        p, want = ref if ref is not None else collapse_ref(a, n, first, num, v)
         gp, st = reg.postselect(first, num, v, strict=False)
     same([gp], [p], f"probability n={n} range=({first},{num}) outcome={v}")
     if want is None:
@@ -135,6 +136,72 @@ def test_postselect_every_outcome(qc):
                 reg.postselect(0, 3, 4)
             assert e.value.status == BAD_ARGUMENTS and e.value.outcome == 4 and bits(e.value.probability) == 0
             assert "outcome 4" in str(e.value) and "probability 0" in str(e.value)
+
+
+# ---- 2b. every launch form of K11 ---------------------------------------------------------------------------------------------
+
+FORCED_N = (9, 10, 11, 13)
+
+
+def forced_ranges(n):
+    out = []
+    for first in sorted({0, 1, 2, 3, 4, 5, 6, 7, n}):
+        nums = {0, 1, 2, 3, n - 6, n - 5, n - first}
+        out += [(first, num) for num in sorted(nums) if 0 <= num and first + num <= n]
+    for num in (0, 1, 2, 3, n - 6, n - 5):                                 # first = n - num
+        if (n - num, num) not in out:
+            out.append((n - num, num))
+    return out
+
+
+@pytest.fixture(scope="module")
+def forced_refs(ob):
+    """the states of test_forced_kernel_forms and collapse_ref's answers, computed once for all launch forms: a dense state
+    (fill_random) and one with -0 amplitudes and outcomes of probability exactly +0"""
+    refs = {}
+    for n in FORCED_N:
+        z = ob.random_state(n, 70 + n)
+        v = z.reshape(-1, 2)
+        v[np.random.RandomState(n).rand(v.shape[0]) < 0.3] = -0.0
+        v[(np.arange(1 << n) & 5) == 4] = 0.0
+        v[3] = (-0.0, 0.0)
+        for kind, a in (("fill", ob.fill_random(n, 40 + n)), ("zeros", z)):
+            calls = []
+            for first, num in forced_ranges(n):
+                ones = (1 << num) - 1
+                for outcome in sorted({ones, (ones * 5 // 8) & ones}):   # the all-ones value and one other (num = 0: the one there is)
+                    calls.append((first, num, outcome, collapse_ref(a, n, first, num, outcome)))
+            refs[(n, kind)] = (a, calls)
+    return refs
+
+
+@pytest.mark.parametrize("cap", [1, 3, 65536])
+@pytest.mark.parametrize("perm", [0, 1])
+@pytest.mark.parametrize("upt", [4, 8])
+def test_forced_kernel_forms(qc, forced_refs, upt, perm, cap):
+    """k_collapse_range<PERM, U> in its four instantiations under a capped grid: with U = 8 a step is 2048 amplitudes, so at
+    n = 13 one workgroup walks 4 steps (cap 1) or the steps split 2/1/1 (cap 3) -- the PERM index map beyond its first step --,
+    and at n = 9, 10 the only step is partial (the e < count guard).  n == num + 6 (PERM applies) next to n == num + 5 (the
+    plain map).  collapse_ref bit for bit."""
+    keys = ("collapse_upt", "collapse_perm", "collapse_grid_cap")
+    defaults = {k: qc.lib().qcx_tune_get(k.encode()) for k in keys}
+    try:
+        qc.tune(collapse_upt=upt, collapse_perm=perm, collapse_grid_cap=cap)
+        for n in FORCED_N:
+            with qc.Register(n, 0) as reg:
+                for kind in ("fill", "zeros"):
+                    a, calls = forced_refs[(n, kind)]
+                    errors = 0
+                    for first, num, outcome, ref in calls:
+                        if kind == "fill":
+                            reg.fill_random(40 + n)
+                        else:
+                            reg.write(a)
+                        check_call(reg, a, n, first, num, outcome=outcome, ref=ref)
+                        errors += ref[1] is None
+                    assert (errors > 0) == (kind == "zeros")
+    finally:
+        qc.tune(**defaults)
 
 
 # ---- 3. circuits against the oracle ----------------------------------------------------------------------------------------

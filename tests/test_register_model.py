@@ -1,0 +1,237 @@
+"""CPU: the host model of the register API (tests/register_model.py) and its sequence generator.
+
+(a) the model composed of the project's restatements against plain linear algebra in numpy.longdouble: every gate an explicit
+    2^n x 2^n matrix, every collapse a projector and a renormalisation, every marginal a plain sum.  This catches a model that is
+    composed wrongly (qubit order, a collapse that forgets to scale, the inverse QFT on the wrong register); rounding is the
+    business of the restatements' own tests.
+(b) the generator reaches what it claims: every legal (state-setting kind, following kind) pair at least three times over the
+    committed seeds with nothing but quiet calls in between, judged on the op lists alone."""
+import numpy as np
+import pytest
+
+import register_model as rm
+
+LD, CLD = np.longdouble, np.clongdouble
+
+
+# ---- (a) the long-double replay ----------------------------------------------------------------------------------------------
+
+class Replay:
+    def __init__(self, L, M):
+        self.L, self.M, self.n = L, M, L + M
+        self.dim = 1 << self.n
+        self.v = np.zeros(self.dim, dtype=CLD)
+        self.saved = {}
+
+    def embed(self, U, qs, control=None):
+        """the 2^n x 2^n matrix of U on the qubits qs (matrix index bit j = qubit qs[j]), identity where `control` reads 0"""
+        G = np.zeros((self.dim, self.dim), dtype=CLD)
+        for i in range(self.dim):
+            if control is not None and not (i >> control) & 1:
+                G[i, i] = 1
+                continue
+            row = sum(((i >> q) & 1) << j for j, q in enumerate(qs))
+            base = i
+            for q in qs:
+                base &= ~(1 << q)
+            for col in range(1 << len(qs)):
+                G[i, base | sum(((col >> j) & 1) << q for j, q in enumerate(qs))] = U[row, col]
+        return G
+
+    def gate(self, U, qs, control=None):
+        self.v = self.embed(np.asarray(U, dtype=CLD), qs, control) @ self.v
+
+    def h(self, q):
+        s = LD(1) / np.sqrt(LD(2))
+        self.gate([[s, s], [s, -s]], [q])
+
+    def cphase(self, c, t, theta):
+        e = np.cos(LD(theta)) + 1j * np.sin(LD(theta))
+        self.gate(np.diag(np.array([1, 1, 1, e], dtype=CLD)), [c, t])
+
+    def camodc(self, Cn, atox, ctl):
+        A, blk = atox % Cn, 1 << self.M
+        G = np.zeros((self.dim, self.dim), dtype=CLD)
+        for i in range(self.dim):
+            f, dst = i & (blk - 1), i
+            if (i >> ctl) & 1 and f < Cn:
+                dst = (i & ~(blk - 1)) | (((A * f) % Cn) & (blk - 1))
+            G[dst, i] += 1
+        self.v = G @ self.v
+
+    def iqft(self):
+        for l in range(self.n - 1, self.M - 1, -1):
+            self.h(l)
+            for k in range(l - 1, self.M - 1, -1):
+                self.cphase(l, k, np.pi / (1 << (l - k)))
+
+    def qcomp(self, Cn, a):
+        for l in range(self.M, self.n):
+            self.h(l)
+        x = a % Cn
+        for l in range(self.M, self.n):
+            self.camodc(Cn, x, l)
+            x = (x * x) % Cn
+        self.iqft()
+
+    def probs(self):
+        return self.v.real * self.v.real + self.v.imag * self.v.imag
+
+    def marginal(self, first, num):
+        p = self.probs().reshape(1 << (self.n - first - num), 1 << num, 1 << first)
+        return p.sum(axis=(0, 2))
+
+    def collapse(self, first, num, outcome):
+        p = self.marginal(first, num)[outcome]
+        keep = ((np.arange(self.dim) >> first) & ((1 << num) - 1)) == outcome
+        self.v = np.where(keep, self.v, 0) / np.sqrt(p)
+        return p
+
+    def interleaved(self):
+        out = np.empty(2 * self.dim, dtype=LD)
+        out[0::2], out[1::2] = self.v.real, self.v.imag
+        return out
+
+
+def index_is_consistent(p, r, idx, tol):
+    """idx is what the reference's scan of the probabilities p gives for the draw r, up to `tol` on the running sums"""
+    if r <= 0:
+        return idx == 0
+    cum = np.cumsum(p)[:-1]
+    lo = int(np.searchsorted(cum, LD(r) - tol))
+    hi = int(np.searchsorted(cum, LD(r) + tol))
+    return min(lo, p.size - 1) <= idx <= min(hi, p.size - 1)
+
+
+def replay_seed(ob, seed, bound):
+    """the largest deviation of the model from the long-double replay over one small sequence"""
+    cfg, ops = rm.generate(ob, seed, small=True, length=30)
+    L, M, Cn, a = cfg.shapes[0]
+    m, x = rm.RegisterModel(ob, L, M), Replay(L, M)
+    worst = 0.0
+
+    def near(got, want, what):
+        nonlocal worst
+        d = float(np.max(np.abs(np.asarray(got, dtype=LD) - np.asarray(want, dtype=LD)))) if np.size(got) else 0.0
+        worst = max(worst, d)
+        assert d <= bound, f"{cfg} op {i} {op!r}: {what} off by {d:.3e}\nops = {[o for _, o in ops[:i + 1]]!r}"
+
+    for i, (_, op) in enumerate(ops):
+        k = op[0]
+        before = m.a.copy()
+        got = rm.apply_to_model(m, op)
+        if k in ("reset", "fill", "write", "load"):                       # data sources: the replay takes the model's doubles
+            if k == "write":
+                d = rm.window_data(m.dim, op[2], op[3], op[4])
+                x.v[op[1]:op[1] + op[2]] = d[0::2].astype(LD) + 1j * d[1::2].astype(LD)
+            elif k == "load":
+                x.v = x.saved[op[1]].copy()
+            else:
+                x.v = m.a[0::2].astype(LD) + 1j * m.a[1::2].astype(LD)
+                if k == "reset":
+                    assert np.count_nonzero(m.a) == 1 and m.a[2] == 1.0
+        elif k == "save": x.saved[op[1]] = x.v.copy()
+        elif k == "h": x.h(op[1])
+        elif k == "cphase": x.cphase(op[1], op[2], op[3])
+        elif k == "camodc": x.camodc(op[1], op[2], op[3])
+        elif k == "iqft": x.iqft()
+        elif k == "qcomp": x.qcomp(op[1], op[2])
+        elif k == "u1": x.gate(rm.matrix_data(2, op[2]), [op[1]])
+        elif k == "cu1": x.gate(rm.matrix_data(2, op[3]), [op[2]], control=op[1])
+        elif k == "u2": x.gate(rm.matrix_data(4, op[3]), [op[1], op[2]])
+        elif k == "cu2": x.gate(rm.matrix_data(4, op[4]), [op[2], op[3]], control=op[1])
+        elif k == "read": near(got, x.interleaved()[2 * op[1]:2 * (op[1] + op[2])], "window")
+        elif k == "marginal": near(got, x.marginal(op[1], op[2]), "marginal")
+        elif k in ("total", "norm2"): near(got, x.probs().sum(), k)
+        elif k == "measure":
+            assert index_is_consistent(x.probs(), op[1], got, bound), (cfg, i, op, got)
+            x.v[:] = 0
+            x.v[got] = 1
+        elif k == "sample":
+            for r, idx in zip(rm.sample_draws(op[1], op[2]), got):
+                assert index_is_consistent(x.probs(), r, int(idx), bound), (cfg, i, op, r, idx)
+        elif k == "measure_qubits":
+            v, p, st = got
+            assert index_is_consistent(x.marginal(op[1], op[2]), op[3], v, bound), (cfg, i, op, got)
+            near(p, x.marginal(op[1], op[2])[v], "probability")
+            if st == rm.NO_ERROR:
+                x.collapse(op[1], op[2], v)
+            else:
+                assert p == 0 and np.array_equal(m.a.view(np.uint64), before.view(np.uint64))
+        elif k == "postselect":
+            p, st = got
+            near(p, x.marginal(op[1], op[2])[op[3]], "probability")
+            if st == rm.NO_ERROR:
+                x.collapse(op[1], op[2], op[3])
+            else:
+                assert p == 0 and np.array_equal(m.a.view(np.uint64), before.view(np.uint64))
+        elif k == "refused":
+            assert np.array_equal(m.a.view(np.uint64), before.view(np.uint64)), "a refused call changed the model"
+        else:
+            assert k in ("flush", "sync", "fusion", "stats"), op
+        near(m.a, x.interleaved(), "state")
+    return worst
+
+
+SMALL_SEEDS = range(24)
+# the largest deviation of the model from the long-double replay over SMALL_SEEDS is 1.110e-15 (amplitudes and probabilities of
+# states of norm 1 to 4 after up to 30 calls, each of a few binary64 roundings); the bound is 16 times that: 1.776e-14
+MEASURED, BOUND = 1.110e-15, 16 * 1.110e-15
+
+
+def test_model_against_long_double_linear_algebra(ob):
+    worst = max(replay_seed(ob, seed, BOUND) for seed in SMALL_SEEDS)
+    print(f"largest deviation of the model from the long-double replay: {worst:.3e} (bound {BOUND:.3e})")
+    assert worst <= BOUND
+
+
+def test_replay_notices_a_wrongly_composed_model(ob):
+    """the replay is not vacuous: a model with the two-qubit gate's qubits swapped, or a postselect that does not scale, fails it"""
+    class Swapped(rm.RegisterModel):
+        def two_qubit_gate(self, q0, q1, U): super().two_qubit_gate(q1, q0, U)
+
+    class Unscaled(rm.RegisterModel):
+        def postselect(self, first, num, outcome):
+            keep = ((np.arange(self.dim) >> first) & ((1 << num) - 1)) == outcome
+            p = self.marginal(first, num)[outcome]
+            self.a = np.where(np.repeat(keep, 2), self.a, 0.0)
+            return p, rm.NO_ERROR
+
+    for broken in (Swapped, Unscaled):
+        real, rm.RegisterModel = rm.RegisterModel, broken
+        try:
+            with pytest.raises(AssertionError):
+                for seed in SMALL_SEEDS:
+                    replay_seed(ob, seed, BOUND)
+        finally:
+            rm.RegisterModel = real
+
+
+# ---- (b) what the generator reaches ----------------------------------------------------------------------------------------------
+
+def test_generator_reaches_every_pair(ob):
+    total, lengths = {}, []
+    for seed in range(rm.NSEEDS):
+        cfg, ops = rm.generate(ob, seed)
+        assert eval(repr(ops)) == ops, "an op list must replay from its printed form"
+        mine = [op for which, op in ops if which == 0]
+        lengths.append(len(mine))
+        for pair, cnt in rm.pairs_reached(cfg.shapes[0], cfg.mode, mine).items():
+            total[pair] = total.get(pair, 0) + cnt
+        full = sum(1 for op in mine if op[0] == "read" and op[2] == 1 << (cfg.shapes[0][0] + cfg.shapes[0][1]))
+        assert mine[-1][0] == "read" and full <= len(mine) // 3, (seed, full, len(mine))
+    legal = [(s, f) for s in rm.SETTING for f in rm.FOLLOWING
+             if any(rm.pair_is_legal(s, f, rm.Config(k).shapes[0], rm.Config(k).compact) for k in range(rm.NSEEDS))]
+    print(f"ops per seed: {min(lengths)} .. {max(lengths)}")
+    print(" " * 20 + " ".join(f"{f[:6]:>6}" for f in rm.FOLLOWING))
+    for s in rm.SETTING:
+        print(f"{s:20}" + " ".join(f"{total.get((s, f), 0):6d}" if (s, f) in legal else "     -" for f in rm.FOLLOWING))
+    short = [(p, total.get(p, 0)) for p in legal if total.get(p, 0) < 3]
+    assert not short, f"pairs reached fewer than 3 times: {short}"
+    assert len(legal) == len(rm.SETTING) * len(rm.FOLLOWING) - 1           # all but (write of an Inf/NaN, norm2)
+    assert 40 <= min(lengths) and max(lengths) <= 90, lengths      # (a circuit front alone is L + a few calls)
+
+
+def test_generator_is_deterministic(ob):
+    assert rm.generate(ob, 3)[1] == rm.generate(ob, 3)[1]
+    assert rm.generate(ob, 3)[1] != rm.generate(ob, 4)[1]
