@@ -260,6 +260,30 @@ int  qcx_postselect_qubits(qcx_register *reg, unsigned first_qubit, unsigned num
  * kernel), 3 = a compact result expanded first; state_reads = the passes that read amplitudes for the probabilities (the
  * marginal's count); state_writes = collapse passes launched (0 or 1) */
 int  qcx_collapse_last_stats(qcx_register *reg, unsigned *source, unsigned long *state_reads, unsigned long *state_writes);
+/* <psi|P|psi> for a Pauli string P, exactly, from one read of the state (no reference counterpart).  The string is two masks
+ * over the n qubits: x_mask = the qubits that carry X or Y, z_mask = those that carry Z or Y (Y sits on x_mask & z_mask).  With
+ * g = popcount(x_mask & z_mask) mod 4, a = amp[i], b = amp[i ^ x_mask] and every fl() one binary64 rounding (no FMA),
+ *   t      = g even ? fl(fl(a.re*b.re) + fl(a.im*b.im)) : fl(fl(a.im*b.re) - fl(a.re*b.im))
+ *   leaf_i = fl(0.0 + (odd ? -t : t)),  odd = (popcount((i ^ x_mask) & z_mask) + (g >> 1)) & 1
+ * and *value is the marginal's ONE PAIRWISE TREE over all n index bits, lowest first, on these leaves (tests/pauli_ref.py
+ * restates it in numpy; with both masks 0 it is qcx_marginal_probabilities(reg, 0, 0, ..) bit for bit).  Inf and NaN propagate
+ * by IEEE rules; a result is never -0.  The state is read once, every amplitude once, whatever the string (K14, DESIGN s4.5h).
+ * The state, and every lazy form of it, is left exactly as it was: a pending basis state k with no gate queued is answered on
+ * the host (no kernel): x_mask == 0 gives +-1.0 by the parity of popcount(k & z_mask), any other string +0.0; a circuit's
+ * compact result stays compact and is read from the expanded state (the register's buffer gets it first).  Queued gates are
+ * flushed first.  Nothing is written to the state, so a register flagged non-finite keeps its flag and needs nothing special.
+ * qcx_pauli_expectation_sum: one pass per term, in order; values[k] (values may be NULL) is term k's value and
+ *   *total = acc after  acc = 0.0; for k in order: acc = fl(acc + fl(coeffs[k] * values[k])).  nterms = 0 gives +0.0 and launches
+ *   nothing (queued gates stay queued).
+ * NULL reg, value or total, or a NULL x_masks / z_masks / coeffs with nterms > 0: QCX_BAD_ARGUMENTS; a mask bit at or above n
+ * (in any term: checked before anything runs): QCX_BAD_QUBIT; a sharded register: QCX_UNSUPPORTED, nothing touched. */
+int  qcx_pauli_expectation(qcx_register *reg, uint64_t x_mask, uint64_t z_mask, double *value);
+int  qcx_pauli_expectation_sum(qcx_register *reg, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks,
+                               const double *coeffs, double *values /* [nterms], may be NULL */, double *total);
+/* the last pauli_expectation / pauli_expectation_sum call on this register: source 0 = the register, 2 = a pending basis state
+ * (no kernel), 3 = a compact result expanded first; state_reads = the passes that read amplitudes: one per term (0 for a basis
+ * state) */
+int  qcx_expectation_last_stats(qcx_register *reg, unsigned *source, unsigned long *state_reads);
 
 /* ---- state access (replaces gsl_vector_complex_get/set uses, T:7-37) ------- */
 int  qcx_state_read(qcx_register *reg, unsigned long first, unsigned long count, double *out_re_im);

@@ -73,6 +73,9 @@ SIGNATURES = {
     "qcx_measure_qubits": (_i, [_p, _p, _u, _u, C.POINTER(_ul), C.POINTER(_d)]),
     "qcx_postselect_qubits": (_i, [_p, _u, _u, _ul, C.POINTER(_d)]),
     "qcx_collapse_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul), C.POINTER(_ul)]),
+    "qcx_pauli_expectation": (_i, [_p, _u64, _u64, C.POINTER(_d)]),
+    "qcx_pauli_expectation_sum": (_i, [_p, _ul, _p, _p, _p, _p, C.POINTER(_d)]),
+    "qcx_expectation_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
     "qcx_marginal_plan": (_i, [_u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_marginal_plan_compact": (_i, [_u, _u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_state_read": (_i, [_p, _ul, _ul, _p]),
@@ -287,6 +290,36 @@ def idle_devices(shard_devices, count, visible=None):
     idle = [d for d in range(visible) if d not in set(shard_devices)]
     pool = idle + sorted(set(shard_devices))
     return [pool[i % len(pool)] for i in range(count)]
+
+
+def pauli_masks(spec, n):
+    """(x_mask, z_mask) of a Pauli string over n qubits (include/qcx.h: qcx_pauli_expectation): x_mask = the qubits that carry X
+    or Y, z_mask = those that carry Z or Y.  spec: a str such as "XIZY" (character k = qubit k; at most n characters, the rest
+    I), a dict {qubit: 'X' | 'Y' | 'Z' | 'I'}, or an (x_mask, z_mask) pair, which is only checked.  Host arithmetic only."""
+    n = int(n)
+    if isinstance(spec, str):
+        if len(spec) > n:
+            raise ValueError(f"a Pauli string of {len(spec)} characters on {n} qubits")
+        items = list(enumerate(spec))
+    elif isinstance(spec, dict):
+        items = list(spec.items())
+    else:
+        x, z = (int(v) for v in spec)
+        if x < 0 or z < 0 or (x | z) >> n:
+            raise ValueError(f"masks ({x:#x}, {z:#x}) do not fit {n} qubits")
+        return x, z
+    x = z = 0
+    for q, p in items:
+        if isinstance(q, bool) or int(q) != q or not 0 <= int(q) < n:
+            raise ValueError(f"qubit {q!r} is not one of the {n} qubits")
+        p = p.upper() if isinstance(p, str) else p
+        if p not in ("I", "X", "Y", "Z"):
+            raise ValueError(f"{p!r} is not one of I, X, Y, Z")
+        if p in ("X", "Y"):
+            x |= 1 << int(q)
+        if p in ("Z", "Y"):
+            z |= 1 << int(q)
+    return x, z
 
 
 def polar(theta):

@@ -1263,6 +1263,8 @@ struct qcx_register {
     size_t     marg_cap;        // doubles marg_buf holds
     unsigned   marg_source;     // the last marginal call: 0 register, 1 compact in place, 2 basis (no kernel), 3 compact expanded first
     unsigned long marg_reads;   // ... and the passes of it that read amplitudes
+    unsigned   exp_source;      // the last pauli_expectation(_sum) call: 0 register, 2 basis (no kernel), 3 compact expanded first
+    unsigned long exp_reads;    // ... and the passes of it that read amplitudes (one per term)
     unsigned   coll_source;     // the last measure_qubits / postselect call: 0 register, 2 basis (no kernel), 3 compact expanded first
     unsigned long coll_reads, coll_writes;   // ... the marginal's reads behind its probabilities, and collapse passes launched (0 or 1)
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
@@ -2220,6 +2222,17 @@ extern "C" int qcx_sample_last_stats(qcx_register *r, unsigned long *state_scans
     return QCX_NO_ERROR;
 }
 
+// the buffer of K10's and K14's stages: at least `need` doubles
+static int marg_reserve(qcx_register *r, size_t need)
+{
+    if (r->marg_cap >= need) return QCX_NO_ERROR;
+    if (r->marg_buf) HIP_TRY(hipFree(r->marg_buf));
+    r->marg_buf = nullptr; r->marg_cap = 0;
+    HIP_TRY(hipMalloc(&r->marg_buf, need * sizeof(double)));
+    r->marg_cap = need;
+    return QCX_NO_ERROR;
+}
+
 // K10: the marginal of bits [first, first + num) (include/qcx.h, DESIGN s4.5d).  The planned stages run on r->stream: the first
 // reads the state (the register, or the compact form in place), the others only the partials; then one copy of the output.
 static int marginal_launch(qcx_register *r, const void *src, bool compact, unsigned first, unsigned num, double *probs, bool *bad_out)
@@ -2231,13 +2244,8 @@ static int marginal_launch(qcx_register *r, const void *src, bool compact, unsig
     size_t scratch = 0;
     for (unsigned i = 0; i < ns; i++)
         if (!st[i].final_stage) scratch = std::max<size_t>(scratch, (size_t)(st[i].out_offset + (((uint64_t)1) << st[i].out_bits)));
-    const size_t nout = (size_t)1 << num, need = scratch + nout + 1;
-    if (r->marg_cap < need) {
-        if (r->marg_buf) HIP_TRY(hipFree(r->marg_buf));
-        r->marg_buf = nullptr; r->marg_cap = 0;
-        HIP_TRY(hipMalloc(&r->marg_buf, need * sizeof(double)));
-        r->marg_cap = need;
-    }
+    const size_t nout = (size_t)1 << num;
+    QCX_TRY(marg_reserve(r, scratch + nout + 1));
     double *const out = r->marg_buf + scratch;
     unsigned *const bad = (unsigned *)(out + nout);
     if (compact) HIP_TRY(hipMemsetAsync(bad, 0, sizeof(unsigned), r->stream));
@@ -2327,6 +2335,115 @@ extern "C" int qcx_marginal_last_stats(qcx_register *r, unsigned *source, unsign
     if (!r) return QCX_BAD_ARGUMENTS;
     if (source) *source = r->marg_source;
     if (state_reads) *state_reads = r->marg_reads;
+    return QCX_NO_ERROR;
+}
+
+// K14: <psi|P|psi> of the Pauli string (x, z) on the state in r->amp (include/qcx.h, DESIGN s4.5h).  The stages are those of
+// qcx_marginal_plan(n, 0, 0) -- "sum everything" --, with k_pauli_leaves in the place of stage 0; partials and result in marg_buf.
+static int pauli_launch(qcx_register *r, uint64_t x, uint64_t z, double *value)
+{
+    qcx_marginal_stage st[QCX_MARGINAL_MAX_STAGES];
+    unsigned ns = 0;
+    QCX_TRY(qcx_marginal_plan(r->n, 0, 0, st, &ns));
+    const unsigned T = st[0].T;
+    const uint64_t low = (((uint64_t)1) << T) - 1u;
+    // what k_pauli_leaves takes for granted of stage 0: tiles of the T = min(n, 12) lowest bits, all summed, tile t -> output t
+    if (st[0].kind != 0 || T != std::min(r->n, 12u) || st[0].tile_mask != low || st[0].sum_mask != low || st[0].out_bits != r->n - T) {
+        set_error("qcx_pauli_expectation: unexpected first stage in the plan of n = %u", r->n);
+        return QCX_UNKNOWN_ERROR;
+    }
+    size_t scratch = 0;
+    for (unsigned i = 0; i < ns; i++)
+        if (!st[i].final_stage) scratch = std::max<size_t>(scratch, (size_t)(st[i].out_offset + (((uint64_t)1) << st[i].out_bits)));
+    QCX_TRY(marg_reserve(r, scratch + 2));
+    double *const out = r->marg_buf + scratch;
+    auto dst_of = [&](unsigned i) { return st[i].final_stage ? out : r->marg_buf + st[i].out_offset; };
+    const unsigned g = (unsigned)__builtin_popcountll(x & z) & 3u;
+    const uint64_t ntiles = ((uint64_t)1) << (r->n - T);
+    const uint64_t nunits = (x >> T) ? ntiles >> 1 : ntiles;       // pairs of tiles when the partner lies in another tile
+#define QCX_PAULI(SHAPE, FULL) hipLaunchKernelGGL((k_pauli_leaves<SHAPE, FULL>), dim3((unsigned)std::min<uint64_t>(nunits, 2048)), dim3(256), 0, \
+                                                  r->stream, (const amp_t *)r->amp, dst_of(0), nunits, T, x, z, g)
+    if (x >> T) QCX_PAULI(2, true);                                  // (n > 12: whole tiles)
+    else if (T == 12) { if (x) QCX_PAULI(1, true); else QCX_PAULI(0, true); }
+    else { if (x) QCX_PAULI(1, false); else QCX_PAULI(0, false); }
+#undef QCX_PAULI
+    HIP_TRY(hipGetLastError());
+    for (unsigned i = 1; i < ns; i++) {
+        MargParams P;
+        marginal_params(st[i], &P);
+        P.src = r->marg_buf + st[i - 1].out_offset;
+        P.dst = dst_of(i);
+        P.bad = nullptr;
+        hipLaunchKernelGGL(k_marginal<MARG_DBL>, dim3((unsigned)std::min<uint64_t>(P.ntiles, 2048)), dim3(256), 0, r->stream, P);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(value, out, sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return QCX_NO_ERROR;
+}
+
+// the terms of one call, in order; values may be null.  Everything is checked before anything runs.
+static int pauli_terms(qcx_register *r, unsigned long nterms, const uint64_t *xs, const uint64_t *zs, double *values)
+{
+    for (unsigned long k = 0; k < nterms; k++)
+        if ((xs[k] | zs[k]) >> r->n) {
+            set_error("qcx_pauli_expectation: masks %#llx / %#llx reach past the %u qubits", (unsigned long long)xs[k],
+                      (unsigned long long)zs[k], r->n);
+            return QCX_BAD_QUBIT;
+        }
+    r->exp_source = 0; r->exp_reads = 0;
+    if (nterms == 0) return QCX_NO_ERROR;
+    if (basis_only(r)) {
+        // amplitude 1 at basis_index: a string with an X or a Y has no diagonal entry there, a Z-type one reads the parity
+        for (unsigned long k = 0; k < nterms; k++) {
+            const double v = xs[k] ? 0.0 : ((__builtin_popcountll(r->basis_index & zs[k]) & 1) ? -1.0 : 1.0);
+            if (values) values[k] = v;
+        }
+        r->exp_source = 2;
+        return QCX_NO_ERROR;
+    }
+    QCX_TRY(settle_for_read(r));
+    if (r->compact_pending) {
+        // as the marginal of a range inside the M register: the register's buffer (stale while the state is compact) gets the
+        // expanded state, and the compact form stays what later calls see
+        QCX_TRY(launch_expand_compact(r->compact_amp, r->amp, r->n, r->compact_E, r->stream));
+        r->exp_source = 3;
+    }
+    for (unsigned long k = 0; k < nterms; k++) {
+        double v = 0.0;
+        QCX_TRY(pauli_launch(r, xs[k], zs[k], &v));
+        r->exp_reads += 1;
+        if (values) values[k] = v;
+    }
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_pauli_expectation(qcx_register *r, uint64_t x_mask, uint64_t z_mask, double *value)
+{
+    if (!r || !value) return QCX_BAD_ARGUMENTS;
+    if (r->sh) return QCX_UNSUPPORTED;
+    return pauli_terms(r, 1, &x_mask, &z_mask, value);
+}
+
+extern "C" int qcx_pauli_expectation_sum(qcx_register *r, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks,
+                                         const double *coeffs, double *values, double *total)
+{
+    if (!r || !total || (nterms && (!x_masks || !z_masks || !coeffs))) return QCX_BAD_ARGUMENTS;
+    if (r->sh) return QCX_UNSUPPORTED;
+    std::vector<double> own;
+    if (!values && nterms) { own.resize(nterms); values = own.data(); }
+    QCX_TRY(pauli_terms(r, nterms, x_masks, z_masks, values));
+    double acc = 0.0;
+    for (unsigned long k = 0; k < nterms; k++) acc = acc + coeffs[k] * values[k];      // (each rounded on its own: -ffp-contract=off)
+    *total = acc;
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_expectation_last_stats(qcx_register *r, unsigned *source, unsigned long *state_reads)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (source) *source = r->exp_source;
+    if (state_reads) *state_reads = r->exp_reads;
     return QCX_NO_ERROR;
 }
 

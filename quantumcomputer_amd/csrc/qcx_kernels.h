@@ -4066,6 +4066,132 @@ __global__ __launch_bounds__(256) void k_marginal(MargParams P)
 }
 
 // ---------------------------------------------------------------------------
+// K14  the first stage of a Pauli string's expectation value (qcx_pauli_expectation, DESIGN s4.5h; tests/pauli_ref.py is the
+// definition).  The string is (x_mask, z_mask), Y on x_mask & z_mask, g = popcount(x_mask & z_mask) mod 4.  The leaf of index i,
+// with a = amp[i] and b = amp[i ^ x_mask], every product and sum rounded on its own (no FMA):
+//     t = g even ? a.re * b.re + a.im * b.im : a.im * b.re - a.re * b.im
+//     leaf_i = 0.0 + (odd ? -t : t),   odd = (popcount((i ^ x_mask) & z_mask) + (g >> 1)) & 1
+// (the "0.0 +" turns a -0 into +0 and nothing else), and the value is K10's pairwise tree over all index bits on these leaves.
+// This kernel is stage 0 of qcx_marginal_plan(n, 0, 0): tiles of the T = min(n, 12) lowest index bits, all of them summed, so
+// tile t's root goes to dst[t] and the later stages are plain k_marginal<MARG_DBL> launches.  Loads, the next unit's loads in
+// flight during the tree levels, and the levels themselves are k_marginal<MARG_AMP>'s.  Sign and g come from the index and the
+// arguments: no table.  A unit of work is
+//   SHAPE 0  a tile, x_mask == 0: b is a itself
+//   SHAPE 1  a tile, the partner inside it (x_mask < 2^T): the tile's amplitudes go through LDS once (64 KiB, the leaves then
+//            take the same space), a thread reads a at e and b at e ^ x_mask back from there
+//   SHAPE 2  the PAIR of tiles (t, t ^ (x_mask >> T)), t the one with the highest set bit of x_mask >> T clear: a from tile t
+//            at e, b from the partner tile at e ^ x_low (whole 128-B lines either way).  leaf_i and leaf_(i ^ x_mask) are the
+//            same bits (products commute; a difference taken the other way round is negated exactly, and the sign flips with
+//            it), so each leaf is computed ONCE and placed at e of t's tree and at e ^ x_low of the partner's.  The two trees
+//            lie behind each other in LDS (2 x 32 KiB) and reduce as one array of 2^13: a level's pairs never straddle them.
+//            Every amplitude comes from HBM once, for any string.
+// FULL: the tile has all 2^12 elements (n >= 12) and nothing in the unit's path is guarded -- a guard around a load makes every
+// wait a wait for all loads, the prefetched ones included; !FULL is the one partial tile of a register below 12 qubits.
+// Nothing is written but dst.
+// ---------------------------------------------------------------------------
+template <int SHAPE, bool FULL>
+__global__ __launch_bounds__(256) void k_pauli_leaves(const amp_t *__restrict__ amp, double *__restrict__ dst, uint64_t nunits,
+                                                      unsigned T, uint64_t x_mask, uint64_t z_mask, unsigned g)
+{
+    constexpr unsigned EPT = 16u;
+    constexpr unsigned NRED = SHAPE == 0 ? 4096u : 8192u;
+    constexpr unsigned VPT = SHAPE == 2 ? 16u : 8u;                  // sums a thread forms at the widest tree level
+    __shared__ double red[NRED];
+    const unsigned tid = threadIdx.x, nel = 1u << T;
+    const unsigned x_low = (unsigned)x_mask & (nel - 1u), z_low = (unsigned)z_mask & (nel - 1u);
+    const uint64_t xh = x_mask >> T, zh = z_mask >> T;
+    const unsigned hb = SHAPE == 2 ? 63u - (unsigned)__clzll((long long)xh) : 0u;      // (SHAPE 2: xh != 0)
+    // element j of this thread: tile-local element e = tid + 256 j (n < 12: a partial tile, the first nld of them exist)
+    unsigned nld = 0, eodd = 0;                                      // bit j of eodd: the parity element j adds to `odd`
+#pragma unroll
+    for (unsigned j = 0; j < EPT; j++) {
+        const unsigned e = tid + 256u * j;
+        if (e < nel) nld = j + 1;
+        eodd |= (unsigned)(__popc((e ^ x_low) & z_low) & 1) << j;
+    }
+    const bool godd = (g & 1u) != 0;
+    auto tile_of = [&](uint64_t u) {
+        if constexpr (SHAPE == 2) return ((u >> hb) << (hb + 1u)) | (u & ((((uint64_t)1) << hb) - 1u));
+        else return u;
+    };
+    amp_t a[EPT], b[SHAPE == 2 ? EPT : 1];
+    auto load = [&](uint64_t u) {
+        const uint64_t t = tile_of(u);
+        const amp_t *pa = amp + (t << T) + tid;
+#pragma unroll
+        for (unsigned j = 0; j < EPT; j++)
+            if (FULL || j < nld) a[j] = __builtin_nontemporal_load(pa + 256u * j);
+        if constexpr (SHAPE == 2) {
+            // (e ^ x_low = (tid ^ x_low's 8 low bits) + 256 (j ^ x_low's bits above): one lane offset, uniform steps)
+            const amp_t *pb = amp + ((t ^ xh) << T) + (tid ^ (x_low & 255u));
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++) b[j] = __builtin_nontemporal_load(pb + 256u * (j ^ (x_low >> 8)));
+        }
+    };
+    auto leaf = [&](amp_t p, amp_t q, unsigned j, unsigned tile_par) {
+        // g even: p.re q.re + p.im q.im; g odd: p.im q.re - p.re q.im = p.im q.re + (-(p.re q.im)), the same rounding; no branch
+        const double u = (godd ? p.y : p.x) * q.x, w = (godd ? p.x : p.y) * q.y;
+        const double t = u + (godd ? -w : w);
+        return 0.0 + (((tile_par + (eodd >> j)) & 1u) ? -t : t);
+    };
+    if (blockIdx.x < nunits) load(blockIdx.x);
+    for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
+        const uint64_t t = tile_of(u);
+        const unsigned tile_par = (unsigned)__popcll((t ^ xh) & zh) + (g >> 1);
+        if constexpr (SHAPE == 1) {
+            // through LDS: once the tile is there, a's registers are free for the next tile's loads, which go out at once;
+            // a thread then reads e and e ^ x_low back, keeps its leaves, and writes them when all have read
+            amp_t *sa = (amp_t *)red;
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (FULL || j < nld) sa[tid + 256u * j] = a[j];
+            __syncthreads();
+            if (u + gridDim.x < nunits) load(u + gridDim.x);
+            double v[EPT];
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (FULL || j < nld) v[j] = leaf(sa[tid + 256u * j], sa[(tid + 256u * j) ^ x_low], j, tile_par);
+            __syncthreads();
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (FULL || j < nld) red[tid + 256u * j] = v[j];
+        } else {
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (FULL || j < nld) {
+                    const double v = leaf(a[j], SHAPE == 2 ? b[SHAPE == 2 ? j : 0] : a[j], j, tile_par);
+                    red[tid + 256u * j] = v;
+                    if constexpr (SHAPE == 2) red[4096u + ((tid + 256u * j) ^ x_low)] = v;
+                }
+            if (u + gridDim.x < nunits) load(u + gridDim.x);
+        }
+        __syncthreads();
+        // the tree levels inside the tile, lowest bit first; in place (read all, barrier, write all)
+        unsigned sz = SHAPE == 2 ? 2u * nel : nel;
+        for (unsigned h = 0; h < T; h++) {
+            const unsigned half = sz >> 1;
+            double v[VPT];
+#pragma unroll
+            for (unsigned m = 0; m < VPT; m++) {
+                const unsigned k = tid + 256u * m;
+                if (k < half) v[m] = red[2u * k] + red[2u * k + 1u];
+            }
+            __syncthreads();
+#pragma unroll
+            for (unsigned m = 0; m < VPT; m++) {
+                const unsigned k = tid + 256u * m;
+                if (k < half) red[k] = v[m];
+            }
+            __syncthreads();
+            sz = half;
+        }
+        if (tid == 0) dst[t] = red[0];
+        if (SHAPE == 2 && tid == 1) dst[t ^ xh] = red[1];
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------
 // K11  collapse of the qubit range [first, first + num) onto `outcome` (qcx_measure_qubits, DESIGN s4.5e).  An amplitude whose
 // range bits equal `outcome` becomes (fl(re * s), fl(im * s)) -- two products, nothing to contract into an FMA --, every other
 // one (+0, +0) and is NEVER READ: its lane only stores.  A wave takes 64 amplitudes per step, lane l the element e = 64 t + l of

@@ -244,6 +244,38 @@ class Register:
         check(lib().qcx_collapse_last_stats(self._h, C.byref(src), C.byref(reads), C.byref(writes)), "qcx_collapse_last_stats")
         return src.value, reads.value, writes.value
 
+    def expectation(self, pauli):
+        """<psi|P|psi> of a Pauli string, exactly, from one read of the state, which stays as it was (include/qcx.h:
+        qcx_pauli_expectation; the pinned arithmetic is restated in tests/pauli_ref.py).  `pauli`: a str such as "XIZY"
+        (character k = qubit k), a dict {qubit: 'X' | 'Y' | 'Z' | 'I'}, or an (x_mask, z_mask) pair (pauli_masks)."""
+        x, z = _lib.pauli_masks(pauli, self.num_qubits)
+        out = C.c_double(float("nan"))
+        check(lib().qcx_pauli_expectation(self._h, x, z, C.byref(out)), "qcx_pauli_expectation")
+        return out.value
+
+    def expectation_sum(self, terms):
+        """terms = [(coeff, pauli), ...]: (total, values) with values[k] = expectation(pauli_k), one pass over the state per
+        term, and total = the terms' coeff * value added up in order (include/qcx.h: qcx_pauli_expectation_sum)."""
+        terms = list(terms)
+        k = len(terms)
+        masks = [_lib.pauli_masks(p, self.num_qubits) for _, p in terms]
+        xs = np.array([m[0] for m in masks], dtype=np.uint64)
+        zs = np.array([m[1] for m in masks], dtype=np.uint64)
+        cs = np.array([float(c) for c, _ in terms], dtype=np.float64)
+        values = np.zeros(k, dtype=np.float64)
+        total = C.c_double(float("nan"))
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if k else (lambda a: None)
+        check(lib().qcx_pauli_expectation_sum(self._h, k, ptr(xs), ptr(zs), ptr(cs), ptr(values), C.byref(total)),
+              "qcx_pauli_expectation_sum")
+        return total.value, values
+
+    def expectation_stats(self):
+        """(source, state reads) of the last expectation / expectation_sum call on this register: source 0 = the register, 2 = a
+        pending basis state (no kernel), 3 = a compact circuit result expanded first; one state read per term"""
+        src, reads = C.c_uint(0), C.c_ulong(0)
+        check(lib().qcx_expectation_last_stats(self._h, C.byref(src), C.byref(reads)), "qcx_expectation_last_stats")
+        return src.value, reads.value
+
     def set_fusion(self, enable=True):
         """Fused LDS-tile passes (bit-identical results).  True/1: every gate call is queued; False/0 (default): only
         the whole-circuit calls (inverse_QFT, quantum_computation) run as fused passes; -1: strictly one kernel launch
