@@ -80,7 +80,8 @@ int  qcx_M_size(const qcx_register *reg);
  * check; qcx_sharded_set_relays runs it again through the relays).
  * M_size > 12 works like on one GPU (the modular multiply then runs in place through a per-device staging buffer instead of
  * LDS tiles; M_size <= 26).  Not available on a sharded register: qcx_register_set_stream, qcx_device_pointer (NULL),
- * the event pool, qcx_one_qubit_gate / qcx_c_one_qubit_gate, qcx_two_qubit_gate / qcx_c_two_qubit_gate (QCX_UNSUPPORTED). */
+ * the event pool, qcx_one_qubit_gate / qcx_c_one_qubit_gate, qcx_two_qubit_gate / qcx_c_two_qubit_gate,
+ * qcx_pauli_rotation (QCX_UNSUPPORTED). */
 int  qcx_register_create_sharded(int L_size, int M_size, unsigned nshards, const int *devices, qcx_register **out);
 int  qcx_spread_devices(unsigned nshards, int visible_devices /* <= 0: ask HIP */, int *devices_out /* [nshards] */);
 int  qcx_sharded_selfcheck(qcx_register *reg);             /* the pre-flight exchange check on demand */
@@ -156,6 +157,30 @@ int  qcx_c_one_qubit_gate(unsigned c_qubit_num, unsigned qubit_num, const double
  * name distinct qubits); a sharded register: QCX_UNSUPPORTED, nothing touched. */
 int  qcx_two_qubit_gate(unsigned qubit0, unsigned qubit1, const double *u, qcx_register *reg);
 int  qcx_c_two_qubit_gate(unsigned c_qubit_num, unsigned qubit0, unsigned qubit1, const double *u, qcx_register *reg);
+/* The rotation about a Pauli string, exp(-i theta/2 P) = cos(theta/2) I - i sin(theta/2) P, in ONE read and one write of the
+ * state for any string (no reference counterpart; the matrix applied as the reference's mat-vec applies every gate, Q:393-413;
+ * tests/pauli_rotation_ref.py restates it in numpy and IS the definition).  The string is qcx_pauli_expectation's pair of masks:
+ * x_mask = the qubits that carry X or Y, z_mask = those that carry Z or Y, <i|P|j> = i^g (-1)^popcount(j & z_mask) for
+ * j = i ^ x_mask, g = popcount(x_mask & z_mask) mod 4.
+ *   (c, s) = qcx_polar(fl(theta / 2)) -- one sincos, as qcx_c_phase_shift_gate obtains its factor.
+ *   (er, ei) = -i * i^g * s = (+0, -s), (s, +0), (+0, s), (-s, +0) for g = 0, 1, 2, 3; the entry of row i at column j is (er, ei)
+ *   with its ONE non-zero component negated when popcount(j & z_mask) is odd; the zero component stays +0.
+ *   Triplets are taken in ascending column order, products as Q:409 / Q:412, every fl() one binary64 rounding, no FMA, zero
+ *   components multiplied out (0 * Inf = NaN, as in the reference):
+ *     P(m, x).re = fl(fl(m.re*x.re) - fl(m.im*x.im)),   P(m, x).im = fl(fl(m.re*x.im) + fl(m.im*x.re))
+ *   x_mask != 0: D = P((c, +0), amp[i]), O = P(entry, amp[j]);  new[i] = fl(fl(0.0 + D) + O) if i < j, else fl(fl(0.0 + O) + D),
+ *   component-wise.  x_mask == 0: the one triplet m = (c, -s) where popcount(i & z_mask) is even, (c, s) where it is odd;
+ *   new[i] = fl(0.0 + P(m, amp[i])).  The empty string is the global phase e^{-i theta/2} and still runs.
+ *   Every amplitude is rewritten: a result is never -0, and an Inf or NaN reaches rows i and i ^ x_mask only, so a register
+ *   flagged non-finite keeps its flag and runs the same kernel.
+ *   On finite states: one letter on qubit q gives qcx_one_qubit_gate(q, .)'s bits with [[c, -is], [-is, c]] (X), [[c, -s], [s, c]]
+ *   (Y), diag(c - is, c + is) (Z); two letters give qcx_two_qubit_gate's with c I - i s P built component by component, in either
+ *   qubit order.
+ * Asynchronous; flushes what is pending in every fusion mode and launches its own kernel, never enters the queue, is not counted
+ * by qcx_fusion_stats, stays exact in mode 2 -- all as qcx_one_qubit_gate.
+ * NULL reg or a theta that is not finite: QCX_BAD_ARGUMENTS; a mask bit at or above n: QCX_BAD_QUBIT; a sharded register:
+ * QCX_UNSUPPORTED, nothing touched. */
+int  qcx_pauli_rotation(uint64_t x_mask, uint64_t z_mask, double theta, qcx_register *reg);
 int  qcx_swap_states(qcx_register *reg);                                           /* Q:242-249: no-op */
 /* host-side gate schedules */
 int  qcx_inverse_QFT(qcx_register *reg);                                           /* Q:678-690 */

@@ -32,6 +32,9 @@ int  qcx_shard_one_qubit(void *amp, unsigned n_local, unsigned q_local, int ctl_
  * bits q0, q1, on the quads whose local bit ctl_local is set (ctl_local < 0: on every quad).  u is read before the call
  * returns.  Not used by the sharded hosts. */
 int  qcx_shard_two_qubit(void *amp, unsigned n_local, unsigned q0, unsigned q1, int ctl_local, const double *u, void *stream);
+/* exp(-i theta/2 P) of the Pauli string (x_mask, z_mask) over the local bits (qcx.h: qcx_pauli_rotation), the launch alone:
+ * c and s are cos and sin of theta / 2 (qcx_polar).  Not used by the sharded hosts. */
+int  qcx_shard_pauli_rotation(void *amp, unsigned n_local, uint64_t x_mask, uint64_t z_mask, double c, double s, void *stream);
 /* multiply by (cos_t + i sin_t) every amplitude whose local index has all bits of
  * `mask_local` set; mask_local has 0, 1 or 2 bits (global control bits that are 1
  * simply drop out of the mask; a global bit that is 0 means: do not call). */

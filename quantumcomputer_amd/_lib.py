@@ -54,6 +54,7 @@ SIGNATURES = {
     "qcx_c_one_qubit_gate": (_i, [_u, _u, _p, _p]),
     "qcx_two_qubit_gate": (_i, [_u, _u, _p, _p]),
     "qcx_c_two_qubit_gate": (_i, [_u, _u, _u, _p, _p]),
+    "qcx_pauli_rotation": (_i, [_u64, _u64, _d, _p]),
     "qcx_swap_states": (_i, [_p]),
     "qcx_inverse_QFT": (_i, [_p]),
     "qcx_quantum_computation": (_i, [_u, _u, _i, _p]),
@@ -99,6 +100,7 @@ SIGNATURES = {
     "qcx_shard_hadamard": (_i, [_p, _u, _u, _p]),
     "qcx_shard_one_qubit": (_i, [_p, _u, _u, _i, _p, _p]),
     "qcx_shard_two_qubit": (_i, [_p, _u, _u, _u, _i, _p, _p]),
+    "qcx_shard_pauli_rotation": (_i, [_p, _u, _u64, _u64, _d, _d, _p]),
     "qcx_shard_phase": (_i, [_p, _u, _u64, _d, _d, _p]),
     "qcx_shard_camodc": (_i, [_p, _u, _u, _u, _u, _i, _p]),
     "qcx_shard_swap_bits": (_i, [_p, _p, _u, _u, C.POINTER(_u), C.POINTER(_u), _p]),

@@ -168,6 +168,7 @@ struct Tune {
     long u2_nt       = 1;      // K13: nontemporal accesses (only where a wave instruction covers whole 128-B lines, as in K12)
     long u2_streams_log2 = -1; // K13: -1 = plain gate: the Hadamard plan's streams for hi; controlled: the phase gate's rule.  Both are guesses taken
                                // over from kernels with two address streams, not four; tools/time_two_qubit_gate.py is there to measure them
+    long prot_grid_cap = 2048; // K15 (k_pauli_rot): workgroups, each walks its units (tiles, or pairs of tiles) with this stride; 0 = one unit each
 };
 static Tune g_tune;
 static std::mutex g_tune_mutex;
@@ -177,7 +178,7 @@ static Tune tune_now() { std::lock_guard<std::mutex> lock(g_tune_mutex); return 
 extern "C" int qcx_tune_set(const char *key, long value)
 {
 #define K(name) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); g_tune.name = value; return QCX_NO_ERROR; }
-    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt) K(u2_variant) K(u2_nt) K(u2_streams_log2)
+    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt) K(u2_variant) K(u2_nt) K(u2_streams_log2) K(prot_grid_cap)
 #undef K
     return QCX_BAD_ARGUMENTS;
 }
@@ -185,7 +186,7 @@ extern "C" int qcx_tune_set(const char *key, long value)
 extern "C" long qcx_tune_get(const char *key)
 {
 #define K(name) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); return g_tune.name; }
-    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt) K(u2_variant) K(u2_nt) K(u2_streams_log2)
+    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt) K(u2_variant) K(u2_nt) K(u2_streams_log2) K(prot_grid_cap)
 #undef K
     return -1;
 }
@@ -697,6 +698,31 @@ extern "C" int qcx_shard_two_qubit(void *amp, unsigned n_local, unsigned q0, uns
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "two-qubit gate launch: %s", hipGetErrorString(e)); return QCX_HIP_ERROR; }
+    return QCX_NO_ERROR;
+}
+
+// ---- K15: the rotation about a Pauli string -----------------------------------------------------------------------------------
+// One launch for any string: the units and the grid are k_pauli_leaves' (tiles of the T = min(n, 12) lowest bits, pairs of tiles
+// when the partner lies in another tile, at most prot_grid_cap = 2048 workgroups).  c and s are cos and sin of theta / 2.
+extern "C" int qcx_shard_pauli_rotation(void *amp, unsigned n_local, uint64_t x_mask, uint64_t z_mask, double c, double s, void *stream)
+{
+    if (!amp || n_local == 0 || n_local > 40) return QCX_BAD_ARGUMENTS;
+    if ((x_mask | z_mask) >> n_local) return QCX_BAD_QUBIT;
+    const unsigned g = (unsigned)__builtin_popcountll(x_mask & z_mask) & 3u;
+    // -i i^g s: (+0, -s), (s, +0), (+0, s), (-s, +0)
+    const PRot R = {c, 0.0, g == 1 ? s : (g == 3 ? -s : 0.0), g == 0 ? -s : (g == 2 ? s : 0.0)};
+    const unsigned T = std::min(n_local, 12u);
+    const uint64_t ntiles = ((uint64_t)1) << (n_local - T);
+    const uint64_t nunits = (x_mask >> T) ? ntiles >> 1 : ntiles;
+    const unsigned grid = grid_for(nunits, 1, tune_now().prot_grid_cap, 256);
+#define QCX_PROT(SHAPE, FULL) hipLaunchKernelGGL((k_pauli_rot<SHAPE, FULL>), dim3(grid), dim3(256), 0, \
+                                                 (hipStream_t)stream, (amp_t *)amp, nunits, T, x_mask, z_mask, g, R)
+    if (x_mask >> T) QCX_PROT(2, true);                              // (n > 12: whole tiles)
+    else if (T == 12) { if (x_mask) QCX_PROT(1, true); else QCX_PROT(0, true); }
+    else { if (x_mask) QCX_PROT(1, false); else QCX_PROT(0, false); }
+#undef QCX_PROT
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "pauli rotation launch: %s", hipGetErrorString(e)); return QCX_HIP_ERROR; }
     return QCX_NO_ERROR;
 }
 
@@ -2004,6 +2030,25 @@ extern "C" int qcx_c_two_qubit_gate(unsigned c, unsigned q0, unsigned q1, const 
 {
     if (r && c >= r->n) return QCX_BAD_QUBIT;         // (before the cast: a control >= 2^31 is a bad qubit, not "no control")
     return two_qubit_gate((int)c, q0, q1, u, r, "c_two_qubit_gate");
+}
+
+// exp(-i theta/2 P) of the Pauli string (x_mask, z_mask).  one_qubit_gate()'s sequence: never queued, in any fusion mode; the
+// call flushes what is pending and launches its own kernel (K15); the fusion statistics do not count it.  The kernel rewrites
+// every amplitude from its own row's products, so it is its own strict pass: a non-finite register keeps its flag and runs it too.
+extern "C" int qcx_pauli_rotation(uint64_t x_mask, uint64_t z_mask, double theta, qcx_register *r)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (!std::isfinite(theta)) { set_error("pauli_rotation: theta is %g", theta); return QCX_BAD_ARGUMENTS; }
+    if ((x_mask | z_mask) >> r->n) {
+        set_error("pauli_rotation: masks %#llx / %#llx reach past the %u qubits", (unsigned long long)x_mask, (unsigned long long)z_mask, r->n);
+        return QCX_BAD_QUBIT;
+    }
+    if (r->sh) { set_error("pauli_rotation: not available on a sharded register"); return QCX_UNSUPPORTED; }
+    double c, s;
+    qcx_polar(theta / 2.0, &c, &s);
+    FLUSH(r);                                         // queued gates, a pending basis state, a compact circuit result
+    r->zeros_dirty = 0;                               // every amplitude is rewritten as 0 + ...: canonical zeros
+    return qcx_shard_pauli_rotation(r->amp, r->n, x_mask, z_mask, c, s, r->stream);
 }
 
 extern "C" int qcx_c_amodc_gate(unsigned C, unsigned long long atox, unsigned c, qcx_register *r)

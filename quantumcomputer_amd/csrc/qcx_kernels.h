@@ -4546,4 +4546,161 @@ __global__ __launch_bounds__(256) void k_strict_cu2(amp_t *__restrict__ amp, uns
     }
 }
 
+// ---------------------------------------------------------------------------
+// K15  the rotation about a Pauli string, exp(-i theta/2 P) = cos(theta/2) I - i sin(theta/2) P, in place (qcx_pauli_rotation,
+// DESIGN s4.5i; tests/pauli_rotation_ref.py is the definition).  The string is K14's (x_mask, z_mask), g = popcount(x_mask &
+// z_mask) mod 4, (c, s) = polar(theta / 2).  The matrix has one or two entries per row and is applied as the reference's
+// mat-vec would apply it from stored triplets taken in ascending column order (Q:396-413), products as Q:409 / Q:412, every
+// product and sum rounded on its own (no FMA), zero components multiplied out:
+//     (er, ei) = -i i^g s = (+0, -s), (s, +0), (+0, s), (-s, +0);   entry(i, j) = (er, ei), its ONE non-zero component negated
+//     when popcount(j & z_mask) is odd (the other stays +0), j = i ^ x_mask
+//     x_mask != 0:  D = (c, +0) * amp[i], O = entry(i, j) * amp[j],  new[i] = i < j ? (0 + D) + O : (0 + O) + D
+//     x_mask == 0:  new[i] = 0 + (c, -+s) * amp[i], -s where popcount(i & z_mask) is even (this is entry(i, i) with re = c)
+// What the definition is, bit for bit, on finite states (tests/test_pauli_rotation_ref.py, and on the GPU
+// tests/test_gpu_pauli_rotation.py):
+//     one letter on qubit q        = qcx_one_qubit_gate(q, .) with [[c, -is], [-is, c]] (X), [[c, -s], [s, c]] (Y),
+//                                    diag(c - is, c + is) (Z)
+//     two letters on qubits q0, q1 = qcx_two_qubit_gate(q0, q1, .) with c I - i s P built component by component, either order
+//     and cos(theta/2) I - i sin(theta/2) P as a dense matrix to 1e-14 on O(1) amplitudes.
+// Every amplitude is rewritten from its own row's products: a result is never -0 (K0c's invariant holds behind this kernel),
+// and an Inf or NaN reaches rows i and i ^ x_mask only -- there is no strict twin.
+// The units of work are k_pauli_leaves' (T = min(n, 12), a tile = 2^T amplitudes, 256 threads, thread element j = tid + 256 j):
+//   SHAPE 0  a tile, x_mask == 0: a streaming diagonal, the sign from the index parity; no LDS
+//   SHAPE 1  a tile, the partner inside it (x_mask < 2^T): the tile goes through LDS once (64 KiB), whole 128-B lines in and
+//            out; behind the barrier -- the whole tile is in LDS before any of its stores is issued -- the next tile's loads
+//            go out, a thread reads e and e ^ x_low back, computes its OWN row and stores its own element
+//   SHAPE 2  the PAIR of tiles (t, t ^ (x_mask >> T)), t the one with the highest set bit of x_mask >> T clear: a at e of
+//            tile t, b at e ^ x_low of the partner (whole lines either way).  i < j on t's side always: a takes D then O, b
+//            takes O then D; both are stored where they came from.  Units are disjoint, so in place is safe; no LDS.
+// SHAPE 0 and 2 hold no more than 8 elements of a thread at a time (8 a's and 8 b's: 64 VGPRs) and prefetch nothing: there is
+// no barrier in them, so the other waves of the CU cover the latency (2, 4 and 16 elements at a time measured the same at
+// n = 30, DESIGN s4.5i).  FULL as in K14: !FULL is the one partial tile of n < 12.
+// ---------------------------------------------------------------------------
+struct PRot { double c, zr, er, ei; };                   // zr = the +0 imaginary part of the diagonal (an argument: never folded)
+
+// entry * x with the entry's sign applied to its non-zero component (er for odd g, ei for even g)
+__device__ __forceinline__ amp_t prot_off(const PRot &R, bool godd, bool neg, amp_t x)
+{
+    const double mr = (godd && neg) ? -R.er : R.er, mi = (!godd && neg) ? -R.ei : R.ei;
+    amp_t o;
+    o.x = (mr * x.x) - (mi * x.y);                      // Q:409
+    o.y = (mr * x.y) + (mi * x.x);                      // Q:412
+    return o;
+}
+
+// the row of `own`: first = its index is below the partner's (the diagonal triplet comes first)
+__device__ __forceinline__ amp_t prot_row(const PRot &R, bool godd, bool neg, bool first, amp_t own, amp_t oth)
+{
+    amp_t d;
+    d.x = (R.c * own.x) - (R.zr * own.y);
+    d.y = (R.c * own.y) + (R.zr * own.x);
+    const amp_t o = prot_off(R, godd, neg, oth);
+    amp_t r;
+    r.x = first ? (0.0 + d.x) + o.x : (0.0 + o.x) + d.x;
+    r.y = first ? (0.0 + d.y) + o.y : (0.0 + o.y) + d.y;
+    return r;
+}
+
+// x_mask == 0: the one triplet (c, -+s) (g = 0: ei = -s carries the sign)
+__device__ __forceinline__ amp_t prot_diag(const PRot &R, bool neg, amp_t x)
+{
+    const double mi = neg ? -R.ei : R.ei;
+    amp_t r;
+    r.x = 0.0 + ((R.c * x.x) - (mi * x.y));
+    r.y = 0.0 + ((R.c * x.y) + (mi * x.x));
+    return r;
+}
+
+template <int SHAPE, bool FULL>
+__global__ __launch_bounds__(256) void k_pauli_rot(amp_t *__restrict__ amp, uint64_t nunits, unsigned T, uint64_t x_mask,
+                                                   uint64_t z_mask, unsigned g, PRot R)
+{
+    constexpr unsigned EPT = 16u, HALF = 8u;
+    const unsigned tid = threadIdx.x, nel = 1u << T;
+    const unsigned x_low = (unsigned)x_mask & (nel - 1u), z_low = (unsigned)z_mask & (nel - 1u);
+    const uint64_t xh = x_mask >> T, zh = z_mask >> T;
+    const bool godd = (g & 1u) != 0;
+    // element j of this thread: tile-local e = tid + 256 j (n < 12: a partial tile, the first nld of them exist).
+    // bit j of podd: the parity its PARTNER's element e ^ x_low adds to the sign; of sodd: its own (SHAPE 2 needs both)
+    unsigned nld = 0, podd = 0, sodd = 0;
+#pragma unroll
+    for (unsigned j = 0; j < EPT; j++) {
+        const unsigned e = tid + 256u * j;
+        if (e < nel) nld = j + 1;
+        podd |= (unsigned)(__popc((e ^ x_low) & z_low) & 1) << j;
+        sodd |= (unsigned)(__popc(e & z_low) & 1) << j;
+    }
+    if constexpr (SHAPE == 1) {
+        __shared__ amp_t sa[4096];
+        const unsigned hbit = 1u << (31u - (unsigned)__clz((int)x_low));      // (SHAPE 1: x_low != 0) i < j <=> this bit of e is clear
+        amp_t a[EPT];
+        auto load = [&](uint64_t u) {
+            const amp_t *pa = amp + (u << T) + tid;
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (FULL || j < nld) a[j] = __builtin_nontemporal_load(pa + 256u * j);
+        };
+        if (blockIdx.x < nunits) load(blockIdx.x);
+        for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
+            const unsigned tile_par = (unsigned)__popcll(u & zh);            // (xh == 0: the partner's tile is this one)
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (FULL || j < nld) sa[tid + 256u * j] = a[j];
+            __syncthreads();
+            if (u + gridDim.x < nunits) load(u + gridDim.x);
+            amp_t *po = amp + (u << T) + tid;
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (FULL || j < nld) {
+                    const unsigned e = tid + 256u * j;
+                    const amp_t r = prot_row(R, godd, ((tile_par + (podd >> j)) & 1u) != 0, (e & hbit) == 0, sa[e], sa[e ^ x_low]);
+                    __builtin_nontemporal_store(r, po + 256u * j);
+                }
+            __syncthreads();
+        }
+    } else if constexpr (SHAPE == 0) {
+        for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
+            const unsigned tile_par = (unsigned)__popcll(u & zh);
+            amp_t *pa = amp + (u << T) + tid;
+#pragma unroll 1
+            for (unsigned h = 0; h < EPT; h += HALF) {
+                amp_t a[HALF];
+#pragma unroll
+                for (unsigned k = 0; k < HALF; k++)
+                    if (FULL || h + k < nld) a[k] = __builtin_nontemporal_load(pa + 256u * (h + k));
+#pragma unroll
+                for (unsigned k = 0; k < HALF; k++)
+                    if (FULL || h + k < nld)
+                        __builtin_nontemporal_store(prot_diag(R, ((tile_par + (sodd >> (h + k))) & 1u) != 0, a[k]), pa + 256u * (h + k));
+            }
+        }
+    } else {
+        const unsigned hb = 63u - (unsigned)__clzll((long long)xh);          // (SHAPE 2: xh != 0, n > 12, whole tiles)
+        for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
+            const uint64_t t = ((u >> hb) << (hb + 1u)) | (u & ((((uint64_t)1) << hb) - 1u));
+            const unsigned par_a = (unsigned)__popcll(t & zh), par_b = (unsigned)__popcll((t ^ xh) & zh);
+            amp_t *pa = amp + (t << T) + tid;
+            // (e ^ x_low = (tid ^ x_low's 8 low bits) + 256 (j ^ x_low's bits above): one lane offset, uniform steps)
+            amp_t *pb = amp + ((t ^ xh) << T) + (tid ^ (x_low & 255u));
+#pragma unroll 1
+            for (unsigned h = 0; h < EPT; h += HALF) {
+                amp_t a[HALF], b[HALF];
+#pragma unroll
+                for (unsigned k = 0; k < HALF; k++) {
+                    a[k] = __builtin_nontemporal_load(pa + 256u * (h + k));
+                    b[k] = __builtin_nontemporal_load(pb + 256u * ((h + k) ^ (x_low >> 8)));
+                }
+#pragma unroll
+                for (unsigned k = 0; k < HALF; k++) {
+                    // a's row meets b's index in the entry's sign, and the other way round
+                    const amp_t ra = prot_row(R, godd, ((par_b + (podd >> (h + k))) & 1u) != 0, true, a[k], b[k]);
+                    const amp_t rb = prot_row(R, godd, ((par_a + (sodd >> (h + k))) & 1u) != 0, false, b[k], a[k]);
+                    __builtin_nontemporal_store(ra, pa + 256u * (h + k));
+                    __builtin_nontemporal_store(rb, pb + 256u * ((h + k) ^ (x_low >> 8)));
+                }
+            }
+        }
+    }
+}
+
 }  // namespace qcx

@@ -398,6 +398,14 @@ def c_two_qubit_gate(c_qubit_num, qubit0, qubit1, U, reg):
     check(lib().qcx_c_two_qubit_gate(int(c_qubit_num), int(qubit0), int(qubit1), u.ctypes.data_as(C.c_void_p), reg._h), "c_two_qubit_gate")
 
 
+def pauli_rotation(pauli, theta, reg):
+    """Apply exp(-i theta/2 P) for the Pauli string P in one pass over the state, for any string (include/qcx.h:
+    qcx_pauli_rotation; the pinned arithmetic is restated in tests/pauli_rotation_ref.py).  `pauli`: what Register.expectation
+    takes -- a str such as "XIZY" (character k = qubit k), a dict {qubit: 'X' | 'Y' | 'Z' | 'I'}, or an (x_mask, z_mask) pair."""
+    x, z = _lib.pauli_masks(pauli, reg.num_qubits)
+    check(lib().qcx_pauli_rotation(x, z, float(theta), reg._h), "pauli_rotation")
+
+
 def controlled(U2):
     """the 4x4 matrix "U2 on qubit1 where qubit0 reads 1": the identity with U2 in rows and columns {1, 3}, so that
     c_two_qubit_gate(c, a, b, controlled(X)) is a Toffoli with controls c and a"""
