@@ -77,98 +77,103 @@ extern "C" int qcx_set_device(int device) { HIP_TRY(hipSetDevice(device)); retur
 // ---------------------------------------------------------------------------
 // launch configuration (tunable at run time so one build can be swept on the GPU)
 // ---------------------------------------------------------------------------
+// the knobs, once: X(name, default) and what the knob does.  The struct, qcx_tune_set and qcx_tune_get are generated from this list
+#define QCX_TUNABLES(X) \
+    X(h_variant, 0)               /* 0: auto, 1: always pair form, 2: wave-tile form where it applies */ \
+    X(h_ppt, 1)                   /* pairs per thread, pair form */ \
+    X(h_nt, 3)                    /* nontemporal: bit 0 loads, bit 1 stores (pair form, q >= 3) */ \
+    X(h_wave_nt, 3)               /* same for the wave-tile form in auto mode */ \
+    X(h_wc, 0)                    /* pair form: per-wave-contiguous load order */ \
+    X(h_block, 64)                /* pair form: threads per block (64/128/256/512) */ \
+    X(h_streams_log2, 0)          /* pair form: deal tiles as 2^k interleaved streams (3 = one per XCD) */ \
+    X(h_skew, 0)                  /* pair form: stream j is rotated by j * skew tiles inside its segment */ \
+    X(h_grid_cap, 0)              /* 0: one tile per block (no cap) */ \
+    X(h_wave_r, 4)                /* registers per lane, wave-tile form (2, 4 or 8) */ \
+    X(h_wave_block, 256)          /* wave-tile form: threads per block (64 or 256) */ \
+    X(h_wave_maxq, 7)             /* auto: use the wave-tile form for q <= this */ \
+    X(ph_apt, 1)                  /* measured (tools/experiments/tune_phase.py): one amplitude per lane, one wave per block, */ \
+    X(ph_grid_cap, 0)             /* nontemporal, 2 or 4 interleaved streams: 6.4-6.9 TB/s on the touched quarter */ \
+    X(ph_block, 64) \
+    X(ph_nt, 1) \
+    X(ph_streams_log2, -1)        /* -1: auto (1 when the lowest mask bit >= 8, else 2) */ \
+    X(ph_lines, 1)                /* masks with a bit below 3: the whole-line kernel k_phase_lines (0: k_phase for every mask) */ \
+    X(cam_grid_cap, 0)            /* (round 3: one tile per workgroup, 2.80-2.89 ms per gate at n = 30 against 2.85-3.0 with 4096 workgroups) */ \
+                                  /* (measured n = 30, C = 21, M = 5: whole tiles 2.9-3.4 ms = 17.2 GB at 5.0-5.9 TB/s, partial 2.8-2.9 ms = 14.5 GB at 5.0-5.2) */ \
+    X(cam_logT, 8)                /* modular multiply: tile = 2^this amplitudes, at least the 2^M block (n = 30, C = 21, M = 5: 2^11 2.65 ms, 2^10 2.50, 2^9 2.3-2.6, 2^8 2.3; 2^12 4.2) */ \
+    X(cam_skip, 1)                /* modular multiply: the 128-B lines of a 2^M block above row C are neither sources nor destinations: not read */ \
+    X(cam_nt_lines, 0)            /* modular multiply: completely rewritten lines leave as nontemporal stores (the partly rewritten one through L2) */ \
+    X(fuse_T, 11)                 /* fused passes: tile = 2^T amplitudes in LDS (8..12) */ \
+    X(fuse_c, 4)                  /* fused passes: contiguous low bits of a tile (runs of 16 * 2^c bytes) */ \
+    X(fuse_grid_cap, 65536)       /* (round 4, chained passes: 65536 beats 24576 by 1-2 %, one per tile loses 15 % on the n = 30 exact Shor circuit) */ \
+                                  /* workgroups of the one-tile-per-workgroup form (each walks several tiles: the table fill at kernel start is amortised) */ \
+    X(fuse_qround, 1)             /* tolerance mode: rounds of the shape H D H D run as straight-line code (FUSE_QROUND) */ \
+    X(fuse_q3_cap, 65536)         /* workgroups of k_fused_q3 with tables (round 3, in place: 3072 best; round 4, chained: n = 28 inverse QFT 6.12 ms with 3072, 5.85 with 65536; */ \
+                                  /* n = 30 Shor circuit 18.7 with 65536, 20.5 with one per tile) */ \
+    X(fuse_q3_cap_exact, 0)       /* all-Hadamard radix-8 passes (no tables to stage): one workgroup per tile (round 4, chained passes: n = 30 sweep 20.2 ms with 8192, 19.2 with one per tile) */ \
+    X(fuse_q3, 1)                 /* tolerance mode: radix-8 fast rounds on 2^12 tiles when they save a pass (k_fused_q3) */ \
+    X(fuse_x8, 1)                 /* bit-exact phase-dominated passes: the walk on 8 amplitudes per thread (k_fused_x8, round 5) */ \
+    X(fuse_x8_T, 12)              /* ... on tiles of 2^this amplitudes (10 .. 12) with */ \
+    X(fuse_x8_c, 4)               /* ... this many contiguous low bits */ \
+    X(fuse_streams_log2, -1)      /* which tile a workgroup of k_fused_q3 / k_fused_x8 / k_fused_rounds takes (fuse_stream_tile): the 2^this low bits of its slot number ... */ \
+    X(fuse_streams_pos, -1)       /* ... go to this bit of the tile number (+ 1; 0 = on top).  -1: by the kind of pass (launch_pass) */ \
+    X(fuse_x8t, 1)                /* tolerance mode: radix-8 fast rounds run on the k_fused_x8 shell (hand-written round, K6x-t) instead of k_fused_q3 */ \
+    X(fuse_x8_min_tiles_log2, 2)  /* ... on registers of at least 2^this tiles */ \
+    X(fuse_x8_ratio, 1)           /* ... for passes without multiplies that hold at least this many phases per Hadamard */ \
+    X(fuse_x8_map, 1)             /* ... the wave number rides on the tile bits most gates of a round test (0: plain ascending order) */ \
+    X(fuse_x8_cap, 65536)         /* ... workgroups */ \
+    X(fuse_gen, 1)                /* a pending reset / collapse + circuit front is GENERATED inside the first fused pass behind it (no write pass, no read) */ \
+    X(fuse_chain_dir, -1)         /* chained passes: 0 = a pass stores gathered so that the NEXT tile is contiguous (reads whole tiles); 1 = stores its own tile contiguously, the next pass gathers; -1 = by the kind of chain */ \
+    X(cam_block, 0)               /* threads per workgroup of k_camodc (0: 256; 1024 for tiles of 2^12 amplitudes) */ \
+    X(cam_stage_mb, 1024)         /* M > 12: staging buffer of the in-place modular multiply (MiB; at least one 2^M-block) */ \
+    X(fuse_compact, 1)            /* behind a circuit front whose M register stays on a small orbit: the flush runs on a compact copy of the state (compact_chain) */ \
+    X(fuse_compact_lazy, 1)       /* ... and stays compact behind a whole-circuit entry point until something other than measure_state looks at the state */ \
+    X(fuse_plan_cache, 1)         /* a flush whose inputs (shape, mode, knobs, front, gate list) are bit for bit those of the last one reuses its plan and, when nothing was uploaded since, its records on the device */ \
+    X(fuse_expand_fused, 1)       /* the last pass of a compact chain stores the real register itself (k_fused_x8's expanding store) instead of k_expand_compact */ \
+    X(fuse_cols_tol, 1)           /* tolerance mode: the by-columns pass of a compact chain keeps its merged diagonals (fast rounds inside k_gen_cols) */ \
+    X(fuse_cols_cap, 12288)       /* workgroups of a k_gen_cols launch (a workgroup's prologue is long; n = 30 Shor circuit 11.06-11.09 ms with 12288-24576, 11.14-11.3 with 65536, 12.07 with 1536; tolerance 7.4-7.8 against 8.1) */ \
+    X(fuse_cols_waves, 0)         /* waves per workgroup of k_gen_cols (4 ... 8; the first four generate and store the tile); 0: 8 for launches of at most 1024 tiles, else 4 */ \
+    X(fuse_expand_direct, 1)      /* k_expand_compact: 1 = gather the compact sources straight from memory (8 per thread in flight) instead of staging 64 blocks in LDS */ \
+    X(fuse_gen_cols, 1)           /* the generated first pass by COLUMNS of the four lowest M-register bits (K6g, k_gen_cols) */ \
+    X(fuse_zskip, 1)              /* passes behind a circuit front: waves whose share of the tile is all +0 skip the rounds (FusePass::zskip) */ \
+    X(fuse_zskip_maxw, 2)         /* ... on tiles of at most 2^(8 + this) amplitudes */ \
+    X(fuse_lowtile, 1)            /* a pass whose hot bits lie below bit 12 takes the whole low end of the index as its (contiguous) tile */ \
+    X(fuse_q3_c3, 1)              /* tolerance mode: radix-8 passes with 2^3-amplitude runs (9 hot bits) when that saves a pass */ \
+    X(fuse_front, 1)              /* a pending reset / collapse is written together with the closed-form front of the queue (K0b) */ \
+    X(fuse_tol_T, 10)             /* tolerance mode: tile bits of diagonal passes when that costs no extra pass (0: same as the rest) */ \
+    X(fuse_tol_occ, 6)            /* tolerance-mode passes (merged diagonals): waves per SIMD the kernel is built for (6 or 8) */ \
+    X(fuse_rounds_occ, 7)         /* rounds-form passes: k_fused_rounds built for this many waves per SIMD (6 or 7; 0 = the general kernel) */ \
+    X(fuse_T_phase, 10)           /* tile bits of phase-dominated passes (one tile per workgroup, not pipelined); 0 = same as the rest */ \
+    X(fuse_c_phase, 4) \
+    X(fuse_phase_ratio, 6)        /* a pass is phase-dominated when it holds at least this many phases per H (and nothing else) */ \
+    X(fuse_camruns, 1)            /* rounds form: fold runs of permutation-type modular multiplies into one gather */ \
+    X(fuse_hsweep_T, 12)          /* tile geometry of an all-Hadamard tail when it saves passes (0: never) */ \
+    X(fuse_hsweep_c, 3) \
+    X(fuse_dbg, 0)                /* diagnostics (tools/experiments/probe_pass.py): bit 0 skip the gates, bit 1 skip the stores, bit 2 skip the fill of a rounds pass */ \
+    X(fuse_rounds, 1)             /* fused passes: rounds form (4 amplitudes per thread in registers, radix-4 H steps) */ \
+    X(fuse_ldsdma, 1)             /* fused passes: fill the tile with global_load_lds (LDS-DMA) */ \
+    X(fuse_max_queue, 4096) \
+    X(fuse_chain, 1)              /* runs of consecutive rounds-form passes go through the register's second buffer: every pass but the first reads */ \
+                                  /* contiguous tiles, only its stores are gathered, the last one stores the identity layout again (FusePass) */ \
+    X(fuse_chain_min_n, 20)       /* ... for registers of at least 2^this amplitudes */ \
+    X(meas_block_log, 0)          /* parallel measurement: 2^this amplitudes per block (8..13); 0 = from the shard size */ \
+    X(meas_parallel, 1)           /* 0: always the single-wave sequential scan */ \
+    X(meas_min_log2, 12)          /* shards below 2^this amplitudes use the single-wave scan (tools/experiments/probe_shots.py) */ \
+    X(meas_dbg, 0)                /* K4c diagnostics: bit 0 = no look-back (every binade guess from cum_in alone: times the pass without it); bit 1 = k_meas_fast hands over to the walk at its third candidate */ \
+    X(meas_host_out, 1)           /* the scan's result is written straight into pinned host memory (no copy back on the stream) */ \
+    X(meas_fast, 1)               /* K4c: the scan's events by k_meas_fast (list of candidate records, 8 waves) with k_meas_walk as the fallback; 0: the walk alone */ \
+    X(meas_spin_limit, 4000000)   /* K4c: polls a look-back may spend on one window before it gives up (the block is then scanned exactly) */ \
+    X(collapse_grid_cap, 65536)   /* K11 (k_collapse_range): workgroups, each walks 16-KiB steps */ \
+    X(collapse_upt, 4)            /* K11: amplitudes per lane and step (4 or 8) */ \
+    X(collapse_perm, 1)           /* K11: ranges starting at qubit 3 .. 5 take the wave-uniform index map (0: the plain map, divergent there) */ \
+    X(u2_variant, 0)              /* K13 (two-qubit gate): 0 = the plan (line forms from n = 9 when lo or the control is below bit 3), 1 = quad form for every qubit pair */ \
+    X(u2_nt, 1)                   /* K13: nontemporal accesses (only where a wave instruction covers whole 128-B lines, as in K12) */ \
+    X(u2_streams_log2, -1)        /* K13: -1 = plain gate: the Hadamard plan's streams for hi; controlled: the phase gate's rule.  Both are guesses taken */ \
+                                  /* over from kernels with two address streams, not four; tools/time_two_qubit_gate.py is there to measure them */ \
+    X(prot_grid_cap, 2048)        /* K15 (k_pauli_rot): workgroups, each walks its units (tiles, or pairs of tiles) with this stride; 0 = one unit each */
 struct Tune {
-    long h_variant   = 0;      // 0: auto, 1: always pair form, 2: wave-tile form where it applies
-    long h_ppt       = 1;      // pairs per thread, pair form
-    long h_nt        = 3;      // nontemporal: bit 0 loads, bit 1 stores (pair form, q >= 3)
-    long h_wave_nt   = 3;      // same for the wave-tile form in auto mode
-    long h_wc        = 0;      // pair form: per-wave-contiguous load order
-    long h_block     = 64;     // pair form: threads per block (64/128/256/512)
-    long h_streams_log2 = 0;   // pair form: deal tiles as 2^k interleaved streams (3 = one per XCD)
-    long h_skew      = 0;      // pair form: stream j is rotated by j * skew tiles inside its segment
-    long h_grid_cap  = 0;      // 0: one tile per block (no cap)
-    long h_wave_r    = 4;      // registers per lane, wave-tile form (2, 4 or 8)
-    long h_wave_block = 256;   // wave-tile form: threads per block (64 or 256)
-    long h_wave_maxq = 7;      // auto: use the wave-tile form for q <= this
-    long ph_apt      = 1;      // measured (tools/experiments/tune_phase.py): one amplitude per lane, one wave per block,
-    long ph_grid_cap = 0;      // nontemporal, 2 or 4 interleaved streams: 6.4-6.9 TB/s on the touched quarter
-    long ph_block    = 64;
-    long ph_nt       = 1;
-    long ph_streams_log2 = -1; // -1: auto (1 when the lowest mask bit >= 8, else 2)
-    long ph_lines    = 1;      // masks with a bit below 3: the whole-line kernel k_phase_lines (0: k_phase for every mask)
-    long cam_grid_cap = 0;     // (round 3: one tile per workgroup, 2.80-2.89 ms per gate at n = 30 against 2.85-3.0 with 4096 workgroups)
-                               // (measured n = 30, C = 21, M = 5: whole tiles 2.9-3.4 ms = 17.2 GB at 5.0-5.9 TB/s, partial 2.8-2.9 ms = 14.5 GB at 5.0-5.2)
-    long cam_logT    = 8;      // modular multiply: tile = 2^this amplitudes, at least the 2^M block (n = 30, C = 21, M = 5: 2^11 2.65 ms, 2^10 2.50, 2^9 2.3-2.6, 2^8 2.3; 2^12 4.2)
-    long cam_skip    = 1;      // modular multiply: the 128-B lines of a 2^M block above row C are neither sources nor destinations: not read
-    long cam_nt_lines = 0;     // modular multiply: completely rewritten lines leave as nontemporal stores (the partly rewritten one through L2)
-    long fuse_T      = 11;     // fused passes: tile = 2^T amplitudes in LDS (8..12)
-    long fuse_c      = 4;      // fused passes: contiguous low bits of a tile (runs of 16 * 2^c bytes)
-    long fuse_grid_cap = 65536; // (round 4, chained passes: 65536 beats 24576 by 1-2 %, one per tile loses 15 % on the n = 30 exact Shor circuit)
-                               // workgroups of the one-tile-per-workgroup form (each walks several tiles: the table fill at kernel start is amortised)
-    long fuse_qround = 1;      // tolerance mode: rounds of the shape H D H D run as straight-line code (FUSE_QROUND)
-    long fuse_q3_cap = 65536;  // workgroups of k_fused_q3 with tables (round 3, in place: 3072 best; round 4, chained: n = 28 inverse QFT 6.12 ms with 3072, 5.85 with 65536;
-                               // n = 30 Shor circuit 18.7 with 65536, 20.5 with one per tile)
-    long fuse_q3_cap_exact = 0;  // all-Hadamard radix-8 passes (no tables to stage): one workgroup per tile (round 4, chained passes: n = 30 sweep 20.2 ms with 8192, 19.2 with one per tile)
-    long fuse_q3 = 1;          // tolerance mode: radix-8 fast rounds on 2^12 tiles when they save a pass (k_fused_q3)
-    long fuse_x8     = 1;      // bit-exact phase-dominated passes: the walk on 8 amplitudes per thread (k_fused_x8, round 5)
-    long fuse_x8_T   = 12;     // ... on tiles of 2^this amplitudes (10 .. 12) with
-    long fuse_x8_c   = 4;      // ... this many contiguous low bits
-    long fuse_streams_log2 = -1;   // which tile a workgroup of k_fused_q3 / k_fused_x8 / k_fused_rounds takes (fuse_stream_tile): the 2^this low bits of its slot number ...
-    long fuse_streams_pos  = -1;   // ... go to this bit of the tile number (+ 1; 0 = on top).  -1: by the kind of pass (launch_pass)
-    long fuse_x8t    = 1;      // tolerance mode: radix-8 fast rounds run on the k_fused_x8 shell (hand-written round, K6x-t) instead of k_fused_q3
-    long fuse_x8_min_tiles_log2 = 2;   // ... on registers of at least 2^this tiles
-    long fuse_x8_ratio = 1;    // ... for passes without multiplies that hold at least this many phases per Hadamard
-    long fuse_x8_map = 1;      // ... the wave number rides on the tile bits most gates of a round test (0: plain ascending order)
-    long fuse_x8_cap = 65536;  // ... workgroups
-    long fuse_gen    = 1;      // a pending reset / collapse + circuit front is GENERATED inside the first fused pass behind it (no write pass, no read)
-    long fuse_chain_dir = -1;  // chained passes: 0 = a pass stores gathered so that the NEXT tile is contiguous (reads whole tiles); 1 = stores its own tile contiguously, the next pass gathers; -1 = by the kind of chain
-    long cam_block   = 0;      // threads per workgroup of k_camodc (0: 256; 1024 for tiles of 2^12 amplitudes)
-    long cam_stage_mb = 1024;  // M > 12: staging buffer of the in-place modular multiply (MiB; at least one 2^M-block)
-    long fuse_compact = 1;     // behind a circuit front whose M register stays on a small orbit: the flush runs on a compact copy of the state (compact_chain)
-    long fuse_compact_lazy = 1; // ... and stays compact behind a whole-circuit entry point until something other than measure_state looks at the state
-    long fuse_plan_cache = 1;   // a flush whose inputs (shape, mode, knobs, front, gate list) are bit for bit those of the last one reuses its plan and, when nothing was uploaded since, its records on the device
-    long fuse_expand_fused = 1;  // the last pass of a compact chain stores the real register itself (k_fused_x8's expanding store) instead of k_expand_compact
-    long fuse_cols_tol = 1;    // tolerance mode: the by-columns pass of a compact chain keeps its merged diagonals (fast rounds inside k_gen_cols)
-    long fuse_cols_cap = 12288; // workgroups of a k_gen_cols launch (a workgroup's prologue is long; n = 30 Shor circuit 11.06-11.09 ms with 12288-24576, 11.14-11.3 with 65536, 12.07 with 1536; tolerance 7.4-7.8 against 8.1)
-    long fuse_cols_waves = 0;  // waves per workgroup of k_gen_cols (4 ... 8; the first four generate and store the tile); 0: 8 for launches of at most 1024 tiles, else 4
-    long fuse_expand_direct = 1; // k_expand_compact: 1 = gather the compact sources straight from memory (8 per thread in flight) instead of staging 64 blocks in LDS
-    long fuse_gen_cols = 1;    // the generated first pass by COLUMNS of the four lowest M-register bits (K6g, k_gen_cols)
-    long fuse_zskip  = 1;      // passes behind a circuit front: waves whose share of the tile is all +0 skip the rounds (FusePass::zskip)
-    long fuse_zskip_maxw = 2;  // ... on tiles of at most 2^(8 + this) amplitudes
-    long fuse_lowtile = 1;     // a pass whose hot bits lie below bit 12 takes the whole low end of the index as its (contiguous) tile
-    long fuse_q3_c3 = 1;       // tolerance mode: radix-8 passes with 2^3-amplitude runs (9 hot bits) when that saves a pass
-    long fuse_front = 1;       // a pending reset / collapse is written together with the closed-form front of the queue (K0b)
-    long fuse_tol_T = 10;      // tolerance mode: tile bits of diagonal passes when that costs no extra pass (0: same as the rest)
-    long fuse_tol_occ = 6;     // tolerance-mode passes (merged diagonals): waves per SIMD the kernel is built for (6 or 8)
-    long fuse_rounds_occ = 7;  // rounds-form passes: k_fused_rounds built for this many waves per SIMD (6 or 7; 0 = the general kernel)
-    long fuse_T_phase = 10;    // tile bits of phase-dominated passes (one tile per workgroup, not pipelined); 0 = same as the rest
-    long fuse_c_phase = 4;
-    long fuse_phase_ratio = 6; // a pass is phase-dominated when it holds at least this many phases per H (and nothing else)
-    long fuse_camruns = 1;     // rounds form: fold runs of permutation-type modular multiplies into one gather
-    long fuse_hsweep_T = 12;   // tile geometry of an all-Hadamard tail when it saves passes (0: never)
-    long fuse_hsweep_c = 3;
-    long fuse_dbg    = 0;      // diagnostics (tools/experiments/probe_pass.py): bit 0 skip the gates, bit 1 skip the stores, bit 2 skip the fill of a rounds pass
-    long fuse_rounds = 1;      // fused passes: rounds form (4 amplitudes per thread in registers, radix-4 H steps)
-    long fuse_ldsdma = 1;      // fused passes: fill the tile with global_load_lds (LDS-DMA)
-    long fuse_max_queue = 4096;
-    long fuse_chain  = 1;      // runs of consecutive rounds-form passes go through the register's second buffer: every pass but the first reads
-                               // contiguous tiles, only its stores are gathered, the last one stores the identity layout again (FusePass)
-    long fuse_chain_min_n = 20; // ... for registers of at least 2^this amplitudes
-    long meas_block_log = 0;   // parallel measurement: 2^this amplitudes per block (8..13); 0 = from the shard size
-    long meas_parallel = 1;    // 0: always the single-wave sequential scan
-    long meas_min_log2 = 12;   // shards below 2^this amplitudes use the single-wave scan (tools/experiments/probe_shots.py)
-    long meas_dbg = 0;         // K4c diagnostics: bit 0 = no look-back (every binade guess from cum_in alone: times the pass without it); bit 1 = k_meas_fast hands over to the walk at its third candidate
-    long meas_host_out = 1;    // the scan's result is written straight into pinned host memory (no copy back on the stream)
-    long meas_fast = 1;        // K4c: the scan's events by k_meas_fast (list of candidate records, 8 waves) with k_meas_walk as the fallback; 0: the walk alone
-    long meas_spin_limit = 4000000;   // K4c: polls a look-back may spend on one window before it gives up (the block is then scanned exactly)
-    long collapse_grid_cap = 65536;   // K11 (k_collapse_range): workgroups, each walks 16-KiB steps
-    long collapse_upt = 4;     // K11: amplitudes per lane and step (4 or 8)
-    long collapse_perm = 1;    // K11: ranges starting at qubit 3 .. 5 take the wave-uniform index map (0: the plain map, divergent there)
-    long u2_variant  = 0;      // K13 (two-qubit gate): 0 = the plan (line forms from n = 9 when lo or the control is below bit 3), 1 = quad form for every qubit pair
-    long u2_nt       = 1;      // K13: nontemporal accesses (only where a wave instruction covers whole 128-B lines, as in K12)
-    long u2_streams_log2 = -1; // K13: -1 = plain gate: the Hadamard plan's streams for hi; controlled: the phase gate's rule.  Both are guesses taken
-                               // over from kernels with two address streams, not four; tools/time_two_qubit_gate.py is there to measure them
-    long prot_grid_cap = 2048; // K15 (k_pauli_rot): workgroups, each walks its units (tiles, or pairs of tiles) with this stride; 0 = one unit each
+#define X(name, value) long name = value;
+    QCX_TUNABLES(X)
+#undef X
 };
 static Tune g_tune;
 static std::mutex g_tune_mutex;
@@ -177,17 +182,17 @@ static Tune tune_now() { std::lock_guard<std::mutex> lock(g_tune_mutex); return 
 
 extern "C" int qcx_tune_set(const char *key, long value)
 {
-#define K(name) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); g_tune.name = value; return QCX_NO_ERROR; }
-    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt) K(u2_variant) K(u2_nt) K(u2_streams_log2) K(prot_grid_cap)
-#undef K
+#define X(name, dflt) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); g_tune.name = value; return QCX_NO_ERROR; }
+    QCX_TUNABLES(X)
+#undef X
     return QCX_BAD_ARGUMENTS;
 }
 
 extern "C" long qcx_tune_get(const char *key)
 {
-#define K(name) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); return g_tune.name; }
-    K(h_variant) K(h_ppt) K(h_nt) K(h_wave_nt) K(h_wc) K(h_block) K(h_streams_log2) K(h_skew) K(h_grid_cap) K(h_wave_r) K(h_wave_block) K(h_wave_maxq) K(ph_apt) K(ph_grid_cap) K(ph_block) K(ph_nt) K(ph_streams_log2) K(ph_lines) K(cam_grid_cap) K(cam_skip) K(cam_nt_lines) K(cam_logT) K(cam_block) K(cam_stage_mb) K(meas_parallel) K(meas_min_log2) K(meas_block_log) K(meas_spin_limit) K(meas_dbg) K(meas_fast) K(meas_host_out) K(fuse_T) K(fuse_c) K(fuse_grid_cap) K(fuse_max_queue) K(fuse_ldsdma) K(fuse_rounds) K(fuse_dbg) K(fuse_hsweep_T) K(fuse_hsweep_c) K(fuse_camruns) K(fuse_T_phase) K(fuse_c_phase) K(fuse_phase_ratio) K(fuse_rounds_occ) K(fuse_tol_occ) K(fuse_qround) K(fuse_tol_T) K(fuse_front) K(fuse_q3) K(fuse_q3_cap) K(fuse_q3_cap_exact) K(fuse_chain) K(fuse_chain_dir) K(fuse_chain_min_n) K(fuse_q3_c3) K(fuse_lowtile) K(fuse_gen) K(fuse_gen_cols) K(fuse_cols_waves) K(fuse_cols_cap) K(fuse_cols_tol) K(fuse_compact) K(fuse_expand_direct) K(fuse_compact_lazy) K(fuse_expand_fused) K(fuse_plan_cache) K(fuse_zskip) K(fuse_zskip_maxw) K(fuse_x8) K(fuse_x8_T) K(fuse_x8_c) K(fuse_x8_map) K(fuse_x8_cap) K(fuse_x8_ratio) K(fuse_x8_min_tiles_log2) K(fuse_x8t) K(fuse_streams_log2) K(fuse_streams_pos) K(collapse_grid_cap) K(collapse_perm) K(collapse_upt) K(u2_variant) K(u2_nt) K(u2_streams_log2) K(prot_grid_cap)
-#undef K
+#define X(name, dflt) if (!strcmp(key, #name)) { std::lock_guard<std::mutex> lock(g_tune_mutex); return g_tune.name; }
+    QCX_TUNABLES(X)
+#undef X
     return -1;
 }
 
@@ -572,6 +577,13 @@ static bool launch_u_wave(amp_t *a, unsigned q, const UMat &U, uint64_t namps, l
 // h_streams_log2, h_nt (pair form only).  The controlled gate touches the control-set half: the pair form with the control as a second
 // squeezed-out bit (streams as for a phase: ph_streams_log2, ph_nt), or, with the control or the target inside a 128-B line
 // and n_local >= 9, the whole-line form (ph_lines = 0: the pair form for every pair of qubits).
+static int launch_status(const char *what)      // did the launch go out?  (the epilogue of the general gates' shard-level entry points)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "%s launch: %s", what, hipGetErrorString(e)); return QCX_HIP_ERROR; }
+    return QCX_NO_ERROR;
+}
+
 extern "C" int qcx_shard_one_qubit(void *amp, unsigned n_local, unsigned q, int ctl, const double *u, void *stream)
 {
     if (!amp || !u || n_local == 0 || n_local > 40) return QCX_BAD_ARGUMENTS;
@@ -620,9 +632,7 @@ extern "C" int qcx_shard_one_qubit(void *amp, unsigned n_local, unsigned q, int 
             else                             launch_u_pair<1, false, true>(a, q, c, U, namps >> 2, slog, st);
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "one-qubit gate launch: %s", hipGetErrorString(e)); return QCX_HIP_ERROR; }
-    return QCX_NO_ERROR;
+    return launch_status("one-qubit gate");
 }
 
 // ---- K13: any two-qubit gate, plain or controlled --------------------------------------------------------------------------
@@ -696,9 +706,29 @@ extern "C" int qcx_shard_two_qubit(void *amp, unsigned n_local, unsigned q0, uns
         if (ctl < 0) { if (ntq) launch_u2_quad<true, false>(a, lo, hi, 0, U, namps >> 2, want, st); else launch_u2_quad<false, false>(a, lo, hi, 0, U, namps >> 2, want, st); }
         else         { if (ntq) launch_u2_quad<true, true>(a, lo, hi, c, U, namps >> 3, want, st);  else launch_u2_quad<false, true>(a, lo, hi, c, U, namps >> 3, want, st); }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "two-qubit gate launch: %s", hipGetErrorString(e)); return QCX_HIP_ERROR; }
-    return QCX_NO_ERROR;
+    return launch_status("two-qubit gate");
+}
+
+// ---- K14 / K15: the units of work of a Pauli string (PauliTiles in qcx_kernels.h) ------------------------------------------------
+// Tiles of the T = min(n, 12) lowest index bits.  shape: 0 = no X or Y in the string, 1 = the partner i ^ x_mask inside the tile,
+// 2 = in another tile: the units are pairs of tiles (n > 12: whole tiles); full: the tile has all 2^12 elements.
+struct PauliUnits { unsigned T; uint64_t nunits; int shape; bool full; };
+template <int SHAPE, bool FULL> struct PauliForm { static constexpr int shape = SHAPE; static constexpr bool full = FULL; };
+
+static PauliUnits pauli_units(unsigned n, uint64_t x_mask)
+{
+    const unsigned T = std::min(n, 12u);
+    const uint64_t ntiles = ((uint64_t)1) << (n - T);
+    if (x_mask >> T) return {T, ntiles >> 1, 2, true};
+    return {T, ntiles, x_mask ? 1 : 0, T == 12};
+}
+
+// launch(PauliForm<shape, full>()): the five forms both kernels are built in
+template <class Launch> static void pauli_dispatch(const PauliUnits &pu, Launch launch)
+{
+    if (pu.shape == 2) launch(PauliForm<2, true>());
+    else if (pu.full) { if (pu.shape) launch(PauliForm<1, true>()); else launch(PauliForm<0, true>()); }
+    else { if (pu.shape) launch(PauliForm<1, false>()); else launch(PauliForm<0, false>()); }
 }
 
 // ---- K15: the rotation about a Pauli string -----------------------------------------------------------------------------------
@@ -711,19 +741,12 @@ extern "C" int qcx_shard_pauli_rotation(void *amp, unsigned n_local, uint64_t x_
     const unsigned g = (unsigned)__builtin_popcountll(x_mask & z_mask) & 3u;
     // -i i^g s: (+0, -s), (s, +0), (+0, s), (-s, +0)
     const PRot R = {c, 0.0, g == 1 ? s : (g == 3 ? -s : 0.0), g == 0 ? -s : (g == 2 ? s : 0.0)};
-    const unsigned T = std::min(n_local, 12u);
-    const uint64_t ntiles = ((uint64_t)1) << (n_local - T);
-    const uint64_t nunits = (x_mask >> T) ? ntiles >> 1 : ntiles;
-    const unsigned grid = grid_for(nunits, 1, tune_now().prot_grid_cap, 256);
-#define QCX_PROT(SHAPE, FULL) hipLaunchKernelGGL((k_pauli_rot<SHAPE, FULL>), dim3(grid), dim3(256), 0, \
-                                                 (hipStream_t)stream, (amp_t *)amp, nunits, T, x_mask, z_mask, g, R)
-    if (x_mask >> T) QCX_PROT(2, true);                              // (n > 12: whole tiles)
-    else if (T == 12) { if (x_mask) QCX_PROT(1, true); else QCX_PROT(0, true); }
-    else { if (x_mask) QCX_PROT(1, false); else QCX_PROT(0, false); }
-#undef QCX_PROT
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "pauli rotation launch: %s", hipGetErrorString(e)); return QCX_HIP_ERROR; }
-    return QCX_NO_ERROR;
+    const PauliUnits pu = pauli_units(n_local, x_mask);
+    const unsigned grid = grid_for(pu.nunits, 1, tune_now().prot_grid_cap, 256);
+    pauli_dispatch(pu, [&](auto f) {
+        hipLaunchKernelGGL((k_pauli_rot<f.shape, f.full>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (amp_t *)amp, pu.nunits, pu.T, x_mask, z_mask, g, R);
+    });
+    return launch_status("pauli rotation");
 }
 
 static unsigned gcd_u32(unsigned a, unsigned b) { while (b) { unsigned t = a % b; a = b; b = t; } return a; }
@@ -1918,13 +1941,22 @@ extern "C" int qcx_reset_register(qcx_register *r)
     return qcx_shard_reset(r->amp, r->n, 1, r->stream);
 }
 
+// the same gate as the sharded queue takes it: LOGICAL qubits q (and q2) in the place of a mask
+static SGate sharded_gate(const QGate &g, unsigned q, unsigned q2 = 0)
+{
+    SGate s; memset(&s, 0, sizeof s); s.type = g.type; s.q = q; s.q2 = q2; s.c = g.c; s.s = g.s; s.C = g.C; s.A = g.A;
+    return s;
+}
+
 extern "C" int qcx_hadamard_gate(unsigned q, qcx_register *r)
 {
     if (!r) return QCX_BAD_ARGUMENTS;
     if (q >= r->n) return QCX_BAD_QUBIT;
-    if (r->sh) { SGate g; memset(&g, 0, sizeof g); g.type = FUSE_H; g.q = q; return sh_push(r->sh, g); }
-    if (r->nonfinite) { QGate g; memset(&g, 0, sizeof g); g.type = FUSE_H; g.q = q; return strict_gate(r, g); }
-    if (r->fusion > 0 || r->composite) { QGate g; memset(&g, 0, sizeof g); g.type = FUSE_H; g.q = q; return fuse_push(r, g); }
+    QGate g; memset(&g, 0, sizeof g);
+    g.type = FUSE_H; g.q = q;
+    if (r->sh) return sh_push(r->sh, sharded_gate(g, q));
+    if (r->nonfinite) return strict_gate(r, g);
+    if (r->fusion > 0 || r->composite) return fuse_push(r, g);
     FLUSH(r);                                         // (a lazily pending reset / collapse is written first)
     QCX_TRY(canon_if_dirty(r));
     return qcx_shard_hadamard(r->amp, r->n, q, r->stream);
@@ -1948,20 +1980,33 @@ extern "C" int qcx_c_phase_shift_gate(unsigned c, unsigned t, double theta, qcx_
     if (c >= r->n || t >= r->n || c == t) return QCX_BAD_QUBIT;
     double er, ei;
     qcx_polar(theta, &er, &ei);
-    if (r->sh) { SGate g; memset(&g, 0, sizeof g); g.type = FUSE_PHASE; g.q = c; g.q2 = t; g.c = er; g.s = ei; return sh_push(r->sh, g); }
-    if (r->nonfinite) {
-        QGate g; memset(&g, 0, sizeof g);
-        g.type = FUSE_PHASE; g.mask = ((uint64_t)1 << c) | ((uint64_t)1 << t); g.c = er; g.s = ei;
-        return strict_gate(r, g);
-    }
-    if (r->fusion > 0 || r->composite) {
-        QGate g; memset(&g, 0, sizeof g);
-        g.type = FUSE_PHASE; g.mask = ((uint64_t)1 << c) | ((uint64_t)1 << t); g.c = er; g.s = ei;
-        return fuse_push(r, g);
-    }
+    QGate g; memset(&g, 0, sizeof g);
+    g.type = FUSE_PHASE; g.mask = ((uint64_t)1 << c) | ((uint64_t)1 << t); g.c = er; g.s = ei;
+    if (r->sh) return sh_push(r->sh, sharded_gate(g, c, t));
+    if (r->nonfinite) return strict_gate(r, g);
+    if (r->fusion > 0 || r->composite) return fuse_push(r, g);
     FLUSH(r);
     QCX_TRY(canon_if_dirty(r));
-    return qcx_shard_phase(r->amp, r->n, ((uint64_t)1 << c) | ((uint64_t)1 << t), er, ei, r->stream);
+    return qcx_shard_phase(r->amp, r->n, g.mask, er, ei, r->stream);
+}
+
+// each component of a gate's matrix must be finite with |.| <= 1 (u: ncomp doubles, re and im interleaved)
+static int check_matrix(const char *who, const double *u, int ncomp)
+{
+    for (int k = 0; k < ncomp; k++)
+        if (!(fabs(u[k]) <= 1.0)) { set_error("%s: matrix component %d is %g (each must be finite with |.| <= 1)", who, k, u[k]); return QCX_BAD_ARGUMENTS; }
+    return QCX_NO_ERROR;
+}
+
+// What a gate that is never queued (K12, K13, K15) does behind its argument checks: a sharded register is refused; queued gates,
+// a pending basis state or a compact circuit result are flushed; a pass that rewrites every amplitude as 0 + ... -- the strict
+// pass of a non-finite register, or a kernel that always does (rewrites_all) -- leaves canonical zeros, any other needs them.
+static int unqueued_gate(qcx_register *r, const char *who, bool rewrites_all)
+{
+    if (r->sh) { set_error("%s: not available on a sharded register", who); return QCX_UNSUPPORTED; }
+    FLUSH(r);
+    if (r->nonfinite || rewrites_all) { r->zeros_dirty = 0; return QCX_NO_ERROR; }
+    return canon_if_dirty(r);
 }
 
 // Any one-qubit gate (ctl < 0: plain).  Never queued, in any fusion mode: the fused passes know H and phase only, so the call
@@ -1969,20 +2014,15 @@ extern "C" int qcx_c_phase_shift_gate(unsigned c, unsigned t, double theta, qcx_
 static int one_qubit_gate(int ctl, unsigned q, const double *u, qcx_register *r, const char *who)
 {
     if (!r || !u) return QCX_BAD_ARGUMENTS;
-    for (int k = 0; k < 8; k++)
-        if (!(fabs(u[k]) <= 1.0)) { set_error("%s: matrix component %d is %g (each must be finite with |.| <= 1)", who, k, u[k]); return QCX_BAD_ARGUMENTS; }
+    QCX_TRY(check_matrix(who, u, 8));
     if (q >= r->n || (ctl >= 0 && ((unsigned)ctl >= r->n || (unsigned)ctl == q))) return QCX_BAD_QUBIT;
-    if (r->sh) { set_error("%s: not available on a sharded register", who); return QCX_UNSUPPORTED; }
-    FLUSH(r);                                         // queued gates, a pending basis state, a compact circuit result
-    if (r->nonfinite) {                               // strict pass: every amplitude rewritten with the mat-vec's own products
-        r->zeros_dirty = 0;
-        if (ctl < 0) return qcx_shard_one_qubit(r->amp, r->n, q, -1, u, r->stream);      // (the plain kernels already are strict)
+    QCX_TRY(unqueued_gate(r, who, false));
+    if (r->nonfinite && ctl >= 0) {                   // (the plain kernels already are strict)
         const UMat U = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]};
         hipLaunchKernelGGL(k_strict_cu, dim3(grid_for(r->dim >> 1, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, q, (unsigned)ctl, U, 1.0, 0.0);
         HIP_TRY(hipGetLastError());
         return QCX_NO_ERROR;
     }
-    QCX_TRY(canon_if_dirty(r));
     return qcx_shard_one_qubit(r->amp, r->n, q, ctl, u, r->stream);
 }
 
@@ -2002,22 +2042,17 @@ extern "C" int qcx_c_one_qubit_gate(unsigned c, unsigned q, const double *u, qcx
 static int two_qubit_gate(int ctl, unsigned q0, unsigned q1, const double *u, qcx_register *r, const char *who)
 {
     if (!r || !u) return QCX_BAD_ARGUMENTS;
-    for (int k = 0; k < 32; k++)
-        if (!(fabs(u[k]) <= 1.0)) { set_error("%s: matrix component %d is %g (each must be finite with |.| <= 1)", who, k, u[k]); return QCX_BAD_ARGUMENTS; }
+    QCX_TRY(check_matrix(who, u, 32));
     if (q0 >= r->n || q1 >= r->n || q0 == q1) return QCX_BAD_QUBIT;
     if (ctl >= 0 && ((unsigned)ctl >= r->n || (unsigned)ctl == q0 || (unsigned)ctl == q1)) return QCX_BAD_QUBIT;
-    if (r->sh) { set_error("%s: not available on a sharded register", who); return QCX_UNSUPPORTED; }
-    FLUSH(r);                                         // queued gates, a pending basis state, a compact circuit result
-    if (r->nonfinite) {                               // strict pass: every amplitude rewritten with the mat-vec's own products
-        r->zeros_dirty = 0;
-        if (ctl < 0) return qcx_shard_two_qubit(r->amp, r->n, q0, q1, -1, u, r->stream);      // (the plain kernels already are strict)
+    QCX_TRY(unqueued_gate(r, who, false));
+    if (r->nonfinite && ctl >= 0) {                   // (the plain kernels already are strict)
         const U4Mat U = u4_ascending(q0, q1, u);
         const unsigned lo = q0 < q1 ? q0 : q1, hi = q0 < q1 ? q1 : q0;
         hipLaunchKernelGGL(k_strict_cu2, dim3(grid_for(r->dim >> 2, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, lo, hi, (unsigned)ctl, U, 1.0, 0.0);
         HIP_TRY(hipGetLastError());
         return QCX_NO_ERROR;
     }
-    QCX_TRY(canon_if_dirty(r));
     return qcx_shard_two_qubit(r->amp, r->n, q0, q1, ctl, u, r->stream);
 }
 
@@ -2043,11 +2078,9 @@ extern "C" int qcx_pauli_rotation(uint64_t x_mask, uint64_t z_mask, double theta
         set_error("pauli_rotation: masks %#llx / %#llx reach past the %u qubits", (unsigned long long)x_mask, (unsigned long long)z_mask, r->n);
         return QCX_BAD_QUBIT;
     }
-    if (r->sh) { set_error("pauli_rotation: not available on a sharded register"); return QCX_UNSUPPORTED; }
+    QCX_TRY(unqueued_gate(r, "pauli_rotation", true));
     double c, s;
     qcx_polar(theta / 2.0, &c, &s);
-    FLUSH(r);                                         // queued gates, a pending basis state, a compact circuit result
-    r->zeros_dirty = 0;                               // every amplitude is rewritten as 0 + ...: canonical zeros
     return qcx_shard_pauli_rotation(r->amp, r->n, x_mask, z_mask, c, s, r->stream);
 }
 
@@ -2055,17 +2088,17 @@ extern "C" int qcx_c_amodc_gate(unsigned C, unsigned long long atox, unsigned c,
 {
     if (!r || C == 0) return QCX_BAD_ARGUMENTS;
     if (c >= r->n) return QCX_BAD_QUBIT;
-    if (r->sh) { SGate g; memset(&g, 0, sizeof g); g.type = FUSE_CAMODC; g.q = c; g.C = C; g.A = (unsigned)(atox % C); return sh_push(r->sh, g); }
-    if (r->nonfinite) { QGate g; memset(&g, 0, sizeof g); g.type = FUSE_CAMODC; g.q = c; g.C = C; g.A = (unsigned)(atox % C); return strict_gate(r, g); }
+    QGate g; memset(&g, 0, sizeof g);
+    g.type = FUSE_CAMODC; g.q = c; g.C = C; g.A = (unsigned)(atox % C);
+    if (r->sh) return sh_push(r->sh, sharded_gate(g, c));
+    if (r->nonfinite) return strict_gate(r, g);
     if (r->fusion > 0 || r->composite) {
-        QGate g; memset(&g, 0, sizeof g);
-        g.q = c; g.C = C; g.A = (unsigned)(atox % C);
-        g.type = camodc_closed_form(r->n, (unsigned)r->M, C, g.A, c) ? (uint32_t)FUSE_CAMODC : 99u;
+        if (!camodc_closed_form(r->n, (unsigned)r->M, C, g.A, c)) g.type = 99u;      // (queued, but runs stand-alone)
         return fuse_push(r, g);
     }
     FLUSH(r);
     QCX_TRY(canon_if_dirty(r));
-    return reg_camodc(r, C, (unsigned)(atox % C), c);
+    return reg_camodc(r, C, g.A, c);
 }
 
 extern "C" int qcx_swap_states(qcx_register *r) { return r ? QCX_NO_ERROR : QCX_BAD_ARGUMENTS; }
@@ -2404,14 +2437,10 @@ static int pauli_launch(qcx_register *r, uint64_t x, uint64_t z, double *value)
     double *const out = r->marg_buf + scratch;
     auto dst_of = [&](unsigned i) { return st[i].final_stage ? out : r->marg_buf + st[i].out_offset; };
     const unsigned g = (unsigned)__builtin_popcountll(x & z) & 3u;
-    const uint64_t ntiles = ((uint64_t)1) << (r->n - T);
-    const uint64_t nunits = (x >> T) ? ntiles >> 1 : ntiles;       // pairs of tiles when the partner lies in another tile
-#define QCX_PAULI(SHAPE, FULL) hipLaunchKernelGGL((k_pauli_leaves<SHAPE, FULL>), dim3((unsigned)std::min<uint64_t>(nunits, 2048)), dim3(256), 0, \
-                                                  r->stream, (const amp_t *)r->amp, dst_of(0), nunits, T, x, z, g)
-    if (x >> T) QCX_PAULI(2, true);                                  // (n > 12: whole tiles)
-    else if (T == 12) { if (x) QCX_PAULI(1, true); else QCX_PAULI(0, true); }
-    else { if (x) QCX_PAULI(1, false); else QCX_PAULI(0, false); }
-#undef QCX_PAULI
+    const PauliUnits pu = pauli_units(r->n, x);                    // (pu.T == T: checked against the plan above)
+    pauli_dispatch(pu, [&](auto f) {
+        hipLaunchKernelGGL((k_pauli_leaves<f.shape, f.full>), dim3((unsigned)std::min<uint64_t>(pu.nunits, 2048)), dim3(256), 0, r->stream, (const amp_t *)r->amp, dst_of(0), pu.nunits, T, x, z, g);
+    });
     HIP_TRY(hipGetLastError());
     for (unsigned i = 1; i < ns; i++) {
         MargParams P;

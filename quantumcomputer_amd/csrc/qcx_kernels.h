@@ -40,6 +40,40 @@ template <bool NT> __device__ __forceinline__ void st(amp_t *p, amp_t v)
     else *p = v;
 }
 
+// The reference's mat-vec on one stored triplet (Q:396-413): the matrix entry (mr, mi) times the amplitude x -- four products
+// and two sums, each rounded on its own (no FMA: this file is compiled with fp contraction off), nothing skipped where a
+// component is zero.  Every general gate (K9, K12, K13, K15) forms its products here and nowhere else.
+struct q_mul {
+    double mr, mi;
+    amp_t x;
+    __device__ __forceinline__ q_mul(double mr_, double mi_, amp_t x_) : mr(mr_), mi(mi_), x(x_) {}
+    __device__ __forceinline__ double re() const { return (mr * x.x) - (mi * x.y); }      // Q:409
+    __device__ __forceinline__ double im() const { return (mr * x.y) + (mi * x.x); }      // Q:412
+};
+
+// One row of that mat-vec: the reference's accumulator starts at (+0, +0) and adds the row's products in the order given
+// (ascending column), ((0 + p0) + p1) + ...  The "0 +" cannot be dropped: it turns a -0 first product into +0, which is what
+// the reference stores, and changes no other value; IEEE rules do not let a compiler fold it either (0 + -0 = +0 is not the
+// identity), and the build tests look for the surviving v_add_f64 with a literal 0.  q_row() alone is the empty sum (+0, +0).
+// (Each component's chain is formed in one piece, its products where they are added: few values are live at a time.)
+template <typename... P> __device__ __forceinline__ amp_t q_row(const P &... p)
+{
+    amp_t acc;
+    acc.x = 0.0; ((acc.x = acc.x + p.re()), ...);
+    acc.y = 0.0; ((acc.y = acc.y + p.im()), ...);
+    return acc;
+}
+
+// The interleaved block -> tile map of the general gates (K12, K13): with slog > 0 the 2^glog tiles are dealt as 2^slog
+// streams, so blocks b, b + 2^slog, ... walk one contiguous region (speed only, any placement is correct).  K1b and K2 keep
+// this line spelled out: their prologues are scheduled around it and they are the benchmark's kernels.
+__device__ __forceinline__ uint64_t stream_tile(unsigned glog, unsigned slog)
+{
+    uint64_t tile = blockIdx.x;
+    if (slog) tile = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    return tile;
+}
+
 // one Hadamard butterfly: a = amplitude with target bit 0, b = with target bit 1
 __device__ __forceinline__ void h_butterfly(amp_t &a, amp_t &b)
 {
@@ -140,7 +174,7 @@ __global__ __launch_bounds__(BLOCK) void k_h_wave(amp_t *__restrict__ amp, uint6
     // tile = 64*R amplitudes, one per wave per iteration; slog: stream-interleaved block order as in k_h_pair
     const unsigned lane = threadIdx.x & 63u;
     uint64_t blk = blockIdx.x;
-    if (slog) blk = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    if (slog) blk = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);      // (= stream_tile(), spelled out: see there)
     const uint64_t wave = (blk * BLOCK + threadIdx.x) >> 6;
     const uint64_t nwaves = ((uint64_t)gridDim.x * BLOCK) >> 6;
     for (uint64_t t = wave; t < ntiles; t += nwaves) {
@@ -164,7 +198,7 @@ __global__ __launch_bounds__(BLOCK) void k_phase(amp_t *__restrict__ amp, unsign
 {
     const uint64_t step = (uint64_t)gridDim.x * (BLOCK * APT);
     uint64_t tile0 = blockIdx.x;              // stream-interleaved tile order as in k_h_pair
-    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);      // (= stream_tile(), spelled out: see there)
     for (uint64_t base = tile0 * (BLOCK * APT); base < count; base += step) {
         amp_t v[APT];
         uint64_t idx[APT];
@@ -206,7 +240,7 @@ __global__ __launch_bounds__(BLOCK) void k_phase_lines(amp_t *__restrict__ amp, 
 {
     const uint64_t step = (uint64_t)gridDim.x * BLOCK;
     uint64_t tile0 = blockIdx.x;
-    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);      // (= stream_tile(), spelled out: see there)
     for (uint64_t p = tile0 * BLOCK + threadIdx.x; p < count; p += step) {
         uint64_t i = p;
         if (NH >= 1) i = insert_zero(i, h0) | ((uint64_t)1 << h0);
@@ -399,12 +433,8 @@ __global__ __launch_bounds__(256) void k_strict_h(amp_t *__restrict__ amp, unsig
     for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < half; p += (uint64_t)gridDim.x * 256u) {
         const uint64_t i0 = ((p & ~low) << 1) | (p & low), i1 = i0 | bitq;
         const amp_t a = amp[i0], b = amp[i1];
-        double lo_r = 0.0, lo_i = 0.0, hi_r = 0.0, hi_i = 0.0;
-        lo_r += (s * a.x) - (z * a.y);    lo_i += (s * a.y) + (z * a.x);        // row i0, column i0
-        lo_r += (s * b.x) - (z * b.y);    lo_i += (s * b.y) + (z * b.x);        // row i0, column i1
-        hi_r += (s * a.x) - (z * a.y);    hi_i += (s * a.y) + (z * a.x);        // row i1, column i0
-        hi_r += (-s * b.x) - (z * b.y);   hi_i += (-s * b.y) + (z * b.x);       // row i1, column i1
-        amp_t lo, hi; lo.x = lo_r; lo.y = lo_i; hi.x = hi_r; hi.y = hi_i;
+        const amp_t lo = q_row(q_mul(s, z, a), q_mul(s, z, b));    // row i0: columns i0, i1
+        const amp_t hi = q_row(q_mul(s, z, a), q_mul(-s, z, b));   // row i1
         amp[i0] = lo; amp[i1] = hi;
     }
 }
@@ -413,11 +443,7 @@ __global__ __launch_bounds__(256) void k_strict_phase(amp_t *__restrict__ amp, u
 {
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256u) {
         const amp_t v = amp[i];
-        double nr = 0.0, ni = 0.0;
-        if ((i & both) == both) { nr += (er * v.x) - (ei * v.y);   ni += (er * v.y) + (ei * v.x); }
-        else                    { nr += (one * v.x) - (z * v.y);   ni += (one * v.y) + (z * v.x); }
-        amp_t o; o.x = nr; o.y = ni;
-        amp[i] = o;
+        amp[i] = (i & both) == both ? q_row(q_mul(er, ei, v)) : q_row(q_mul(one, z, v));
     }
 }
 
@@ -438,14 +464,13 @@ __global__ __launch_bounds__(256) void k_strict_camodc(amp_t *__restrict__ amp, 
         __syncthreads();
         const int on = (ctl >= (int)M) ? (int)(((b << M) >> ctl) & 1u) : -1;      // -1: the control is a bit of the row
         for (unsigned d = threadIdx.x; d < B; d += 256u) {
-            double ar = 0.0, ai = 0.0;
+            amp_t acc = q_row();                                   // (a row of as many triplets as sources map to d)
             for (unsigned f = 0; f < B; f++) {
                 const bool cbit = on >= 0 ? on != 0 : ((f >> ctl) & 1u) != 0;
                 const unsigned to = cbit ? dst_on[f] : f;
-                if (to == d) { const amp_t v = blk[f]; ar += (one * v.x) - (z * v.y); ai += (one * v.y) + (z * v.x); }
+                if (to == d) { const q_mul p(one, z, blk[f]); acc.x += p.re(); acc.y += p.im(); }
             }
-            amp_t o; o.x = ar; o.y = ai;
-            g[d] = o;
+            g[d] = acc;
         }
     }
 }
@@ -4066,23 +4091,61 @@ __global__ __launch_bounds__(256) void k_marginal(MargParams P)
 }
 
 // ---------------------------------------------------------------------------
+// The tiling K14 and K15 walk a Pauli string (x_mask, z_mask) with.  A tile is the 2^T lowest index bits, T = min(n, 12); a
+// workgroup of 256 threads owns one, thread element j = tile-local e = tid + 256 j, j < EPT (n < 12: one partial tile, the
+// first nld elements of a thread exist).  The partner of index i is i ^ x_mask: element e ^ x_low of tile t ^ xh.
+//   PAIR (xh != 0): a unit of work is the pair of tiles (t, t ^ xh), t the one with the highest set bit hb of xh clear:
+//        tile_of(u) puts a zero into u at that bit.  Otherwise a unit is a tile.
+//   e ^ x_low = (tid ^ x_low's 8 low bits) + 256 (j ^ x_low's bits above): one lane offset (partner_lane), uniform steps
+//        (partner_elem), whole 128-B lines either way.
+//   popcount(i & z_mask) mod 2 = par(tile) + bit j of sodd (the thread's own element e) or of podd (its partner's e ^ x_low)
+// ---------------------------------------------------------------------------
+template <bool PAIR>
+struct PauliTiles {
+    static constexpr unsigned EPT = 16u;
+    unsigned T, nel, x_low, z_low, hb, nld, podd, sodd;
+    uint64_t xh, zh;
+    __device__ __forceinline__ PauliTiles(unsigned T_, uint64_t x_mask, uint64_t z_mask, unsigned tid)
+        : T(T_), nel(1u << T_), x_low((unsigned)x_mask & (nel - 1u)), z_low((unsigned)z_mask & (nel - 1u)),
+          hb(PAIR ? 63u - (unsigned)__clzll((long long)(x_mask >> T_)) : 0u), nld(0), podd(0), sodd(0),
+          xh(x_mask >> T_), zh(z_mask >> T_)
+    {
+#pragma unroll
+        for (unsigned j = 0; j < EPT; j++) {
+            const unsigned e = tid + 256u * j;
+            if (e < nel) nld = j + 1;
+            podd |= (unsigned)(__popc((e ^ x_low) & z_low) & 1) << j;
+            sodd |= (unsigned)(__popc(e & z_low) & 1) << j;
+        }
+    }
+    __device__ __forceinline__ uint64_t tile_of(uint64_t u) const
+    {
+        if constexpr (PAIR) return ((u >> hb) << (hb + 1u)) | (u & ((((uint64_t)1) << hb) - 1u));
+        else return u;
+    }
+    __device__ __forceinline__ unsigned par(uint64_t tile) const { return (unsigned)__popcll(tile & zh); }
+    __device__ __forceinline__ unsigned partner_lane(unsigned tid) const { return tid ^ (x_low & 255u); }
+    __device__ __forceinline__ unsigned partner_elem(unsigned j) const { return j ^ (x_low >> 8); }
+};
+
+// ---------------------------------------------------------------------------
 // K14  the first stage of a Pauli string's expectation value (qcx_pauli_expectation, DESIGN s4.5h; tests/pauli_ref.py is the
 // definition).  The string is (x_mask, z_mask), Y on x_mask & z_mask, g = popcount(x_mask & z_mask) mod 4.  The leaf of index i,
 // with a = amp[i] and b = amp[i ^ x_mask], every product and sum rounded on its own (no FMA):
 //     t = g even ? a.re * b.re + a.im * b.im : a.im * b.re - a.re * b.im
 //     leaf_i = 0.0 + (odd ? -t : t),   odd = (popcount((i ^ x_mask) & z_mask) + (g >> 1)) & 1
 // (the "0.0 +" turns a -0 into +0 and nothing else), and the value is K10's pairwise tree over all index bits on these leaves.
-// This kernel is stage 0 of qcx_marginal_plan(n, 0, 0): tiles of the T = min(n, 12) lowest index bits, all of them summed, so
+// This kernel is stage 0 of qcx_marginal_plan(n, 0, 0): PauliTiles' tiles (T = min(n, 12) lowest index bits), all of them summed, so
 // tile t's root goes to dst[t] and the later stages are plain k_marginal<MARG_DBL> launches.  Loads, the next unit's loads in
 // flight during the tree levels, and the levels themselves are k_marginal<MARG_AMP>'s.  Sign and g come from the index and the
 // arguments: no table.  A unit of work is
 //   SHAPE 0  a tile, x_mask == 0: b is a itself
 //   SHAPE 1  a tile, the partner inside it (x_mask < 2^T): the tile's amplitudes go through LDS once (64 KiB, the leaves then
 //            take the same space), a thread reads a at e and b at e ^ x_mask back from there
-//   SHAPE 2  the PAIR of tiles (t, t ^ (x_mask >> T)), t the one with the highest set bit of x_mask >> T clear: a from tile t
-//            at e, b from the partner tile at e ^ x_low (whole 128-B lines either way).  leaf_i and leaf_(i ^ x_mask) are the
-//            same bits (products commute; a difference taken the other way round is negated exactly, and the sign flips with
-//            it), so each leaf is computed ONCE and placed at e of t's tree and at e ^ x_low of the partner's.  The two trees
+//   SHAPE 2  the PAIR of tiles (t, t ^ xh) (PauliTiles): a from tile t at e, b from the partner tile at e ^ x_low.  leaf_i and
+//            leaf_(i ^ x_mask) are the same bits (products commute; a difference taken the other way round is negated
+//            exactly, and the sign flips with it), so each leaf is computed ONCE and placed at e of t's tree and at
+//            e ^ x_low of the partner's.  The two trees
 //            lie behind each other in LDS (2 x 32 KiB) and reduce as one array of 2^13: a level's pairs never straddle them.
 //            Every amplitude comes from HBM once, for any string.
 // FULL: the tile has all 2^12 elements (n >= 12) and nothing in the unit's path is guarded -- a guard around a load makes every
@@ -4093,51 +4156,39 @@ template <int SHAPE, bool FULL>
 __global__ __launch_bounds__(256) void k_pauli_leaves(const amp_t *__restrict__ amp, double *__restrict__ dst, uint64_t nunits,
                                                       unsigned T, uint64_t x_mask, uint64_t z_mask, unsigned g)
 {
-    constexpr unsigned EPT = 16u;
+    using Tiles = PauliTiles<SHAPE == 2>;
+    constexpr unsigned EPT = Tiles::EPT;
     constexpr unsigned NRED = SHAPE == 0 ? 4096u : 8192u;
     constexpr unsigned VPT = SHAPE == 2 ? 16u : 8u;                  // sums a thread forms at the widest tree level
     __shared__ double red[NRED];
-    const unsigned tid = threadIdx.x, nel = 1u << T;
-    const unsigned x_low = (unsigned)x_mask & (nel - 1u), z_low = (unsigned)z_mask & (nel - 1u);
-    const uint64_t xh = x_mask >> T, zh = z_mask >> T;
-    const unsigned hb = SHAPE == 2 ? 63u - (unsigned)__clzll((long long)xh) : 0u;      // (SHAPE 2: xh != 0)
-    // element j of this thread: tile-local element e = tid + 256 j (n < 12: a partial tile, the first nld of them exist)
-    unsigned nld = 0, eodd = 0;                                      // bit j of eodd: the parity element j adds to `odd`
-#pragma unroll
-    for (unsigned j = 0; j < EPT; j++) {
-        const unsigned e = tid + 256u * j;
-        if (e < nel) nld = j + 1;
-        eodd |= (unsigned)(__popc((e ^ x_low) & z_low) & 1) << j;
-    }
+    const unsigned tid = threadIdx.x;
+    const Tiles P(T, x_mask, z_mask, tid);
+    const unsigned nel = P.nel, x_low = P.x_low, nld = P.nld;
+    const uint64_t xh = P.xh;
     const bool godd = (g & 1u) != 0;
-    auto tile_of = [&](uint64_t u) {
-        if constexpr (SHAPE == 2) return ((u >> hb) << (hb + 1u)) | (u & ((((uint64_t)1) << hb) - 1u));
-        else return u;
-    };
     amp_t a[EPT], b[SHAPE == 2 ? EPT : 1];
     auto load = [&](uint64_t u) {
-        const uint64_t t = tile_of(u);
+        const uint64_t t = P.tile_of(u);
         const amp_t *pa = amp + (t << T) + tid;
 #pragma unroll
         for (unsigned j = 0; j < EPT; j++)
             if (FULL || j < nld) a[j] = __builtin_nontemporal_load(pa + 256u * j);
         if constexpr (SHAPE == 2) {
-            // (e ^ x_low = (tid ^ x_low's 8 low bits) + 256 (j ^ x_low's bits above): one lane offset, uniform steps)
-            const amp_t *pb = amp + ((t ^ xh) << T) + (tid ^ (x_low & 255u));
+            const amp_t *pb = amp + ((t ^ xh) << T) + P.partner_lane(tid);
 #pragma unroll
-            for (unsigned j = 0; j < EPT; j++) b[j] = __builtin_nontemporal_load(pb + 256u * (j ^ (x_low >> 8)));
+            for (unsigned j = 0; j < EPT; j++) b[j] = __builtin_nontemporal_load(pb + 256u * P.partner_elem(j));
         }
     };
     auto leaf = [&](amp_t p, amp_t q, unsigned j, unsigned tile_par) {
         // g even: p.re q.re + p.im q.im; g odd: p.im q.re - p.re q.im = p.im q.re + (-(p.re q.im)), the same rounding; no branch
         const double u = (godd ? p.y : p.x) * q.x, w = (godd ? p.x : p.y) * q.y;
         const double t = u + (godd ? -w : w);
-        return 0.0 + (((tile_par + (eodd >> j)) & 1u) ? -t : t);
+        return 0.0 + (((tile_par + (P.podd >> j)) & 1u) ? -t : t);
     };
     if (blockIdx.x < nunits) load(blockIdx.x);
     for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
-        const uint64_t t = tile_of(u);
-        const unsigned tile_par = (unsigned)__popcll((t ^ xh) & zh) + (g >> 1);
+        const uint64_t t = P.tile_of(u);
+        const unsigned tile_par = P.par(t ^ xh) + (g >> 1);
         if constexpr (SHAPE == 1) {
             // through LDS: once the tile is there, a's registers are free for the next tile's loads, which go out at once;
             // a thread then reads e and e ^ x_low back, keeps its leaves, and writes them when all have read
@@ -4238,22 +4289,18 @@ __global__ __launch_bounds__(256) void k_collapse_range(amp_t *__restrict__ amp,
 // K12  any one-qubit gate, plain or controlled (qcx_one_qubit_gate / qcx_c_one_qubit_gate, DESIGN s4.5f): the 2x2 matrix
 // u = (u00 u01; u10 u11) on the pairs (i0, i1 = i0 | 2^q), as the reference's mat-vec would apply it from four stored
 // triplets per pair taken in column order (Q:396-413; the construction of Q:456-481 / Q:529-562 with free entries):
-//     lo = (0 + u00 * a) + u01 * b,   hi = (0 + u10 * a) + u11 * b,    complex products spelled out as Q:409 / Q:412,
-// every product and sum rounded on its own (no FMA), all four entries multiplied out even where they are zero.  The "0 +"
-// is the accumulator's start: it turns a -0 first product into +0 and nothing else, and IEEE rules do not let a compiler
-// drop it.  The eight components are kernel arguments (SGPRs); no LDS, no table, one arithmetic path for every matrix.
+//     lo = q_row(u00 * a, u01 * b),   hi = q_row(u10 * a, u11 * b),    products by q_mul (the pinned arithmetic: see there),
+// all four entries multiplied out even where they are zero.  The eight components are kernel arguments (SGPRs); no LDS, no
+// table, one arithmetic path for every matrix.
 // The kernels are k_h_pair / k_h_wave / k_phase / k_phase_lines with this butterfly in place of theirs.  A result is never
 // -0 (the second addend meets a first sum that is not -0), so the invariant of K0c holds behind them.
 // ---------------------------------------------------------------------------
 struct UMat { double r00, i00, r01, i01, r10, i10, r11, i11; };
 
-// one row: (0 + m0 * a) + m1 * b; a = the pair's amplitude with the target bit clear, b = with it set
+// one row; a = the pair's amplitude with the target bit clear, b = with it set
 __device__ __forceinline__ amp_t u_row(double m0r, double m0i, double m1r, double m1i, amp_t a, amp_t b)
 {
-    amp_t o;
-    o.x = (0.0 + ((m0r * a.x) - (m0i * a.y))) + ((m1r * b.x) - (m1i * b.y));      // Q:409, columns i0 then i1
-    o.y = (0.0 + ((m0r * a.y) + (m0i * a.x))) + ((m1r * b.y) + (m1i * b.x));      // Q:412
-    return o;
+    return q_row(q_mul(m0r, m0i, a), q_mul(m1r, m1i, b));          // columns i0 then i1
 }
 
 __device__ __forceinline__ void u_butterfly(const UMat &U, amp_t &a, amp_t &b)
@@ -4273,8 +4320,7 @@ __global__ __launch_bounds__(BLOCK) void k_u_pair(amp_t *__restrict__ amp, unsig
     const uint64_t bit = (uint64_t)1 << q, cbit = (uint64_t)1 << c;
     const unsigned b0 = (CTL && c < q) ? c : q, b1 = (c < q) ? q : c;      // the squeezed-out bits, ascending
     const uint64_t step = (uint64_t)gridDim.x * (BLOCK * PPT);
-    uint64_t tile0 = blockIdx.x;
-    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    const uint64_t tile0 = stream_tile(glog, slog);
     for (uint64_t base = tile0 * (BLOCK * PPT); base < npairs; base += step) {
         amp_t a[PPT], b[PPT];
         uint64_t i0[PPT];
@@ -4326,8 +4372,7 @@ template <int Q, int R, bool NT, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_u_wave(amp_t *__restrict__ amp, UMat U, uint64_t ntiles, unsigned glog, unsigned slog)
 {
     const unsigned lane = threadIdx.x & 63u;
-    uint64_t blk = blockIdx.x;
-    if (slog) blk = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    const uint64_t blk = stream_tile(glog, slog);
     const uint64_t wave = (blk * BLOCK + threadIdx.x) >> 6;
     const uint64_t nwaves = ((uint64_t)gridDim.x * BLOCK) >> 6;
     for (uint64_t t = wave; t < ntiles; t += nwaves) {
@@ -4356,8 +4401,7 @@ __global__ __launch_bounds__(64) void k_cu_lines(amp_t *__restrict__ amp, unsign
                                                  uint64_t count, unsigned glog, unsigned slog)
 {
     const uint64_t step = (uint64_t)gridDim.x * 64u;
-    uint64_t tile0 = blockIdx.x;
-    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    const uint64_t tile0 = stream_tile(glog, slog);
     for (uint64_t p = tile0 * 64u + threadIdx.x; p < count; p += step) {
         if (LOWQ) {
             uint64_t i = p;
@@ -4381,8 +4425,8 @@ __global__ __launch_bounds__(64) void k_cu_lines(amp_t *__restrict__ amp, unsign
 }
 
 // K12s  the controlled gate as a STRICT pass (K9's reason: a register that holds non-finite amplitudes): the same rows on the
-// control-set pairs, and every control-clear amplitude rewritten through the reference's identity row 0 + (1 * x - 0 * y),
-// 0 + (1 * y + 0 * x); `one` and `z` are kernel arguments so that no product is folded.  (The plain gate needs no strict
+// control-set pairs, and every control-clear amplitude rewritten through the reference's identity row q_row((1, 0) * x);
+// `one` and `z` are kernel arguments so that no product is folded.  (The plain gate needs no strict
 // twin: K12a / K12b already multiply every stored triplet out and rewrite every amplitude.)
 __global__ __launch_bounds__(256) void k_strict_cu(amp_t *__restrict__ amp, unsigned n, unsigned q, unsigned c, UMat U, double one, double z)
 {
@@ -4391,12 +4435,7 @@ __global__ __launch_bounds__(256) void k_strict_cu(amp_t *__restrict__ amp, unsi
         const uint64_t i0 = insert_zero(p, q), i1 = i0 | ((uint64_t)1 << q);
         amp_t a = amp[i0], b = amp[i1];
         if ((i0 >> c) & 1u) u_butterfly(U, a, b);
-        else {
-            amp_t lo, hi;
-            lo.x = 0.0 + ((one * a.x) - (z * a.y));   lo.y = 0.0 + ((one * a.y) + (z * a.x));
-            hi.x = 0.0 + ((one * b.x) - (z * b.y));   hi.y = 0.0 + ((one * b.y) + (z * b.x));
-            a = lo; b = hi;
-        }
+        else { a = q_row(q_mul(one, z, a)); b = q_row(q_mul(one, z, b)); }
         amp[i0] = a; amp[i1] = b;
     }
 }
@@ -4405,8 +4444,8 @@ __global__ __launch_bounds__(256) void k_strict_cu(amp_t *__restrict__ amp, unsi
 // K13  any two-qubit gate, plain or controlled (qcx_two_qubit_gate / qcx_c_two_qubit_gate, DESIGN s4.5g): the 4x4 matrix m on
 // the quads (i, i | 2^lo, i | 2^hi, i | 2^lo | 2^hi), lo < hi, as the reference's mat-vec would apply it from sixteen stored
 // triplets per quad taken in ascending state index (Q:396-413):
-//     out_r = (((0 + m[r][0] * x0) + m[r][1] * x1) + m[r][2] * x2) + m[r][3] * x3,   complex products as Q:409 / Q:412,
-// every product and sum rounded on its own (no FMA), all sixteen entries multiplied out even where they are zero.  The host
+//     out_r = q_row(m[r][0] * x0, m[r][1] * x1, m[r][2] * x2, m[r][3] * x3),   products by q_mul (the pinned arithmetic),
+// all sixteen entries multiplied out even where they are zero.  The host
 // has already permuted the caller's matrix when qubit0 > qubit1 (P u P, P = the index swap 1 <-> 2): a kernel only sees
 // lo < hi and matrix index k = bit(lo) + 2 * bit(hi).  The 32 components are kernel arguments (SGPRs), read with constant
 // indices only -- a lane that needs "its own" row picks it with selects, never with a run-time index, so nothing goes to
@@ -4432,10 +4471,7 @@ __device__ __forceinline__ U4Row u4_row_sel(const U4Mat &U, bool lb, bool hb)
 // one row, the 4-column extension of u_row: x0 .. x3 = the quad's amplitudes in ascending index order
 __device__ __forceinline__ amp_t u4_row(const U4Row &m, amp_t x0, amp_t x1, amp_t x2, amp_t x3)
 {
-    amp_t o;
-    o.x = (((0.0 + ((m.r0 * x0.x) - (m.i0 * x0.y))) + ((m.r1 * x1.x) - (m.i1 * x1.y))) + ((m.r2 * x2.x) - (m.i2 * x2.y))) + ((m.r3 * x3.x) - (m.i3 * x3.y));      // Q:409
-    o.y = (((0.0 + ((m.r0 * x0.y) + (m.i0 * x0.x))) + ((m.r1 * x1.y) + (m.i1 * x1.x))) + ((m.r2 * x2.y) + (m.i2 * x2.x))) + ((m.r3 * x3.y) + (m.i3 * x3.x));      // Q:412
-    return o;
+    return q_row(q_mul(m.r0, m.i0, x0), q_mul(m.r1, m.i1, x1), q_mul(m.r2, m.i2, x2), q_mul(m.r3, m.i3, x3));
 }
 
 __device__ __forceinline__ void u4_quad(const U4Mat &U, amp_t &x0, amp_t &x1, amp_t &x2, amp_t &x3)
@@ -4455,8 +4491,7 @@ __global__ __launch_bounds__(BLOCK) void k_u2_quad(amp_t *__restrict__ amp, unsi
 {
     const uint64_t lob = (uint64_t)1 << lo, hib = (uint64_t)1 << hi;
     const uint64_t step = (uint64_t)gridDim.x * BLOCK;
-    uint64_t tile0 = blockIdx.x;
-    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    const uint64_t tile0 = stream_tile(glog, slog);
     for (uint64_t base = tile0 * BLOCK; base < count; base += step) {
         const uint64_t p = base + threadIdx.x;
         if (p < count) {
@@ -4488,8 +4523,7 @@ __global__ __launch_bounds__(64) void k_u2_lines(amp_t *__restrict__ amp, unsign
 {
     const uint64_t lob = (uint64_t)1 << lo, hib = (uint64_t)1 << hi;
     const uint64_t step = (uint64_t)gridDim.x * 64u;
-    uint64_t tile0 = blockIdx.x;
-    if (slog) tile0 = ((uint64_t)(blockIdx.x & ((1u << slog) - 1u)) << (glog - slog)) | (blockIdx.x >> slog);
+    const uint64_t tile0 = stream_tile(glog, slog);
     for (uint64_t p = tile0 * 64u + threadIdx.x; p < count; p += step) {
         uint64_t i = p;
         if constexpr (NS == 0) i = insert_zero(insert_zero(p, lo), hi);      // (only with a control < 3: nothing else is squeezed out)
@@ -4536,11 +4570,7 @@ __global__ __launch_bounds__(256) void k_strict_cu2(amp_t *__restrict__ amp, uns
         if ((i >> c) & 1u) u4_quad(U, x[0], x[1], x[2], x[3]);
         else {
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                amp_t o;
-                o.x = 0.0 + ((one * x[k].x) - (z * x[k].y));   o.y = 0.0 + ((one * x[k].y) + (z * x[k].x));
-                x[k] = o;
-            }
+            for (int k = 0; k < 4; k++) x[k] = q_row(q_mul(one, z, x[k]));
         }
         amp[i] = x[0]; amp[i | lob] = x[1]; amp[i | hib] = x[2]; amp[i | lob | hib] = x[3];
     }
@@ -4550,12 +4580,12 @@ __global__ __launch_bounds__(256) void k_strict_cu2(amp_t *__restrict__ amp, uns
 // K15  the rotation about a Pauli string, exp(-i theta/2 P) = cos(theta/2) I - i sin(theta/2) P, in place (qcx_pauli_rotation,
 // DESIGN s4.5i; tests/pauli_rotation_ref.py is the definition).  The string is K14's (x_mask, z_mask), g = popcount(x_mask &
 // z_mask) mod 4, (c, s) = polar(theta / 2).  The matrix has one or two entries per row and is applied as the reference's
-// mat-vec would apply it from stored triplets taken in ascending column order (Q:396-413), products as Q:409 / Q:412, every
-// product and sum rounded on its own (no FMA), zero components multiplied out:
+// mat-vec would apply it from stored triplets taken in ascending column order: rows by q_row, products by q_mul (the pinned
+// arithmetic), zero components multiplied out:
 //     (er, ei) = -i i^g s = (+0, -s), (s, +0), (+0, s), (-s, +0);   entry(i, j) = (er, ei), its ONE non-zero component negated
 //     when popcount(j & z_mask) is odd (the other stays +0), j = i ^ x_mask
-//     x_mask != 0:  D = (c, +0) * amp[i], O = entry(i, j) * amp[j],  new[i] = i < j ? (0 + D) + O : (0 + O) + D
-//     x_mask == 0:  new[i] = 0 + (c, -+s) * amp[i], -s where popcount(i & z_mask) is even (this is entry(i, i) with re = c)
+//     x_mask != 0:  D = (c, +0) * amp[i], O = entry(i, j) * amp[j],  new[i] = i < j ? q_row(D, O) : q_row(O, D)
+//     x_mask == 0:  new[i] = q_row((c, -+s) * amp[i]), -s where popcount(i & z_mask) is even (this is entry(i, i) with re = c)
 // What the definition is, bit for bit, on finite states (tests/test_pauli_rotation_ref.py, and on the GPU
 // tests/test_gpu_pauli_rotation.py):
 //     one letter on qubit q        = qcx_one_qubit_gate(q, .) with [[c, -is], [-is, c]] (X), [[c, -s], [s, c]] (Y),
@@ -4564,13 +4594,12 @@ __global__ __launch_bounds__(256) void k_strict_cu2(amp_t *__restrict__ amp, uns
 //     and cos(theta/2) I - i sin(theta/2) P as a dense matrix to 1e-14 on O(1) amplitudes.
 // Every amplitude is rewritten from its own row's products: a result is never -0 (K0c's invariant holds behind this kernel),
 // and an Inf or NaN reaches rows i and i ^ x_mask only -- there is no strict twin.
-// The units of work are k_pauli_leaves' (T = min(n, 12), a tile = 2^T amplitudes, 256 threads, thread element j = tid + 256 j):
+// The units of work, the partner's addresses and the sign bitmaps are PauliTiles' (shared with K14):
 //   SHAPE 0  a tile, x_mask == 0: a streaming diagonal, the sign from the index parity; no LDS
 //   SHAPE 1  a tile, the partner inside it (x_mask < 2^T): the tile goes through LDS once (64 KiB), whole 128-B lines in and
 //            out; behind the barrier -- the whole tile is in LDS before any of its stores is issued -- the next tile's loads
 //            go out, a thread reads e and e ^ x_low back, computes its OWN row and stores its own element
-//   SHAPE 2  the PAIR of tiles (t, t ^ (x_mask >> T)), t the one with the highest set bit of x_mask >> T clear: a at e of
-//            tile t, b at e ^ x_low of the partner (whole lines either way).  i < j on t's side always: a takes D then O, b
+//   SHAPE 2  the PAIR of tiles (t, t ^ xh): a at e of tile t, b at e ^ x_low of the partner.  i < j on t's side always: a takes D then O, b
 //            takes O then D; both are stored where they came from.  Units are disjoint, so in place is safe; no LDS.
 // SHAPE 0 and 2 hold no more than 8 elements of a thread at a time (8 a's and 8 b's: 64 VGPRs) and prefetch nothing: there is
 // no barrier in them, so the other waves of the CU cover the latency (2, 4 and 16 elements at a time measured the same at
@@ -4579,57 +4608,35 @@ __global__ __launch_bounds__(256) void k_strict_cu2(amp_t *__restrict__ amp, uns
 struct PRot { double c, zr, er, ei; };                   // zr = the +0 imaginary part of the diagonal (an argument: never folded)
 
 // entry * x with the entry's sign applied to its non-zero component (er for odd g, ei for even g)
-__device__ __forceinline__ amp_t prot_off(const PRot &R, bool godd, bool neg, amp_t x)
+__device__ __forceinline__ q_mul prot_off(const PRot &R, bool godd, bool neg, amp_t x)
 {
-    const double mr = (godd && neg) ? -R.er : R.er, mi = (!godd && neg) ? -R.ei : R.ei;
-    amp_t o;
-    o.x = (mr * x.x) - (mi * x.y);                      // Q:409
-    o.y = (mr * x.y) + (mi * x.x);                      // Q:412
-    return o;
+    return q_mul((godd && neg) ? -R.er : R.er, (!godd && neg) ? -R.ei : R.ei, x);
 }
 
 // the row of `own`: first = its index is below the partner's (the diagonal triplet comes first)
 __device__ __forceinline__ amp_t prot_row(const PRot &R, bool godd, bool neg, bool first, amp_t own, amp_t oth)
 {
-    amp_t d;
-    d.x = (R.c * own.x) - (R.zr * own.y);
-    d.y = (R.c * own.y) + (R.zr * own.x);
-    const amp_t o = prot_off(R, godd, neg, oth);
-    amp_t r;
-    r.x = first ? (0.0 + d.x) + o.x : (0.0 + o.x) + d.x;
-    r.y = first ? (0.0 + d.y) + o.y : (0.0 + o.y) + d.y;
-    return r;
+    const q_mul d(R.c, R.zr, own), o = prot_off(R, godd, neg, oth);
+    const amp_t d_first = q_row(d, o), o_first = q_row(o, d);      // (both, then a select: `first` differs from lane to lane)
+    return first ? d_first : o_first;
 }
 
 // x_mask == 0: the one triplet (c, -+s) (g = 0: ei = -s carries the sign)
 __device__ __forceinline__ amp_t prot_diag(const PRot &R, bool neg, amp_t x)
 {
-    const double mi = neg ? -R.ei : R.ei;
-    amp_t r;
-    r.x = 0.0 + ((R.c * x.x) - (mi * x.y));
-    r.y = 0.0 + ((R.c * x.y) + (mi * x.x));
-    return r;
+    return q_row(q_mul(R.c, neg ? -R.ei : R.ei, x));
 }
 
 template <int SHAPE, bool FULL>
 __global__ __launch_bounds__(256) void k_pauli_rot(amp_t *__restrict__ amp, uint64_t nunits, unsigned T, uint64_t x_mask,
                                                    uint64_t z_mask, unsigned g, PRot R)
 {
-    constexpr unsigned EPT = 16u, HALF = 8u;
-    const unsigned tid = threadIdx.x, nel = 1u << T;
-    const unsigned x_low = (unsigned)x_mask & (nel - 1u), z_low = (unsigned)z_mask & (nel - 1u);
-    const uint64_t xh = x_mask >> T, zh = z_mask >> T;
+    using Tiles = PauliTiles<SHAPE == 2>;
+    constexpr unsigned EPT = Tiles::EPT, HALF = 8u;
+    const unsigned tid = threadIdx.x;
+    const Tiles P(T, x_mask, z_mask, tid);
+    const unsigned x_low = P.x_low, nld = P.nld, podd = P.podd, sodd = P.sodd;      // (SHAPE 2 needs both bitmaps)
     const bool godd = (g & 1u) != 0;
-    // element j of this thread: tile-local e = tid + 256 j (n < 12: a partial tile, the first nld of them exist).
-    // bit j of podd: the parity its PARTNER's element e ^ x_low adds to the sign; of sodd: its own (SHAPE 2 needs both)
-    unsigned nld = 0, podd = 0, sodd = 0;
-#pragma unroll
-    for (unsigned j = 0; j < EPT; j++) {
-        const unsigned e = tid + 256u * j;
-        if (e < nel) nld = j + 1;
-        podd |= (unsigned)(__popc((e ^ x_low) & z_low) & 1) << j;
-        sodd |= (unsigned)(__popc(e & z_low) & 1) << j;
-    }
     if constexpr (SHAPE == 1) {
         __shared__ amp_t sa[4096];
         const unsigned hbit = 1u << (31u - (unsigned)__clz((int)x_low));      // (SHAPE 1: x_low != 0) i < j <=> this bit of e is clear
@@ -4642,7 +4649,7 @@ __global__ __launch_bounds__(256) void k_pauli_rot(amp_t *__restrict__ amp, uint
         };
         if (blockIdx.x < nunits) load(blockIdx.x);
         for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
-            const unsigned tile_par = (unsigned)__popcll(u & zh);            // (xh == 0: the partner's tile is this one)
+            const unsigned tile_par = P.par(u);                              // (xh == 0: the partner's tile is this one)
 #pragma unroll
             for (unsigned j = 0; j < EPT; j++)
                 if (FULL || j < nld) sa[tid + 256u * j] = a[j];
@@ -4660,7 +4667,7 @@ __global__ __launch_bounds__(256) void k_pauli_rot(amp_t *__restrict__ amp, uint
         }
     } else if constexpr (SHAPE == 0) {
         for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
-            const unsigned tile_par = (unsigned)__popcll(u & zh);
+            const unsigned tile_par = P.par(u);
             amp_t *pa = amp + (u << T) + tid;
 #pragma unroll 1
             for (unsigned h = 0; h < EPT; h += HALF) {
@@ -4675,20 +4682,18 @@ __global__ __launch_bounds__(256) void k_pauli_rot(amp_t *__restrict__ amp, uint
             }
         }
     } else {
-        const unsigned hb = 63u - (unsigned)__clzll((long long)xh);          // (SHAPE 2: xh != 0, n > 12, whole tiles)
-        for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
-            const uint64_t t = ((u >> hb) << (hb + 1u)) | (u & ((((uint64_t)1) << hb) - 1u));
-            const unsigned par_a = (unsigned)__popcll(t & zh), par_b = (unsigned)__popcll((t ^ xh) & zh);
+        for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {                  // (SHAPE 2: xh != 0, n > 12, whole tiles)
+            const uint64_t t = P.tile_of(u);
+            const unsigned par_a = P.par(t), par_b = P.par(t ^ P.xh);
             amp_t *pa = amp + (t << T) + tid;
-            // (e ^ x_low = (tid ^ x_low's 8 low bits) + 256 (j ^ x_low's bits above): one lane offset, uniform steps)
-            amp_t *pb = amp + ((t ^ xh) << T) + (tid ^ (x_low & 255u));
+            amp_t *pb = amp + ((t ^ P.xh) << T) + P.partner_lane(tid);
 #pragma unroll 1
             for (unsigned h = 0; h < EPT; h += HALF) {
                 amp_t a[HALF], b[HALF];
 #pragma unroll
                 for (unsigned k = 0; k < HALF; k++) {
                     a[k] = __builtin_nontemporal_load(pa + 256u * (h + k));
-                    b[k] = __builtin_nontemporal_load(pb + 256u * ((h + k) ^ (x_low >> 8)));
+                    b[k] = __builtin_nontemporal_load(pb + 256u * P.partner_elem(h + k));
                 }
 #pragma unroll
                 for (unsigned k = 0; k < HALF; k++) {
@@ -4696,7 +4701,7 @@ __global__ __launch_bounds__(256) void k_pauli_rot(amp_t *__restrict__ amp, uint
                     const amp_t ra = prot_row(R, godd, ((par_b + (podd >> (h + k))) & 1u) != 0, true, a[k], b[k]);
                     const amp_t rb = prot_row(R, godd, ((par_a + (sodd >> (h + k))) & 1u) != 0, false, b[k], a[k]);
                     __builtin_nontemporal_store(ra, pa + 256u * (h + k));
-                    __builtin_nontemporal_store(rb, pb + 256u * ((h + k) ^ (x_low >> 8)));
+                    __builtin_nontemporal_store(rb, pb + 256u * P.partner_elem(h + k));
                 }
             }
         }

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import one_qubit_ref as oq
+from bitwise import bits, minus_zero_state, random_unitary, same, same_with_nans
 from collapse_ref import collapse_ref, measure_ref
 from marginal_ref import marginal_ref
 
@@ -16,44 +17,7 @@ pytestmark = pytest.mark.gpu
 BAD_ARGUMENTS, BAD_QUBIT, UNSUPPORTED = 2, 6, 7
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(got, want, what=""):
-    g, w = bits(got), bits(want)
-    if not np.array_equal(g, w):
-        bad = np.nonzero(g != w)[0]
-        raise AssertionError(f"{what}: {bad.size}/{g.size} doubles differ; first at {bad[0]}: got {np.asarray(got)[bad[0]]!r} "
-                             f"want {np.asarray(want)[bad[0]]!r}")
-
-
-def same_with_nans(got, want, what):
-    got = np.ascontiguousarray(got, dtype=np.float64); want = np.ascontiguousarray(want, dtype=np.float64)
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), f"{what}: NaN pattern differs at {np.nonzero(gn != wn)[0][:8]}"
-    same(got[~gn], want[~wn], what)
-
-
-def random_unitary(seed):
-    rs = np.random.RandomState(seed)
-    q, r = np.linalg.qr(rs.randn(2, 2) + 1j * rs.randn(2, 2))
-    u = q * (np.diag(r) / np.abs(np.diag(r)))
-    return np.clip(u.real, -1.0, 1.0) + 1j * np.clip(u.imag, -1.0, 1.0)       # (rounding may leave a component at 1 + 1 ulp)
-
-
 NAMES = ["X", "Y", "Z", "S", "T", "H"]
-
-
-def minus_zero_state(ob, n, seed):
-    """a state for qcx_state_write with -0 components, exact zeros and cancelling pairs"""
-    a = ob.random_state(n, seed)
-    a[0] = -0.0
-    a[1::7] = -0.0
-    a[4::11] = 0.0
-    if n >= 2:
-        a[6] = -a[2]; a[7] = -a[3]
-    return a
 
 
 @pytest.fixture(scope="module")
@@ -79,7 +43,7 @@ def apply_gate(qc, reg, c, q, U):
 def check_forms(qc, reg, n, st, what, controlled=True):
     filled, written = st
     for k, (c, q) in enumerate(forms(n, controlled)):
-        U = random_unitary(1000 * n + k)
+        U = random_unitary(1000 * n + k, 2)
         reg.fill_random(n)
         apply_gate(qc, reg, c, q, U)
         same(reg.read(), oq.apply(filled, n, q, U, control=c), f"{what} n={n} c={c} q={q} unitary, fill_random")
@@ -180,7 +144,7 @@ def test_lands_in_issue_order_behind_queued_gates(qc, ob, n, mode):
     """the expected state: what the register holds in this mode before the new gate (read on a first run: in mode 2 that is
     the tolerance mode's own result), then the ref; in mode 1 that reading is also the oracle's, bit for bit"""
     M = 3
-    U = random_unitary(n)
+    U = random_unitary(n, 2)
     for c, q in ((None, 1), (None, n - 2), (n - 1, 0), (2, n - 1), (5, 6)):
         with qc.Register(n - M, M) as reg:
             reg.set_fusion(mode)
@@ -234,7 +198,7 @@ def test_directly_after_quantum_computation(qc, ob, L, M):
     at (7, 5); at (15, 5) the compact chain's last pass, which the circuit defers to whoever looks at the state first."""
     n, Cn, a = L + M, 21, 2
     want = oracle_shor(ob, L, M, Cn, a)
-    U = random_unitary(77)
+    U = random_unitary(77, 2)
     with qc.Register(L, M) as twin:
         qc.reset_register(twin); qc.quantum_computation(Cn, a, twin)
         t0 = twin.fusion_stats()
@@ -254,7 +218,7 @@ def test_directly_after_quantum_computation(qc, ob, L, M):
 @pytest.mark.parametrize("n", [9, 11])
 def test_after_postselect_and_seen_by_what_follows(qc, ob, n):
     a = ob.fill_random(n, 3)
-    U = random_unitary(5 * n)
+    U = random_unitary(5 * n, 2)
     for c, q in ((None, 2), (1, n - 1), (n - 1, 4)):
         with qc.Register(n - 3, 3) as reg:
             reg.fill_random(3)
@@ -318,7 +282,7 @@ def test_measure_one_qubit_then_flip_it_back(qc, ob):
 def test_non_finite_states_take_the_strict_pass(qc, ob, poison):
     """the identity rows of the controlled form are multiplied out too (0 * Inf = NaN), and the register stays strict"""
     n = 6
-    U = random_unitary(3)
+    U = random_unitary(3, 2)
     for where in (0, 2 * 21 + 1, 2 * 63):                       # component index: control clear / mixed / control set
         for c, q in ((None, 0), (None, 5), (0, 3), (4, 1), (5, 0)):
             a = ob.random_state(n, 50 + where)
@@ -343,7 +307,7 @@ def test_non_finite_states_take_the_strict_pass(qc, ob, poison):
 def test_arguments(qc):
     lib = qc.lib()
     n = 8
-    good = oq.matrix8(random_unitary(1))
+    good = oq.matrix8(random_unitary(1, 2))
     gp = good.ctypes.data_as(C.c_void_p)
 
     def with_component(k, v):
@@ -391,7 +355,7 @@ def test_n29_windows_beyond_4_gib(qc, ob):
     if free < 10 * 2 ** 30:
         pytest.skip(f"needs 10 GiB of free device memory, {free / 2 ** 30:.1f} GiB are free")
     n, W, top = 29, 1 << 12, 1 << 28
-    U = random_unitary(29)
+    U = random_unitary(29, 2)
     starts = [0, (1 << 27) + 5 * W, top - W]
     with qc.Register(n, 0) as reg:
         for c, q in ((None, 28), (28, 0), (0, 28)):

@@ -10,9 +10,10 @@ import numpy as np
 import pytest
 
 import pauli_rotation_ref as prr
+from bitwise import bits, same_with_nans as same
+from pauli_cases import PAIR_13, TILE_13, adversarial, g_of, with_every_g
 from pauli_ref import pauli_masks, pauli_ref
 from register_model import RegisterModel
-from test_gpu_pauli_expectation import PAIR_13, TILE_13, adversarial, bits, g_of, same, with_every_g
 
 pytestmark = pytest.mark.gpu
 

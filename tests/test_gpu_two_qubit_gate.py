@@ -10,6 +10,7 @@ import pytest
 
 import one_qubit_ref as oq
 import two_qubit_ref as tq
+from bitwise import bits, minus_zero_state, random_unitary, same, same_with_nans
 from collapse_ref import collapse_ref
 from marginal_ref import marginal_ref
 
@@ -19,43 +20,7 @@ BAD_ARGUMENTS, BAD_QUBIT, UNSUPPORTED = 2, 6, 7
 KNOBS = ("u2_variant", "u2_nt", "u2_streams_log2")
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(got, want, what=""):
-    g, w = bits(got), bits(want)
-    if not np.array_equal(g, w):
-        bad = np.nonzero(g != w)[0]
-        raise AssertionError(f"{what}: {bad.size}/{g.size} doubles differ; first at {bad[0]}: got {np.asarray(got)[bad[0]]!r} "
-                             f"want {np.asarray(want)[bad[0]]!r}")
-
-
-def same_with_nans(got, want, what):
-    got = np.ascontiguousarray(got, dtype=np.float64); want = np.ascontiguousarray(want, dtype=np.float64)
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), f"{what}: NaN pattern differs at {np.nonzero(gn != wn)[0][:8]}"
-    same(got[~gn], want[~wn], what)
-
-
-def random_unitary(seed, d=4):
-    rs = np.random.RandomState(seed)
-    q, r = np.linalg.qr(rs.randn(d, d) + 1j * rs.randn(d, d))
-    u = q * (np.diag(r) / np.abs(np.diag(r)))
-    return np.clip(u.real, -1.0, 1.0) + 1j * np.clip(u.imag, -1.0, 1.0)       # (rounding may leave a component at 1 + 1 ulp)
-
-
 NAMES = ["SWAP", "ISWAP", "CNOT", "CZ"]
-
-
-def minus_zero_state(ob, n, seed):
-    """a state for qcx_state_write with -0 components, exact zeros and cancelling pairs"""
-    a = ob.random_state(n, seed)
-    a[0] = -0.0
-    a[1::7] = -0.0
-    a[4::11] = 0.0
-    a[6] = -a[2]; a[7] = -a[3]
-    return a
 
 
 @pytest.fixture(scope="module")
@@ -95,7 +60,7 @@ def apply_gate(qc, reg, c, q0, q1, U):
 def check_forms(qc, reg, n, st, what):
     filled, written = st
     for k, (c, q0, q1) in enumerate(cases(n)):
-        U = random_unitary(1000 * n + k)
+        U = random_unitary(1000 * n + k, 4)
         reg.fill_random(n)
         apply_gate(qc, reg, c, q0, q1, U)
         same(reg.read(), tq.apply(filled, n, q0, q1, U, control=c), f"{what} n={n} c={c} ({q0}, {q1}) unitary, fill_random")
@@ -193,7 +158,7 @@ def test_named_gates_are_the_exact_matrices(qc):
                 qc.two_qubit_gate(0, 1, bad, reg)
             with pytest.raises(ValueError):
                 qc.c_two_qubit_gate(2, 0, 1, bad, reg)
-        V = random_unitary(2)
+        V = random_unitary(2, 4)
         reg.fill_random(1); qc.two_qubit_gate(2, 0, V, reg); first = reg.read()
         reg.fill_random(1); qc.two_qubit_gate(2, 0, tq.matrix32(V), reg)          # the 32 doubles themselves
         same(reg.read(), first, "32 doubles")
@@ -214,7 +179,7 @@ def test_lands_in_issue_order_behind_queued_gates(qc, ob, n, mode):
     """the expected state: what the register holds in this mode before the new gate (read on a first run: in mode 2 that is
     the tolerance mode's own result), then the ref; in mode 1 that reading is also the oracle's, bit for bit"""
     M = 3
-    U = random_unitary(n)
+    U = random_unitary(n, 4)
     for c, q0, q1 in ((None, 1, n - 2), (None, n - 1, 4), (n - 1, 0, 6), (2, n - 1, 5), (5, 6, 7)):
         with qc.Register(n - M, M) as reg:
             reg.set_fusion(mode)
@@ -262,7 +227,7 @@ def test_directly_after_quantum_computation(qc, ob):
     L, M, Cn, a = 7, 5, 21, 2
     n = L + M
     want = np.zeros(2 << n); ob.reset(want, n); ob.quantum_computation(want, n, M, Cn, a)
-    U = random_unitary(77)
+    U = random_unitary(77, 4)
     with qc.Register(L, M) as twin:
         qc.reset_register(twin); qc.quantum_computation(Cn, a, twin)
         t0 = twin.fusion_stats()
@@ -280,7 +245,7 @@ def test_directly_after_quantum_computation(qc, ob):
 def test_after_postselect_and_seen_by_what_follows(qc, ob):
     n = 9
     a = ob.fill_random(n, 3)
-    U = random_unitary(5 * n)
+    U = random_unitary(5 * n, 4)
     for c, q0, q1 in ((None, 2, 7), (1, n - 1, 4), (n - 1, 4, 0)):
         with qc.Register(n - 3, 3) as reg:
             reg.fill_random(3)
@@ -305,7 +270,7 @@ def test_non_finite_states_take_the_strict_pass(qc, ob, poison):
     """the identity rows of the controlled form are multiplied out too (0 * Inf = NaN), the plain forms rewrite every amplitude
     from all sixteen products as they stand, and the register stays strict"""
     n = 9
-    U = random_unitary(3)
+    U = random_unitary(3, 4)
     for where in (0, 2 * 21 + 1, 2 * 511):                     # component index: controls clear / mixed / every control set
         for c, q0, q1 in ((None, 0, 1), (None, 8, 2), (None, 4, 7), (0, 3, 1), (4, 1, 8), (8, 0, 5), (6, 7, 3)):
             a = ob.random_state(n, 50 + where)
@@ -328,7 +293,7 @@ def test_non_finite_states_take_the_strict_pass(qc, ob, poison):
 def test_arguments(qc):
     lib = qc.lib()
     n = 8
-    good = tq.matrix32(random_unitary(1))
+    good = tq.matrix32(random_unitary(1, 4))
     gp = good.ctypes.data_as(C.c_void_p)
 
     def with_component(k, v):
@@ -384,7 +349,7 @@ def test_n29_windows_beyond_4_gib(qc, ob):
     if free < 10 * 2 ** 30:
         pytest.skip(f"needs 10 GiB of free device memory, {free / 2 ** 30:.1f} GiB are free")
     n, W, top = 29, 1 << 12, 1 << 28
-    U = random_unitary(29)
+    U = random_unitary(29, 4)
     starts = [0, (1 << 27) + 5 * W, top - W]
 
     def local(q):

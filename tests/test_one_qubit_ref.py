@@ -18,19 +18,10 @@ import numpy as np
 import pytest
 
 import one_qubit_ref as oq
+from bitwise import same_with_nans as same
 
 S12 = 0.70710678118654752440          # M_SQRT1_2
 H = np.array([[S12, S12], [S12, -S12]], dtype=complex)
-
-
-def same(got, want, what):
-    """bit for bit; where the oracle has a NaN a NaN (its sign and payload are the hardware's business)"""
-    got = np.ascontiguousarray(got, dtype=np.float64); want = np.ascontiguousarray(want, dtype=np.float64)
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), f"{what}: NaN pattern differs at {np.nonzero(gn != wn)[0][:8]}"
-    g, w = got[~gn].view(np.uint64), want[~wn].view(np.uint64)
-    bad = np.nonzero(g != w)[0]
-    assert bad.size == 0, f"{what}: {bad.size} doubles differ, first {got[~gn][bad[0]]!r} vs {want[~wn][bad[0]]!r}"
 
 
 def inputs(ob, n):

@@ -7,6 +7,7 @@ import itertools
 import numpy as np
 import pytest
 
+from bitwise import bits
 from marginal_ref import marginal_ref
 from pauli_ref import pauli_leaves, pauli_masks, pauli_ref, pauli_sum_ref
 
@@ -16,10 +17,6 @@ PAULI = {
     "Y": np.array([[0, -1j], [1j, 0]], dtype=complex),
     "Z": np.array([[1, 0], [0, -1]], dtype=complex),
 }
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def letters(n, x, z):

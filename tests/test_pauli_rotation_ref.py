@@ -9,13 +9,10 @@ import pytest
 import one_qubit_ref
 import pauli_rotation_ref as prr
 import two_qubit_ref
+from bitwise import bits
 from pauli_ref import pauli_masks
 
 THETAS = [0.0, np.pi, -0.7, 7.5, 1e-9, np.pi / 2]                   # 0, pi, a negative value, one above 2 pi
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def finite_adversarial(n, seed):

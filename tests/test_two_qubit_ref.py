@@ -20,29 +20,13 @@ import pytest
 
 import one_qubit_ref as oq
 import two_qubit_ref as tq
+from bitwise import bits, random_unitary, same
 
 S12 = 0.70710678118654752440          # M_SQRT1_2
 H = np.array([[S12, S12], [S12, -S12]], dtype=complex)
 I2 = np.eye(2, dtype=complex)
 P = np.eye(4)[[0, 2, 1, 3]]
 BAD_ARGUMENTS = 2
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(got, want, what):
-    g, w = bits(got), bits(want)
-    bad = np.nonzero(g != w)[0]
-    assert bad.size == 0, f"{what}: {bad.size} doubles differ, first at {bad[0]}: {np.asarray(got)[bad[0]]!r} vs {np.asarray(want)[bad[0]]!r}"
-
-
-def random_unitary(seed, d):
-    rs = np.random.RandomState(seed)
-    q, r = np.linalg.qr(rs.randn(d, d) + 1j * rs.randn(d, d))
-    u = q * (np.diag(r) / np.abs(np.diag(r)))
-    return np.clip(u.real, -1.0, 1.0) + 1j * np.clip(u.imag, -1.0, 1.0)
 
 
 def controlled(U):
