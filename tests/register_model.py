@@ -4,14 +4,22 @@
 The model holds the state as interleaved float64 and has one method per public call; every method does what the project already
 defines for that call -- the oracle (oracle/binding.py) for reset, fill, the reference's gates, the circuits and measure_state,
 tests/one_qubit_ref.py / two_qubit_ref.py for the matrix gates, tests/marginal_ref.py / collapse_ref.py for the marginal and the
-range collapse -- so a sequence of calls on the model is the bit-for-bit expectation for the same calls on the GPU, whatever lazy
-form (queue, pending basis state, compact result, owed zero pass, strict mode) the library keeps the state in between them.
+range collapse, tests/pauli_ref.py / pauli_rotation_ref.py for the Pauli calls -- so a sequence of calls on the model is the
+bit-for-bit expectation for the same calls on the GPU, whatever lazy form (queue, pending basis state, compact result, owed zero
+pass, strict mode, a handed-out buffer pointer, a caller's stream) the library keeps the state in between them.
+
+The generator has two vocabularies.  Seeds below NSEEDS_V1 draw from the calls up to the matrix gates; their op lists are frozen
+(tests/golden/sequence_digests.json: whatever is added here must leave them as they are).  The seeds from NSEEDS_V1 on add
+expect / expect_sum / prot (the Pauli calls), devptr (a read through qcx_device_pointer, after which the register works in
+place for the rest of its life) and stream (qcx_register_set_stream: a caller's non-blocking stream, or the own one again).
 
 An op is a tuple of a name and plain numbers / strings, so that a failing sequence prints as a Python literal and replays:
 written data and matrices are regenerated from the seed inside the op (window_data, matrix_data).  Host only."""
 import numpy as np
 
 import one_qubit_ref
+import pauli_ref
+import pauli_rotation_ref
 import two_qubit_ref
 from collapse_ref import collapse_ref, measure_ref
 from marginal_ref import marginal_ref
@@ -78,6 +86,42 @@ def sample_draws(seed, shots):
     if shots > 2 and rs.randint(0, 2):
         r[int(rs.randint(0, shots))] = float(rs.choice([0.0, 1.0, 1.5, -0.25, 1e-300]))
     return r
+
+
+def draw_masks(rs, n):
+    """(x_mask, z_mask) of a Pauli string over n qubits, drawn over the three unit shapes of k_pauli_leaves / k_pauli_rot with
+    equal weight: x_mask = 0 (a diagonal string), x_mask != 0 inside the low min(n, 12) bits (the partner amplitude sits in the
+    same tile and goes through LDS), x_mask with a bit >= 12 (pairs of tiles; n >= 13 -- a smaller register draws the second
+    shape in its place).  z_mask is random; one draw in four has z_mask = x_mask: every letter a Y"""
+    c = int(rs.randint(0, 3))
+    if c == 2 and n < 13:
+        c = 1
+    if c == 0:
+        x = 0
+    elif c == 1:
+        x = int(rs.randint(1, 1 << min(n, 12)))
+    else:
+        x = int(rs.randint(0, 1 << n)) | (1 << int(rs.randint(12, n)))
+    z = x if rs.randint(0, 4) == 0 else int(rs.randint(0, 1 << n))
+    return x, z
+
+
+def mask_shape(x_mask):
+    """0, 1, 2: which of draw_masks' three unit shapes x_mask has"""
+    return 0 if x_mask == 0 else 1 if x_mask < (1 << 12) else 2
+
+
+def sum_terms(n, seed, k):
+    """the k terms (coeff, x_mask, z_mask) of an expect_sum op: coefficients U(-2, 2), one of them exactly 0.0 when k >= 3"""
+    rs = np.random.RandomState(seed)
+    terms = []
+    for _ in range(k):
+        c = float(rs.uniform(-2.0, 2.0))
+        terms.append((c,) + draw_masks(rs, n))
+    if k >= 3:
+        j = int(rs.randint(0, k))
+        terms[j] = (0.0,) + terms[j][1:]
+    return terms
 
 
 # ---- the model --------------------------------------------------------------------------------------------------------------
@@ -156,6 +200,17 @@ class RegisterModel:
         self.a = out
         return p, NO_ERROR
 
+    def expectation(self, x_mask, z_mask):
+        return pauli_ref.pauli_ref(self.a, self.n, x_mask, z_mask)
+
+    def expectation_sum(self, terms):
+        """terms: (coeff, x_mask, z_mask); (total, values)"""
+        total, values = pauli_ref.pauli_sum_ref(self.a, self.n, terms)
+        return total, np.array(values, dtype=np.float64)
+
+    def pauli_rotation(self, x_mask, z_mask, theta):
+        self.a = pauli_rotation_ref.apply(self.a, self.n, x_mask, z_mask, theta)
+
     def total_probability(self):
         with np.errstate(over="ignore", invalid="ignore"):
             return self.ob.norm2(self.a, self.n)                          # the sequential sum (testing_and_debug.c:28-37)
@@ -169,9 +224,13 @@ class RegisterModel:
 
 FOLLOWING = ("reset", "fill", "write", "read", "h", "cphase", "camodc", "iqft", "qcomp", "u1", "cu1", "u2", "cu2", "measure",
              "sample", "marginal", "measure_qubits", "postselect", "total", "norm2", "save", "load", "flush", "sync", "fusion")
+# the second vocabulary (seeds NSEEDS_V1 .. NSEEDS - 1): the Pauli calls, the handed-out buffer pointer, the caller's stream
+FOLLOWING_V2 = FOLLOWING + ("expect", "expect_sum", "prot", "devptr", "stream")
 SETTING = ("reset", "measure_state", "fill", "write_full_negzero", "write_partial", "write_nonfinite", "collapse", "compact",
            "queued_mode1", "queued_behind_basis", "load")
 QUEUED = ("h", "cphase", "camodc", "iqft", "qcomp")
+# calls that leave a lazily pending basis state pending (answered from the basis index, or refused before anything runs)
+QUIET_FOR_PENDING = ("sample", "marginal", "stats", "measure_qubits", "postselect", "refused", "expect", "expect_sum")
 
 
 def apply_to_model(m, op):
@@ -203,6 +262,11 @@ def apply_to_model(m, op):
     elif k == "sync": m.synchronize()
     elif k == "fusion": m.set_fusion(op[1])
     elif k == "stats": pass
+    elif k == "expect": return m.expectation(op[1], op[2])
+    elif k == "expect_sum": return m.expectation_sum(sum_terms(m.n, op[1], op[2]))
+    elif k == "prot": m.pauli_rotation(op[1], op[2], op[3])
+    elif k == "devptr": return m.read(op[1], op[2])
+    elif k == "stream": pass
     elif k == "refused":
         inner, status = op[1], op[2]
         if inner[0] == "postselect" and inner[3] < (1 << inner[2]) and inner[1] + inner[2] <= m.n:
@@ -217,7 +281,8 @@ def apply_to_model(m, op):
 
 # ---- the generator -----------------------------------------------------------------------------------------------------------
 
-NSEEDS = 64
+NSEEDS_V1, NSEEDS = 64, 128              # seeds < NSEEDS_V1: vocabulary 1, frozen (tests/golden/sequence_digests.json); the others: 2
+SMALL_V1 = 24                             # the same for the small sequences of generate(.., small=True)
 # (L, M, C, a); n = 6 .. 14, M = 0 and n < 9 (partial tiles in several kernels) included
 SHAPES = [(8, 4, 15, 7), (9, 5, 21, 2), (8, 5, 21, 2), (6, 0, 1, 1), (10, 0, 1, 1), (2, 4, 15, 7), (3, 4, 15, 7), (4, 4, 15, 7),
           (5, 5, 21, 2), (13, 0, 1, 1), (7, 6, 35, 2), (10, 4, 15, 7), (4, 5, 21, 2), (8, 0, 1, 1)]
@@ -229,12 +294,15 @@ SMALL_SHAPES = [(2, 2, 3, 2), (3, 3, 7, 3), (2, 4, 15, 7), (5, 0, 1, 1), (6, 0, 
 KNOBS_N9 = [dict(h_variant=1, h_ppt=2, h_streams_log2=3), dict(h_variant=2, h_wave_r=4, h_nt=0, h_streams_log2=0), dict(ph_lines=0),
             dict(ph_lines=0, ph_nt=0, ph_streams_log2=0), dict(u2_variant=1), dict(u2_streams_log2=3), dict(u2_variant=1, u2_nt=0)]
 KNOBS_ANY = [dict(collapse_upt=8), dict(collapse_perm=0), dict(collapse_grid_cap=1), dict(collapse_grid_cap=3, collapse_upt=8)]
+# vocabulary 2 adds K15's grid cap, at values that do not divide the number of units a rotation walks
+KNOBS_V2 = [dict(prot_grid_cap=1), dict(prot_grid_cap=3)]
 
 
 class Config:
     def __init__(self, seed, small=False):
         rs = np.random.RandomState(7919 * seed + 13)
         self.seed, self.small = seed, small
+        self.vocab = 1 if seed < (SMALL_V1 if small else NSEEDS_V1) else 2
         self.compact = (not small) and seed % 8 == 5
         if small:
             shapes = [SMALL_SHAPES[seed % len(SMALL_SHAPES)]]
@@ -249,12 +317,12 @@ class Config:
         self.modes = [self.mode] + [int(rs.choice([-1, 0, 1])) for _ in shapes[1:]]      # the start mode of every register
         self.knobs = {}
         if not small and seed % 3 == 1:
-            pool = KNOBS_ANY + (KNOBS_N9 if min(s[0] + s[1] for s in shapes) >= 9 else [])
+            pool = KNOBS_ANY + (KNOBS_V2 if self.vocab == 2 else []) + (KNOBS_N9 if min(s[0] + s[1] for s in shapes) >= 9 else [])
             for i in rs.choice(len(pool), 3, replace=False):
                 self.knobs.update(pool[int(i)])
 
     def __repr__(self):
-        return f"seed {self.seed}: shapes (L, M, C, a) {self.shapes} start mode {self.mode} knobs {self.knobs}"
+        return f"seed {self.seed}: vocabulary {self.vocab} shapes (L, M, C, a) {self.shapes} start mode {self.mode} knobs {self.knobs}"
 
 
 def pair_is_legal(s, f, shape, compact):
@@ -265,34 +333,47 @@ def pair_is_legal(s, f, shape, compact):
         return False
     if s == "write_nonfinite" and f == "norm2":                            # (norm2 is not compared on a non-finite state)
         return False
+    if f == "devptr" and compact:          # (the pointer ends compact chains for that register, and run_ops asserts them)
+        return False
     return True
 
 
-def _schedule():
-    """every legal (state-setting kind, following kind) pair three times, dealt round-robin to the seeds whose register allows it"""
-    cfgs = [Config(s) for s in range(NSEEDS)]
-    out = [[] for _ in range(NSEEDS)]
-    at = 0
+def seeds_of(vocab):
+    return range(NSEEDS_V1) if vocab == 1 else range(NSEEDS_V1, NSEEDS)
+
+
+def following_of(vocab):
+    return FOLLOWING if vocab == 1 else FOLLOWING_V2
+
+
+def _schedule(vocab):
+    """every legal (state-setting kind, following kind) pair of one vocabulary three times, dealt round-robin to those of its
+    seeds whose register allows it; the list of seed k is out[k - the vocabulary's first seed]"""
+    seeds = seeds_of(vocab)
+    cfgs = [Config(s) for s in seeds]
+    out = [[] for _ in seeds]
+    at, ns = 0, len(seeds)
     for _ in range(3):
         for s in SETTING:
-            for f in FOLLOWING:
-                for k in range(NSEEDS):
-                    c = cfgs[(at + k) % NSEEDS]
+            for f in following_of(vocab):
+                for k in range(ns):
+                    c = cfgs[(at + k) % ns]
                     if pair_is_legal(s, f, c.shapes[0], c.compact):
-                        out[c.seed].append((s, f))
-                        at = (at + k + 1) % NSEEDS
+                        out[c.seed - seeds[0]].append((s, f))
+                        at = (at + k + 1) % ns
                         break
     return out
 
 
-_SCHEDULE = None
+_SCHEDULE = {}
 
 
 class _Gen:
     """the ops of ONE register: scheduled (setting, following) probes with random parameters, random ops between them"""
 
-    def __init__(self, ob, shape, mode, rs, allow_nonfinite=True, tag=0):
+    def __init__(self, ob, shape, mode, rs, allow_nonfinite=True, tag=0, vocab=1, devptr=True):
         self.ob, self.rs, self.tag = ob, rs, tag
+        self.vocab, self.following, self.devptr = vocab, following_of(vocab), devptr
         self.L, self.M, self.Cn, self.a0 = shape
         self.n = self.L + self.M
         self.dim = 1 << self.n
@@ -314,7 +395,7 @@ class _Gen:
             self.mode = op[1]
         if k in ("reset", "measure"):
             self.pending = self.mode >= 0
-        elif k in ("sample", "marginal", "stats", "measure_qubits", "postselect", "refused") or (k in QUEUED and self.mode == 1):
+        elif k in QUIET_FOR_PENDING or (k in QUEUED and self.mode == 1):
             pass
         else:
             self.pending = False
@@ -417,19 +498,54 @@ class _Gen:
                 return ("save", 0)
             return ("load", int(rs.choice(sorted(self.slots))))
         if f == "fusion": return ("fusion", int(rs.choice([-1, 0, 1])))
+        if f == "expect": return ("expect", *draw_masks(rs, n))
+        if f == "expect_sum": return ("expect_sum", self.seed(), int(rs.choice([0, 1, 3, 6])))
+        if f == "prot": return ("prot", *draw_masks(rs, n), self.theta())
+        if f == "devptr":
+            if rs.randint(0, 3) == 0:
+                return ("devptr", 0, self.dim)
+            first = int(rs.randint(0, self.dim))
+            return ("devptr", first, int(rs.randint(1, min(self.dim - first, 2000) + 1)))
+        if f == "stream": return ("stream", int(rs.randint(0, 2)))
         raise ValueError(f)
+
+    def theta(self):
+        """uniform in (-7, 7); one draw in six is 0.0, pi, 2 pi or -0.0 (the two zeros leave the state's bits as they are)"""
+        rs = self.rs
+        if rs.randint(0, 6) == 0:
+            return float([0.0, np.pi, 2.0 * np.pi, -0.0][int(rs.randint(0, 4))])
+        return float(rs.uniform(-7.0, 7.0))
+
+    def pauli(self):
+        """a burst of Pauli calls with nothing between them: value, two rotations, then the value of the same string again or a sum"""
+        x, z = draw_masks(self.rs, self.n)
+        self.emit(("expect", x, z))
+        self.emit(("prot", *draw_masks(self.rs, self.n), self.theta()))
+        self.emit(("prot", x, z, self.theta()))
+        self.emit(("expect", x, z) if self.rs.randint(0, 2) else ("expect_sum", self.seed(), int(self.rs.choice([1, 3, 6]))))
 
     def quiet(self):
         """a call that leaves every lazy form as it is (the issue's "non-flushing" calls)"""
-        c = int(self.rs.randint(0, 3))
+        c = int(self.rs.randint(0, 3 if self.vocab == 1 else 4))
         if c == 0: return ("sample", self.seed(), int(self.rs.choice([1, 4, 9])))
         if c == 1: return ("marginal", *self.a_range(self.M))
+        if c == 3: return ("expect", *draw_masks(self.rs, self.n))
         return ("stats",)
 
     def refused(self):
         """a call the library must refuse with the state untouched: (inner op, status)"""
         rs, n = self.rs, self.n
-        c = int(rs.randint(0, 4))
+        c = int(rs.randint(0, 4 if self.vocab == 1 else 6))
+        if c >= 4:                                                           # the Pauli calls: a mask that reaches bit n, an angle that is not finite
+            x, z = draw_masks(rs, n)
+            k = int(rs.randint(0, 3))
+            if k == 2:
+                return ("prot", x, z, str(rs.choice(["inf", "-inf", "nan"]))), BAD_ARGUMENTS
+            if rs.randint(0, 2):
+                x |= 1 << n
+            else:
+                z |= 1 << n
+            return (("expect", x, z) if k == 0 else ("prot", x, z, self.theta())), BAD_QUBIT
         if c == 0:                                                           # bad qubit
             k = int(rs.randint(0, 4))
             if k == 0: return ("h", n), BAD_QUBIT
@@ -565,8 +681,11 @@ class _Gen:
         if rs.randint(0, 12) == 0:
             self.underflow()
             return
-        f = FOLLOWING[int(rs.randint(0, len(FOLLOWING)))]
-        if (f in ("camodc", "qcomp") and self.M == 0) or (f == "norm2" and self.m.holds_nonfinite()):
+        if self.vocab == 2 and rs.randint(0, 8) == 0:
+            self.pauli()
+            return
+        f = self.following[int(rs.randint(0, len(self.following)))]
+        if (f in ("camodc", "qcomp") and self.M == 0) or (f == "norm2" and self.m.holds_nonfinite()) or (f == "devptr" and not self.devptr):
             f = "h"
         if f == "write" and not self.allow_nonfinite:
             self.cleanse()
@@ -576,21 +695,21 @@ class _Gen:
 def generate(ob, seed, small=False, length=None):
     """(Config, ops) of one seed; an op of the list is (register number, op tuple).  small: registers of n <= 6, no non-finite
     values, `length` ops (the sequences test_register_model.py replays in long double)"""
-    global _SCHEDULE
     cfg = Config(seed, small)
     rs = np.random.RandomState(104729 * seed + 71)
-    g = _Gen(ob, cfg.shapes[0], cfg.mode, rs, allow_nonfinite=not small)
+    g = _Gen(ob, cfg.shapes[0], cfg.mode, rs, allow_nonfinite=not small, vocab=cfg.vocab, devptr=not cfg.compact)
+    following = following_of(cfg.vocab)
     if small:
         while len(g.ops) < length:
-            s, f = SETTING[int(rs.randint(0, len(SETTING)))], FOLLOWING[int(rs.randint(0, len(FOLLOWING)))]
+            s, f = SETTING[int(rs.randint(0, len(SETTING)))], following[int(rs.randint(0, len(following)))]
             if pair_is_legal(s, f, cfg.shapes[0], False) and s != "write_nonfinite" and rs.randint(0, 2):
                 g.probe(s, f)
             else:
                 g.extra()
         return cfg, [(0, op) for op in g.ops[:length]]
-    if _SCHEDULE is None:
-        _SCHEDULE = _schedule()
-    probes = list(_SCHEDULE[seed])
+    if cfg.vocab not in _SCHEDULE:
+        _SCHEDULE[cfg.vocab] = _schedule(cfg.vocab)
+    probes = list(_SCHEDULE[cfg.vocab][seed - seeds_of(cfg.vocab)[0]])
     rs.shuffle(probes)
     for s, f in probes:
         g.probe(s, f)
@@ -600,12 +719,14 @@ def generate(ob, seed, small=False, length=None):
             g.refuse()
         if rs.randint(0, 10) < 2:
             g.extra()
+        if cfg.vocab == 2 and rs.randint(0, 10) < (5 if g.m.holds_nonfinite() else 1):    # (often where the state is not finite:
+            g.pauli()                                                                       #  the strict register's Pauli calls)
     while len(g.ops) < 40:
         g.extra()
     g.emit(("read", 0, g.dim))
     ops = [(0, op) for op in g.ops]
     if len(cfg.shapes) > 1:                                                  # the second register: random ops, dealt in between
-        h = _Gen(ob, cfg.shapes[1], cfg.modes[1], rs, tag=1)
+        h = _Gen(ob, cfg.shapes[1], cfg.modes[1], rs, tag=1, vocab=cfg.vocab)
         while len(h.ops) < max(12, len(g.ops) // 3):
             h.extra()
         h.emit(("read", 0, h.dim))
@@ -617,8 +738,8 @@ def generate(ob, seed, small=False, length=None):
 
 # ---- what a list of ops reaches (judged on the list alone) ---------------------------------------------------------------------
 
-def is_quiet(op, M):
-    return op[0] in ("sample", "stats") or (op[0] == "marginal" and op[1] >= M)
+def is_quiet(op, M, vocab=1):
+    return op[0] in ("sample", "stats") or (op[0] == "marginal" and op[1] >= M) or (vocab == 2 and op[0] == "expect")
 
 
 def compact_shape(shape):
@@ -627,7 +748,7 @@ def compact_shape(shape):
     return M in (4, 5) and L >= 8 and L + M >= 12 and cb is not None and L + cb >= 14
 
 
-def pairs_reached(shape, start_mode, ops):
+def pairs_reached(shape, start_mode, ops, vocab=1):
     """{(setting kind, following kind): count} over the ops of one register: a pair counts when nothing but quiet calls stand
     between the two"""
     L, M, Cn, a = shape
@@ -651,7 +772,7 @@ def pairs_reached(shape, start_mode, ops):
         kinds.append(s)
         if k == "fusion": mode = op[1]
         if k in ("reset", "measure"): pending = mode >= 0
-        elif k in ("sample", "marginal", "stats", "measure_qubits", "postselect", "refused") or (k in QUEUED and mode == 1 and not strict): pass
+        elif k in QUIET_FOR_PENDING or (k in QUEUED and mode == 1 and not strict): pass
         else: pending = False
         if k == "write" and op[4] in ("inf", "nan"): strict = True
         elif k in ("reset", "measure", "fill"): strict = False
@@ -660,8 +781,8 @@ def pairs_reached(shape, start_mode, ops):
         if s is None:
             continue
         for op in ops[i + 1:]:
-            if op[0] in FOLLOWING:
+            if op[0] in following_of(vocab):
                 out[(s, op[0])] = out.get((s, op[0]), 0) + 1
-            if not is_quiet(op, M):
+            if not is_quiet(op, M, vocab):
                 break
     return out

@@ -1,8 +1,14 @@
-"""GPU: random call sequences over the whole API of an unsharded register, and a dozen named chains, against the host model of
-tests/register_model.py.  A register carries lazy state between calls (the strict flag, the owed zero pass, the gate queue, a
-pending basis state, a compact circuit result, the fusion mode) and every entry point settles it in its own way; the files of
-the single features check each call next to a few hand-picked neighbours, this one checks chains of them.  Everything a call
-returns is compared bit for bit (NaN matching NaN) with the model; full reads are rare, so that the lazy forms live long.
+"""GPU: random call sequences over the whole API of an unsharded register, and some twenty named chains, against the host model
+of tests/register_model.py.  A register carries lazy state between calls (the strict flag, the owed zero pass, the gate queue, a
+pending basis state, a compact circuit result, the fusion mode, a handed-out buffer pointer, the caller's stream) and every
+entry point settles it in its own way; the files of the single features check each call next to a few hand-picked neighbours,
+this one checks chains of them.  Everything a call returns is compared bit for bit (NaN matching NaN) with the model; full
+reads are rare, so that the lazy forms live long.
+
+Two vocabularies: the seeds below register_model.NSEEDS_V1 draw from the calls up to the matrix gates and are frozen
+(tests/golden/sequence_digests.json); the others add the Pauli calls (expectation, expectation_sum, pauli_rotation), reads
+through qcx_device_pointer (after which the register works in place for the rest of its life) and qcx_register_set_stream with
+a non-blocking stream of PyTorch's, which is not ordered with the null stream the way the register's own stream is.
 
 One seed alone:  QCX_SEQ_CASE=<seed> [QCX_SEQ_OPS=<k>] python -m pytest tests/test_gpu_api_sequences.py -m gpu -q -s -k random
 (a failure prints the seed, the index of the failing op and the ops up to it as a Python literal)."""
@@ -16,7 +22,7 @@ import register_model as rm
 
 pytestmark = pytest.mark.gpu
 
-KNOB_KEYS = sorted({k for d in rm.KNOBS_N9 + rm.KNOBS_ANY for k in d})
+KNOB_KEYS = sorted({k for d in rm.KNOBS_N9 + rm.KNOBS_ANY + rm.KNOBS_V2 for k in d})
 
 
 def bits(a):
@@ -51,6 +57,56 @@ def measure_last_stats(qc):
     return s.value, b.value
 
 
+def chain_stats(qc, reg):
+    v = C.c_ulong(0)
+    assert qc.lib().qcx_chain_stats(reg._h, C.byref(v)) == 0
+    return int(v.value)
+
+
+_hip_memcpy = None
+
+
+def hip_memcpy():
+    """hipMemcpy of the HIP runtime this process already holds (quantumcomputer_amd/_lib.py arranges that there is one): looked
+    up in the process image, or, where the runtime was not loaded into the global scope, in the one copy that is mapped"""
+    global _hip_memcpy
+    if _hip_memcpy is None:
+        try:
+            fn = C.CDLL(None).hipMemcpy
+        except AttributeError:
+            with open("/proc/self/maps") as f:
+                mapped = sorted({line.split()[-1] for line in f if "libamdhip64.so" in line})
+            assert len(mapped) == 1, f"one HIP runtime per process, mapped are {mapped}"
+            fn = C.CDLL(mapped[0]).hipMemcpy
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        _hip_memcpy = fn
+    return _hip_memcpy
+
+
+def read_through_pointer(reg, first, count, ctx):
+    """`count` amplitudes from qcx_device_pointer() + 16 * first, copied by the caller; the pointer never changes"""
+    assert 0 <= first and 0 < count and first + count <= reg.num_states
+    ptr = reg.device_pointer()
+    assert ptr, "qcx_device_pointer returned null"
+    assert ctx.setdefault("pointer", ptr) == ptr, f"the buffer that was handed out as {ctx['pointer']:#x} is now {ptr:#x}"
+    reg.synchronize()
+    out = np.empty(2 * count, dtype=np.float64)
+    st = hip_memcpy()(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr + 16 * first), 16 * count, 2)      # hipMemcpyDeviceToHost
+    assert st == 0, f"hipMemcpy: error {st}"
+    return out
+
+
+def set_stream(reg, on, ctx):
+    """on: the register works on ONE non-blocking stream of PyTorch's, alive until the register is closed; off: on its own"""
+    if on:
+        if "stream" not in ctx:
+            import torch
+            ctx["stream"] = torch.cuda.Stream()
+        reg.set_stream(ctx["stream"].cuda_stream)
+    else:
+        reg.set_stream(0)
+
+
 def status_of(qc, call):
     try:
         call()
@@ -59,8 +115,9 @@ def status_of(qc, call):
     return rm.NO_ERROR
 
 
-def apply_to_register(qc, reg, op, path_of):
-    """one op on the GPU register; returns what the call returns, in the form register_model.apply_to_model gives"""
+def apply_to_register(qc, reg, op, path_of, ctx):
+    """one op on the GPU register; returns what the call returns, in the form register_model.apply_to_model gives.  ctx: a dict
+    per register that lives until the register is closed (the handed-out pointer, the caller's stream)"""
     k = op[0]
     if k == "reset": qc.reset_register(reg)
     elif k == "fill": reg.fill_random(op[1])
@@ -89,6 +146,12 @@ def apply_to_register(qc, reg, op, path_of):
     elif k == "fusion": reg.set_fusion(op[1])
     elif k == "stats":
         reg.fusion_stats(); reg.marginal_stats(); reg.sample_stats(); reg.collapse_stats(); compact_measures(qc, reg)
+        reg.expectation_stats()
+    elif k == "expect": return reg.expectation((op[1], op[2]))
+    elif k == "expect_sum": return reg.expectation_sum([(c, (x, z)) for c, x, z in rm.sum_terms(reg.num_qubits, op[1], op[2])])
+    elif k == "prot": qc.pauli_rotation((op[1], op[2]), op[3], reg)
+    elif k == "devptr": return read_through_pointer(reg, op[1], op[2], ctx)
+    elif k == "stream": set_stream(reg, op[1], ctx)
     elif k == "refused":
         inner = op[1]
         j = inner[0]
@@ -100,6 +163,10 @@ def apply_to_register(qc, reg, op, path_of):
         if j == "cphase": return status_of(qc, lambda: qc.c_phase_shift_gate(inner[1], inner[2], inner[3], reg))
         if j == "u1": return status_of(qc, lambda: qc.one_qubit_gate(inner[1], rm.matrix_data(2, inner[2]), reg))
         if j == "u1x": return status_of(qc, lambda: qc.one_qubit_gate(inner[1], rm.matrix_data(2, inner[2], ulp=True), reg))
+        if j == "expect":                                                  # (through the library: pauli_masks would raise first)
+            v = C.c_double(0.0)
+            return qc.lib().qcx_pauli_expectation(reg._h, inner[1], inner[2], C.byref(v))
+        if j == "prot": return qc.lib().qcx_pauli_rotation(inner[1], inner[2], float(inner[3]), reg._h)
         if j == "u2x": return status_of(qc, lambda: qc.two_qubit_gate(inner[1], inner[2], rm.matrix_data(4, inner[3], ulp=True), reg))
         raise ValueError(f"unknown refused op {op!r}")
     else:
@@ -109,8 +176,13 @@ def apply_to_register(qc, reg, op, path_of):
 
 def compare(op, got, want):
     k = op[0]
-    if k in ("read", "marginal"):
+    if k in ("read", "marginal", "devptr"):
         same(got, want, k)
+    elif k == "expect":
+        same([got], [want], "expectation")
+    elif k == "expect_sum":
+        same([got[0]], [want[0]], "the terms' sum")
+        same(got[1], want[1], "the values of the terms")
     elif k in ("measure",):
         assert got == want, f"index {got} != {want}"
     elif k == "sample":
@@ -143,7 +215,7 @@ def run_ops(qc, ob, shapes, modes, ops, tmp_path, header, compact=False):
     """the ops on fresh registers and fresh models, everything returned compared; ends with a full read of every register.
     compact: register 0 has a shape at which reset + quantum_computation must run as a compact chain (qcx_compact_stats moves:
     with the call in mode 0, with the first call that flushes the queue in mode 1)"""
-    regs, models = [], []
+    regs, models, ctxs = [], [], []
     done = []
     modes = list(modes)
     owed = None                                 # the compact-chain count register 0 must show after its next flushing call
@@ -152,12 +224,13 @@ def run_ops(qc, ob, shapes, modes, ops, tmp_path, header, compact=False):
             reg = qc.Register(L, M)
             reg.set_fusion(mode)
             regs.append(reg)
+            ctxs.append({})
             models.append(rm.RegisterModel(ob, L, M))
         for i, (which, op) in enumerate(ops):
             done.append((which, op))
             try:
                 chains = compact_chains(qc, regs[0]) if compact and which == 0 else 0
-                got = apply_to_register(qc, regs[which], op, lambda slot: str(tmp_path / f"reg{which}_slot{slot}.qcx"))
+                got = apply_to_register(qc, regs[which], op, lambda slot: str(tmp_path / f"reg{which}_slot{slot}.qcx"), ctxs[which])
                 want = rm.apply_to_model(models[which], op)
                 compare(op, got, want)
                 if op[0] == "fusion":
@@ -180,6 +253,7 @@ def run_ops(qc, ob, shapes, modes, ops, tmp_path, header, compact=False):
     finally:
         for reg in regs:
             reg.close()
+        ctxs.clear()                                # (the callers' streams go after the registers that worked on them)
 
 
 # ---- random sequences ----------------------------------------------------------------------------------------------------------
@@ -216,12 +290,12 @@ class Chain:
         self.reg.set_fusion(mode)
         self.m = rm.RegisterModel(ob, L, M)
         self.n, self.dim = L + M, 1 << (L + M)
-        self.done = []
+        self.done, self.ctx = [], {}
 
     def do(self, *op):
         self.done.append(op)
         try:
-            got = apply_to_register(self.qc, self.reg, op, lambda slot: str(self.tmp / f"{self.tag}_slot{slot}.qcx"))
+            got = apply_to_register(self.qc, self.reg, op, lambda slot: str(self.tmp / f"{self.tag}_slot{slot}.qcx"), self.ctx)
             compare(op, got, rm.apply_to_model(self.m, op))
         except Exception as e:
             raise AssertionError(f"op {len(self.done) - 1}: {op!r}\n{type(e).__name__}: {e}\nops = {self.done!r}") from e
@@ -232,6 +306,7 @@ class Chain:
 
     def close(self):
         self.reg.close()
+        self.ctx.clear()
 
     def __enter__(self):
         return self
@@ -450,8 +525,8 @@ def test_chain_negative_zeros_wait_for_the_first_gate(qc, ob, tmp_path):
 
 def test_chain_collapse_that_underflows_to_negative_zero_owes_the_zero_pass(qc, ob, tmp_path):
     """the collapse itself makes -0 (negative subnormals times s < 1/2) on a register whose zero pass was not owed: the next gate
-    must still canonicalise every amplitude, also those it does not act on"""
-    for follow in (("cphase", 9, 10, 0.7), ("cu1", 10, 9, 6), ("cu2", 10, 9, 8, 7), ("h", 10)):
+    must still canonicalise every amplitude, also those it does not act on (the rotation rewrites every amplitude itself)"""
+    for follow in (("cphase", 9, 10, 0.7), ("cu1", 10, 9, 6), ("cu2", 10, 9, 8, 7), ("h", 10), ("prot", 1 << 10 | 1 << 9, 1 << 9, 0.7)):
         with Chain(qc, ob, 7, 4, 0, tmp_path) as c:
             c.do("write", 0, c.dim, 77, "subnormal")
             c.do("cphase", 9, 10, 0.4)                                    # runs the pass the write owes; touches a quarter of the state
@@ -482,3 +557,222 @@ def test_chain_pending_basis_state_through_the_flushing_observers(qc, ob, tmp_pa
         c.do("measure_qubits", 4, 8, 0.35)
         c.do("qcomp", 15, 7)
         c.state()
+
+
+# ---- named chains: the Pauli calls, the handed-out pointer, the caller's stream ------------------------------------------------------
+
+def popcount(v):
+    return bin(v).count("1")
+
+
+def test_chain_pending_basis_state_answers_pauli_values_on_the_host(qc, ob, tmp_path):
+    with Chain(qc, ob, 9, 5, 0, tmp_path) as c:
+        for start in ("reset", "measure"):
+            if start == "reset":
+                c.do("reset")
+                idx = 1
+            else:
+                c.do("fill", 5)
+                idx = c.do("measure", 0.61)
+                assert popcount(idx) >= 3, "the chain wants a basis state with several bits set"
+            z = 0x2A5F
+            assert c.do("expect", 0, z) == (-1.0 if popcount(idx & z) & 1 else 1.0)
+            assert c.reg.expectation_stats() == (2, 0), "a Z string on a pending basis state is answered on the host"
+            assert bits([c.do("expect", 0x0106, 0x0003)])[0] == 0, "a string with an X or a Y has no diagonal entry: +0"
+            assert c.reg.expectation_stats() == (2, 0)
+            total, values = c.do("expect_sum", 17, 6)
+            assert c.reg.expectation_stats() == (2, 0) and set(np.abs(values).tolist()) <= {0.0, 1.0}
+            c.do("marginal", 3, 6)
+            assert c.reg.marginal_stats() == (2, 0), "the Pauli values left the basis state pending"
+            c.do("prot", 0x1803, 0x0801, 1.1)                             # writes the basis state, then pairs of tiles
+            c.do("expect", 0, z)
+            assert c.reg.expectation_stats() == (0, 1)
+            c.do("expect", 0x1803, 0x0801)
+            c.state()
+
+
+def test_chain_compact_result_pauli_values_keep_the_compact_form(qc, ob, tmp_path, shor_20):
+    with Chain(qc, ob, 15, 5, 0, tmp_path) as c:
+        k0 = compact_chains(qc, c.reg)
+        compact_start(c, shor_20)
+        assert compact_chains(qc, c.reg) == k0 + 1
+        m0 = compact_measures(qc, c.reg)
+        c.do("expect_sum", 23, 3)                                         # expanded into the register's stale buffer ...
+        assert c.reg.expectation_stats() == (3, 3)
+        c.do("sample", 3, 8)                                              # ... and the compact form is still what is scanned
+        assert compact_measures(qc, c.reg) == m0 + 1
+        c.do("marginal", 1, 3)                                            # inside the M register: borrows marg_buf after the Pauli tree did
+        assert c.reg.marginal_stats() == (3, 1)
+        c.do("expect", 0x81020, 0x01021)
+        assert c.reg.expectation_stats() == (3, 1)
+        c.do("sample", 4, 4)
+        assert compact_measures(qc, c.reg) == m0 + 2
+        c.do("prot", 0x40011, 0x40101, -2.3)                              # the compact form is history
+        c.do("marginal", 0, 6)
+        assert c.reg.marginal_stats() == (0, 1)
+        c.do("expect", 0x40011, 0x40101)
+        assert c.reg.expectation_stats() == (0, 1)
+        c.do("read", 12345, 4096)
+
+
+def test_chain_mode_1_queue_pauli_value_runs_it_rotation_flushes_uncounted(qc, ob, tmp_path):
+    with Chain(qc, ob, 9, 5, 1, tmp_path) as c:
+        c.do("fill", 7)
+        c.do("flush")
+        s0 = c.reg.fusion_stats()
+        c.do("h", 3); c.do("cphase", 4, 9, 0.3); c.do("h", 13)
+        assert c.reg.fusion_stats() == s0, "mode 1 queues the gates"
+        c.do("expect", 0x2008, 0x0218)                                    # an observer: the queue runs first
+        s1 = c.reg.fusion_stats()
+        assert s1 != s0 and c.reg.expectation_stats() == (0, 1)
+        c.do("h", 6); c.do("cphase", 6, 2, 0.8)
+        assert c.reg.fusion_stats() == s1
+        c.do("prot", 0x0040, 0x0041, 0.9)                                 # never queued: flushes the two gates ...
+        s2 = c.reg.fusion_stats()
+        assert s2 != s1
+        c.do("prot", 0, 0x1040, -0.4)                                     # ... and nothing is counted for a rotation
+        assert c.reg.fusion_stats() == s2
+        total, values = c.do("expect_sum", 5, 0)                          # no terms: nothing runs
+        assert bits([total])[0] == 0 and len(values) == 0 and c.reg.expectation_stats() == (0, 0)
+        c.state()
+
+
+@pytest.mark.parametrize("x_mask, z_mask", [(0, 0x405), (0x0C1, 0x441)], ids=["diagonal", "pairs"])
+def test_chain_negative_zeros_rotation_rewrites_them_all(qc, ob, tmp_path, x_mask, z_mask):
+    with Chain(qc, ob, 7, 4, 0, tmp_path) as c:
+        c.do("write", 0, c.dim, 31, "negzero")
+        c.do("expect", x_mask, z_mask)
+        got = c.do("read", 0, c.dim)                                      # the -0 are still there
+        assert np.count_nonzero((got == 0) & np.signbit(got)) > 100
+        c.do("prot", x_mask, z_mask, 0.7)                                 # clears the owed zero pass without one: it writes 0 + ... everywhere
+        assert not np.any((c.m.a == 0) & np.signbit(c.m.a)), "the definition leaves no -0"
+        c.state()
+        c.do("h", 10)                                                     # nothing is owed
+        c.state()
+
+
+def test_chain_non_finite_register_pauli_calls_stay_strict(qc, ob, tmp_path):
+    with Chain(qc, ob, 8, 4, 0, tmp_path) as c:
+        c.do("fill", 3)
+        c.do("write", 700, 64, 21, "inf")
+        v = c.do("expect", 0x0A3, 0x821)                                  # whatever the definition gives
+        assert not np.isfinite(v)
+        c.do("expect_sum", 9, 3)
+        c.do("prot", 0x0A3, 0x821, 2.2)                                   # runs unchanged on a non-finite register
+        c.do("read", 600, 300)
+        c.do("h", 7)                                                      # still strict
+        got = c.do("postselect", 0, 0, 0)                                 # the total is not finite: refused, state kept
+        assert got[1] == rm.BAD_ARGUMENTS
+        c.do("prot", 0, 0x003, -1.0)
+        c.do("fill", 9)
+        assert np.isfinite(c.do("expect", 0x0A3, 0x821))
+        c.do("prot", 0x0A3, 0x821, 2.2)
+        c.state()
+
+
+def test_chain_handed_out_pointer_ends_the_compact_chains(qc, ob, tmp_path, shor_20):
+    with Chain(qc, ob, 15, 5, 0, tmp_path) as c:
+        k0 = compact_chains(qc, c.reg)
+        compact_start(c, shor_20)
+        assert compact_chains(qc, c.reg) == k0 + 1
+        c.do("devptr", 12345, 4096)                                       # the compact result was expanded into the buffer
+        k1, p1 = compact_chains(qc, c.reg), chain_stats(qc, c.reg)
+        compact_start(c, shor_20)                                         # in place from now on: no compact copy, no second buffer
+        assert compact_chains(qc, c.reg) == k1 and chain_stats(qc, c.reg) == p1
+        c.do("read", 1 << 19, 1 << 14)
+        c.do("devptr", 0, 1 << 14)
+        c.do("iqft")
+        assert compact_chains(qc, c.reg) == k1 and chain_stats(qc, c.reg) == p1
+        c.do("devptr", 0, c.dim)                                          # (read_through_pointer: the same pointer all along)
+
+
+def test_chain_handed_out_pointer_behind_a_basis_state_and_a_queue(qc, ob, tmp_path):
+    with Chain(qc, ob, 9, 5, 0, tmp_path) as c:
+        c.do("reset")
+        c.do("devptr", 0, 64)                                             # the basis state is in the buffer
+        c.do("fusion", 1)
+        c.do("h", 13); c.do("h", 2); c.do("h", 7)
+        c.do("devptr", 0, c.dim)
+        idx = c.do("measure", 0.7)
+        c.do("devptr", max(0, idx - 100), 200)
+        c.do("h", 12)
+        c.do("expect", 0x1000, 0)
+        c.do("devptr", 0, c.dim)
+
+
+def test_chain_callers_stream(qc, ob, tmp_path):
+    """every kind of call on a non-blocking stream: the synchronous copies of write / read, the scan of what was written and the
+    kernels before and after them must be ordered by the library, not by the null stream"""
+    with Chain(qc, ob, 9, 5, 0, tmp_path) as c:
+        c.do("stream", 1)
+        c.do("fill", 3)
+        c.do("write", 1000, 300, 6, "negzero")
+        c.do("h", 3)
+        c.do("read", 900, 500)
+        c.do("write", 5000, 40, 8, "nan")
+        c.do("cu1", 5, 1, 4)
+        c.do("read", 4990, 60)
+        c.do("fill", 4)
+        c.do("measure", 0.37)
+        c.do("fill", 5)
+        c.do("sample", 5, 9)
+        c.do("marginal", 2, 4)
+        c.do("postselect", 2, 4, int(np.argmax(c.m.marginal(2, 4))))
+        c.do("prot", 0x2011, 0x0013, 0.8)
+        c.do("expect", 0x2011, 0x0013)
+        c.do("iqft")
+        c.do("save", 0)
+        c.do("h", 1)
+        c.do("load", 0)
+        c.do("devptr", 8000, 500)
+        c.do("fusion", 1)
+        c.do("h", 4); c.do("cphase", 4, 11, 0.3)
+        c.do("write", 0, 16, 9, "plain")
+        c.do("total")
+        c.state()
+    with Chain(qc, ob, 11, 5, 0, tmp_path) as c:                          # the compact form
+        c.do("stream", 1)
+        k0, m0 = compact_chains(qc, c.reg), compact_measures(qc, c.reg)
+        c.do("reset")
+        c.do("qcomp", 21, 2)
+        assert compact_chains(qc, c.reg) == k0 + 1, "reset + quantum_computation runs as a compact chain on the caller's stream too"
+        c.do("sample", 2, 9)
+        assert compact_measures(qc, c.reg) == m0 + 1
+        c.do("stream", 0)
+        c.do("h", 0)
+        c.state()
+
+
+def plain(v):
+    """what a call returned, as something == compares bit for bit"""
+    if v is None or isinstance(v, (int, np.integer)):
+        return v
+    if isinstance(v, tuple):
+        return tuple(plain(e) for e in v)
+    return bits(np.atleast_1d(v)).tolist()
+
+
+def test_random_sequence_gives_the_same_on_the_callers_stream(qc, ob, tmp_path):
+    """one op list of vocabulary 2, twice: on the register's own stream throughout, and with ("stream", 1) behind the first op"""
+    seed = next(s for s in rm.seeds_of(2) if len(rm.Config(s).shapes) == 1 and not rm.Config(s).compact and sum(rm.Config(s).shapes[0][:2]) >= 13)
+    cfg, ops = rm.generate(ob, seed)
+    ops = [op for _, op in ops if op[0] != "stream"]
+    (L, M, Cn, a), mode = cfg.shapes[0], cfg.mode
+
+    def run(ops):
+        out, ctx = [], {}
+        with qc.Register(L, M) as reg:
+            reg.set_fusion(mode)
+            for i, op in enumerate(ops):
+                got = apply_to_register(qc, reg, op, lambda slot: str(tmp_path / f"twice_slot{slot}.qcx"), ctx)
+                if op[0] != "stream":
+                    out.append((i - (1 if "stream" in ctx else 0), op[0], plain(got)))
+            out.append(plain(reg.read()))
+        ctx.clear()
+        return out
+
+    own = run(ops)
+    callers = run(ops[:1] + [("stream", 1)] + ops[1:])
+    assert len(own) == len(callers)
+    for a_, b_ in zip(own, callers):
+        assert a_ == b_, f"{cfg!r}: op {a_[:2]} returned something else on the caller's stream\nops = {ops!r}"

@@ -4,8 +4,14 @@
     2^n x 2^n matrix, every collapse a projector and a renormalisation, every marginal a plain sum.  This catches a model that is
     composed wrongly (qubit order, a collapse that forgets to scale, the inverse QFT on the wrong register); rounding is the
     business of the restatements' own tests.
-(b) the generator reaches what it claims: every legal (state-setting kind, following kind) pair at least three times over the
-    committed seeds with nothing but quiet calls in between, judged on the op lists alone."""
+(b) the generator reaches what it claims: every legal (state-setting kind, following kind) pair of each vocabulary at least
+    three times over that vocabulary's seeds with nothing but quiet calls in between, judged on the op lists alone; the op lists
+    of vocabulary 1 are the committed ones (tests/golden/sequence_digests.json); the Pauli calls of vocabulary 2 are not vacuous
+    (masks of all three unit shapes, Y letters, values other than 0, non-finite states, rotations that change the state)."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -87,6 +93,23 @@ class Replay:
         self.v = np.where(keep, self.v, 0) / np.sqrt(p)
         return p
 
+    def pauli(self, x_mask, z_mask):
+        """the Pauli string as a 2^n x 2^n matrix: the Kronecker product of its letters, qubit 0 least significant; Y on x & z"""
+        I, X = np.eye(2, dtype=CLD), np.array([[0, 1], [1, 0]], dtype=CLD)
+        Y, Z = np.array([[0, -1j], [1j, 0]], dtype=CLD), np.array([[1, 0], [0, -1]], dtype=CLD)
+        P = np.ones((1, 1), dtype=CLD)
+        for q in range(self.n):
+            xb, zb = (x_mask >> q) & 1, (z_mask >> q) & 1
+            P = np.kron(Y if xb and zb else X if xb else Z if zb else I, P)
+        return P
+
+    def expect(self, x_mask, z_mask):
+        return (np.conj(self.v) @ (self.pauli(x_mask, z_mask) @ self.v)).real
+
+    def prot(self, x_mask, z_mask, theta):
+        h = LD(theta) / LD(2)
+        self.v = (np.cos(h) * np.eye(self.dim, dtype=CLD) - 1j * np.sin(h) * self.pauli(x_mask, z_mask)) @ self.v
+
     def interleaved(self):
         out = np.empty(2 * self.dim, dtype=LD)
         out[0::2], out[1::2] = self.v.real, self.v.imag
@@ -140,7 +163,14 @@ def replay_seed(ob, seed, bound):
         elif k == "cu1": x.gate(rm.matrix_data(2, op[3]), [op[2]], control=op[1])
         elif k == "u2": x.gate(rm.matrix_data(4, op[3]), [op[1], op[2]])
         elif k == "cu2": x.gate(rm.matrix_data(4, op[4]), [op[2], op[3]], control=op[1])
-        elif k == "read": near(got, x.interleaved()[2 * op[1]:2 * (op[1] + op[2])], "window")
+        elif k == "prot": x.prot(op[1], op[2], op[3])
+        elif k == "expect": near(got, x.expect(op[1], op[2]), "expectation")
+        elif k == "expect_sum":
+            terms = rm.sum_terms(m.n, op[1], op[2])
+            values = [x.expect(xm, zm) for _, xm, zm in terms]
+            near(got[1], values, "the values of the terms")
+            near(got[0], sum((LD(c) * v for (c, _, _), v in zip(terms, values)), LD(0)), "the terms' sum")
+        elif k in ("read", "devptr"): near(got, x.interleaved()[2 * op[1]:2 * (op[1] + op[2])], "window")
         elif k == "marginal": near(got, x.marginal(op[1], op[2]), "marginal")
         elif k in ("total", "norm2"): near(got, x.probs().sum(), k)
         elif k == "measure":
@@ -168,7 +198,7 @@ def replay_seed(ob, seed, bound):
         elif k == "refused":
             assert np.array_equal(m.a.view(np.uint64), before.view(np.uint64)), "a refused call changed the model"
         else:
-            assert k in ("flush", "sync", "fusion", "stats"), op
+            assert k in ("flush", "sync", "fusion", "stats", "stream"), op
         near(m.a, x.interleaved(), "state")
     return worst
 
@@ -179,14 +209,31 @@ SMALL_SEEDS = range(24)
 MEASURED, BOUND = 1.110e-15, 16 * 1.110e-15
 
 
+# the same over SMALL_SEEDS_V2, the small sequences of vocabulary 2 (expectation values of up to 64 leaves, sums of up to six
+# terms with coefficients below 2, rotations of one or two products per amplitude): 9.688e-16; the bound is 16 times that: 1.550e-14
+SMALL_SEEDS_V2 = range(rm.SMALL_V1, 2 * rm.SMALL_V1)
+MEASURED_V2, BOUND_V2 = 9.688e-16, 16 * 9.688e-16
+
+
 def test_model_against_long_double_linear_algebra(ob):
+    assert all(rm.Config(seed, small=True).vocab == 1 for seed in SMALL_SEEDS)
     worst = max(replay_seed(ob, seed, BOUND) for seed in SMALL_SEEDS)
     print(f"largest deviation of the model from the long-double replay: {worst:.3e} (bound {BOUND:.3e})")
     assert worst <= BOUND
 
 
+def test_model_of_vocabulary_2_against_long_double_linear_algebra(ob):
+    assert all(rm.Config(seed, small=True).vocab == 2 for seed in SMALL_SEEDS_V2)
+    kinds = {op[0] for seed in SMALL_SEEDS_V2 for _, op in rm.generate(ob, seed, small=True, length=30)[1]}
+    assert {"expect", "expect_sum", "prot", "devptr", "stream"} <= kinds
+    worst = max(replay_seed(ob, seed, BOUND_V2) for seed in SMALL_SEEDS_V2)
+    print(f"largest deviation of the model from the long-double replay, vocabulary 2: {worst:.3e} (bound {BOUND_V2:.3e})")
+    assert worst <= BOUND_V2
+
+
 def test_replay_notices_a_wrongly_composed_model(ob):
-    """the replay is not vacuous: a model with the two-qubit gate's qubits swapped, or a postselect that does not scale, fails it"""
+    """the replay is not vacuous: a model with the two-qubit gate's qubits swapped, or a postselect that does not scale, fails it;
+    so do, on the sequences of vocabulary 2, an expectation with x_mask and z_mask swapped and a rotation by -theta"""
     class Swapped(rm.RegisterModel):
         def two_qubit_gate(self, q0, q1, U): super().two_qubit_gate(q1, q0, U)
 
@@ -197,41 +244,118 @@ def test_replay_notices_a_wrongly_composed_model(ob):
             self.a = np.where(np.repeat(keep, 2), self.a, 0.0)
             return p, rm.NO_ERROR
 
-    for broken in (Swapped, Unscaled):
+    class MasksSwapped(rm.RegisterModel):
+        def expectation(self, x_mask, z_mask): return super().expectation(z_mask, x_mask)
+
+    class Backwards(rm.RegisterModel):
+        def pauli_rotation(self, x_mask, z_mask, theta): super().pauli_rotation(x_mask, z_mask, -theta)
+
+    for broken, seeds, bound in ((Swapped, SMALL_SEEDS, BOUND), (Unscaled, SMALL_SEEDS, BOUND),
+                                 (MasksSwapped, SMALL_SEEDS_V2, BOUND_V2), (Backwards, SMALL_SEEDS_V2, BOUND_V2)):
         real, rm.RegisterModel = rm.RegisterModel, broken
         try:
             with pytest.raises(AssertionError):
-                for seed in SMALL_SEEDS:
-                    replay_seed(ob, seed, BOUND)
+                for seed in seeds:
+                    replay_seed(ob, seed, bound)
         finally:
             rm.RegisterModel = real
 
 
 # ---- (b) what the generator reaches ----------------------------------------------------------------------------------------------
 
+_GENERATED = {}
+
+
+def generated(ob, seed):
+    """(Config, ops) of one seed, generated once per session"""
+    if seed not in _GENERATED:
+        _GENERATED[seed] = rm.generate(ob, seed)
+    return _GENERATED[seed]
+
+
 def test_generator_reaches_every_pair(ob):
-    total, lengths = {}, []
-    for seed in range(rm.NSEEDS):
-        cfg, ops = rm.generate(ob, seed)
+    for vocab in (1, 2):
+        pairs_of_vocabulary(ob, vocab)
+
+
+def pairs_of_vocabulary(ob, vocab):
+    total, lengths, calls = {}, [], {}
+    seeds, following = rm.seeds_of(vocab), rm.following_of(vocab)
+    for seed in seeds:
+        cfg, ops = generated(ob, seed)
+        assert cfg.vocab == vocab
         assert eval(repr(ops)) == ops, "an op list must replay from its printed form"
         mine = [op for which, op in ops if which == 0]
         lengths.append(len(mine))
-        for pair, cnt in rm.pairs_reached(cfg.shapes[0], cfg.mode, mine).items():
+        for pair, cnt in rm.pairs_reached(cfg.shapes[0], cfg.mode, mine, vocab).items():
             total[pair] = total.get(pair, 0) + cnt
         full = sum(1 for op in mine if op[0] == "read" and op[2] == 1 << (cfg.shapes[0][0] + cfg.shapes[0][1]))
         assert mine[-1][0] == "read" and full <= len(mine) // 3, (seed, full, len(mine))
-    legal = [(s, f) for s in rm.SETTING for f in rm.FOLLOWING
-             if any(rm.pair_is_legal(s, f, rm.Config(k).shapes[0], rm.Config(k).compact) for k in range(rm.NSEEDS))]
-    print(f"ops per seed: {min(lengths)} .. {max(lengths)}")
-    print(" " * 20 + " ".join(f"{f[:6]:>6}" for f in rm.FOLLOWING))
+        if cfg.compact:
+            assert not any(op[0] == "devptr" for op in mine), "a handed-out pointer ends the compact chains run_ops asserts"
+        for _, op in ops:
+            calls[op[0]] = calls.get(op[0], 0) + 1
+    legal = [(s, f) for s in rm.SETTING for f in following
+             if any(rm.pair_is_legal(s, f, rm.Config(k).shapes[0], rm.Config(k).compact) for k in seeds)]
+    print(f"vocabulary {vocab}, seeds {seeds[0]} .. {seeds[-1]}; ops per seed: {min(lengths)} .. {max(lengths)}")
+    print(" " * 20 + " ".join(f"{f[:6]:>6}" for f in following))
     for s in rm.SETTING:
-        print(f"{s:20}" + " ".join(f"{total.get((s, f), 0):6d}" if (s, f) in legal else "     -" for f in rm.FOLLOWING))
+        print(f"{s:20}" + " ".join(f"{total.get((s, f), 0):6d}" if (s, f) in legal else "     -" for f in following))
+    print("calls: " + ", ".join(f"{k} {calls.get(k, 0)}" for k in following))
     short = [(p, total.get(p, 0)) for p in legal if total.get(p, 0) < 3]
     assert not short, f"pairs reached fewer than 3 times: {short}"
-    assert len(legal) == len(rm.SETTING) * len(rm.FOLLOWING) - 1           # all but (write of an Inf/NaN, norm2)
-    assert 40 <= min(lengths) and max(lengths) <= 90, lengths      # (a circuit front alone is L + a few calls)
+    # all but (write of an Inf/NaN, norm2) and, in vocabulary 2, (compact, devptr)
+    assert len(legal) == len(rm.SETTING) * len(following) - vocab
+    assert (len(rm.SETTING), len(following)) == ((11, 25) if vocab == 1 else (11, 30))
+    assert 40 <= min(lengths) and max(lengths) <= (90 if vocab == 1 else 140), lengths      # (a circuit front alone is L + a few calls)
+
+
+def test_vocabulary_1_generates_the_committed_op_lists(ob):
+    """the seeds below NSEEDS_V1 (and the small seeds below SMALL_V1) are frozen: sha256 of repr(ops), recorded with the generator
+    as it was before vocabulary 2 existed.  What these seeds assert on the GPU cannot drift when the generator grows."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sequence_digests.json")) as f:
+        golden = json.load(f)
+    assert sorted(golden["big"], key=int) == [str(s) for s in range(rm.NSEEDS_V1)]
+    assert sorted(golden["small"], key=int) == [str(s) for s in range(rm.SMALL_V1)]
+    digest = lambda ops: hashlib.sha256(repr(ops).encode()).hexdigest()
+    drifted = [s for s in range(rm.NSEEDS_V1) if digest(generated(ob, s)[1]) != golden["big"][str(s)]]
+    drifted += [("small", s) for s in range(rm.SMALL_V1) if digest(rm.generate(ob, s, small=True, length=30)[1]) != golden["small"][str(s)]]
+    assert not drifted, f"the op lists of these vocabulary-1 seeds changed: {drifted}"
+
+
+def test_pauli_calls_of_vocabulary_2_are_not_vacuous(ob):
+    """on the model alone, over the seeds of vocabulary 2: what the expect and prot ops meet"""
+    ex = dict(n=0, x=0, y=0, nonzero=0, nonfinite=0, shape=[0, 0, 0])
+    pr = dict(n=0, changed=0, shape=[0, 0, 0])
+    for seed in rm.seeds_of(2):
+        cfg, ops = generated(ob, seed)
+        models = [rm.RegisterModel(ob, L, M) for L, M, _, _ in cfg.shapes]
+        for which, op in ops:
+            m = models[which]
+            if op[0] == "expect":
+                ex["nonfinite"] += m.holds_nonfinite()
+            before = m.a
+            got = rm.apply_to_model(m, op)
+            if op[0] == "expect":
+                ex["n"] += 1
+                ex["x"] += op[1] != 0
+                ex["y"] += (op[1] & op[2]) != 0
+                ex["nonzero"] += got != 0                                  # (a NaN is a value other than 0)
+                ex["shape"][rm.mask_shape(op[1])] += 1
+            elif op[0] == "prot":
+                pr["n"] += 1
+                pr["changed"] += not np.array_equal(before.view(np.uint64), m.a.view(np.uint64))
+                pr["shape"][rm.mask_shape(op[1])] += 1
+    print(f"expect: {ex}\nprot: {pr}")
+    assert 2 * ex["x"] >= ex["n"], "at least half of the expect ops have x_mask != 0"
+    assert 5 * ex["y"] >= ex["n"], "at least a fifth carry a Y"
+    assert 2 * ex["nonzero"] >= ex["n"], "at least half return a value other than 0"
+    assert 10 * ex["nonfinite"] >= ex["n"], "at least a tenth fall on a non-finite state"
+    assert 10 * pr["changed"] >= 9 * pr["n"], "at least 90 % of the prot ops change the bits of the state"
+    assert min(ex["shape"]) >= 20 and min(pr["shape"]) >= 20, "each of the three unit shapes in >= 20 expect and >= 20 prot ops"
 
 
 def test_generator_is_deterministic(ob):
     assert rm.generate(ob, 3)[1] == rm.generate(ob, 3)[1]
     assert rm.generate(ob, 3)[1] != rm.generate(ob, 4)[1]
+    assert rm.generate(ob, 70)[1] == rm.generate(ob, 70)[1]
