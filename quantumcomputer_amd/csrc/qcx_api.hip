@@ -1577,6 +1577,16 @@ static int descs_to_gates(unsigned n_local, unsigned M, unsigned count, const qc
     return QCX_NO_ERROR;
 }
 
+// the leading descriptors that can be part of a circuit front (Hadamards and multiplies), as gates: the front ends at the first
+// descriptor that cannot -- a phase, or one that is not valid
+static std::vector<QGate> front_prefix(unsigned n, unsigned M, unsigned count, const qcx_gate_desc *gates)
+{
+    std::vector<QGate> q;
+    for (unsigned k = 0; k < count; k++)
+        if (gates[k].type == 1 || descs_to_gates(n, M, 1, gates + k, q) != QCX_NO_ERROR) break;
+    return q;
+}
+
 // ---- compact circuits for a one-process-per-GPU host (quantumcomputer_amd/sharded.py; the C host: sh_compact) ----------------
 // qcx_compact_plan: pure host.  The closed-form front of `gates` on basis state `basis` (as qcx_shard_basis_front consumes it)
 // and, when the M register stays on a small orbit behind it (compact_orbit), the compact form's column bits and the orbit.
@@ -1586,12 +1596,7 @@ extern "C" int qcx_compact_plan(unsigned n, unsigned M, uint64_t basis, unsigned
 {
     if (!used || !cb || !ncols || !orbit16 || n == 0 || n > 40 || M > n || (count && !gates) || (basis >> n)) return QCX_BAD_ARGUMENTS;
     *used = *cb = *ncols = 0;
-    std::vector<QGate> q;
-    for (unsigned k = 0; k < count; k++) {
-        std::vector<QGate> one;
-        if (gates[k].type == 1 || descs_to_gates(n, M, 1, gates + k, one) != QCX_NO_ERROR) break;
-        q.push_back(one[0]);
-    }
+    const std::vector<QGate> q = front_prefix(n, M, count, gates);
     BasisFront B;
     const Tune tn = tune_now();
     const size_t k = (M <= 26) ? front_plan(n, M, basis, tn, q, &B) : 0;
@@ -1654,11 +1659,8 @@ extern "C" int qcx_shard_run_fused_mode(int mode, void *amp, unsigned n_local, u
         sq = slot;
     }
     std::lock_guard<std::mutex> use(sq->use);
-    qcx_register tmp;
-    memset(&tmp, 0, sizeof tmp);
-    tmp.L = (int)(n_local - M); tmp.M = (int)M; tmp.n = n_local; tmp.dim = (uint64_t)1 << n_local;
-    tmp.amp = (amp_t *)amp; tmp.stream = tmp.own_stream = (hipStream_t)stream;
-    tmp.fusion = mode == 2 ? 2 : 1; tmp.queue = &sq->q;
+    qcx_register tmp = reg_view(n_local - M, M, (amp_t *)amp, nullptr, (hipStream_t)stream, (hipStream_t)stream, mode == 2 ? 2 : 1);
+    tmp.queue = &sq->q;
     tmp.no_chain = 1;                                    // a view of somebody else's memory: there is no second buffer behind it
     tmp.queue->gates.clear();
     QCX_TRY(descs_to_gates(n_local, M, count, gates, tmp.queue->gates));
@@ -1686,16 +1688,16 @@ extern "C" int qcx_fusion_plan_mode(int mode, unsigned n_local, unsigned M, unsi
     if (n_local == 0 || n_local > 40 || M > n_local || (count && !gates) || !n_actions || !n_records) return QCX_BAD_ARGUMENTS;
     if ((mode & 3) != 1 && (mode & 3) != 2) return QCX_BAD_ARGUMENTS;
     static_assert(sizeof(qcx_fuse_record) == sizeof(FuseOp), "record layout");
-    qcx_register tmp;
-    memset(&tmp, 0, sizeof tmp);
-    tmp.L = (int)(n_local - M); tmp.M = (int)M; tmp.n = n_local; tmp.dim = (uint64_t)1 << n_local;
+    const qcx_register tmp = reg_view(n_local - M, M, nullptr, nullptr, nullptr, nullptr, 0);
     std::vector<QGate> q;
     QCX_TRY(descs_to_gates(n_local, M, count, gates, q));
     std::vector<FuseAction> acts;
     std::vector<FuseOp> ops;
-    // mode | 4: with chained passes (a register with a second buffer); | 8: as compact_chain plans the virtual register of a compact
+    // mode | 4: with chained passes (a register with a second buffer); | 8: as compact_chain_plan plans the virtual register of a compact
     // chain (the first pass generated by columns: a tile of the M register's bits x 8 hot bits)
-    fuse_plan(&tmp, tune_now(), q, acts, ops, (mode & 3) == 2, (mode & 4) != 0, (mode & 8) ? (((mode & 3) == 2 && tune_now().fuse_cols_tol) ? 2 : 1) : 0);
+    const Tune tn = tune_now();
+    const bool tol = (mode & 3) == 2;
+    fuse_plan(&tmp, tn, q, acts, ops, tol, (mode & 4) != 0, (mode & 8) ? compact_first_cols(tn, tol) : 0);
     *n_actions = (unsigned)acts.size();
     *n_records = ops.size();
     if (acts.size() > max_actions || ops.size() > max_records || (!actions && !acts.empty()) || (!records && !ops.empty()))
@@ -1735,12 +1737,7 @@ extern "C" int qcx_shard_basis_front(void *amp, unsigned n_local, uint64_t first
     if (basis >> n) return QCX_BAD_ARGUMENTS;
     if (first_global & (((uint64_t)1 << n_local) - 1)) return QCX_BAD_ARGUMENTS;
     *used = 0;
-    std::vector<QGate> q;
-    for (unsigned k = 0; k < count; k++) {                 // the front ends at the first gate that cannot be part of it
-        std::vector<QGate> one;
-        if (gates[k].type == 1 || descs_to_gates(n, M, 1, gates + k, one) != QCX_NO_ERROR) break;
-        q.push_back(one[0]);
-    }
+    const std::vector<QGate> q = front_prefix(n, M, count, gates);
     BasisFront B;
     size_t k = 0;
     if (M <= 26) k = front_plan(n, M, basis, tune_now(), q, &B);

@@ -101,11 +101,9 @@ struct GateQueue {
     // expanding store (FusePass::xp_on: straight into the register, no k_expand_compact) for everybody else -- or never, when
     // a reset comes first.  Its records stay in d_ops: nothing uploads before the pending state is resolved (fuse_flush).
     struct {
-        FusePass P, Pxp;            // as planned / with the expanding store
-        size_t   op_off = 0;
-        bool     nopipe = false;
+        FuseAction act, act_xp;     // as planned / with the expanding store
         amp_t   *in = nullptr, *out = nullptr;      // compact buffers: the pass reads in, an ordinary launch writes out (== in: in place)
-        unsigned nv = 0, cb = 0, ngates = 0;
+        unsigned nv = 0, cb = 0;
         Tune     tn;                // the knobs the plan was made under
     } last;
     // The plan of the last flush, kept: a period-finding run issues the same circuit attempt after attempt, and planning it
@@ -113,19 +111,20 @@ struct GateQueue {
     // QFT, on the host, with the GPU idle) plus uploading the records is pure repetition.  A flush whose inputs are bit for
     // bit those of the cached one -- register shape, fusion mode, every knob, the circuit front, the gate list -- reuses
     // actions and records; when nothing has been uploaded since, the records are still on the device as well.
-    // kind 1: a flush without a front (fuse_flush's plain path); 2: a compact chain.
+    // kind 1: fuse_flush's plain path; 2: a compact chain.  The inputs are one PlanKey (plan_cache_hit compares it, plan_cache_store
+    // keeps it); the entry is valid once its records are on the device (plan_records_resident).
     struct {
         bool     valid = false;
         int      kind = 0;
         unsigned n = 0, M = 0;
         int      fusion = 0;
         bool     chain = false;
-        bool     front_flush = false, gen_try = false;      // kind 1: the flush stood behind a lazily pending basis state / generated its front
-        bool     gen_built = false, gen2 = false;           // ... and how that went (what a hit replays)
+        bool     front_flush = false, gen_try = false;      // the flush stood behind a lazily pending basis state / tried to generate its front
         Tune     tn;
-        BasisFront Bf;
+        BasisFront Bf;                                      // (Bf, kfront: behind a front only -- gen_try)
         size_t   kfront = 0;
         std::vector<QGate> gates;
+        bool     gen_built = false, gen2 = false;           // kind 1: how generating the front went (what a hit replays)
         std::vector<FuseAction> acts;
         std::vector<FuseOp> all_ops;
         std::vector<uint16_t> orbit;    // kind 2
@@ -138,6 +137,30 @@ struct GateQueue {
 static bool same_gate_list(const std::vector<QGate> &a, const std::vector<QGate> &b)
 {
     return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(QGate)) == 0);
+}
+
+// the inputs of a flush's plan, as the plan cache compares and keeps them (GateQueue::pc)
+struct PlanKey {
+    int      kind;                  // 1: fuse_flush's plain path; 2: a compact chain
+    unsigned n, M;                  // the register's shape
+    int      fusion;
+    bool     chain, front_flush, gen_try;
+    size_t   kfront;                // with Bf: looked at behind a front only (gen_try)
+    const Tune *tn;
+    const BasisFront *Bf;
+    const std::vector<QGate> *gates;
+};
+
+// a register view over somebody else's memory: an (L, M) register in amp (second buffer: scratch) that owns nothing -- a compact
+// chain's virtual register, a shard of a multi-process host, the planner's stand-in (no memory at all)
+static qcx_register reg_view(unsigned L, unsigned M, amp_t *amp, amp_t *scratch, hipStream_t own_stream, hipStream_t stream, int fusion)
+{
+    qcx_register v;
+    memset(&v, 0, sizeof v);
+    v.L = (int)L; v.M = (int)M; v.n = L + M; v.dim = (uint64_t)1 << (L + M);
+    v.amp = amp; v.scratch = scratch;
+    v.own_stream = own_stream; v.stream = stream; v.fusion = fusion;
+    return v;
 }
 
 static void queue_free(GateQueue *gq)
@@ -1344,9 +1367,6 @@ static int launch_basis_front(amp_t *amp, unsigned n_local, const BasisFront &B,
 // The register is the basis state r->basis_index but nothing has been written yet (lazy reset / collapse).  Write it now --
 // together with the longest prefix of the queue that has a closed form on a basis state: Hadamards on distinct qubits, then
 // controlled modular multiplies (K0b, k_basis_front; the front of Q:712-737 is exactly that).  *used = gates consumed.
-// The register is the basis state r->basis_index but nothing has been written yet (lazy reset / collapse).  Write it now --
-// together with the longest prefix of the queue that has a closed form on a basis state: Hadamards on distinct qubits, then
-// controlled modular multiplies (K0b, k_basis_front; the front of Q:712-737 is exactly that).  *used = gates consumed.
 // the separate write of the basis state + the closed-form front B (k gates of the queue)
 static int launch_front(qcx_register *r, const BasisFront &B, size_t k)
 {
@@ -1373,43 +1393,87 @@ static int basis_front(qcx_register *r, const std::vector<QGate> &gates, size_t 
     return QCX_NO_ERROR;
 }
 
-// Can the front B be generated tile by tile inside the pass `act` -- the first pass behind it, which reads the identity
-// layout: its tile-local bit j IS qubit in_pos[j] -- instead of being written by a pass of its own?  (GenFront, qcx_kernels.h:
-// one modulus for the whole ladder, the basis residue below it; a rounds-form pass without multiplies.)  Fills G.
-static bool gen_front_build(unsigned n, unsigned M, const BasisFront &B, const FuseAction &act, GenFront *G)
+// ---- front facts: what the closed-form front B leaves in the M register (DESIGN s4.4) --------------------------------------
+// The multiply ladder as ONE modulus *C (0: no multiplies) and the basis residue *f0 below it.  false: not one ladder -- two
+// moduli, or C > 4096 or f0 >= C (the generating kernels' tables and their reduction).
+static bool front_ladder(const BasisFront &B, unsigned M, uint32_t *C, uint32_t *f0)
 {
-    const FusePass &P = act.P;
-    if (!act.fused || P.has_cam || P.cam_ctl_local[0] != 1 || P.T < 10 || P.T > 12 || M > 12 || B.first != 0 || n > 40) return false;
+    *C = B.ncam ? B.C[0] : 0u;
+    *f0 = (uint32_t)(B.basis & (((uint64_t)1 << M) - 1));
+    if (B.ncam > 64) return false;
+    for (unsigned g = 0; g < B.ncam; g++) if (B.C[g] != *C) return false;
+    return !B.ncam || (*C != 0 && *C <= 4096u && *f0 < *C);
+}
+
+// The residues the M register can read behind the front, ascending: the closure of f0 under every multiplier of the ladder -- a
+// superset of the subset products the front can reach.  false: not one ladder, or a Hadamard of the front sits on the M register.
+static bool front_residues(const BasisFront &B, unsigned M, std::vector<uint16_t> &res)
+{
+    res.clear();
+    uint32_t C, f0;
+    if ((B.hmask & (((uint64_t)1 << M) - 1)) != 0 || !front_ladder(B, M, &C, &f0)) return false;
+    if (!B.ncam) { res.push_back((uint16_t)f0); return true; }
+    std::vector<char> seen(C, 0);
+    std::vector<uint32_t> todo(1, f0);
+    seen[f0] = 1;
+    while (!todo.empty()) {
+        const uint32_t x = todo.back(); todo.pop_back();
+        for (unsigned g = 0; g < B.ncam; g++) { const uint32_t y = (uint32_t)(((uint64_t)x * (B.A[g] % C)) % C); if (!seen[y]) { seen[y] = 1; todo.push_back(y); } }
+    }
+    for (uint32_t x = 0; x < C; x++) if (seen[x]) res.push_back((uint16_t)x);
+    return true;
+}
+
+// Does the gate list leave the M register alone?  No Hadamard on it and no multiply: no amplitude moves between its values (what
+// the by-columns first pass and the zero-wave skipping rest on); phases_too: nor does a controlled phase look at it (a compact
+// chain renumbers the qubits above it).
+static bool leaves_m_alone(const std::vector<QGate> &gates, unsigned M, bool phases_too)
+{
+    const uint64_t lowmask = ((uint64_t)1 << M) - 1;
+    for (const QGate &g : gates) {
+        if (g.type == FUSE_H) { if (g.q < M) return false; }
+        else if (g.type == FUSE_PHASE) { if (phases_too && (g.mask & lowmask)) return false; }
+        else return false;
+    }
+    return true;
+}
+
+// Has the first pass of a plan the by-columns shape (K6g)?  A tile of the colb lowest bits, in place, x 8 hot bits above the
+// register's M (a compact chain's virtual register: M = colb), rounds form, no round on a column bit; diags: it may hold merged diagonals.
+static bool cols_shape_ok(const std::vector<FuseAction> &acts, const std::vector<FuseOp> &all_ops, unsigned colb, unsigned M, bool diags)
+{
+    if (acts.empty() || !acts[0].fused) return false;
+    const FusePass &P0 = acts[0].P;
+    if (P0.T != colb + 8 || P0.c != colb || P0.cam_ctl_local[0] != 1 || P0.has_cam) return false;
+    if (diags ? (P0.dg_slim == 2 || P0.dg_cnt > 64) : (P0.dg_cnt || P0.dg_slim)) return false;
+    for (unsigned j = 0; j < colb; j++) if (acts[0].tl[j] != j) return false;
+    for (unsigned j = colb; j < colb + 8; j++) if (acts[0].tl[j] < M) return false;
+    for (size_t o = acts[0].op_off; o < acts[0].op_off + P0.nops; ) {
+        const FuseOp &hdr = all_ops[o];
+        const uint32_t ty = hdr.type & 0xffu;
+        if ((ty != FUSE_ROUND && !(ty == FUSE_QROUND && P0.dg_cnt)) || (hdr.a & 0xffu) < colb || ((hdr.a >> 8) & 0xffu) < colb) return false;
+        o += 1 + (size_t)hdr.mask;
+    }
+    return true;
+}
+
+// The generated fill of a tile (GenFront, qcx_kernels.h) from the front B, for a generating pass whose tile holds the real qubits
+// of tilemask, slot_of[q] = the hot slot of qubit q >= M in it (-1: not in the tile).  Everything but the pass's own bit numbering,
+// which the two callers add.  false: a control the tables cannot take.
+static bool gen_front_fill(unsigned n, unsigned M, const BasisFront &B, const int *slot_of, uint64_t tilemask, GenFront *G)
+{
     memset(G, 0, sizeof *G);
     const uint32_t lowmask = (1u << M) - 1u;
-    const uint32_t f0 = (uint32_t)(B.basis & lowmask);
-    uint32_t C = 0;
-    for (unsigned g = 0; g < B.ncam; g++) {
-        if (g == 0) C = B.C[0]; else if (B.C[g] != C) return false;
-    }
-    if (B.ncam && (C == 0 || f0 >= C || C > 4096u || B.ncam > 64)) return false;
-    uint64_t tilemask = 0;
-    unsigned h = 0;
-    int slot_of[64];
-    for (unsigned q = 0; q < 64; q++) slot_of[q] = -1;
-    for (unsigned j = 0; j < P.T; j++) {
-        const unsigned q = P.in_pos[j];
-        tilemask |= (uint64_t)1 << q;
-        G->slotbit[j] = G->lowbit[j] = 0xff;
-        G->signbit[j] = (uint8_t)((B.sign_mask >> q) & 1u);
-        if (q < M) G->lowbit[j] = (uint8_t)q;
-        else { slot_of[q] = (int)h; G->slotbit[j] = (uint8_t)h; h++; }
-    }
-    if (h > (P.dg_slim == 2 ? 9u : 10u)) return false;              // the slot tables' room in LDS (k_fused_x8, dg_slim 3: 1024 slots like the radix-4 kernel)
-    G->h = h;
+    uint32_t C, f0;
+    if (!front_ladder(B, M, &C, &f0)) return false;
     for (unsigned q = M; q < n; q++)
         if (slot_of[q] >= 0 && ((B.fixed_mask >> q) & 1u)) { G->sfm |= 1u << slot_of[q]; G->sbv |= (uint32_t)((B.basis >> q) & 1u) << slot_of[q]; }
     G->basis = B.basis;
     G->fixed_out = B.fixed_mask & ~tilemask;
     G->sign_out = B.sign_mask & ~tilemask;
     G->v = B.v;
-    G->M = M; G->ncam = B.ncam; G->C = B.ncam ? C : 0u; G->f0 = f0;
-    G->Cinv = G->C ? (uint32_t)(((uint64_t)1 << 32) / G->C) : 0u;
+    G->M = M; G->ncam = B.ncam; G->C = C; G->f0 = f0;
+    G->Cinv = C ? (uint32_t)(((uint64_t)1 << 32) / C) : 0u;
     G->cmpmask = ~(uint32_t)(B.hmask & lowmask) & lowmask;
     G->lowout_mask = lowmask & ~(uint32_t)tilemask;
     for (unsigned f = 0; f < 5; f++) for (unsigned b = 0; b < 256; b++) G->tabP[f][b] = 1;
@@ -1424,6 +1488,44 @@ static bool gen_front_build(unsigned n, unsigned M, const BasisFront &B, const F
         G->present |= 1u << f;
         for (unsigned b = 0; b < 256; b++)
             if ((b >> bit) & 1u) G->tabP[f][b] = (uint16_t)(((uint32_t)G->tabP[f][b] * G->camA[g]) % C);
+    }
+    return true;
+}
+
+// the GenFront record behind the flush's records; the generating pass finds it at gen_rec_off
+static void gen_front_append(std::vector<FuseOp> &all_ops, FuseAction &act, const GenFront &G)
+{
+    const size_t at = all_ops.size(), nrec = (sizeof(GenFront) + sizeof(FuseOp) - 1) / sizeof(FuseOp);
+    all_ops.resize(at + nrec);
+    memset(&all_ops[at], 0, nrec * sizeof(FuseOp));
+    memcpy(&all_ops[at], &G, sizeof G);
+    act.P.gen_rec_off = (uint32_t)(at - act.op_off);
+}
+
+// Can the front B be generated tile by tile inside the pass `act` -- the first pass behind it, which reads the identity
+// layout: its tile-local bit j IS qubit in_pos[j] -- instead of being written by a pass of its own?  (GenFront, qcx_kernels.h:
+// one modulus for the whole ladder, the basis residue below it; a rounds-form pass without multiplies.)  Fills G.
+static bool gen_front_build(unsigned n, unsigned M, const BasisFront &B, const FuseAction &act, GenFront *G)
+{
+    const FusePass &P = act.P;
+    if (!act.fused || P.has_cam || P.cam_ctl_local[0] != 1 || P.T < 10 || P.T > 12 || M > 12 || B.first != 0 || n > 40) return false;
+    uint64_t tilemask = 0;
+    unsigned h = 0;
+    int slot_of[64];
+    for (unsigned q = 0; q < 64; q++) slot_of[q] = -1;
+    for (unsigned j = 0; j < P.T; j++) {
+        const unsigned q = P.in_pos[j];
+        tilemask |= (uint64_t)1 << q;
+        if (q >= M) slot_of[q] = (int)h++;
+    }
+    if (h > (P.dg_slim == 2 ? 9u : 10u)) return false;              // the slot tables' room in LDS (k_fused_x8, dg_slim 3: 1024 slots like the radix-4 kernel)
+    if (!gen_front_fill(n, M, B, slot_of, tilemask, G)) return false;
+    G->h = h;
+    for (unsigned j = 0; j < P.T; j++) {
+        const unsigned q = P.in_pos[j];
+        G->slotbit[j] = q < M ? 0xff : (uint8_t)slot_of[q];
+        G->lowbit[j] = q < M ? (uint8_t)q : 0xff;
+        G->signbit[j] = (uint8_t)((B.sign_mask >> q) & 1u);
     }
     return true;
 }
@@ -1498,36 +1600,31 @@ static int upload_ops(qcx_register *r, GateQueue *gq, const std::vector<FuseOp> 
 // (K6g, gen = 3), the ordinary planner and pass kernels take the rest of the gate list through it (chained between two
 // compact buffers carved out of the register's second buffer), and k_expand_compact writes the real register once at the
 // end: 2^(M - cb) times less memory traffic in every pass but the last write.  Same arithmetic on the same amplitudes in the
-// same order: same bits.  *done = false: not applicable, nothing was launched.
-// The orbit a circuit front leaves the M register on, and whether a compact form pays: one modulus, f0 < C <= 4096, every residue
-// inside the register, at most 16 of them, and 2^cb columns (cb >= 2) at least four times fewer than 2^M.  The orbit is the
-// closure of f0 under every multiplier of the ladder -- a superset of the subset products the front can reach.
+// same order: same bits.
+// The orbit a circuit front leaves the M register on (front_residues), and whether a compact form pays: every residue inside the
+// register, at most 16 of them, and 2^cb columns (cb >= 2) at least four times fewer than 2^M.
 static bool compact_orbit(const BasisFront &B, unsigned M, std::vector<uint16_t> &orbit, unsigned *cb_out)
 {
-    orbit.clear();
-    if (M < 4 || M > 12) return false;
-    const uint32_t lowmask = (1u << M) - 1u;
-    if ((B.hmask & lowmask) != 0 || B.ncam > 64) return false;
-    const uint32_t Cn = B.ncam ? B.C[0] : 0u, f0 = (uint32_t)(B.basis & lowmask);
-    for (unsigned g = 0; g < B.ncam; g++) if (B.C[g] != Cn) return false;
-    if (!B.ncam) orbit.push_back((uint16_t)f0);
-    else {
-        if (Cn == 0 || Cn > 4096u || f0 >= Cn) return false;
-        std::vector<char> seen(Cn, 0);
-        std::vector<uint32_t> todo(1, f0);
-        seen[f0] = 1;
-        while (!todo.empty()) {
-            const uint32_t x = todo.back(); todo.pop_back();
-            for (unsigned g = 0; g < B.ncam; g++) { const uint32_t y = (uint32_t)(((uint64_t)x * (B.A[g] % Cn)) % Cn); if (!seen[y]) { seen[y] = 1; todo.push_back(y); } }
-        }
-        for (uint32_t x = 0; x < Cn; x++) if (seen[x]) { if (x > lowmask) { orbit.clear(); return false; } orbit.push_back((uint16_t)x); }
-    }
-    if (orbit.size() > 16) { orbit.clear(); return false; }
     unsigned cb = 2;
-    while ((1u << cb) < orbit.size()) cb++;
-    if (cb + 2 > M) { orbit.clear(); return false; }
-    *cb_out = cb;
-    return true;
+    if (M >= 4 && M <= 12 && front_residues(B, M, orbit) && orbit.back() < (1u << M) && orbit.size() <= 16) {
+        while ((1u << cb) < orbit.size()) cb++;
+        if (cb + 2 <= M) { *cb_out = cb; return true; }
+    }
+    orbit.clear();
+    return false;
+}
+
+// The by-columns first pass (K6g) keeps, per value of the other M-register bits, the columns of the four lowest ones that the orbit
+// populates in LDS: the largest number of them, at most 8 (M >= 4).  0: no such pass behind this front.
+static unsigned cols_bound(const BasisFront &B, unsigned M)
+{
+    std::vector<uint16_t> res;
+    if (!front_residues(B, M, res)) return 0;
+    std::vector<uint16_t> colsets((size_t)1 << (M - 4), 0);
+    for (uint16_t x : res) if (x < (1u << M)) colsets[x >> 4] |= (uint16_t)(1u << (x & 15u));
+    unsigned maxcols = 0;
+    for (uint16_t s : colsets) maxcols = std::max(maxcols, (unsigned)__builtin_popcount(s));
+    return maxcols > 8 ? 0 : maxcols;
 }
 
 // ---- the compact form, read and written by these helpers only (DESIGN s4.4).  Every host that keeps a compact result -- the
@@ -1570,34 +1667,95 @@ static bool compact_real_index(const ExpandParams &E, uint64_t cidx, uint64_t *i
     return true;
 }
 
+// ---- the plan cache (GateQueue::pc): one key, one lookup, one store, one step that makes the records resident ---------------------
+static bool plan_cache_hit(const GateQueue *gq, const PlanKey &k)
+{
+    const auto &pc = gq->pc;
+    return k.tn->fuse_plan_cache && pc.valid && pc.kind == k.kind && pc.n == k.n && pc.M == k.M && pc.fusion == k.fusion && pc.chain == k.chain
+           && pc.front_flush == k.front_flush && pc.gen_try == k.gen_try
+           && (!k.gen_try || (pc.kfront == k.kfront && memcmp(&pc.Bf, k.Bf, sizeof pc.Bf) == 0))
+           && memcmp(&pc.tn, k.tn, sizeof pc.tn) == 0 && same_gate_list(pc.gates, *k.gates);
+}
+
+// the plan of a miss, kept -- not valid before its records are uploaded (plan_records_resident).  false: the cache is switched off
+static bool plan_cache_store(GateQueue *gq, const PlanKey &k, const std::vector<FuseAction> &acts, const std::vector<FuseOp> &all_ops)
+{
+    auto &pc = gq->pc;
+    pc.valid = false;
+    if (!k.tn->fuse_plan_cache) return false;
+    pc.kind = k.kind; pc.n = k.n; pc.M = k.M; pc.fusion = k.fusion; pc.chain = k.chain; pc.front_flush = k.front_flush; pc.gen_try = k.gen_try;
+    pc.tn = *k.tn;
+    if (k.gen_try) { pc.Bf = *k.Bf; pc.kfront = k.kfront; }
+    pc.gates = *k.gates; pc.acts = acts; pc.all_ops = all_ops;
+    return true;
+}
+
+// the records of this flush on the device.  A hit's are still there unless something was uploaded in between; a miss uploads its
+// own, and only then is the entry that plan_cache_store made of it valid
+static int plan_records_resident(qcx_register *r, GateQueue *gq, bool hit, const std::vector<FuseOp> &all_ops, const Tune &tn)
+{
+    auto &pc = gq->pc;
+    if (hit) {
+        if (pc.stamp != gq->upload_stamp) { QCX_TRY(upload_ops(r, gq, pc.all_ops)); pc.stamp = gq->upload_stamp; }
+        return QCX_NO_ERROR;
+    }
+    QCX_TRY(upload_ops(r, gq, all_ops));
+    if (tn.fuse_plan_cache) { pc.stamp = gq->upload_stamp; pc.valid = true; }
+    return QCX_NO_ERROR;
+}
+
+// ---- launching -------------------------------------------------------------------------------------------------------------------
+// The register's second buffer, allocated on first use.  false: no room (n = 34 fills the card) -- in place from now on (no_chain)
+static bool second_buffer(qcx_register *r)
+{
+    if (r->scratch) return true;
+    if (hipMalloc(&r->scratch, r->dim * sizeof(amp_t)) == hipSuccess) return true;
+    (void)hipGetLastError();
+    r->scratch = nullptr; r->no_chain = 1;
+    return false;
+}
+
+// the record buffers are in use until everything launched on st so far is through (upload_ops waits for it)
+static int mark_records_in_use(GateQueue *gq, hipStream_t st)
+{
+    if (!gq->ev_valid) { HIP_TRY(hipEventCreateWithFlags(&gq->ev, hipEventDisableTiming)); gq->ev_valid = true; }
+    HIP_TRY(hipEventRecord(gq->ev, st));
+    return QCX_NO_ERROR;
+}
+
+// The actions of a plan, in order, on the register or view v (stand-alone gates: gates[act.gate]).  A chained pass goes out of
+// place into v's other buffer, which then IS v's state (a chain ends on the identity layout, and nothing between its passes looks
+// at the buffers).  last_out: where the last pass stores instead (the expanding store of a compact chain: the real register);
+// hold_last: the last action is not launched (a compact chain's deferred last pass).
+static int launch_actions(qcx_register *v, GateQueue *gq, const Tune &tn, const FuseAction *acts, size_t count, const std::vector<QGate> *gates,
+                          amp_t *last_out = nullptr, bool hold_last = false)
+{
+    for (size_t ai = 0; ai + (hold_last ? 1 : 0) < count; ai++) {
+        const FuseAction &act = acts[ai];
+        if (!act.fused) { QCX_TRY(launch_standalone(v, (*gates)[act.gate])); continue; }
+        amp_t *out = (last_out && ai + 1 == count) ? last_out : (act.P.chained ? v->scratch : v->amp);
+        QCX_TRY(launch_pass(v, tn, act.P, gq->d_ops + act.op_off, act.nopipe != 0, v->amp, out));
+        if (out == v->scratch) std::swap(v->amp, v->scratch);
+        if (act.P.chained) gq->chained_passes++;
+        gq->passes_launched++;
+        gq->gates_fused += act.ngates;
+    }
+    return QCX_NO_ERROR;
+}
+
 // the deferred last pass of a compact chain (compact_pending == 2, GateQueue::last): into_register: with the expanding store,
 // the state is then in r->amp (compact_pending = 0); otherwise as planned, the compact form is complete (compact_pending = 1)
-static int launch_pass(qcx_register *r, const Tune &tn, const FusePass &P_in, const FuseOp *d_ops, bool nopipe, amp_t *amp_in, amp_t *amp_out);
 static int compact_finish_last(qcx_register *r, bool into_register)
 {
     if (r->compact_pending != 2) return QCX_NO_ERROR;
     GateQueue *gq = r->queue;
     if (!gq) return QCX_UNKNOWN_ERROR;
-    qcx_register v;
-    memset(&v, 0, sizeof v);
-    v.L = (int)(gq->last.nv - gq->last.cb); v.M = (int)gq->last.cb; v.n = gq->last.nv; v.dim = (uint64_t)1 << gq->last.nv;
-    v.amp = gq->last.in; v.scratch = gq->last.out;
-    v.own_stream = r->own_stream; v.stream = r->stream; v.fusion = r->fusion;
-    if (into_register) {
-        QCX_TRY(launch_pass(&v, gq->last.tn, gq->last.Pxp, gq->d_ops + gq->last.op_off, gq->last.nopipe, gq->last.in, r->amp));
-        r->compact_pending = 0;
-        gq->expanding_stores++;
-    } else {
-        QCX_TRY(launch_pass(&v, gq->last.tn, gq->last.P, gq->d_ops + gq->last.op_off, gq->last.nopipe, gq->last.in, gq->last.out));
-        r->compact_amp = gq->last.out;
-        r->compact_pending = 1;
-    }
-    if (gq->last.P.chained) gq->chained_passes++;
-    gq->passes_launched++;
-    gq->gates_fused += gq->last.ngates;
-    if (!gq->ev_valid) { HIP_TRY(hipEventCreateWithFlags(&gq->ev, hipEventDisableTiming)); gq->ev_valid = true; }
-    HIP_TRY(hipEventRecord(gq->ev, r->stream));            // (the record buffers are in use until this pass is through)
-    return QCX_NO_ERROR;
+    const auto &last = gq->last;
+    qcx_register v = reg_view(last.nv - last.cb, last.cb, last.in, last.out, r->own_stream, r->stream, r->fusion);
+    QCX_TRY(launch_actions(&v, gq, last.tn, into_register ? &last.act_xp : &last.act, 1, nullptr, into_register ? r->amp : nullptr));
+    if (into_register) { r->compact_pending = 0; gq->expanding_stores++; }
+    else { r->compact_amp = v.amp; r->compact_pending = 1; }
+    return mark_records_in_use(gq, r->stream);
 }
 
 // the real register from a pending compact form
@@ -1625,159 +1783,102 @@ static bool xp_setup(FusePass &PL, unsigned M, unsigned cb, const std::vector<ui
     return true;
 }
 
-// keep: leave the result in its compact form (r->compact_pending; measure_state reads it there, everything else expands it first)
-static int compact_chain(qcx_register *r, GateQueue *gq, const Tune &tn, const BasisFront &Bf, size_t kfront, const std::vector<QGate> &gates, bool keep, bool *done)
-{
-    *done = false;
-    const unsigned M = (unsigned)r->M, n = r->n, L = n - M;
-    if (!tn.fuse_compact || !tn.fuse_gen_cols || !tn.fuse_chain || !tn.fuse_ldsdma || tn.fuse_rounds_occ < 6 || !tn.fuse_rounds) return QCX_NO_ERROR;
-    if (M < 4 || M > 12 || r->no_chain || !r->own_stream || Bf.first != 0 || gates.empty()) return QCX_NO_ERROR;
-    const uint32_t lowmask = (1u << M) - 1u;
-    if ((Bf.hmask & lowmask) != 0 || Bf.ncam > 64) return QCX_NO_ERROR;
-    for (const QGate &g : gates) {
-        if (g.type == FUSE_H) { if (g.q < M) return QCX_NO_ERROR; }
-        else if (g.type == FUSE_PHASE) { if (g.mask & lowmask) return QCX_NO_ERROR; }
-        else return QCX_NO_ERROR;
-    }
+// first_cols of fuse_plan for the virtual register of a compact chain: the first pass by columns; 2: it may keep merged diagonals
+static int compact_first_cols(const Tune &tn, bool tol) { return (tol && tn.fuse_cols_tol) ? 2 : 1; }
+
+// the plan of a compact chain: the virtual register's gates, actions and records (GenFront of the first pass included)
+struct CompactPlan {
+    bool     hit = false;               // from the plan cache: all_ops stays empty (GateQueue::pc holds the records)
+    unsigned cb = 0, nv = 0;            // column bits; qubits of the virtual register
     std::vector<uint16_t> orbit;
-    unsigned cb = 0;
-    // (the plan cache, GateQueue::pc: the same front and the same gate list under the same knobs as the last chain -- the next
-    //  attempt of a period-finding run -- take orbit, actions and records from there)
-    const bool hit = tn.fuse_plan_cache && gq->pc.valid && gq->pc.kind == 2 && gq->pc.n == n && gq->pc.M == M && gq->pc.fusion == r->fusion
-                     && gq->pc.kfront == kfront && memcmp(&gq->pc.tn, &tn, sizeof tn) == 0 && memcmp(&gq->pc.Bf, &Bf, sizeof Bf) == 0
-                     && same_gate_list(gq->pc.gates, gates);
-    if (hit) { orbit = gq->pc.orbit; cb = gq->pc.cb; }
-    else if (!compact_orbit(Bf, M, orbit, &cb)) return QCX_NO_ERROR;
-    const uint32_t Cn = Bf.ncam ? Bf.C[0] : 0u, f0 = (uint32_t)(Bf.basis & lowmask);
-    const unsigned nv = L + cb;
-    if (nv < 14 || L < 8) return QCX_NO_ERROR;
-    // the virtual register's gate list
-    std::vector<QGate> vg(gates);
-    for (QGate &g : vg) { if (g.type == FUSE_H) g.q -= M - cb; else g.mask >>= (M - cb); }
-    if (!r->scratch) {
-        if (hipMalloc(&r->scratch, r->dim * sizeof(amp_t)) != hipSuccess) { (void)hipGetLastError(); r->scratch = nullptr; r->no_chain = 1; return QCX_NO_ERROR; }
-    }
-    qcx_register v;
-    memset(&v, 0, sizeof v);
-    v.L = (int)L; v.M = (int)cb; v.n = nv; v.dim = (uint64_t)1 << nv;
-    v.amp = r->scratch; v.scratch = r->scratch + v.dim;             // (2 * 2^nv <= 2^n amplitudes: cb + 1 <= M)
-    v.own_stream = r->own_stream; v.stream = r->stream; v.fusion = r->fusion;
+    std::vector<QGate> vg;
     std::vector<FuseAction> acts;
     std::vector<FuseOp> all_ops;
-    if (hit) { acts = gq->pc.acts; gq->plan_hits++; }
+    bool     xp = false;                // the last pass can store the real register itself (xp_setup) ...
+    FusePass Pxp;                       // ... and looks like this when it does
+};
+
+// The planning half of a compact chain: does the flush `gates` behind the front Bf qualify, and as what.  No HIP call.
+// (the plan cache: the same front and the same gate list under the same knobs as the last chain -- the next attempt of a
+//  period-finding run -- take orbit, actions and records from there)
+static bool compact_chain_plan(const qcx_register *r, const GateQueue *gq, const Tune &tn, const PlanKey &key, const BasisFront &Bf,
+                               const std::vector<QGate> &gates, CompactPlan &cp)
+{
+    const unsigned M = (unsigned)r->M, n = r->n, L = n - M;
+    if (!tn.fuse_compact || !tn.fuse_gen_cols || !tn.fuse_chain || !tn.fuse_ldsdma || tn.fuse_rounds_occ < 6 || !tn.fuse_rounds) return false;
+    if (M < 4 || M > 12 || r->no_chain || !r->own_stream || Bf.first != 0 || gates.empty() || !leaves_m_alone(gates, M, true)) return false;
+    cp.hit = plan_cache_hit(gq, key);
+    if (cp.hit) { cp.orbit = gq->pc.orbit; cp.cb = gq->pc.cb; }
+    else if (!compact_orbit(Bf, M, cp.orbit, &cp.cb)) return false;
+    const unsigned cb = cp.cb;
+    cp.nv = L + cb;
+    if (cp.nv < 14 || L < 8) return false;
+    cp.vg = gates;                                   // the virtual register's gate list
+    for (QGate &g : cp.vg) { if (g.type == FUSE_H) g.q -= M - cb; else g.mask >>= (M - cb); }
+    if (cp.hit) cp.acts = gq->pc.acts;
     else {
-    fuse_plan(&v, tn, vg, acts, all_ops, r->fusion == 2, true, (r->fusion == 2 && tn.fuse_cols_tol) ? 2 : 1);
-    if (acts.empty() || !acts[0].fused) return QCX_NO_ERROR;
-    {
-        const FusePass &P0 = acts[0].P;
-        if (P0.T != cb + 8 || P0.c != cb || P0.cam_ctl_local[0] != 1 || P0.has_cam || P0.dg_slim == 2 || P0.dg_cnt > 64) return QCX_NO_ERROR;
-        for (unsigned j = 0; j < cb; j++) if (acts[0].tl[j] != j) return QCX_NO_ERROR;
-        for (unsigned j = cb; j < cb + 8; j++) if (acts[0].tl[j] < cb) return QCX_NO_ERROR;
-        for (size_t o = acts[0].op_off; o < acts[0].op_off + P0.nops; ) {
-            const FuseOp &hdr = all_ops[o];
-            const uint32_t ty = hdr.type & 0xffu;
-            if ((ty != FUSE_ROUND && !(ty == FUSE_QROUND && P0.dg_cnt)) || (hdr.a & 0xffu) < cb || ((hdr.a >> 8) & 0xffu) < cb) return QCX_NO_ERROR;
-            o += 1 + (size_t)hdr.mask;
-        }
-    }
-    // (columns beyond the orbit hold nothing -- 2 of 8 for the six residues of N = 21 -- but letting the waves that sit on them
-    //  skip the rounds of the later passes, zskip_setup, does not pay: 2.50 / 2.09 ms against 2.28 / 1.96 for the two 2^10-tile
-    //  passes at n = 30: the busy waves are a tile's critical path either way, and the lanes' stride costs bank conflicts)
-    // the generated fill of the first pass, in REAL qubit numbers (its controls, fixed bits and signs), by hot slot
-    GenFront G;
-    memset(&G, 0, sizeof G);
-    {
-        uint64_t tilemask = lowmask;
+        const qcx_register v = reg_view(L, cb, nullptr, nullptr, r->own_stream, r->stream, r->fusion);
+        fuse_plan(&v, tn, cp.vg, cp.acts, cp.all_ops, r->fusion == 2, true, compact_first_cols(tn, r->fusion == 2));
+        if (!cols_shape_ok(cp.acts, cp.all_ops, cb, cb, true)) return false;
+        // (columns beyond the orbit hold nothing -- 2 of 8 for the six residues of N = 21 -- but letting the waves that sit on them
+        //  skip the rounds of the later passes, zskip_setup, does not pay: 2.50 / 2.09 ms against 2.28 / 1.96 for the two 2^10-tile
+        //  passes at n = 30: the busy waves are a tile's critical path either way, and the lanes' stride costs bank conflicts)
+        // the generated fill of the first pass, in REAL qubit numbers (its controls, fixed bits and signs), by hot slot: the tile
+        // holds the whole M register
+        FuseAction &a0 = cp.acts[0];
+        GenFront G;
+        uint64_t tilemask = ((uint64_t)1 << M) - 1;
         int slot_of[64];
         for (unsigned q = 0; q < 64; q++) slot_of[q] = -1;
-        for (unsigned j = cb; j < cb + 8; j++) {
-            const unsigned rq = acts[0].tl[j] - cb + M, slot = j - cb;
-            slot_of[rq] = (int)slot; tilemask |= (uint64_t)1 << rq;
-            if ((Bf.sign_mask >> rq) & 1u) G.sgn_slots |= 1u << slot;
-            if ((Bf.fixed_mask >> rq) & 1u) { G.sfm |= 1u << slot; G.sbv |= (uint32_t)((Bf.basis >> rq) & 1u) << slot; }
-        }
-        G.basis = Bf.basis; G.fixed_out = Bf.fixed_mask & ~tilemask; G.sign_out = Bf.sign_mask & ~tilemask;
-        G.v = Bf.v; G.M = M; G.ncam = Bf.ncam; G.C = Bf.ncam ? Cn : 0u; G.f0 = f0;
-        G.Cinv = G.C ? (uint32_t)(((uint64_t)1 << 32) / G.C) : 0u;
-        G.cmpmask = lowmask; G.lowout_mask = 0; G.h = 8;
-        for (unsigned f = 0; f < 5; f++) for (unsigned b = 0; b < 256; b++) G.tabP[f][b] = 1;
-        for (unsigned g = 0; g < Bf.ncam; g++) {
-            const unsigned ctl = Bf.ctl[g];
-            G.camA[g] = Bf.A[g] % Cn;
-            if (ctl >= 40 || ctl < M) return QCX_NO_ERROR;
-            if (slot_of[ctl] >= 0) { G.camloc[g] = (uint8_t)slot_of[ctl]; continue; }
-            G.camloc[g] = 0xff;
-            const unsigned f = ctl >> 3, bit = ctl & 7u;
-            G.present |= 1u << f;
-            for (unsigned b = 0; b < 256; b++)
-                if ((b >> bit) & 1u) G.tabP[f][b] = (uint16_t)(((uint32_t)G.tabP[f][b] * G.camA[g]) % Cn);
-        }
-        G.cb = cb; G.ncols = (uint32_t)orbit.size();
-        for (size_t j = 0; j < orbit.size(); j++) G.orbit[j] = orbit[j];
-    }
-    {
-        const size_t at = all_ops.size(), nrec = (sizeof(GenFront) + sizeof(FuseOp) - 1) / sizeof(FuseOp);
-        all_ops.resize(at + nrec);
-        memset(&all_ops[at], 0, nrec * sizeof(FuseOp));
-        memcpy(&all_ops[at], &G, sizeof G);
-        acts[0].P.gen = 3;
-        acts[0].P.gen_tab_bytes = (uint32_t)(((G.C ? G.C : (1u << M)) + 15u) & ~15u);
-        acts[0].P.zpad = (uint16_t)orbit.size();
-        acts[0].P.zskip = 0;
-        acts[0].P.gen_rec_off = (uint32_t)(at - acts[0].op_off);
-    }
-    gq->pc.valid = false;
-    if (tn.fuse_plan_cache) {               // (valid once the records are uploaded, below)
-        gq->pc.kind = 2; gq->pc.n = n; gq->pc.M = M; gq->pc.fusion = r->fusion; gq->pc.chain = true; gq->pc.tn = tn; gq->pc.Bf = Bf; gq->pc.kfront = kfront;
-        gq->pc.gates = gates; gq->pc.acts = acts; gq->pc.all_ops = all_ops; gq->pc.orbit = orbit; gq->pc.cb = cb;
-    }
+        for (unsigned j = cb; j < cb + 8; j++) { const unsigned rq = a0.tl[j] - cb + M; slot_of[rq] = (int)(j - cb); tilemask |= (uint64_t)1 << rq; }
+        if (!gen_front_fill(n, M, Bf, slot_of, tilemask, &G)) return false;
+        G.h = 8; G.cb = cb; G.ncols = (uint32_t)cp.orbit.size();
+        for (size_t j = 0; j < cp.orbit.size(); j++) G.orbit[j] = cp.orbit[j];
+        for (unsigned j = cb; j < cb + 8; j++) if ((Bf.sign_mask >> (a0.tl[j] - cb + M)) & 1u) G.sgn_slots |= 1u << (j - cb);
+        gen_front_append(cp.all_ops, a0, G);
+        a0.P.gen = 3;
+        a0.P.gen_tab_bytes = (uint32_t)(((G.C ? G.C : (1u << M)) + 15u) & ~15u);
+        a0.P.zpad = (uint16_t)cp.orbit.size();
+        a0.P.zskip = 0;
     }
     // Round 5: when the chain's last pass is a k_fused_x8 pass whose tile holds the column bits, that pass can store the REAL
     // register itself (FusePass::xp_on) -- k_expand_compact's extra read and write of the compact form (8.6 of its 21.5 GB at
-    // n = 30, M = 5) disappear.  keep = false: it does.  keep = true (a whole-circuit entry point: measure_state may come next and
-    // wants the compact form): the last pass is DEFERRED (GateQueue::last, compact_pending = 2) until somebody looks.
-    // (The last pass of a plan always stores the identity layout.)
-    bool expanded = false, deferred = false;
-    if (tn.fuse_expand_fused && acts.size() > 1 && acts.back().fused && pass_is_x8(acts.back().P, tn) && M <= 9 && cb <= 4) {
-        FusePass PL = acts.back().P;
-        if (xp_setup(PL, M, cb, orbit)) {
-            if (keep) {
-                deferred = true;
-                gq->last.P = acts.back().P; gq->last.Pxp = PL;
-                gq->last.op_off = acts.back().op_off; gq->last.nopipe = acts.back().nopipe != 0; gq->last.ngates = acts.back().ngates;
-                gq->last.nv = nv; gq->last.cb = cb; gq->last.tn = tn;
-            } else { acts.back().P = PL; expanded = true; }
-        }
+    // n = 30, M = 5) disappear.  (The last pass of a plan always stores the identity layout.)
+    if (tn.fuse_expand_fused && cp.acts.size() > 1 && cp.acts.back().fused && pass_is_x8(cp.acts.back().P, tn) && M <= 9 && cb <= 4) {
+        cp.Pxp = cp.acts.back().P;
+        cp.xp = xp_setup(cp.Pxp, M, cb, cp.orbit);
     }
-    if (hit) {
-        if (gq->pc.stamp != gq->upload_stamp) { QCX_TRY(upload_ops(r, gq, gq->pc.all_ops)); gq->pc.stamp = gq->upload_stamp; }
-    } else {
-        QCX_TRY(upload_ops(r, gq, all_ops));
-        if (tn.fuse_plan_cache) { gq->pc.stamp = gq->upload_stamp; gq->pc.valid = true; }
+    return true;
+}
+
+// The launching half.  keep: leave the result in its compact form (r->compact_pending; measure_state reads it there, everything
+// else expands it first).  *done = false: not applicable, nothing was launched -- but no_chain may be set: no room for the second buffer.
+static int compact_chain(qcx_register *r, GateQueue *gq, const Tune &tn, const BasisFront &Bf, size_t kfront, const std::vector<QGate> &gates, bool keep, bool *done)
+{
+    *done = false;
+    const unsigned M = (unsigned)r->M;
+    const PlanKey key = { 2, r->n, M, r->fusion, true, true, true, kfront, &tn, &Bf, &gates };
+    CompactPlan cp;
+    if (!compact_chain_plan(r, gq, tn, key, Bf, gates, cp) || !second_buffer(r)) return QCX_NO_ERROR;
+    qcx_register v = reg_view(cp.nv - cp.cb, cp.cb, r->scratch, r->scratch + ((uint64_t)1 << cp.nv), r->own_stream, r->stream, r->fusion);   // (2 * 2^nv <= 2^n amplitudes: cb + 1 <= M)
+    if (cp.hit) gq->plan_hits++;
+    else if (plan_cache_store(gq, key, cp.acts, cp.all_ops)) { gq->pc.orbit = cp.orbit; gq->pc.cb = cp.cb; }
+    // the last pass with the expanding store: at once, or -- keep (a whole-circuit entry point: measure_state may come next and
+    // wants the compact form) -- DEFERRED (GateQueue::last, compact_pending = 2) until somebody looks
+    const bool expanded = cp.xp && !keep, deferred = cp.xp && keep;
+    if (deferred) {
+        gq->last.act = gq->last.act_xp = cp.acts.back();
+        gq->last.act_xp.P = cp.Pxp;
+        gq->last.nv = cp.nv; gq->last.cb = cp.cb; gq->last.tn = tn;
     }
-    for (size_t ai = 0; ai < acts.size(); ai++) {
-        const FuseAction &act = acts[ai];
-        if (!act.fused) { QCX_TRY(launch_standalone(&v, vg[act.gate])); continue; }
-        if (deferred && ai + 1 == acts.size()) {
-            gq->last.in = v.amp; gq->last.out = act.P.chained ? v.scratch : v.amp;
-            break;
-        }
-        if (act.P.xp_on) {
-            QCX_TRY(launch_pass(&v, tn, act.P, gq->d_ops + act.op_off, act.nopipe != 0, v.amp, r->amp));
-            if (act.P.chained) gq->chained_passes++;
-        } else if (act.P.chained) {
-            QCX_TRY(launch_pass(&v, tn, act.P, gq->d_ops + act.op_off, act.nopipe != 0, v.amp, v.scratch));
-            std::swap(v.amp, v.scratch);
-            gq->chained_passes++;
-        } else
-            QCX_TRY(launch_pass(&v, tn, act.P, gq->d_ops + act.op_off, act.nopipe != 0, v.amp, v.amp));
-        gq->passes_launched++;
-        gq->gates_fused += act.ngates;
-    }
+    if (expanded) cp.acts.back().P = cp.Pxp;
+    QCX_TRY(plan_records_resident(r, gq, cp.hit, cp.all_ops, tn));
+    QCX_TRY(launch_actions(&v, gq, tn, cp.acts.data(), cp.acts.size(), &cp.vg, expanded ? r->amp : nullptr, deferred));
+    if (deferred) { gq->last.in = v.amp; gq->last.out = cp.acts.back().P.chained ? v.scratch : v.amp; }
     if (expanded) { r->compact_pending = 0; gq->expanding_stores++; }
     else {
         r->compact_pending = deferred ? 2 : 1;
-        r->compact_amp = v.amp; r->compact_E = compact_params(M, cb, orbit.data(), (unsigned)orbit.size());
+        r->compact_amp = v.amp; r->compact_E = compact_params(M, cp.cb, cp.orbit.data(), (unsigned)cp.orbit.size());
         if (!keep) QCX_TRY(expand_pending(r));
     }
     r->basis_pending = 0;
@@ -1785,33 +1886,34 @@ static int compact_chain(qcx_register *r, GateQueue *gq, const Tune &tn, const B
     r->fronts++;
     gq->gen_fronts++; gq->gen_cols++; gq->compact_chains++;
     gq->gates_fused += kfront;
-    if (!gq->ev_valid) { HIP_TRY(hipEventCreateWithFlags(&gq->ev, hipEventDisableTiming)); gq->ev_valid = true; }
-    HIP_TRY(hipEventRecord(gq->ev, r->stream));
+    QCX_TRY(mark_records_in_use(gq, r->stream));
     *done = true;
     return QCX_NO_ERROR;
 }
 
-// plan -> upload every pass's records in one copy -> launch in order.  No host synchronisation except waiting for
+// settle -> front -> plan or cache hit -> records in one upload -> launch in order.  No host synchronisation except waiting for
 // the PREVIOUS flush's kernels before its record buffers are reused.
 static int fuse_flush(qcx_register *r, bool keep_compact = false)
 {
     GateQueue *gq = r->queue;
     const Tune tn = tune_now();
-    if (r->compact_pending) {                    // an earlier flush left the state compact
+    const unsigned M = (unsigned)r->M;
+    // ---- settle what is pending: an earlier flush left the state compact
+    if (r->compact_pending) {
         if (keep_compact && (!gq || gq->gates.empty()) && !r->basis_pending) return QCX_NO_ERROR;
         if (r->basis_pending) r->compact_pending = 0;       // (a reset / collapse came after it: the compact form is history)
         else QCX_TRY(expand_pending(r));
     }
-    // A lazily pending reset / collapse: the register IS a basis state that has not been written.  The closed-form front of
-    // the queue (Hadamards, then the multiply ladder) is either written by a pass of its own (K0b) or -- when a fused pass
-    // follows it -- generated tile by tile inside that pass (GenFront): no write pass, and that pass reads nothing.
+    // ---- the front.  A lazily pending reset / collapse: the register IS a basis state that has not been written.  The closed-form
+    // front of the queue (Hadamards, then the multiply ladder) is either written by a pass of its own (K0b) or -- when a fused
+    // pass follows it -- generated tile by tile inside that pass (GenFront): no write pass, and that pass reads nothing.
     bool gen_try = false;
     const bool front_flush = r->basis_pending != 0;
     BasisFront Bf;
     size_t kfront = 0;
     if (r->basis_pending) {
         if (gq && !gq->gates.empty() && tn.fuse_gen && r->own_stream && r->n >= 12) {
-            kfront = front_plan(r->n, (unsigned)r->M, r->basis_index, tn, gq->gates, &Bf);
+            kfront = front_plan(r->n, M, r->basis_index, tn, gq->gates, &Bf);
             gen_try = gq->gates.size() > kfront;
         }
         if (!gen_try) {
@@ -1825,156 +1927,72 @@ static int fuse_flush(qcx_register *r, bool keep_compact = false)
     if (r->own_stream && !gen_try) QCX_TRY(canon_if_dirty(r));      // gates are about to run on a state the caller wrote (a shard view: its host's business)
     std::vector<QGate> gates;
     gates.swap(gq->gates);                       // the queue is empty from here on (re-entrancy safe)
-    if (gen_try) gates.erase(gates.begin(), gates.begin() + kfront);
-    if (gen_try) {                                // the whole flush on a compact copy of the state, when the front allows it
+    if (gen_try) {                               // the whole flush on a compact copy of the state, when the front allows it
+        gates.erase(gates.begin(), gates.begin() + kfront);
         bool done = false;
         QCX_TRY(compact_chain(r, gq, tn, Bf, kfront, gates, keep_compact && tn.fuse_compact_lazy, &done));
         if (done) return QCX_NO_ERROR;
     }
+    // ---- plan, or cache hit (a flush whose inputs are those of the last one -- the front it stands behind included).  Chains of
+    // passes go through the register's second buffer (a register whose buffer pointer has been handed out, a shard view and a
+    // register too large for a second buffer work in place)
+    const bool chain = tn.fuse_chain && r->own_stream && !r->no_chain && r->n >= (unsigned)std::max<long>(tn.fuse_chain_min_n, 13);
+    const PlanKey key = { 1, r->n, M, r->fusion, chain, front_flush, gen_try, kfront, &tn, &Bf, &gates };
     std::vector<FuseAction> acts;
     std::vector<FuseOp> all_ops;
-    // chains of passes go through the register's second buffer (allocated on first use; a register whose buffer pointer has
-    // been handed out, a shard view and a register too large for a second buffer work in place)
-    bool chain = tn.fuse_chain && r->own_stream && !r->no_chain && r->n >= (unsigned)std::max<long>(tn.fuse_chain_min_n, 13);
-    // The generated first pass by columns (K6g): possible when nothing of the list touches the M register (>= 4 qubits), the front
-    // left it on the orbit of ONE multiplier ladder, and that orbit populates at most 8 of the 16 values of the four lowest
-    // M-register bits per value of the others (the columns a workgroup keeps in LDS).  maxcols = that bound.
     unsigned maxcols = 0;
-    if (gen_try && tn.fuse_gen_cols && r->M >= 4 && r->M <= 12 && r->n >= 14 && tn.fuse_ldsdma && tn.fuse_rounds_occ >= 6) {
-        const uint32_t lowmask = (1u << r->M) - 1u;
-        bool ok = (Bf.hmask & lowmask) == 0 && Bf.ncam <= 64;
-        for (const QGate &g : gates) ok &= !((g.type == FUSE_H && g.q < (unsigned)r->M) || g.type == FUSE_CAMODC || g.type == 99);
-        const uint32_t Cn = Bf.ncam ? Bf.C[0] : 0u, f0 = (uint32_t)(Bf.basis & lowmask);
-        for (unsigned g = 0; g < Bf.ncam && ok; g++) ok &= Bf.C[g] == Cn;
-        if (Bf.ncam) ok &= Cn > 0 && Cn <= 4096u && f0 < Cn;
-        if (ok && !Bf.ncam) maxcols = 1;                            // no multiplies: every populated block holds f0
-        else if (ok) {
-            std::vector<char> seen(Cn, 0);
-            std::vector<uint32_t> todo(1, f0);
-            seen[f0] = 1;
-            while (!todo.empty()) {                                 // closure under every multiplier: a superset of the subset products
-                const uint32_t x = todo.back(); todo.pop_back();
-                for (unsigned g = 0; g < Bf.ncam; g++) { const uint32_t y = (uint32_t)(((uint64_t)x * (Bf.A[g] % Cn)) % Cn); if (!seen[y]) { seen[y] = 1; todo.push_back(y); } }
-            }
-            std::vector<uint16_t> colsets(((size_t)lowmask >> 4) + 1, 0);
-            for (uint32_t x = 0; x < Cn; x++) if (seen[x] && x <= lowmask) colsets[x >> 4] |= (uint16_t)(1u << (x & 15u));
-            for (uint16_t s : colsets) maxcols = std::max(maxcols, (unsigned)__builtin_popcount(s));
-            if (maxcols > 8) maxcols = 0;
-        }
-    }
-    auto cols_shape_ok = [&]() {
-        if (acts.empty() || !acts[0].fused) return false;
-        const FusePass &P0 = acts[0].P;
-        if (P0.T != 12 || P0.c != 4 || P0.cam_ctl_local[0] != 1 || P0.has_cam || P0.dg_cnt || P0.dg_slim) return false;
-        for (unsigned j = 0; j < 4; j++) if (acts[0].tl[j] != j) return false;
-        for (unsigned j = 4; j < 12; j++) if (acts[0].tl[j] < (unsigned)r->M) return false;
-        for (size_t o = acts[0].op_off; o < acts[0].op_off + P0.nops; ) {
-            const FuseOp &hdr = all_ops[o];
-            if ((hdr.type & 0xffu) != FUSE_ROUND || (hdr.a & 0xffu) < 4 || ((hdr.a >> 8) & 0xffu) < 4) return false;
-            o += 1 + (size_t)hdr.mask;
-        }
-        return true;
-    };
-    // (the plan cache, GateQueue::pc: a flush whose inputs are those of the last one -- the front it stands behind included --
-    //  takes its plan from there)
-    const bool cacheable = tn.fuse_plan_cache != 0;
     bool hit = false;
-    if (cacheable && gq->pc.valid && gq->pc.kind == 1 && gq->pc.n == r->n && gq->pc.M == (unsigned)r->M && gq->pc.fusion == r->fusion && gq->pc.chain == chain
-        && gq->pc.front_flush == front_flush && gq->pc.gen_try == gen_try
-        && (!gen_try || (gq->pc.kfront == kfront && memcmp(&gq->pc.Bf, &Bf, sizeof Bf) == 0))
-        && memcmp(&gq->pc.tn, &tn, sizeof tn) == 0 && same_gate_list(gq->pc.gates, gates)) {
+    if (plan_cache_hit(gq, key)) {
         bool needs_scratch = false;
         for (const FuseAction &a : gq->pc.acts) needs_scratch |= a.fused && a.P.chained;
         hit = !needs_scratch || r->scratch;
     }
-    if (hit) { acts = gq->pc.acts; all_ops.clear(); gq->plan_hits++; }
+    if (hit) { acts = gq->pc.acts; gq->plan_hits++; }
     else {
-    fuse_plan(r, tn, gates, acts, all_ops, r->fusion == 2, chain, maxcols != 0);
-    if (maxcols && !cols_shape_ok()) { maxcols = 0; acts.clear(); all_ops.clear(); fuse_plan(r, tn, gates, acts, all_ops, r->fusion == 2, chain); }
-    }
-    bool chained_any = false;
-    for (const FuseAction &a : acts) chained_any |= a.fused && a.P.chained;
-    if (chained_any && !r->scratch) {
-        if (hipMalloc(&r->scratch, r->dim * sizeof(amp_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            r->scratch = nullptr; r->no_chain = 1;                 // no room (n = 34 fills the card): in place from now on
+        const bool m_alone = front_flush && leaves_m_alone(gates, M, false);
+        // The generated first pass by columns (K6g): possible when nothing of the list touches the M register (>= 4 qubits) and the
+        // front left it on the orbit of ONE multiplier ladder that populates few enough columns (cols_bound)
+        if (gen_try && m_alone && tn.fuse_gen_cols && M >= 4 && M <= 12 && r->n >= 14 && tn.fuse_ldsdma && tn.fuse_rounds_occ >= 6) maxcols = cols_bound(Bf, M);
+        auto plan = [&](bool ch) {
             acts.clear(); all_ops.clear();
-            fuse_plan(r, tn, gates, acts, all_ops, r->fusion == 2, false, maxcols != 0);
-            if (maxcols && !cols_shape_ok()) { maxcols = 0; acts.clear(); all_ops.clear(); fuse_plan(r, tn, gates, acts, all_ops, r->fusion == 2, false); }
-        }
+            fuse_plan(r, tn, gates, acts, all_ops, r->fusion == 2, ch, maxcols != 0);
+            if (maxcols && !cols_shape_ok(acts, all_ops, 4, M, false)) { maxcols = 0; acts.clear(); all_ops.clear(); fuse_plan(r, tn, gates, acts, all_ops, r->fusion == 2, ch); }
+        };
+        plan(chain);
+        bool chained_any = false;
+        for (const FuseAction &a : acts) chained_any |= a.fused && a.P.chained;
+        if (chained_any && !second_buffer(r)) plan(false);
+        // Behind a circuit front only a few of the 2^M low index values are populated (the multiply ladder's orbit), and no gate of
+        // an inverse QFT touches the M register: whole waves of a tile hold nothing but +0.  Passes of such a flush map their wave
+        // number onto M-register bits of the tile and let all-zero waves skip the rounds (FusePass::zskip; found at run time, so
+        // any state is handled correctly)
+        if (m_alone && tn.fuse_zskip && M >= 2) zskip_setup(acts, all_ops, M, tn, maxcols != 0);
     }
-    // Behind a circuit front only a few of the 2^M low index values are populated (the multiply ladder's orbit), and no gate of
-    // an inverse QFT touches the M register: whole waves of a tile hold nothing but +0.  Passes of such a flush map their wave
-    // number onto M-register bits of the tile and let all-zero waves skip the rounds (FusePass::zskip; found at run time, so
-    // any state is handled correctly)
-    if (!hit && front_flush && tn.fuse_zskip && r->M >= 2) {
-        bool h_on_m = false;
-        for (const QGate &g : gates) h_on_m |= (g.type == FUSE_H && g.q < (unsigned)r->M) || g.type == FUSE_CAMODC || g.type == 99;
-        if (!h_on_m) zskip_setup(acts, all_ops, (unsigned)r->M, tn, maxcols != 0);
-    }
+    // ---- the front again: generated inside the first pass, or written by a pass of its own (a hit: what the cached flush did)
     bool gen_built = false, gen2 = false;
-    if (gen_try && hit) {                            // what the cached flush did with its front, again
-        if (gq->pc.gen_built) {
-            r->basis_pending = 0; r->fronts++; gq->gen_fronts++; r->zeros_dirty = 0;
-            if (gq->pc.gen2) gq->gen_cols++;
-        } else {
-            QCX_TRY(launch_front(r, Bf, kfront));
-            r->zeros_dirty = 0;
-        }
-        gq->gates_fused += kfront;
-    } else if (gen_try) {
+    if (gen_try) {
         GenFront G;
-        if (!acts.empty() && gen_front_build(r->n, (unsigned)r->M, Bf, acts[0], &G)) {
+        if (hit) { gen_built = gq->pc.gen_built; gen2 = gq->pc.gen2; }
+        else if (!acts.empty() && gen_front_build(r->n, M, Bf, acts[0], &G)) {
             gen_built = true;
-            const size_t at = all_ops.size(), nrec = (sizeof(GenFront) + sizeof(FuseOp) - 1) / sizeof(FuseOp);
-            all_ops.resize(at + nrec);
-            memset(&all_ops[at], 0, nrec * sizeof(FuseOp));
-            memcpy(&all_ops[at], &G, sizeof G);
+            gen_front_append(all_ops, acts[0], G);
             acts[0].P.gen = 1;
-            if (maxcols && G.cmpmask == (1u << r->M) - 1u && G.h == 8) { acts[0].P.gen = 2; acts[0].P.zpad = (uint16_t)maxcols; gq->gen_cols++; gen2 = true; }
-            acts[0].P.gen_rec_off = (uint32_t)(at - acts[0].op_off);
+            if (maxcols && G.cmpmask == (1u << M) - 1u && G.h == 8) { acts[0].P.gen = 2; acts[0].P.zpad = (uint16_t)maxcols; gen2 = true; }
+        }
+        if (gen_built) {
             r->basis_pending = 0;                                 // (the pass that generates it is launched below; a failed launch returns its error)
             r->fronts++;
             gq->gen_fronts++;
-            r->zeros_dirty = 0;
-        } else {
-            QCX_TRY(launch_front(r, Bf, kfront));                 // the separate write pass after all
-            r->zeros_dirty = 0;
-        }
+            if (gen2) gq->gen_cols++;
+        } else QCX_TRY(launch_front(r, Bf, kfront));              // the separate write pass after all
+        r->zeros_dirty = 0;
         gq->gates_fused += kfront;
     }
-    if (hit) {
-        // the cached records: still on the device unless something was uploaded in between
-        if (gq->pc.stamp != gq->upload_stamp) { QCX_TRY(upload_ops(r, gq, gq->pc.all_ops)); gq->pc.stamp = gq->upload_stamp; }
-    } else {
-        QCX_TRY(upload_ops(r, gq, all_ops));
-        gq->pc.valid = false;
-        if (cacheable) {
-            gq->pc.kind = 1; gq->pc.n = r->n; gq->pc.M = (unsigned)r->M; gq->pc.fusion = r->fusion; gq->pc.chain = chain; gq->pc.tn = tn;
-            gq->pc.front_flush = front_flush; gq->pc.gen_try = gen_try; gq->pc.gen_built = gen_built; gq->pc.gen2 = gen2;
-            if (gen_try) { gq->pc.Bf = Bf; gq->pc.kfront = kfront; }
-            gq->pc.gates = gates; gq->pc.acts = acts; gq->pc.all_ops = all_ops; gq->pc.stamp = gq->upload_stamp;
-            gq->pc.valid = true;
-        }
-    }
-    const bool any_records = hit ? !gq->pc.all_ops.empty() : !all_ops.empty();
-    for (const FuseAction &act : acts) {
-        if (!act.fused) { QCX_TRY(launch_standalone(r, gates[act.gate])); continue; }
-        if (act.P.chained) {
-            // out of place into the other buffer, which then IS the register's state (a chain ends on the identity layout, and
-            // nothing between its passes looks at the buffers)
-            QCX_TRY(launch_pass(r, tn, act.P, gq->d_ops + act.op_off, act.nopipe != 0, r->amp, r->scratch));
-            std::swap(r->amp, r->scratch);
-            gq->chained_passes++;
-        } else
-            QCX_TRY(launch_pass(r, tn, act.P, gq->d_ops + act.op_off, act.nopipe != 0, r->amp, r->amp));
-        gq->passes_launched++;
-        gq->gates_fused += act.ngates;
-    }
-    if (any_records) {
-        if (!gq->ev_valid) { HIP_TRY(hipEventCreateWithFlags(&gq->ev, hipEventDisableTiming)); gq->ev_valid = true; }
-        HIP_TRY(hipEventRecord(gq->ev, r->stream));
-    }
+    // ---- records, launch
+    if (!hit && plan_cache_store(gq, key, acts, all_ops)) { gq->pc.gen_built = gen_built; gq->pc.gen2 = gen2; }
+    QCX_TRY(plan_records_resident(r, gq, hit, all_ops, tn));
+    QCX_TRY(launch_actions(r, gq, tn, acts.data(), acts.size(), &gates));
+    if (hit ? !gq->pc.all_ops.empty() : !all_ops.empty()) QCX_TRY(mark_records_in_use(gq, r->stream));
     return QCX_NO_ERROR;
 }
 

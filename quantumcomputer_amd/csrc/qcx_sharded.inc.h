@@ -628,8 +628,6 @@ static int sh_compact(ShardSet *sh, bool *done)
     BasisFront B;
     const size_t used = front_plan(sh->n, M, 1, tn, qg, &B);
     if (!used || used >= sh->queue.size()) return QCX_NO_ERROR;
-    const uint32_t lowmask = (1u << M) - 1u;
-    if ((B.hmask & lowmask) != 0 || B.ncam > 64) return QCX_NO_ERROR;
     for (size_t i = used; i < sh->queue.size(); i++) {
         const SGate &g = sh->queue[i];
         if (g.type == FUSE_H) { if (g.q < M) return QCX_NO_ERROR; }

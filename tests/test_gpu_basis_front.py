@@ -363,3 +363,45 @@ def test_compact_chain_under_random_programs(qc, ob, seed, mode):
                 assert float(np.max(np.abs(got - want))) <= 1e-12, (seed, batch)
             if batch == 0 and L + max(2, (len({pow(a, e, C) for e in range(4 * C)}) - 1).bit_length()) >= 14:
                 assert _compact(qc, reg) - k0 == 1, "the first flush ran as a compact chain"
+
+
+def _plan_hits(qc, reg):
+    import ctypes as C
+    out = C.c_ulong(0)
+    qc.lib().qcx_plan_cache_stats(reg._h, C.byref(out))
+    return out.value
+
+
+def test_cached_flush_replays_the_front_written_by_its_own_pass(qc, ob):
+    """a flush behind a front that the first pass cannot generate -- a ladder of two moduli: no compact chain, no GenFront --
+    writes the front with a pass of its own, and a plan-cache hit replays exactly that: three rounds of the same circuit
+    (n = 13: the smallest register for which the flush tries to generate that also has more than one tile), the second and
+    third flush are hits.  Every read bit for bit the oracle's, gate by gate; no front is counted as generated; the pass and
+    gate counters of a hit advance like those of the flush that planned."""
+    L, M = 9, 4
+    n = L + M
+    want = np.zeros(2 << n); ob.reset(want, n)
+    for l in range(M, n):
+        ob.hadamard(want, n, l)
+    ob.camodc(want, n, M, 15, 7, 4); ob.camodc(want, n, M, 13, 3, 5)
+    ob.iqft(want, n, M)
+    with qc.Register(L, M) as reg:
+        reg.set_fusion(1)
+        g0 = _gen_fronts(qc, reg)
+        deltas, hits = [], []
+        for rnd in range(3):
+            p0, h0 = reg.fusion_stats(), _plan_hits(qc, reg)
+            qc.reset_register(reg)
+            for l in range(M, n):
+                qc.hadamard_gate(l, reg)
+            qc.c_amodc_gate(15, 7, 4, reg)
+            qc.c_amodc_gate(13, 3, 5, reg)
+            qc.inverse_QFT(reg)
+            got = reg.read()
+            assert np.array_equal(bits(got), bits(want)), rnd
+            p1 = reg.fusion_stats()
+            deltas.append((p1[0] - p0[0], p1[1] - p0[1]))
+            hits.append(_plan_hits(qc, reg) - h0)
+        assert _gen_fronts(qc, reg) == g0
+        assert hits[1] + hits[2] == 2, hits
+        assert deltas[1] == deltas[0] and deltas[2] == deltas[0], deltas
