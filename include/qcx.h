@@ -305,9 +305,20 @@ int  qcx_collapse_last_stats(qcx_register *reg, unsigned *source, unsigned long 
 int  qcx_pauli_expectation(qcx_register *reg, uint64_t x_mask, uint64_t z_mask, double *value);
 int  qcx_pauli_expectation_sum(qcx_register *reg, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks,
                                const double *coeffs, double *values /* [nterms], may be NULL */, double *total);
-/* the last pauli_expectation / pauli_expectation_sum call on this register: source 0 = the register, 2 = a pending basis state
- * (no kernel), 3 = a compact result expanded first; state_reads = the passes that read amplitudes: one per term (0 for a basis
- * state) */
+/* qcx_pauli_expectation_sum with the terms that SHARE an x_mask served by one read of the state (K14b, DESIGN s4.5h): what a
+ * term's leaf takes from the amplitudes depends on x_mask alone, z_mask only picks one of two sums and a sign, and each term
+ * keeps its own tree.  values[k] and *total are, bit for bit, what qcx_pauli_expectation_sum gives for the same arguments on
+ * the same state, and everything it documents holds here -- checks, NULLs, nterms = 0, the lazy forms (a compact result is
+ * expanded once per call), errors.  The passes: walk the terms in order; term k joins the open pass of its x_mask while that
+ * holds fewer than W = qcx_pauli_batch_width() terms, otherwise it opens a new pass; passes run in the order they were opened,
+ * each one read of the state (qcx_pauli_batch_plan in qcx_plan.h is this rule on its own).  The all-Z strings of an Ising or
+ * Heisenberg model share x_mask = 0.  qcx_expectation_last_stats reports the reads of this call: one per pass. */
+int  qcx_pauli_expectation_batch(qcx_register *reg, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks,
+                                 const double *coeffs, double *values /* [nterms], may be NULL */, double *total);
+unsigned qcx_pauli_batch_width(void);   /* W: the most terms one read of the state serves; a build constant, 8 <= W <= 64 */
+/* the last pauli_expectation / pauli_expectation_sum / pauli_expectation_batch call on this register: source 0 = the register,
+ * 2 = a pending basis state (no kernel), 3 = a compact result expanded first; state_reads = the passes that read amplitudes:
+ * one per term, or per pass of the batch call (0 for a basis state) */
 int  qcx_expectation_last_stats(qcx_register *reg, unsigned *source, unsigned long *state_reads);
 
 /* ---- state access (replaces gsl_vector_complex_get/set uses, T:7-37) ------- */

@@ -79,6 +79,13 @@ typedef struct {
 int  qcx_marginal_plan(unsigned n, unsigned first, unsigned num, qcx_marginal_stage *stages, unsigned *n_stages);
 /* the same for a compact circuit result (M-register bits = the orbit residues, include/qcx.h): needs first >= M */
 int  qcx_marginal_plan_compact(unsigned n, unsigned M, unsigned first, unsigned num, qcx_marginal_stage *stages, unsigned *n_stages);
+
+/* The passes of qcx_pauli_expectation_batch (include/qcx.h), on the host: walk the terms in order; term k joins the open pass of
+ * its x_mask while that holds fewer than `width` terms, otherwise it opens a new pass (a full pass is closed).  Passes are
+ * numbered in the order they are opened; pass_of_term[k] is term k's.  The library calls it with width =
+ * qcx_pauli_batch_width().  width = 0, a NULL npasses, or NULL arrays with nterms > 0: QCX_BAD_ARGUMENTS. */
+int  qcx_pauli_batch_plan(unsigned long nterms, const uint64_t *x_masks, unsigned width,
+                          unsigned long *pass_of_term /* [nterms] */, unsigned long *npasses);
 #ifdef __cplusplus
 }
 #endif

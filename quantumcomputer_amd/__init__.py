@@ -3,7 +3,7 @@
 Only what the path needs: csrc/ (HIP kernels + the C ABI, built into libqcx.so),
 the ctypes loader and the host-side mirror of the reference's gate interface.
 """
-from ._lib import LIB_PATH, QcxError, front_plan, fusion_plan, idle_devices, lib, marginal_plan, pauli_masks, polar, spread_devices, tune  # noqa: F401
+from ._lib import LIB_PATH, QcxError, front_plan, fusion_plan, idle_devices, lib, marginal_plan, pauli_batch_plan, pauli_batch_width, pauli_masks, polar, spread_devices, tune  # noqa: F401
 from .register import (Register, Rng, load_state_file, c_amodc_gate, c_one_qubit_gate, c_phase_shift_gate,  # noqa: F401
                        c_two_qubit_gate, check_normalisation, controlled, display_state, hadamard_gate,
                        inverse_QFT, measure_qubits, measure_state, omega_distribution, one_qubit_gate, pauli_rotation, phase, postselect_qubits,
@@ -26,4 +26,4 @@ __all__ = ["FUSION_TOLERANCE", "Register", "Rng", "reset_register", "hadamard_ga
            "one_qubit_gate", "c_one_qubit_gate", "GATES", "rz", "phase",
            "two_qubit_gate", "c_two_qubit_gate", "GATES2", "controlled", "pauli_rotation",
            "swap_states", "inverse_QFT", "quantum_computation", "measure_state", "measure_qubits", "postselect_qubits", "sample_states", "omega_distribution", "read_omega",
-           "display_state", "check_normalisation", "lib", "tune", "polar", "pauli_masks", "QcxError", "LIB_PATH", "spread_devices", "idle_devices"]
+           "display_state", "check_normalisation", "lib", "tune", "polar", "pauli_masks", "pauli_batch_width", "pauli_batch_plan", "QcxError", "LIB_PATH", "spread_devices", "idle_devices"]

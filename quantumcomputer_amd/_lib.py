@@ -76,6 +76,9 @@ SIGNATURES = {
     "qcx_collapse_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul), C.POINTER(_ul)]),
     "qcx_pauli_expectation": (_i, [_p, _u64, _u64, C.POINTER(_d)]),
     "qcx_pauli_expectation_sum": (_i, [_p, _ul, _p, _p, _p, _p, C.POINTER(_d)]),
+    "qcx_pauli_expectation_batch": (_i, [_p, _ul, _p, _p, _p, _p, C.POINTER(_d)]),
+    "qcx_pauli_batch_width": (_u, []),
+    "qcx_pauli_batch_plan": (_i, [_ul, _p, _u, _p, C.POINTER(_ul)]),
     "qcx_expectation_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
     "qcx_marginal_plan": (_i, [_u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_marginal_plan_compact": (_i, [_u, _u, _u, _u, _p, C.POINTER(_u)]),
@@ -201,6 +204,24 @@ def marginal_plan(n, first, num, M=None):
         st = lib().qcx_marginal_plan_compact(n, M, first, num, C.cast(arr, C.c_void_p), C.byref(ns))
     check(st, "qcx_marginal_plan")
     return [arr[i] for i in range(ns.value)]
+
+
+def pauli_batch_width():
+    """W: the most terms one read of the state serves in Register.expectation_batch (qcx_pauli_batch_width)"""
+    return int(lib().qcx_pauli_batch_width())
+
+
+def pauli_batch_plan(x_masks, width=None):
+    """The passes of Register.expectation_batch (host code, no GPU needed; include/qcx_plan.h: qcx_pauli_batch_plan):
+    (pass_of_term, npasses) for the terms' x_masks in order; width=None: the library's W."""
+    import numpy as np
+    xs = np.array([int(x) for x in x_masks], dtype=np.uint64)
+    out = np.zeros(xs.size, dtype=np.uint64)
+    np_ = C.c_ulong(0)
+    ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if xs.size else (lambda a: None)
+    check(lib().qcx_pauli_batch_plan(xs.size, ptr(xs), pauli_batch_width() if width is None else int(width), ptr(out), C.byref(np_)),
+          "qcx_pauli_batch_plan")
+    return [int(v) for v in out], int(np_.value)
 
 
 def fusion_plan(n_local, M, descs, mode=1):

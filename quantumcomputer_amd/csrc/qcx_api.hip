@@ -2413,48 +2413,152 @@ extern "C" int qcx_marginal_last_stats(qcx_register *r, unsigned *source, unsign
     return QCX_NO_ERROR;
 }
 
-// K14: <psi|P|psi> of the Pauli string (x, z) on the state in r->amp (include/qcx.h, DESIGN s4.5h).  The stages are those of
-// qcx_marginal_plan(n, 0, 0) -- "sum everything" --, with k_pauli_leaves in the place of stage 0; partials and result in marg_buf.
-static int pauli_launch(qcx_register *r, uint64_t x, uint64_t z, double *value)
+// K14 / K14b: the stages of a Pauli string's value are those of qcx_marginal_plan(n, 0, 0) -- "sum everything" --, with a Pauli
+// kernel in the place of stage 0.  row: the doubles of the non-final stages' outputs, one string's partials.
+struct PauliStages { qcx_marginal_stage st[QCX_MARGINAL_MAX_STAGES]; unsigned ns, T; size_t row; };
+static int pauli_stages(qcx_register *r, PauliStages *ps)
 {
-    qcx_marginal_stage st[QCX_MARGINAL_MAX_STAGES];
-    unsigned ns = 0;
-    QCX_TRY(qcx_marginal_plan(r->n, 0, 0, st, &ns));
-    const unsigned T = st[0].T;
+    ps->ns = 0;
+    QCX_TRY(qcx_marginal_plan(r->n, 0, 0, ps->st, &ps->ns));
+    const qcx_marginal_stage *st = ps->st;
+    const unsigned T = ps->T = st[0].T;
     const uint64_t low = (((uint64_t)1) << T) - 1u;
-    // what k_pauli_leaves takes for granted of stage 0: tiles of the T = min(n, 12) lowest bits, all summed, tile t -> output t
+    // what the Pauli kernels take for granted of stage 0: tiles of the T = min(n, 12) lowest bits, all summed, tile t -> output t
     if (st[0].kind != 0 || T != std::min(r->n, 12u) || st[0].tile_mask != low || st[0].sum_mask != low || st[0].out_bits != r->n - T) {
         set_error("qcx_pauli_expectation: unexpected first stage in the plan of n = %u", r->n);
         return QCX_UNKNOWN_ERROR;
     }
-    size_t scratch = 0;
-    for (unsigned i = 0; i < ns; i++)
-        if (!st[i].final_stage) scratch = std::max<size_t>(scratch, (size_t)(st[i].out_offset + (((uint64_t)1) << st[i].out_bits)));
-    QCX_TRY(marg_reserve(r, scratch + 2));
-    double *const out = r->marg_buf + scratch;
-    auto dst_of = [&](unsigned i) { return st[i].final_stage ? out : r->marg_buf + st[i].out_offset; };
-    const unsigned g = (unsigned)__builtin_popcountll(x & z) & 3u;
-    const PauliUnits pu = pauli_units(r->n, x);                    // (pu.T == T: checked against the plan above)
-    pauli_dispatch(pu, [&](auto f) {
-        hipLaunchKernelGGL((k_pauli_leaves<f.shape, f.full>), dim3((unsigned)std::min<uint64_t>(pu.nunits, 2048)), dim3(256), 0, r->stream, (const amp_t *)r->amp, dst_of(0), pu.nunits, T, x, z, g);
-    });
-    HIP_TRY(hipGetLastError());
-    for (unsigned i = 1; i < ns; i++) {
+    ps->row = 0;
+    for (unsigned i = 0; i < ps->ns; i++)
+        if (!st[i].final_stage) ps->row = std::max<size_t>(ps->row, (size_t)(st[i].out_offset + (((uint64_t)1) << st[i].out_bits)));
+    return QCX_NO_ERROR;
+}
+
+// the stages behind the first on one string's partials at `row`: plain k_marginal<MARG_DBL> launches, the value to *out
+static int pauli_later_stages(qcx_register *r, const PauliStages &ps, double *row, double *out)
+{
+    for (unsigned i = 1; i < ps.ns; i++) {
         MargParams P;
-        marginal_params(st[i], &P);
-        P.src = r->marg_buf + st[i - 1].out_offset;
-        P.dst = dst_of(i);
+        marginal_params(ps.st[i], &P);
+        P.src = row + ps.st[i - 1].out_offset;
+        P.dst = ps.st[i].final_stage ? out : row + ps.st[i].out_offset;
         P.bad = nullptr;
         hipLaunchKernelGGL(k_marginal<MARG_DBL>, dim3((unsigned)std::min<uint64_t>(P.ntiles, 2048)), dim3(256), 0, r->stream, P);
         HIP_TRY(hipGetLastError());
     }
+    return QCX_NO_ERROR;
+}
+
+// K14: <psi|P|psi> of the Pauli string (x, z) on the state in r->amp (include/qcx.h, DESIGN s4.5h); partials and result in marg_buf.
+static int pauli_launch(qcx_register *r, uint64_t x, uint64_t z, double *value)
+{
+    PauliStages ps;
+    QCX_TRY(pauli_stages(r, &ps));
+    QCX_TRY(marg_reserve(r, ps.row + 2));
+    double *const out = r->marg_buf + ps.row;
+    const unsigned g = (unsigned)__builtin_popcountll(x & z) & 3u;
+    const PauliUnits pu = pauli_units(r->n, x);                    // (pu.T == ps.T: checked against the plan)
+    double *const dst0 = ps.st[0].final_stage ? out : r->marg_buf + ps.st[0].out_offset;
+    pauli_dispatch(pu, [&](auto f) {
+        hipLaunchKernelGGL((k_pauli_leaves<f.shape, f.full>), dim3((unsigned)std::min<uint64_t>(pu.nunits, 2048)), dim3(256), 0, r->stream, (const amp_t *)r->amp, dst0, pu.nunits, ps.T, x, z, g);
+    });
+    HIP_TRY(hipGetLastError());
+    QCX_TRY(pauli_later_stages(r, ps, r->marg_buf, out));
     HIP_TRY(hipMemcpyAsync(value, out, sizeof(double), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
     return QCX_NO_ERROR;
 }
 
-// the terms of one call, in order; values may be null.  Everything is checked before anything runs.
-static int pauli_terms(qcx_register *r, unsigned long nterms, const uint64_t *xs, const uint64_t *zs, double *values)
+// ---- K14b: the terms of a call that share an x_mask, QCX_PAULI_BATCH_W at the most, from one read of the state -------------------
+extern "C" unsigned qcx_pauli_batch_width(void) { return QCX_PAULI_BATCH_W; }
+
+// The passes of qcx_pauli_expectation_batch (include/qcx_plan.h): term k joins the open pass of its x_mask while that holds fewer
+// than `width` terms, otherwise it opens a new one; passes are numbered in the order they are opened.
+extern "C" int qcx_pauli_batch_plan(unsigned long nterms, const uint64_t *x_masks, unsigned width, unsigned long *pass_of_term,
+                                    unsigned long *npasses)
+{
+    if (!npasses || width == 0 || (nterms && (!x_masks || !pass_of_term))) return QCX_BAD_ARGUMENTS;
+    std::map<uint64_t, std::pair<unsigned long, unsigned>> open;     // x_mask -> (its open pass, terms in it)
+    unsigned long np = 0;
+    for (unsigned long k = 0; k < nterms; k++) {
+        auto it = open.find(x_masks[k]);
+        if (it == open.end() || it->second.second >= width) {
+            open[x_masks[k]] = {np, 1u};
+            pass_of_term[k] = np++;
+        } else {
+            it->second.second++;
+            pass_of_term[k] = it->second.first;
+        }
+    }
+    *npasses = np;
+    return QCX_NO_ERROR;
+}
+
+// One pass: the K terms idx[0 .. K) of (xs, zs), all with the x_mask x.  k_pauli_leaves_batch writes term k's tile roots to row k
+// of the stage buffer; the later stages are K14's, row by row, and the K results, side by side behind the rows, come back in
+// one copy.
+static int pauli_batch_launch(qcx_register *r, uint64_t x, unsigned K, const unsigned long *idx, const uint64_t *zs, double *values,
+                              unsigned rows /* of the call's widest pass: one allocation for all of them */)
+{
+    PauliStages ps;
+    QCX_TRY(pauli_stages(r, &ps));
+    if (K == 0 || K > rows || rows > QCX_PAULI_BATCH_W) {
+        set_error("qcx_pauli_expectation_batch: a pass of %u terms", K);
+        return QCX_UNKNOWN_ERROR;
+    }
+    QCX_TRY(marg_reserve(r, (ps.row + 1) * rows));
+    double *const out = r->marg_buf + ps.row * rows;
+    const uint64_t low = (((uint64_t)1) << ps.T) - 1u;
+    PauliBatchTerms tm = {};
+    bool odd = false;
+    for (unsigned k = 0; k < K; k++) {
+        const uint64_t z = zs[idx[k]];
+        const unsigned g = (unsigned)__builtin_popcountll(x & z) & 3u, xi = (unsigned)(x & low) & 15u, zi = (unsigned)(z & low) & 15u;
+        unsigned iodd = 0;
+        for (unsigned i = 0; i < 16; i++) iodd |= (unsigned)(__builtin_popcount((i ^ xi) & zi) & 1) << i;
+        tm.z[k] = z;
+        tm.meta[k] = iodd | g << 16;
+        odd = odd || (g & 1u);
+    }
+    const PauliUnits pu = pauli_units(r->n, x);                    // (pu.T == ps.T: checked against the plan)
+    double *const dst0 = ps.st[0].final_stage ? out : r->marg_buf + ps.st[0].out_offset;
+    const uint64_t stride0 = ps.st[0].final_stage ? 1 : ps.row;
+    const unsigned grid = (unsigned)std::min<uint64_t>(pu.nunits, 2048);
+    pauli_dispatch(pu, [&](auto f) {
+        if (odd) hipLaunchKernelGGL((k_pauli_leaves_batch<f.shape, f.full, true>), dim3(grid), dim3(256), 0, r->stream, (const amp_t *)r->amp, dst0, stride0, pu.nunits, ps.T, x, K, tm);
+        else hipLaunchKernelGGL((k_pauli_leaves_batch<f.shape, f.full, false>), dim3(grid), dim3(256), 0, r->stream, (const amp_t *)r->amp, dst0, stride0, pu.nunits, ps.T, x, K, tm);
+    });
+    HIP_TRY(hipGetLastError());
+    for (unsigned k = 0; k < K; k++) QCX_TRY(pauli_later_stages(r, ps, r->marg_buf + k * ps.row, out + k));
+    double got[QCX_PAULI_BATCH_W];
+    HIP_TRY(hipMemcpyAsync(got, out, K * sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    for (unsigned k = 0; k < K; k++) values[idx[k]] = got[k];
+    return QCX_NO_ERROR;
+}
+
+// the passes of qcx_pauli_batch_plan, in the order they were opened; values is not null here.  Every pass goes through K14b, a
+// pass of one term too: it measured faster than K14 in every shape (DESIGN s4.5h).
+static int pauli_batches(qcx_register *r, unsigned long nterms, const uint64_t *xs, const uint64_t *zs, double *values)
+{
+    std::vector<unsigned long> pass_of(nterms);
+    unsigned long np = 0;
+    QCX_TRY(qcx_pauli_batch_plan(nterms, xs, QCX_PAULI_BATCH_W, pass_of.data(), &np));
+    std::vector<std::vector<unsigned long>> members(np);
+    for (unsigned long k = 0; k < nterms; k++) members[pass_of[k]].push_back(k);
+    size_t rows = 1;
+    for (unsigned long p = 0; p < np; p++) rows = std::max(rows, members[p].size());
+    for (unsigned long p = 0; p < np; p++) {
+        const std::vector<unsigned long> &m = members[p];
+        QCX_TRY(pauli_batch_launch(r, xs[m[0]], (unsigned)m.size(), m.data(), zs, values, (unsigned)rows));
+        r->exp_reads += 1;
+    }
+    return QCX_NO_ERROR;
+}
+
+// the terms of one call, in order; values may be null (not with batch).  Everything is checked before anything runs.
+// batch: the terms run as the passes of qcx_pauli_expectation_batch, otherwise one by one.
+static int pauli_terms(qcx_register *r, unsigned long nterms, const uint64_t *xs, const uint64_t *zs, double *values, bool batch = false)
 {
     for (unsigned long k = 0; k < nterms; k++)
         if ((xs[k] | zs[k]) >> r->n) {
@@ -2480,6 +2584,7 @@ static int pauli_terms(qcx_register *r, unsigned long nterms, const uint64_t *xs
         QCX_TRY(launch_expand_compact(r->compact_amp, r->amp, r->n, r->compact_E, r->stream));
         r->exp_source = 3;
     }
+    if (batch) return pauli_batches(r, nterms, xs, zs, values);
     for (unsigned long k = 0; k < nterms; k++) {
         double v = 0.0;
         QCX_TRY(pauli_launch(r, xs[k], zs[k], &v));
@@ -2496,18 +2601,31 @@ extern "C" int qcx_pauli_expectation(qcx_register *r, uint64_t x_mask, uint64_t 
     return pauli_terms(r, 1, &x_mask, &z_mask, value);
 }
 
-extern "C" int qcx_pauli_expectation_sum(qcx_register *r, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks,
-                                         const double *coeffs, double *values, double *total)
+// qcx_pauli_expectation_sum and qcx_pauli_expectation_batch: the same call but for how the terms share reads of the state
+static int pauli_sum(qcx_register *r, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks, const double *coeffs,
+                     double *values, double *total, bool batch)
 {
     if (!r || !total || (nterms && (!x_masks || !z_masks || !coeffs))) return QCX_BAD_ARGUMENTS;
     if (r->sh) return QCX_UNSUPPORTED;
     std::vector<double> own;
     if (!values && nterms) { own.resize(nterms); values = own.data(); }
-    QCX_TRY(pauli_terms(r, nterms, x_masks, z_masks, values));
+    QCX_TRY(pauli_terms(r, nterms, x_masks, z_masks, values, batch));
     double acc = 0.0;
     for (unsigned long k = 0; k < nterms; k++) acc = acc + coeffs[k] * values[k];      // (each rounded on its own: -ffp-contract=off)
     *total = acc;
     return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_pauli_expectation_sum(qcx_register *r, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks,
+                                         const double *coeffs, double *values, double *total)
+{
+    return pauli_sum(r, nterms, x_masks, z_masks, coeffs, values, total, false);
+}
+
+extern "C" int qcx_pauli_expectation_batch(qcx_register *r, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks,
+                                           const double *coeffs, double *values, double *total)
+{
+    return pauli_sum(r, nterms, x_masks, z_masks, coeffs, values, total, true);
 }
 
 extern "C" int qcx_expectation_last_stats(qcx_register *r, unsigned *source, unsigned long *state_reads)

@@ -4243,6 +4243,163 @@ __global__ __launch_bounds__(256) void k_pauli_leaves(const amp_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// K14b  K14's stage 0 for K <= QCX_PAULI_BATCH_W strings that SHARE their x_mask, from one read of the state
+// (qcx_pauli_expectation_batch, DESIGN s4.5h).  What depends on x_mask alone -- the operands a = amp[i], b = amp[i ^ x_mask] and
+// the two candidate sums t_even = a.re b.re + a.im b.im, t_odd = a.im b.re - a.re b.im -- is formed once per tile and kept in
+// registers (ODD: some term of the pass has odd g; otherwise t_odd is never formed); a term then only picks one of the two
+// (kernel-uniform), puts its signs on and reduces the tile's tree.  Units, shapes, FULL and the loads are K14's.
+// The tree is K14's tree, level h adding the partial sums that differ in bit h of the tile-local e, but no term has a tree in
+// LDS.  ONCE per tile the t values change hands through LDS so that a thread holds 16 CONSECUTIVE elements, e = 16 tid + i
+// (in the exchange shape the amplitudes already go through LDS, as in K14: a thread reads a and b back in that layout and forms
+// t there).  Per term, then:
+//   bits 0-3 (i)          15 sums in the thread, lowest bit first
+//   bits 4-9 (the lane)   six butterfly levels on ONE value (IEEE addition commutes: both lanes of a pair form the same sum)
+//   bits 10-11 (the wave) one double per wave and term through LDS (wsum); ONE barrier per tile serves all terms, and thread k
+//                         forms (w0 + w1) + (w2 + w3) of term k
+// Rows of 16 elements lie 16 B apart in LDS, so that the 128-bit reads of a row hit all banks.
+// Three facts about the arithmetic make this K14's bits (tests/test_pauli_batch_plan.py checks them against the definition):
+//   - in the pair shape the partner tile's tree holds the same leaves at e ^ x_low, so every level adds the same two numbers
+//     (perhaps the other way round) and its root is tile t's root: one tree, written to both partials
+//   - a leaf's "0.0 +" may wait until the root: with signed-zero leaves a node differs from the canonical tree only where it is
+//     a zero of the other sign, and 0.0 + root is then the same +0
+//   - for the same reason the leaves a partial tile (n < 12) does not have are zeros of either sign: the levels above T add
+//     zeros to the T-level root.
+// The sign of term k on element i: par((e ^ x_low) & z_low) = par((tid ^ (x_low >> 4)) & (z_low >> 4)) + bit i of the term's
+// iodd (the same for every thread: the host computes it), + par((tile ^ xh) & zh) + (g >> 1), scalar.  Terms come as a kernel
+// argument.  Term k's root of tile t goes to dst[k * row_stride + t].  Nothing is written but dst.
+// ---------------------------------------------------------------------------
+#define QCX_PAULI_BATCH_W 32
+struct PauliBatchTerms {
+    uint64_t z[QCX_PAULI_BATCH_W];
+    uint32_t meta[QCX_PAULI_BATCH_W];            // iodd (bit i: par((i ^ (x_low & 15)) & (z_low & 15))) | g << 16
+};
+
+template <int CTRL> __device__ __forceinline__ double pauli_dpp(double v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+constexpr int PAULI_DPP_XOR1 = 0xB1, PAULI_DPP_XOR2 = 0x4E;       // quad_perm [1, 0, 3, 2] and [2, 3, 0, 1]
+
+template <int SHAPE, bool FULL, bool ODD>
+__global__ __launch_bounds__(256) void k_pauli_leaves_batch(const amp_t *__restrict__ amp, double *__restrict__ dst, uint64_t row_stride,
+                                                            uint64_t nunits, unsigned T, uint64_t x_mask, unsigned K, PauliBatchTerms terms)
+{
+    using Tiles = PauliTiles<SHAPE == 2>;
+    constexpr unsigned EPT = Tiles::EPT;
+    static_assert(EPT == 16, "a thread's elements are one row of 16");
+    // a tile in LDS, 16 B of padding behind every row of 16: its amplitudes (the exchange shape), or else its t values
+    constexpr unsigned AMPS = 256u * 17u, TVAL2 = 256u * 9u;         // in amplitudes, and in pairs of doubles
+    __shared__ __attribute__((aligned(16))) double lds[SHAPE == 1 ? 2u * AMPS : (ODD ? 4u : 2u) * TVAL2];
+    __shared__ double wsum[QCX_PAULI_BATCH_W * 4];                   // [term][wave]
+    const unsigned tid = threadIdx.x, wave = tid >> 6;
+    const Tiles P(T, x_mask, 0, tid);
+    const unsigned nel = P.nel, x_low = P.x_low, nld = P.nld;
+    const uint64_t xh = P.xh;
+    auto amp_pos = [](unsigned e) { return e + (e >> 4); };
+    amp_t a[EPT], b[SHAPE == 2 ? EPT : 1];
+    auto load = [&](uint64_t u) {
+        const uint64_t t = P.tile_of(u);
+        const amp_t *pa = amp + (t << T) + tid;
+#pragma unroll
+        for (unsigned j = 0; j < EPT; j++)
+            if (FULL || j < nld) a[j] = __builtin_nontemporal_load(pa + 256u * j);
+        if constexpr (SHAPE == 2) {
+            const amp_t *pb = amp + ((t ^ xh) << T) + P.partner_lane(tid);
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++) b[j] = __builtin_nontemporal_load(pb + 256u * P.partner_elem(j));
+        }
+    };
+    auto t_even = [](amp_t p, amp_t q) { return p.x * q.x + p.y * q.y; };
+    auto t_odd = [](amp_t p, amp_t q) { return p.y * q.x - p.x * q.y; };
+    // term k on the thread's row of t values: signs, the tree's levels up to the wave, the wave's sum into wsum
+    auto reduce = [&](const double (&tv)[EPT], unsigned k, unsigned flip, unsigned iodd) {
+        double v[EPT];
+#pragma unroll
+        for (unsigned i = 0; i < EPT; i++)
+            v[i] = __hiloint2double(__double2hiint(tv[i]) ^ (int)(flip ^ (((iodd >> i) & 1u) << 31)), __double2loint(tv[i]));
+#pragma unroll
+        for (unsigned i = 0; i < 8u; i++) v[i] = v[2u * i] + v[2u * i + 1u];
+#pragma unroll
+        for (unsigned i = 0; i < 4u; i++) v[i] = v[2u * i] + v[2u * i + 1u];
+        double s = (v[0] + v[1]) + (v[2] + v[3]);
+        s = s + pauli_dpp<PAULI_DPP_XOR1>(s);
+        s = s + pauli_dpp<PAULI_DPP_XOR2>(s);
+        s = s + __shfl_xor(s, 4);
+        s = s + __shfl_xor(s, 8);
+        s = s + __shfl_xor(s, 16);
+        s = s + __shfl_xor(s, 32);
+        if ((tid & 63u) == 0) wsum[k * 4u + wave] = s;
+    };
+    if (blockIdx.x < nunits) load(blockIdx.x);
+    for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
+        const uint64_t t = P.tile_of(u);
+        double te[EPT], to[ODD ? EPT : 1];
+        if constexpr (SHAPE == 1) {
+            // as K14: once the tile is in LDS, a's registers take the next tile's loads; a thread reads its row and the partners'
+            amp_t *sa = (amp_t *)lds;
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (FULL || j < nld) sa[amp_pos(tid + 256u * j)] = a[j];
+            __syncthreads();
+            if (u + gridDim.x < nunits) load(u + gridDim.x);
+#pragma unroll
+            for (unsigned i = 0; i < EPT; i++) {
+                const unsigned e = 16u * tid + i;
+                if (FULL || e < nel) {
+                    const amp_t p = sa[amp_pos(e)], q = sa[amp_pos(e ^ x_low)];
+                    te[i] = t_even(p, q);
+                    if constexpr (ODD) to[i] = t_odd(p, q);
+                } else { te[i] = 0.0; if constexpr (ODD) to[i] = 0.0; }
+            }
+        } else {
+            double2 *se = (double2 *)lds, *so = (double2 *)lds + TVAL2;
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++)
+                if (FULL || j < nld) {
+                    const unsigned e = tid + 256u * j;
+                    const amp_t q = SHAPE == 2 ? b[SHAPE == 2 ? j : 0] : a[j];
+                    ((double *)(se + (e >> 4) * 9u))[e & 15u] = t_even(a[j], q);
+                    if constexpr (ODD) ((double *)(so + (e >> 4) * 9u))[e & 15u] = t_odd(a[j], q);
+                }
+            __syncthreads();
+            if (u + gridDim.x < nunits) load(u + gridDim.x);
+#pragma unroll
+            for (unsigned i = 0; i < EPT; i += 2) {
+                const bool there = FULL || 16u * tid + i < nel;      // (nel is even: the two are there together)
+                const double2 ve = se[tid * 9u + (i >> 1)];
+                te[i] = there ? ve.x : 0.0;
+                te[i + 1] = there ? ve.y : 0.0;
+                if constexpr (ODD) {
+                    const double2 vo = so[tid * 9u + (i >> 1)];
+                    to[i] = there ? vo.x : 0.0;
+                    to[i + 1] = there ? vo.y : 0.0;
+                }
+            }
+        }
+        for (unsigned k = 0; k < K; k++) {
+            const uint64_t z = terms.z[k];
+            const unsigned meta = terms.meta[k], g = meta >> 16, z_low = (unsigned)z & (nel - 1u);
+            const unsigned odd = (unsigned)__popc((tid ^ (x_low >> 4)) & (z_low >> 4)) + (unsigned)__popcll((t ^ xh) & (z >> T)) + (g >> 1);
+            if constexpr (ODD) {
+                if (g & 1u) reduce(to, k, odd << 31, meta & 0xFFFFu);
+                else reduce(te, k, odd << 31, meta & 0xFFFFu);
+            } else
+                reduce(te, k, odd << 31, meta & 0xFFFFu);
+        }
+        __syncthreads();
+        if (tid < K) {
+            const double *w = wsum + 4u * tid;
+            const double root = 0.0 + ((w[0] + w[1]) + (w[2] + w[3]));
+            dst[tid * row_stride + t] = root;
+            if constexpr (SHAPE == 2) dst[tid * row_stride + (t ^ xh)] = root;
+        }
+        // (the next tile writes lds, which all have read before the barrier above, and wsum only behind its own first barrier)
+    }
+}
+
+// ---------------------------------------------------------------------------
 // K11  collapse of the qubit range [first, first + num) onto `outcome` (qcx_measure_qubits, DESIGN s4.5e).  An amplitude whose
 // range bits equal `outcome` becomes (fl(re * s), fl(im * s)) -- two products, nothing to contract into an FMA --, every other
 // one (+0, +0) and is NEVER READ: its lane only stores.  A wave takes 64 amplitudes per step, lane l the element e = 64 t + l of

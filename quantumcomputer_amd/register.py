@@ -253,9 +253,7 @@ class Register:
         check(lib().qcx_pauli_expectation(self._h, x, z, C.byref(out)), "qcx_pauli_expectation")
         return out.value
 
-    def expectation_sum(self, terms):
-        """terms = [(coeff, pauli), ...]: (total, values) with values[k] = expectation(pauli_k), one pass over the state per
-        term, and total = the terms' coeff * value added up in order (include/qcx.h: qcx_pauli_expectation_sum)."""
+    def _expectation_terms(self, terms, entry):
         terms = list(terms)
         k = len(terms)
         masks = [_lib.pauli_masks(p, self.num_qubits) for _, p in terms]
@@ -265,13 +263,23 @@ class Register:
         values = np.zeros(k, dtype=np.float64)
         total = C.c_double(float("nan"))
         ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if k else (lambda a: None)
-        check(lib().qcx_pauli_expectation_sum(self._h, k, ptr(xs), ptr(zs), ptr(cs), ptr(values), C.byref(total)),
-              "qcx_pauli_expectation_sum")
+        check(getattr(lib(), entry)(self._h, k, ptr(xs), ptr(zs), ptr(cs), ptr(values), C.byref(total)), entry)
         return total.value, values
 
+    def expectation_sum(self, terms):
+        """terms = [(coeff, pauli), ...]: (total, values) with values[k] = expectation(pauli_k), one pass over the state per
+        term, and total = the terms' coeff * value added up in order (include/qcx.h: qcx_pauli_expectation_sum)."""
+        return self._expectation_terms(terms, "qcx_pauli_expectation_sum")
+
+    def expectation_batch(self, terms):
+        """expectation_sum(terms), bit for bit, with the terms that share an x_mask served by one read of the state, up to
+        pauli_batch_width() of them a read (include/qcx.h: qcx_pauli_expectation_batch; pauli_batch_plan gives the passes)."""
+        return self._expectation_terms(terms, "qcx_pauli_expectation_batch")
+
     def expectation_stats(self):
-        """(source, state reads) of the last expectation / expectation_sum call on this register: source 0 = the register, 2 = a
-        pending basis state (no kernel), 3 = a compact circuit result expanded first; one state read per term"""
+        """(source, state reads) of the last expectation / expectation_sum / expectation_batch call on this register: source 0 =
+        the register, 2 = a pending basis state (no kernel), 3 = a compact circuit result expanded first; one state read per
+        term, or per pass of expectation_batch"""
         src, reads = C.c_uint(0), C.c_ulong(0)
         check(lib().qcx_expectation_last_stats(self._h, C.byref(src), C.byref(reads)), "qcx_expectation_last_stats")
         return src.value, reads.value
