@@ -172,7 +172,7 @@ static int sh_create(int L, int M, unsigned nshards, const int *devices, ShardSe
     const unsigned k = sh->k;
     sh_set_slices(sh, sh_default_sigma());
     if (sh->n_local < sh->min_evict + 2 * k) {
-        set_error("register too small for %u shards (need n_local - max(M, 6) >= 2 log2(shards))", nshards);
+        set_error("register too small for %u shards (need n_local - M >= 2 log2(shards), n_local = L + M - log2(shards))", nshards);
         delete sh; return QCX_BAD_ARGUMENTS;
     }
     sh->perm.resize(sh->n); sh->inv.resize(sh->n);

@@ -13,6 +13,11 @@ The generator has two vocabularies.  Seeds below NSEEDS_V1 draw from the calls u
 expect / expect_sum / prot (the Pauli calls), devptr (a read through qcx_device_pointer, after which the register works in
 place for the rest of its life) and stream (qcx_register_set_stream: a caller's non-blocking stream, or the own one again).
 
+A third family, generate_sharded (seeds 0 .. NSEEDS_SH - 1 of its own, at the end of this file), draws sequences for a SHARDED
+register (qcx_register_create_sharded): the same model -- a sharded register promises the same bits for the calls it supports --
+with the calls it refuses (QCX_UNSUPPORTED, nothing touched) as refused ops, and relays / selfcheck / stats ops the model does
+nothing for.  tests/test_sharded_sequences_dry.py replays them on a dry-run register, tests/test_gpu_sharded_sequences.py on the GPU.
+
 An op is a tuple of a name and plain numbers / strings, so that a failing sequence prints as a Python literal and replays:
 written data and matrices are regenerated from the seed inside the op (window_data, matrix_data).  Host only."""
 import numpy as np
@@ -24,7 +29,7 @@ import two_qubit_ref
 from collapse_ref import collapse_ref, measure_ref
 from marginal_ref import marginal_ref
 
-NO_ERROR, BAD_ARGUMENTS, BAD_QUBIT = 0, 2, 6
+NO_ERROR, BAD_ARGUMENTS, BAD_QUBIT, UNSUPPORTED = 0, 2, 6, 7
 THREADS = 8
 
 
@@ -267,8 +272,11 @@ def apply_to_model(m, op):
     elif k == "prot": m.pauli_rotation(op[1], op[2], op[3])
     elif k == "devptr": return m.read(op[1], op[2])
     elif k == "stream": pass
+    elif k in ("relays", "selfcheck"): pass                                 # (a sharded register's; no amplitude changes)
     elif k == "refused":
         inner, status = op[1], op[2]
+        if status == UNSUPPORTED:                                           # (a sharded register refuses the call before it looks at it)
+            return status
         if inner[0] == "postselect" and inner[3] < (1 << inner[2]) and inner[1] + inner[2] <= m.n:
             p, out = collapse_ref(m.a, m.n, inner[1], inner[2], inner[3])
             assert out is None, ("the generator drew an outcome the state CAN be collapsed onto", op)
@@ -784,5 +792,335 @@ def pairs_reached(shape, start_mode, ops, vocab=1):
             if op[0] in following_of(vocab):
                 out[(s, op[0])] = out.get((s, op[0]), 0) + 1
             if not is_quiet(op, M, vocab):
+                break
+    return out
+
+
+# ---- the sharded family ------------------------------------------------------------------------------------------------------------
+# Sequences for a register of 2, 4 or 8 shards.  Between calls such a register keeps a logical -> physical qubit layout that
+# trades leave swapped, a gate queue (in EVERY fusion mode: mode 0 behaves as 1, mode -1 only launches gate by gate), a pending
+# basis state (reset in a mode >= 0; measure_state collapses at once), a circuit front written per shard, a compact circuit on a
+# companion register, an owed zero pass, relays and the slice / window geometry.  The model is RegisterModel, unchanged.
+
+NSEEDS_SH = 48
+FOLLOWING_SH = ("reset", "fill", "write", "read", "h", "cphase", "camodc", "iqft", "qcomp", "measure", "total", "norm2", "save",
+                "load", "flush", "sync", "fusion", "relays", "selfcheck", "stats", "refused")
+SETTING_SH = ("reset", "measure_state", "fill", "write_full_negzero", "write_partial", "load", "swapped_layout", "queued",
+              "queued_behind_basis", "compact")
+QUIET_SH = ("stats", "selfcheck", "refused")          # calls that leave every lazy form of a sharded register as it is
+RESTORES_IDENTITY = ("reset", "fill", "write", "read", "measure", "total", "save", "load")      # (relays too, but not on a dry run)
+# (L, M, C, a) by shard count.  ordinary: n_local = n - k >= 2 k + 6; tiny: n_local < 2 k + 6, where sh_set_slices lets runs
+# shorter than 1 KiB be traded (min_evict = M): the smallest registers qcx_register_create_sharded accepts are among them;
+# compact: the smallest shapes per shard count at which reset + quantum_computation runs on the companion register (sh_compact:
+# 4 <= M <= 12 and n_local >= M + 6; the companion of L + cb qubits is accepted whenever the register itself is); on 8 shards
+# that is (11, 4) of the ordinary list, and the list holds the smallest whose trade zone is large enough for a relay as well.  Shapes of the other two lists that meet the condition -- (9, 4) and
+# (8, 5) on 4 shards, (11, 4) and the tiny (9, 4) on 8 -- are compact shapes as well (ShardedConfig.compact) and asserted as such
+SH_SHAPES = {
+    "ordinary": {2: [(9, 0, 1, 1), (5, 4, 15, 7), (6, 5, 21, 2)], 4: [(12, 0, 1, 1), (9, 4, 15, 7), (8, 5, 21, 2)], 8: [(15, 0, 1, 1), (11, 4, 15, 7)]},
+    "tiny": {2: [(3, 0, 1, 1), (4, 0, 1, 1), (6, 0, 1, 1), (3, 4, 15, 7), (3, 5, 21, 2)], 4: [(6, 0, 1, 1), (8, 0, 1, 1), (6, 4, 15, 7), (6, 5, 21, 2)],
+             8: [(9, 0, 1, 1), (12, 0, 1, 1), (9, 4, 15, 7)]},
+    "compact": {2: [(7, 4, 15, 7)], 4: [(8, 4, 15, 7)], 8: [(12, 4, 15, 7)]},
+}
+MEASURE_EDGES = ("nan", "1.5", "-0.25")                # draws outside [0, 1): ops carry them as strings (a NaN does not replay from its repr)
+# every entry point include/qcx.h lists as QCX_UNSUPPORTED on a sharded register
+REFUSED_SH = ("sample_rng", "marginal", "measure_qubits_rng", "postselect", "expect", "expect_sum", "expect_batch", "u1", "cu1", "u2",
+              "cu2", "prot", "set_stream", "events_create", "devptr")
+
+
+class ShardedConfig:
+    """shards, shape list, shape, start mode and the environment at creation of one seed of the sharded family"""
+
+    def __init__(self, seed):
+        rs = np.random.RandomState(6007 * seed + 29)
+        self.seed = seed
+        self.shards = (2, 4, 8)[(seed // 3) % 3]
+        self.kind = ("ordinary", "tiny", "compact" if (seed // 3) % 2 == 0 else ("ordinary", "tiny")[(seed // 6) % 2])[seed % 3]
+        shapes = SH_SHAPES[self.kind][self.shards]
+        self.shape = shapes[(seed // 9) % len(shapes)]
+        self.k = self.shards.bit_length() - 1
+        self.n = self.shape[0] + self.shape[1]
+        self.n_local = self.n - self.k
+        self.compact = 4 <= self.shape[1] <= 12 and self.n_local >= self.shape[1] + 6      # sh_compact's condition
+        self.mode = int(rs.choice([-1, 0, 1]))
+        self.env = {}
+        sl, ov = int(rs.randint(0, 4)), int(rs.randint(0, 3))
+        if sl: self.env["QCX_SHARD_SLICES_LOG2"] = str((0, 0, 2, 3)[sl])
+        if ov: self.env["QCX_SHARD_OVERLAP"] = str(ov - 1)
+        if (seed + seed // 6) % 6 == 4: self.env["QCX_SHARD_FORCE_STAGED"] = "1"     # (staggered: seeds of every shape list)
+        # one relay set right after creation for one seed in six, over the three shape lists: 0, 18, 36 ordinary, 13, 31 tiny,
+        # 8, 26, 44 compact on 8 shards (where the relay is really set up: smaller trade zones are not striped); five seeds of
+        # the compact list start without
+        self.relays = int(seed % 6 == (0, 2, 1)[(seed // 6) % 3])
+
+    def __repr__(self):
+        return (f"sharded seed {self.seed}: {self.shards} shards, {self.kind} shape (L, M, C, a) {self.shape} start mode {self.mode} "
+                f"environment {self.env} relays {self.relays}")
+
+
+def sh_pair_is_legal(s, f, cfg):
+    if s == "compact" and not cfg.compact:
+        return False
+    if f in ("camodc", "qcomp") and cfg.shape[1] == 0:
+        return False
+    return True
+
+
+def _sh_schedule():
+    """every legal (state-setting kind, following kind) pair of the sharded family three times, dealt round-robin to the seeds
+    whose register allows it, evenly"""
+    cfgs = [ShardedConfig(s) for s in range(NSEEDS_SH)]
+    out = [[] for _ in cfgs]
+    at = 0
+    for _ in range(3):
+        for s in SETTING_SH:
+            for f in FOLLOWING_SH:
+                legal = [c.seed for c in cfgs if sh_pair_is_legal(s, f, c)]
+                seed = min(legal, key=lambda k: (len(out[k]), (k - at) % NSEEDS_SH))        # the seed with the fewest probes so far
+                out[seed].append((s, f))
+                at = (seed + 1) % NSEEDS_SH
+    return out
+
+
+class _ShGen(_Gen):
+    """the ops of one sharded register"""
+
+    def __init__(self, ob, cfg, rs):
+        self.cfg, self.k, self.n_local = cfg, cfg.k, cfg.n_local
+        self.refused_next = 7 * cfg.seed                # (where this seed starts in REFUSED_SH)
+        super().__init__(ob, cfg.shape, cfg.mode, rs, allow_nonfinite=False, vocab="sharded", devptr=False)
+        self.following = FOLLOWING_SH
+
+    def emit(self, op):
+        self.ops.append(op)
+        apply_to_model(self.m, op)
+        k = op[0]
+        if k == "fusion":
+            self.mode = op[1]
+        if k == "reset":
+            self.pending = self.mode >= 0
+        elif k in QUIET_SH or k in QUEUED:              # (a sharded register queues in every mode)
+            pass
+        else:
+            self.pending = False
+        if k == "save":
+            self.slots[op[1]] = True
+
+    def r(self):
+        if self.rs.randint(0, 8) == 0:
+            return str(self.rs.choice(MEASURE_EDGES))
+        return super().r()
+
+    def cleanse(self): pass                             # (no non-finite values in this family)
+
+    def window(self, cap):
+        """(first, count) of a partial window; two in three straddle a multiple of 2^n_local (a shard boundary)"""
+        rs, per = self.rs, 1 << self.n_local
+        if rs.randint(0, 3):
+            b = int(rs.randint(1, self.cfg.shards)) * per
+            first = b - int(rs.randint(1, min(b, cap // 2) + 1))
+            hi = min(self.dim - first, cap, self.dim - 1)
+            return first, int(rs.randint(b - first + 1, hi + 1))
+        first = int(rs.randint(0, self.dim - 1))
+        return first, int(rs.randint(1, min(self.dim - first, cap, self.dim - 1) + 1))
+
+    def gate(self):
+        rs = self.rs
+        k = int(rs.randint(0, 3)) if self.M else int(rs.randint(0, 2))
+        if k == 0:                                      # two Hadamards in five on one of the top k + 1 qubits
+            top = self.n - 1 - int(rs.randint(0, self.k + 1))
+            return ("h", top if rs.randint(0, 5) < 2 else int(rs.randint(0, self.n)))
+        if k == 1:
+            c, t = self.qubits(2)
+            th = float(rs.uniform(-3.2, 3.2)) if rs.randint(0, 2) else float(np.pi / (1 << int(rs.randint(1, 12))))
+            return ("cphase", c, t, th)
+        return ("camodc", self.Cn, int(rs.randint(1, 4 * self.Cn)), int(rs.randint(self.M, self.n)))
+
+    def op_of(self, f):
+        rs = self.rs
+        if f == "write":
+            fl = str(rs.choice(("plain", "negzero")))
+            if rs.randint(0, 4) == 0:
+                return ("write", 0, self.dim, self.seed(), fl)
+            return ("write", *self.window(600), self.seed(), fl)
+        if f == "read":
+            if rs.randint(0, 4) == 0:
+                return ("read", 0, self.dim)
+            return ("read", *self.window(2000))
+        if f == "relays": return ("relays", int(rs.randint(0, 2)))
+        if f in ("selfcheck", "stats"): return (f,)
+        if f == "refused": return ("refused", *self.refused())
+        return super().op_of(f)
+
+    def quiet(self):
+        c = int(self.rs.randint(0, 4))
+        return ("stats",) if c < 2 else ("selfcheck",) if c == 2 else ("refused", *self.refused())
+
+    def refused(self):
+        """(inner op, status): one of the calls a sharded register refuses (dealt in turn, so that every one occurs), arguments
+        the unsharded register would accept; one draw in eight is the BAD_QUBIT kind instead"""
+        rs, n = self.rs, self.n
+        if rs.randint(0, 8) == 0:
+            if rs.randint(0, 2) or n < 2:
+                return ("h", n), BAD_QUBIT
+            q = int(rs.randint(0, n))
+            return ("cphase", q, q, 0.5), BAD_QUBIT
+        j = REFUSED_SH[self.refused_next % len(REFUSED_SH)]
+        self.refused_next += 1
+        if j in ("cu1", "u2") and n < 2: j = "u1"
+        if j == "cu2" and n < 3: j = "u1"
+        if j == "sample_rng": inner = (j, self.seed(), int(rs.choice([1, 3, 8])))
+        elif j == "marginal": inner = (j, *self.a_range())
+        elif j == "measure_qubits_rng": inner = (j, *self.a_range(), self.seed())
+        elif j == "postselect":
+            first, num = self.a_range()
+            inner = (j, first, num, int(rs.randint(0, 1 << num)))
+        elif j == "expect": inner = (j, *draw_masks(rs, n))
+        elif j in ("expect_sum", "expect_batch"): inner = (j, self.seed(), int(rs.choice([1, 3, 6])))
+        elif j == "u1": inner = (j, int(rs.randint(0, n)), self.seed())
+        elif j in ("cu1", "u2"): inner = (j, *self.qubits(2), self.seed())
+        elif j == "cu2": inner = (j, *self.qubits(3), self.seed())
+        elif j == "prot": inner = (j, *draw_masks(rs, n), self.theta())
+        elif j == "events_create": inner = (j, int(rs.randint(1, 9)))
+        else: inner = (j,)
+        return inner, UNSUPPORTED
+
+    def setting(self, s, f):
+        rs = self.rs
+        if f == "load" and not self.slots:
+            self.emit(("save", int(rs.randint(0, 2))))
+        if s == "reset": self.emit(("reset",))
+        elif s == "measure_state": self.emit(("measure", self.r()))
+        elif s == "fill": self.emit(("fill", self.seed()))
+        elif s == "write_full_negzero": self.emit(("write", 0, self.dim, self.seed(), "negzero"))
+        elif s == "write_partial": self.emit(("write", *self.window(600), self.seed(), str(rs.choice(["plain", "negzero"]))))
+        elif s == "load":
+            if not self.slots:
+                self.emit(("save", int(rs.randint(0, 2))))
+            slot = int(rs.choice(sorted(self.slots)))
+            if rs.randint(0, 2):
+                self.emit(self.op_of(str(rs.choice(["h", "fill", "reset"]))))
+            self.emit(("load", slot))
+        elif s == "swapped_layout":                     # from the identity layout with nothing pending: the H needs a trade
+            if self.ops[-1][0] not in RESTORES_IDENTITY or self.pending:
+                self.emit(("fill", self.seed()) if rs.randint(0, 2) else ("total",))
+            self.emit(("h", self.n - 1 - int(rs.randint(0, self.k))))
+            self.emit(("flush",))
+        elif s == "queued":
+            if self.pending:
+                self.emit(("fill", self.seed()) if rs.randint(0, 2) else ("flush",))
+            for _ in range(int(rs.randint(1, 6))):
+                self.emit(self.gate())
+        elif s == "queued_behind_basis":
+            if self.mode < 0:
+                self.emit(("fusion", int(rs.choice([0, 1]))))
+            self.emit(("reset",))
+            if rs.randint(0, 2):                        # the front form: the H layer, then part of the multiply ladder
+                for l in range(self.M, self.n):
+                    self.emit(("h", l))
+                x = self.a0 % self.Cn
+                for l in range(self.M, self.M + (int(rs.randint(0, min(self.L, 3) + 1)) if self.M else 0)):
+                    self.emit(("camodc", self.Cn, x, l))
+                    x = (x * x) % self.Cn
+                if rs.randint(0, 2):
+                    self.emit(self.gate())
+            else:                                       # the other form: the basis state is written, then the gates run
+                g = self.gate()
+                while g[0] == "h":                      # (an H first would be a front of one gate)
+                    g = self.gate()
+                self.emit(g)
+                for _ in range(int(rs.randint(0, 4))):
+                    self.emit(self.gate())
+        elif s == "compact":
+            if self.mode < 0:
+                self.emit(("fusion", int(rs.choice([0, 1]))))
+            self.emit(("reset",))
+            self.emit(("qcomp", self.Cn, self.a0))
+        else:
+            raise ValueError(s)
+
+    def probe(self, s, f):
+        self.setting(s, f)
+        for _ in range(int(self.rs.choice([0, 0, 1, 2]))):
+            self.emit(self.quiet())
+        self.emit(self.op_of(f))
+
+    def refuse(self):
+        self.emit(("refused", *self.refused()))
+        self.emit(("read", *self.window(2000)))
+
+    def extra(self):
+        rs = self.rs
+        if rs.randint(0, 6) == 0:
+            self.refuse()
+            return
+        f = self.following[int(rs.randint(0, len(self.following)))]
+        if f in ("camodc", "qcomp") and self.M == 0:
+            f = "h"
+        self.emit(self.op_of(f))
+
+
+def generate_sharded(ob, seed):
+    """(ShardedConfig, ops) of one seed of the sharded family; an op of the list is (0, op tuple), as generate() gives them"""
+    cfg = ShardedConfig(seed)
+    rs = np.random.RandomState(15485863 * seed + 101)
+    g = _ShGen(ob, cfg, rs)
+    if "sharded" not in _SCHEDULE:
+        _SCHEDULE["sharded"] = _sh_schedule()
+    probes = list(_SCHEDULE["sharded"][seed])
+    rs.shuffle(probes)
+    for s, f in probes:
+        g.probe(s, f)
+        if rs.randint(0, 8) == 0:
+            g.emit(("read", 0, g.dim))
+        if rs.randint(0, 6) == 0:
+            g.refuse()
+        if rs.randint(0, 10) < 2:
+            g.extra()
+    while len(g.ops) < 40:
+        g.extra()
+    g.probe("swapped_layout", "read")                    # every list trades at least once and reads under a swapped layout
+    g.emit(("read", 0, g.dim))
+    return cfg, [(0, op) for op in g.ops]
+
+
+def sh_pairs_reached(cfg, ops):
+    """pairs_reached for one sharded register, judged on the op list alone: {(setting kind, following kind): count}, a pair
+    counting when nothing but quiet calls (QUIET_SH) stand between the two.  swapped_layout: a flush right behind an H on a
+    shard-id qubit that was queued in the identity layout with no basis state pending (that H cannot run without a trade)"""
+    L, M, Cn, a = cfg.shape
+    n, dim = L + M, 1 << (L + M)
+    mode, pending, identity = cfg.mode, False, True         # identity: the layout is known to be the identity
+    was_identity = True                                     # ... and was before the previous op
+    kinds = []
+    for i, op in enumerate(ops):
+        k, s = op[0], None
+        if k == "reset": s = "reset"
+        elif k == "measure": s = "measure_state"
+        elif k == "fill": s = "fill"
+        elif k == "load": s = "load"
+        elif k == "write":
+            if op[2] < dim: s = "write_partial"
+            elif op[4] == "negzero": s = "write_full_negzero"
+        elif k == "flush" and i and ops[i - 1][0] == "h" and ops[i - 1][1] >= n - cfg.k and was_identity and not pending:
+            s = "swapped_layout"
+        elif k == "qcomp" and i and ops[i - 1][0] == "reset" and mode >= 0 and cfg.compact: s = "compact"
+        elif k in QUEUED:
+            s = "queued_behind_basis" if pending else "queued"
+        kinds.append(s)
+        if k == "fusion": mode = op[1]
+        if k == "reset": pending = mode >= 0
+        elif k in QUIET_SH or k in QUEUED: pass
+        else: pending = False
+        was_identity = identity
+        if k in RESTORES_IDENTITY: identity = True
+        elif k in QUEUED: identity = False                  # (a queued gate may cost a trade when it runs)
+    out = {}
+    for i, s in enumerate(kinds):
+        if s is None:
+            continue
+        for op in ops[i + 1:]:
+            if op[0] in FOLLOWING_SH:
+                out[(s, op[0])] = out.get((s, op[0]), 0) + 1
+            if op[0] not in QUIET_SH:
                 break
     return out

@@ -7,7 +7,10 @@
 (b) the generator reaches what it claims: every legal (state-setting kind, following kind) pair of each vocabulary at least
     three times over that vocabulary's seeds with nothing but quiet calls in between, judged on the op lists alone; the op lists
     of vocabulary 1 are the committed ones (tests/golden/sequence_digests.json); the Pauli calls of vocabulary 2 are not vacuous
-    (masks of all three unit shapes, Y letters, values other than 0, non-finite states, rotations that change the state)."""
+    (masks of all three unit shapes, Y letters, values other than 0, non-finite states, rotations that change the state); the op
+    lists of vocabulary 2 are pinned as well.
+(c) the sharded family (register_model.generate_sharded): every legal pair of its own setting and following kinds at least three
+    times, every refused entry point, every shard count and shape list; its op lists are the committed ones."""
 import hashlib
 import json
 import os
@@ -359,3 +362,110 @@ def test_generator_is_deterministic(ob):
     assert rm.generate(ob, 3)[1] == rm.generate(ob, 3)[1]
     assert rm.generate(ob, 3)[1] != rm.generate(ob, 4)[1]
     assert rm.generate(ob, 70)[1] == rm.generate(ob, 70)[1]
+
+
+def golden_digests():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sequence_digests.json")) as f:
+        return json.load(f)
+
+
+def digest(ops):
+    return hashlib.sha256(repr(ops).encode()).hexdigest()
+
+
+def test_vocabulary_2_generates_the_committed_op_lists(ob):
+    """the seeds NSEEDS_V1 .. NSEEDS - 1 and the small seeds SMALL_V1 .. 2 SMALL_V1 - 1 are frozen like those of vocabulary 1:
+    what the GPU asserts for them cannot drift when the generator grows"""
+    golden = golden_digests()
+    assert sorted(golden["big_v2"], key=int) == [str(s) for s in rm.seeds_of(2)]
+    assert sorted(golden["small_v2"], key=int) == [str(s) for s in SMALL_SEEDS_V2]
+    drifted = [s for s in rm.seeds_of(2) if digest(generated(ob, s)[1]) != golden["big_v2"][str(s)]]
+    drifted += [("small", s) for s in SMALL_SEEDS_V2 if digest(rm.generate(ob, s, small=True, length=30)[1]) != golden["small_v2"][str(s)]]
+    assert not drifted, f"the op lists of these vocabulary-2 seeds changed: {drifted}"
+
+
+# ---- (c) the sharded family ----------------------------------------------------------------------------------------------------------
+
+_SHARDED = {}
+
+
+def sharded(ob, seed):
+    if seed not in _SHARDED:
+        _SHARDED[seed] = rm.generate_sharded(ob, seed)
+    return _SHARDED[seed]
+
+
+def test_sharded_family_reaches_every_pair(ob):
+    """the reach table of the 48 seeds (3274 ops, 48 .. 93 a seed): the fewest times a legal pair is reached is 3; 53 % of the
+    Hadamard ops fall on one of the top k + 1 qubits and 77 % of the partial windows straddle a shard boundary; every refused
+    entry point occurs 12 to 23 times; 20 ordinary, 20 tiny and 8 compact seeds, 18 / 15 / 15 seeds on 2 / 4 / 8 shards"""
+    total, lengths, calls, refused, lists, counts = {}, [], {}, {}, {}, {}
+    hs, windows = [0, 0], [0, 0]
+    for seed in range(rm.NSEEDS_SH):
+        cfg, ops = sharded(ob, seed)
+        assert eval(repr(ops)) == ops, "an op list must replay from its printed form"
+        mine = [op for _, op in ops]
+        lengths.append(len(mine))
+        lists[cfg.kind] = lists.get(cfg.kind, 0) + 1
+        counts[cfg.shards] = counts.get(cfg.shards, 0) + 1
+        assert cfg.shape in rm.SH_SHAPES[cfg.kind][cfg.shards]
+        assert (cfg.n_local < 2 * cfg.k + 6) == (cfg.kind == "tiny"), cfg
+        assert cfg.compact or cfg.kind != "compact", cfg
+        for pair, cnt in rm.sh_pairs_reached(cfg, mine).items():
+            total[pair] = total.get(pair, 0) + cnt
+        full = sum(1 for op in mine if op[0] == "read" and op[2] == 1 << cfg.n)
+        assert mine[-1] == ("read", 0, 1 << cfg.n) and full <= len(mine) // 3, (seed, full, len(mine))
+        per = 1 << cfg.n_local
+        for op in mine:
+            calls[op[0]] = calls.get(op[0], 0) + 1
+            if op[0] == "h":
+                hs[0] += 1
+                hs[1] += op[1] >= cfg.n - cfg.k - 1
+            elif op[0] in ("read", "write") and op[2] < 1 << cfg.n:
+                windows[0] += 1
+                windows[1] += op[1] // per != (op[1] + op[2] - 1) // per
+            elif op[0] == "refused":
+                refused[op[1][0]] = refused.get(op[1][0], 0) + 1
+                assert op[2] == (rm.BAD_QUBIT if op[1][0] in ("h", "cphase") else rm.UNSUPPORTED)
+            elif op[0] == "fusion":
+                assert op[1] in (-1, 0, 1), "no mode 2"
+            elif op[0] == "write":
+                assert op[4] in ("plain", "negzero"), "no Inf / NaN writes on a sharded register"
+    cfgs = [rm.ShardedConfig(k) for k in range(rm.NSEEDS_SH)]
+    legal = [(s, f) for s in rm.SETTING_SH for f in rm.FOLLOWING_SH if any(rm.sh_pair_is_legal(s, f, c) for c in cfgs)]
+    print(f"sharded family, seeds 0 .. {rm.NSEEDS_SH - 1}; ops per seed: {min(lengths)} .. {max(lengths)}, {sum(lengths)} in all")
+    print(" " * 20 + " ".join(f"{f[:6]:>6}" for f in rm.FOLLOWING_SH))
+    for s in rm.SETTING_SH:
+        print(f"{s:20}" + " ".join(f"{total.get((s, f), 0):6d}" if (s, f) in legal else "     -" for f in rm.FOLLOWING_SH))
+    print("calls: " + ", ".join(f"{k} {calls.get(k, 0)}" for k in rm.FOLLOWING_SH))
+    print(f"refused: {refused}\nH ops {hs[0]}, on the top k + 1 qubits {hs[1]}; partial windows {windows[0]}, across a shard boundary {windows[1]}")
+    print(f"shape lists {lists}, shard counts {counts}; fewest times a legal pair is reached: {min(total.get(p, 0) for p in legal)}")
+    short = [(p, total.get(p, 0)) for p in legal if total.get(p, 0) < 3]
+    assert not short, f"pairs reached fewer than 3 times: {short}"
+    assert len(legal) == len(rm.SETTING_SH) * len(rm.FOLLOWING_SH) and (len(rm.SETTING_SH), len(rm.FOLLOWING_SH)) == (10, 21)
+    assert all(refused.get(j, 0) >= 2 for j in rm.REFUSED_SH + ("h", "cphase")), refused
+    assert all(lists.get(k, 0) >= 6 for k in rm.SH_SHAPES) and all(counts.get(w, 0) >= 6 for w in (2, 4, 8))
+    assert {(c.kind, c.shards) for c in cfgs} >= {(k, w) for k in rm.SH_SHAPES for w in (2, 4, 8)}
+    assert 3 * hs[1] >= hs[0], "at least a third of the Hadamards target one of the top k + 1 qubits"
+    assert 2 * windows[1] >= windows[0], "at least half of the partial windows straddle a multiple of 2^n_local"
+    assert 40 <= min(lengths) and max(lengths) < 100, lengths
+    assert any(c.kind == "compact" and c.relays and c.shards == 8 for c in cfgs), "a compact seed whose relay is really set up"
+    assert {c.kind for c in cfgs if c.relays} == set(rm.SH_SHAPES) and sum(1 for c in cfgs if c.relays) == rm.NSEEDS_SH // 6
+    assert sum(1 for c in cfgs if c.kind == "compact" and not c.relays) >= 3, "compact seeds that start without relays"
+    assert max(c.n for c in cfgs) <= 16
+    assert sum(1 for c in cfgs if "QCX_SHARD_FORCE_STAGED" in c.env) == rm.NSEEDS_SH // 6
+    edges = {op[1] for seed in range(rm.NSEEDS_SH) for _, op in sharded(ob, seed)[1] if op[0] == "measure" and isinstance(op[1], str)}
+    assert edges == set(rm.MEASURE_EDGES), edges
+
+
+def test_sharded_family_generates_the_committed_op_lists(ob):
+    golden = golden_digests()
+    assert sorted(golden["sharded"], key=int) == [str(s) for s in range(rm.NSEEDS_SH)]
+    drifted = [s for s in range(rm.NSEEDS_SH) if digest(sharded(ob, s)[1]) != golden["sharded"][str(s)]]
+    assert not drifted, f"the op lists of these seeds of the sharded family changed: {drifted}"
+
+
+def test_sharded_generator_is_deterministic(ob):
+    assert rm.generate_sharded(ob, 7)[1] == rm.generate_sharded(ob, 7)[1]
+    assert rm.generate_sharded(ob, 7)[1] != rm.generate_sharded(ob, 8)[1]
+    assert repr(rm.ShardedConfig(7)) == repr(rm.ShardedConfig(7))
