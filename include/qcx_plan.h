@@ -1,8 +1,9 @@
 /*
  * qcx_plan.h -- the fused-pass PLANNER of libqcx.so on its own, host code only (no GPU needed).  A test and tooling
  * interface: the CPU-only suite plans gate lists, interprets the returned records with a numpy restatement of the pass
- * kernels (tests/fuse_emulator.py) and compares with the oracle; tools/plan_cost.py prices plans.  Nothing a user of the
- * gate engine needs.
+ * kernels (tests/fuse_emulator.py) and compares with the oracle; tools/plan_cost.py prices plans.  Every pass comes with
+ * the launch it would get -- kernel instantiation, grid, block, LDS bytes -- and qcx_pass_launch_plan answers that question
+ * for one pass on its own (tests/test_pass_launch_plan.py).  Nothing a user of the gate engine needs.
  */
 #ifndef QCX_PLAN_H
 #define QCX_PLAN_H
@@ -45,6 +46,11 @@ typedef struct {
     unsigned char tl[16], in_pos[16], st_loc[16], st_pos[16];
     unsigned char nseg_in, nseg_out, nseg_lg, pad_;
     struct { unsigned char src, dst, len, pad; } seg_in[16], seg_out[16], seg_lg[16];
+    /* how the pass would be launched (qcx_pass_launch_plan below, under the knobs of the moment, in place or chained as planned):
+     * the kernel instantiation as a kernel trace spells it, e.g. "k_fused_x8<512, 12, false, false>", its grid and block, and
+     * the dynamic LDS of a workgroup.  kernel = "" when the launch would be refused. */
+    char     kernel[64];
+    unsigned grid, block, lds_bytes;
 } qcx_plan_action;
 int  qcx_fusion_plan(unsigned n_local, unsigned M, unsigned count, const qcx_gate_desc *gates,
                      qcx_plan_action *actions, unsigned max_actions, unsigned *n_actions,
@@ -54,6 +60,36 @@ int  qcx_fusion_plan(unsigned n_local, unsigned M, unsigned count, const qcx_gat
 int  qcx_fusion_plan_mode(int mode, unsigned n_local, unsigned M, unsigned count, const qcx_gate_desc *gates,
                           qcx_plan_action *actions, unsigned max_actions, unsigned *n_actions,
                           qcx_fuse_record *records, size_t max_records, size_t *n_records);
+
+/* The launch of one fused pass, decided on the host: which kernel instantiation interprets the pass's records, with which grid,
+ * block and dynamic LDS layout.  qcx_pass_launch_in is everything that decision reads: the fields below of the pass as planned
+ * (FusePass, csrc/qcx_kernels.h) -- a flush adds gen, zskip, zpad, gen_tab_bytes and xp_on to what the planner sets -- the
+ * register's shape, and what the launch knows about its buffers; plus the knobs of the moment (qcx_tune_set). */
+typedef struct {
+    unsigned n, M;                  /* the register: n index bits, the low M of them the M register */
+    unsigned T;                     /* tile = 2^T amplitudes */
+    unsigned rounds_form;           /* records in ROUNDS form */
+    unsigned table_bytes;           /* folded modular-multiply tables behind the records */
+    unsigned has_cam;               /* the pass holds modular multiplies */
+    unsigned xm_cnt;                /* records whose outside-tile masks go to LDS */
+    unsigned dg_cnt, dg_slim;       /* merged diagonals; 1: fast rounds only, 2: radix-8 fast rounds, 3: the exact walk on 8 amplitudes */
+    unsigned chained;               /* reads one buffer, writes the other */
+    unsigned gen;                   /* 1: tiles generated, 2 / 3: by columns (3: of a compact chain) */
+    unsigned gen_tab_bytes, zpad;   /* by columns: the residue -> column table, the padded column count */
+    unsigned zskip;
+    unsigned xp_on;                 /* the expanding store of a compact chain's last pass */
+    unsigned tables_cover;          /* the addressing tables deposit all n - T bits of the tile number */
+    unsigned buffers_differ;        /* the launch got two different buffers */
+} qcx_pass_launch_in;
+typedef struct {
+    char     kernel[64];            /* as in qcx_plan_action */
+    unsigned grid, block, lds_bytes;
+    unsigned waves;                 /* k_gen_cols: waves per workgroup (else 0) */
+    unsigned xm_off, dg_lds_off, gen_lds_off, table_lds_off, dbg;   /* the FusePass fields the launch fills in (table_lds_off: cam_ctl_local[3]) */
+    unsigned expanding_store_ok;    /* could this pass take the expanding store (asked of the pass with xp_on = 0, in place)? */
+} qcx_pass_launch_out;
+/* QCX_NO_ERROR and *out, or the status of the refusal with its text in qcx_last_error() (out->expanding_store_ok is set either way) */
+int  qcx_pass_launch_plan(const qcx_pass_launch_in *in, qcx_pass_launch_out *out);
 
 /* The stage plan of qcx_marginal_probabilities (include/qcx.h; K10, DESIGN s4.5d), on the host.  The marginal sums the bits
  * outside [first, first + num) as one pairwise tree, lowest summed bit first; each stage reduces the lowest summed bits that

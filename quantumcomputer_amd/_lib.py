@@ -119,6 +119,7 @@ SIGNATURES = {
     "qcx_state_load": (_i, [_p, C.c_char_p]),
     "qcx_fusion_plan": (_i, [_u, _u, _u, _p, _p, _u, C.POINTER(_u), _p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "qcx_fusion_plan_mode": (_i, [_i, _u, _u, _u, _p, _p, _u, C.POINTER(_u), _p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "qcx_pass_launch_plan": (_i, [_p, _p]),
     "qcx_shard_measure_scan": (_i, [_p, _u, _u64, _u64, _d, _d, C.POINTER(_i), C.POINTER(_u64), C.POINTER(_d), _p]),
     "qcx_shard_collapse": (_i, [_p, _u, _i64, _p]),
     "qcx_shard_canon_zeros": (_i, [_p, _u, _p]),
@@ -181,7 +182,28 @@ class PlanAction(C.Structure):
                 ("table_rec_off", C.c_uint), ("diag_cnt", C.c_uint), ("diag_rec_off", C.c_uint),
                 ("chained", C.c_uint), ("tl", C.c_ubyte * 16), ("in_pos", C.c_ubyte * 16), ("st_loc", C.c_ubyte * 16),
                 ("st_pos", C.c_ubyte * 16), ("nseg_in", C.c_ubyte), ("nseg_out", C.c_ubyte), ("nseg_lg", C.c_ubyte), ("pad_", C.c_ubyte),
-                ("seg_in", C.c_ubyte * 64), ("seg_out", C.c_ubyte * 64), ("seg_lg", C.c_ubyte * 64)]      # segments: (src, dst, len, pad) x 16
+                ("seg_in", C.c_ubyte * 64), ("seg_out", C.c_ubyte * 64), ("seg_lg", C.c_ubyte * 64),      # segments: (src, dst, len, pad) x 16
+                ("kernel", C.c_char * 64), ("grid", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint)]     # the launch (qcx_pass_launch_plan)
+
+
+class PassLaunchIn(C.Structure):
+    """qcx_pass_launch_in (include/qcx_plan.h): what the launch of a fused pass depends on"""
+    _fields_ = [(k, C.c_uint) for k in ("n", "M", "T", "rounds_form", "table_bytes", "has_cam", "xm_cnt", "dg_cnt", "dg_slim", "chained", "gen",
+                                        "gen_tab_bytes", "zpad", "zskip", "xp_on", "tables_cover", "buffers_differ")]
+
+
+class PassLaunchOut(C.Structure):
+    """qcx_pass_launch_out (include/qcx_plan.h)"""
+    _fields_ = [("kernel", C.c_char * 64)] + [(k, C.c_uint) for k in ("grid", "block", "lds_bytes", "waves", "xm_off", "dg_lds_off", "gen_lds_off",
+                                                                      "table_lds_off", "dbg", "expanding_store_ok")]
+
+
+def pass_launch_plan(**fields):
+    """How one fused pass would be launched under the knobs of the moment (host code, no GPU needed): (status, PassLaunchOut,
+    the refusal's text or "")."""
+    I, O = PassLaunchIn(**fields), PassLaunchOut()
+    st = lib().qcx_pass_launch_plan(C.byref(I), C.byref(O))
+    return st, O, (lib().qcx_last_error().decode() if st else "")
 
 
 MARGINAL_MAX_STAGES = 8     # QCX_MARGINAL_MAX_STAGES (include/qcx_plan.h)

@@ -1721,8 +1721,30 @@ extern "C" int qcx_fusion_plan_mode(int mode, unsigned n_local, unsigned M, unsi
         o.nseg_in = a.P.nseg_in; o.nseg_out = a.P.nseg_out; o.nseg_lg = a.P.nseg_lg;
         static_assert(sizeof o.seg_in == sizeof a.P.seg_in, "segment layout");
         memcpy(o.seg_in, a.P.seg_in, sizeof o.seg_in); memcpy(o.seg_out, a.P.seg_out, sizeof o.seg_out); memcpy(o.seg_lg, a.P.seg_lg, sizeof o.seg_lg);
+        PassLaunch L;
+        if (pass_launch_plan(pass_launch_in(a.P, n_local, M, a.P.chained != 0), tn, L) == QCX_NO_ERROR) {
+            snprintf(o.kernel, sizeof o.kernel, "%s", pass_kernel_text(L.kernel));
+            o.grid = L.grid; o.block = L.block; o.lds_bytes = (unsigned)L.lds;
+        }
     }
     if (!ops.empty()) memcpy(records, ops.data(), ops.size() * sizeof(FuseOp));
+    return QCX_NO_ERROR;
+}
+
+// The launch plan of one pass on its own (include/qcx_plan.h): pass_launch_plan under the knobs of the moment.
+extern "C" int qcx_pass_launch_plan(const qcx_pass_launch_in *in, qcx_pass_launch_out *out)
+{
+    if (!in || !out || in->n == 0 || in->n > 40) return QCX_BAD_ARGUMENTS;
+    memset(out, 0, sizeof *out);
+    qcx_pass_launch_in I = *in;
+    if (I.T > I.n) I.tables_cover = 0;
+    const Tune tn = tune_now();
+    out->expanding_store_ok = pass_expanding_store_ok(I, tn);
+    PassLaunch L;
+    if (pass_launch_plan(I, tn, L) != QCX_NO_ERROR) { set_error("%s", L.err); return QCX_UNKNOWN_ERROR; }
+    snprintf(out->kernel, sizeof out->kernel, "%s", pass_kernel_text(L.kernel));
+    out->grid = L.grid; out->block = L.block; out->lds_bytes = (unsigned)L.lds; out->waves = L.waves;
+    out->xm_off = L.xm_off; out->dg_lds_off = L.dg_lds_off; out->gen_lds_off = L.gen_lds_off; out->table_lds_off = (unsigned)L.table_lds_off; out->dbg = L.dbg;
     return QCX_NO_ERROR;
 }
 

@@ -666,176 +666,203 @@ static void to_rounds(const Tune &tn, const std::vector<FuseOp> &legacy, unsigne
     if (x8 || (maxrb == 3 && T == 12)) x8_assign_maps(out, out_first, T, tn);
 }
 
-// the rounds-only kernel, built for 6, 7 or 8 waves per SIMD; false when the geometry has no rounds form
-template <int B, int TT>
-static bool launch_rounds_kernel(int occ, int tol_occ, unsigned grid, size_t lds, hipStream_t st, const amp_t *amp, amp_t *amp_out, unsigned n, const FusePass &P,
-                                 const FuseOp *d_ops, uint64_t ntiles)
+// ---- the launch of a pass: plan (pure host code: kernel, grid, LDS layout), then dispatch ------------------------------------
+// Every instantiation of the pass kernels, once: X(kernel, template arguments in the template's order).  launch_pass
+// dispatches over this list and pass_kernel_text spells it; nothing else instantiates a pass kernel.
+// k_fused_rounds exists where a thread holds 4 amplitudes (block = 2^TT / 4), built for 6, 7 or 8 waves per SIMD:
+// <BLOCK, TT, OCC, CAM, TOL, GEN>, TOL 1 = the pass holds merged diagonals (K6t), 2 = and every round is a fast round (slim
+// kernel); GEN = the tiles are generated (circuit front on an unwritten basis state): passes without multiplies only.
+// (round 5: no 8-wave build of the kernels that hold the walk any more.  Its 16 record SGPRs lay beyond the allocator's
+//  budget there -- hipcc: "reserved registers" on the clobber list -- and with 96 SGPRs a CU admits 7 blocks of 256 threads,
+//  not 8, anyway; measured 11.81 (8) / 11.95 (7) / 11.89 (6) ms on the n = 28 inverse QFT, 12.71 / 12.53 on the n = 30
+//  Shor circuit: no difference beyond the noise between boxes.  profiles/r05_occupancy.txt)
+#define QCX_ROUNDS_KERNELS(X, B, TT) \
+    X(k_fused_rounds, B, TT, 8, false, 2, true) X(k_fused_rounds, B, TT, 6, false, 2, true) X(k_fused_rounds, B, TT, 6, false, 1, true) X(k_fused_rounds, B, TT, 7, false, 0, true) X(k_fused_rounds, B, TT, 6, false, 0, true) \
+    X(k_fused_rounds, B, TT, 8, true, 2, false) X(k_fused_rounds, B, TT, 8, false, 2, false) X(k_fused_rounds, B, TT, 6, true, 2, false) X(k_fused_rounds, B, TT, 6, false, 2, false) X(k_fused_rounds, B, TT, 6, true, 1, false) \
+    X(k_fused_rounds, B, TT, 6, false, 1, false) X(k_fused_rounds, B, TT, 7, true, 0, false) X(k_fused_rounds, B, TT, 7, false, 0, false) X(k_fused_rounds, B, TT, 6, true, 0, false) X(k_fused_rounds, B, TT, 6, false, 0, false)
+// k_fused<BLOCK, TT, LDSDMA>: 4 amplitudes per thread (all loads of a tile in flight at once, few registers): block = 2^T / 4.
+// Registers of the reference's own sizes (n = 5 ... 8: the whole state is one tile): one wave, everything known at compile time
+// (the generic kernel <256, 0> took 60 us for the 13 gates of the C = 15, L = 3, M = 4 circuit; these take ~10)
+#define QCX_PASS_KERNELS(X) \
+    X(k_fused_x8, 512, 12, true, false) X(k_fused_x8, 512, 12, false, false) X(k_fused_x8, 256, 11, true, false) X(k_fused_x8, 256, 11, false, false) \
+    X(k_fused_x8, 128, 10, true, false) X(k_fused_x8, 128, 10, false, false) X(k_gen_cols, 6, true) X(k_gen_cols, 6, false) X(k_fused_x8, 512, 12, false, true) \
+    X(k_fused_q3, 512, 12, 4, false, true) X(k_fused_q3, 512, 12, 4, true, true) X(k_fused_q3, 512, 12, 4, false, false) X(k_fused_q3, 512, 12, 4, true, false) \
+    QCX_ROUNDS_KERNELS(X, 1024, 12) X(k_fused, 1024, 12, true) X(k_fused, 1024, 12, false) \
+    QCX_ROUNDS_KERNELS(X, 512, 11)  X(k_fused, 512, 11, true)  X(k_fused, 512, 11, false) \
+    QCX_ROUNDS_KERNELS(X, 256, 10)  X(k_fused, 256, 10, true)  X(k_fused, 256, 10, false) \
+    X(k_fused, 256, 9, true) X(k_fused, 256, 9, false) X(k_fused, 64, 8, false) X(k_fused, 64, 7, false) X(k_fused, 64, 6, false) X(k_fused, 64, 5, false) X(k_fused, 256, 0, false)
+// ... and the arguments each family takes (launch_pass's names)
+#define QCX_ARGS_k_fused        amp_in, n, P, d_ops, ntiles, d_ops
+#define QCX_ARGS_k_fused_rounds amp_in, amp_out, n, P, d_ops, ntiles, d_ops
+#define QCX_ARGS_k_fused_x8     amp_in, amp_out, n, P, d_ops, ntiles, d_ops
+#define QCX_ARGS_k_fused_q3     amp_in, amp_out, n, P, d_ops, ntiles
+#define QCX_ARGS_k_gen_cols     amp_out, n, P, d_ops, ntiles, d_ops
+
+// one instantiation as a value: the family and its template arguments, in the template's order
+enum PassFamily { PK_k_fused = 1, PK_k_fused_rounds, PK_k_fused_q3, PK_k_fused_x8, PK_k_gen_cols };
+typedef uint64_t PassKernel;
+static constexpr PassKernel pass_kernel(PassFamily f, uint64_t a0, uint64_t a1 = 0, uint64_t a2 = 0, uint64_t a3 = 0, uint64_t a4 = 0, uint64_t a5 = 0)
+{ return f | a0 << 3 | a1 << 14 | a2 << 18 | a3 << 22 | a4 << 26 | a5 << 30; }
+static PassFamily pass_kernel_family(PassKernel k) { return (PassFamily)(k & 7u); }
+
+// as a kernel trace spells it (the planner interface only: no launch builds the text)
+static const char *pass_kernel_text(PassKernel k)
 {
-    if constexpr ((1u << TT) == 4u * B) {
-        const bool cam = P.has_cam != 0;
-        if (P.gen) {          // the tiles are generated (circuit front on an unwritten basis state): passes without multiplies only
-#define QCX_GEN_LAUNCH(O, S) hipLaunchKernelGGL((k_fused_rounds<B, TT, O, false, S, true>), dim3(grid), dim3(B), lds, st, amp, amp_out, n, P, d_ops, ntiles, d_ops)
-            if (P.dg_cnt) { if (P.dg_slim) { if (tol_occ >= 8) QCX_GEN_LAUNCH(8, 2); else QCX_GEN_LAUNCH(6, 2); } else QCX_GEN_LAUNCH(6, 1); }
-            else if (occ >= 7) QCX_GEN_LAUNCH(7, 0);
-            else QCX_GEN_LAUNCH(6, 0);
-#undef QCX_GEN_LAUNCH
-            return true;
-        }
-        if (P.dg_cnt) {       // tolerance mode: the pass holds merged diagonals (K6t); 2 = every round is a fast round (slim kernel)
-#define QCX_TOL_LAUNCH(O, C, S) hipLaunchKernelGGL((k_fused_rounds<B, TT, O, C, S>), dim3(grid), dim3(B), lds, st, amp, amp_out, n, P, d_ops, ntiles, d_ops)
-            if (P.dg_slim) {
-                if (tol_occ >= 8) { if (cam) QCX_TOL_LAUNCH(8, true, 2); else QCX_TOL_LAUNCH(8, false, 2); }
-                else { if (cam) QCX_TOL_LAUNCH(6, true, 2); else QCX_TOL_LAUNCH(6, false, 2); }
-            } else { if (cam) QCX_TOL_LAUNCH(6, true, 1); else QCX_TOL_LAUNCH(6, false, 1); }
-#undef QCX_TOL_LAUNCH
-            return true;
-        }
-#define QCX_ROUNDS_LAUNCH(O, C) hipLaunchKernelGGL((k_fused_rounds<B, TT, O, C>), dim3(grid), dim3(B), lds, st, amp, amp_out, n, P, d_ops, ntiles, d_ops)
-        // (round 5: no 8-wave build of the kernels that hold the walk any more.  Its 16 record SGPRs lay beyond the allocator's
-        //  budget there -- hipcc: "reserved registers" on the clobber list -- and with 96 SGPRs a CU admits 7 blocks of 256 threads,
-        //  not 8, anyway; measured 11.81 (8) / 11.95 (7) / 11.89 (6) ms on the n = 28 inverse QFT, 12.71 / 12.53 on the n = 30
-        //  Shor circuit: no difference beyond the noise between boxes.  profiles/r05_occupancy.txt)
-        if (occ >= 7) { if (cam) QCX_ROUNDS_LAUNCH(7, true); else QCX_ROUNDS_LAUNCH(7, false); }
-        else { if (cam) QCX_ROUNDS_LAUNCH(6, true); else QCX_ROUNDS_LAUNCH(6, false); }
-#undef QCX_ROUNDS_LAUNCH
-        return true;
-    } else {
-        (void)occ; (void)tol_occ; (void)grid; (void)lds; (void)st; (void)amp; (void)amp_out; (void)n; (void)P; (void)d_ops; (void)ntiles;
-        return false;
+    switch (k) {
+#define X(NAME, ...) case pass_kernel(PK_##NAME, __VA_ARGS__): return #NAME "<" #__VA_ARGS__ ">";
+    QCX_PASS_KERNELS(X)
+#undef X
+    default: return "";
     }
 }
+
+// A workgroup's dynamic LDS: the tile (k_gen_cols: the columns) in front, then the areas in the order they are added, each at
+// its alignment.  The kernels find an area by its offset BEHIND the front (FusePass::xm_off, dg_lds_off, gen_lds_off, cam_ctl_local[3]).
+struct LdsAreas {
+    size_t front, behind = 0;
+    uint32_t add(size_t bytes, size_t align) { const size_t at = (behind + align - 1) & ~(align - 1); behind = at + bytes; return (uint32_t)at; }
+};
+static size_t lds_scratch_bytes(bool has_cam, unsigned M) { return has_cam ? cam_lut_bytes(M) : 16; }      // scratch of the modular-multiply steps (a pass without multiplies carries none: see emit)
+static size_t lds_mask_bytes(size_t records) { return 8 * (records + 66); }       // the records' outside-tile masks (phase runs), padded: lanes look up to 64 entries past a run
+static size_t lds_diag_bytes(size_t diagonals) { return 16 * diagonals * 49; }    // tolerance mode: E_out slots and G tables of the merged diagonals
+// the generated fill's slot tables (2 x 1024 entries of 2 B; 2 x 512 for the radix-8 kernel k_fused_q3, whose two workgroups per CU have no room for more)
+static size_t lds_gen_bytes(unsigned dg_slim) { return 2 * (dg_slim == 2 ? 512 : 1024) * sizeof(unsigned short); }
 
 static bool pass_tables_cover(const FusePass &P, unsigned n);
-
-// does launch_pass hand this pass to k_fused_x8<512, 12> (exact walk on 8 amplitudes, or its tolerance round)?  The only kernel
-// with the expanding store of a compact chain's last pass.
-static bool pass_is_x8(const FusePass &P, const Tune &tn)
+static qcx_pass_launch_in pass_launch_in(const FusePass &P, unsigned n, unsigned M, bool buffers_differ)
 {
-    if (P.T != 12 || P.gen || P.has_cam || P.zskip || !tn.fuse_ldsdma) return false;
-    return P.dg_slim == 3 || (P.dg_slim == 2 && P.dg_cnt && tn.fuse_x8t);
+    return qcx_pass_launch_in{n, M, P.T, (unsigned)P.cam_ctl_local[0], (unsigned)P.cam_ctl_local[1], P.has_cam, P.xm_cnt, P.dg_cnt, P.dg_slim, P.chained, P.gen,
+                              P.gen_tab_bytes, P.zpad, P.zskip, P.xp_on, pass_tables_cover(P, n), buffers_differ};
 }
 
-// amp_in / amp_out: the buffer the pass reads / writes (the same for a pass that works in place; a chained pass goes from one of
-// the register's two buffers to the other)
-static int launch_pass(qcx_register *r, const Tune &tn, const FusePass &P_in, const FuseOp *d_ops, bool nopipe, amp_t *amp_in, amp_t *amp_out)
+struct PassLaunch {
+    PassKernel kernel;
+    unsigned grid, block, waves;        // waves: of a k_gen_cols workgroup
+    size_t   lds;                       // dynamic LDS bytes
+    uint32_t xm_off, dg_lds_off, gen_lds_off, dbg;      // the FusePass fields the launch fills in ...
+    int32_t  table_lds_off;                             // ... and cam_ctl_local[3]
+    char     err[96];                   // the refusal's text
+};
+static bool pass_expanding_store_ok(qcx_pass_launch_in I, const Tune &tn);
+
+// How a pass is launched; no HIP call, nothing read but I and tn.  QCX_NO_ERROR, or the refusal's status with L.err.
+static int pass_launch_plan(const qcx_pass_launch_in &I, const Tune &tn, PassLaunch &L)
 {
-    (void)nopipe;
-    FusePass P = P_in;
-    if (!P.xp_on && (P.chained != 0) != (amp_in != amp_out)) { set_error("fused pass: chained flag and buffers disagree"); return QCX_UNKNOWN_ERROR; }
-    if (P.xp_on && !pass_is_x8(P, tn)) { set_error("expanding store on a pass that is not a k_fused_x8 pass"); return QCX_UNKNOWN_ERROR; }
-    const unsigned n = r->n;
-    if (!pass_tables_cover(P, n)) { set_error("fused pass: the addressing tables do not cover the %u tile-number bits", n - P.T); return QCX_UNKNOWN_ERROR; }
-    const uint64_t ntiles = (uint64_t)1 << (n - P.T);
-    const unsigned grid = grid_for(ntiles, 1, tn.fuse_grid_cap);
-    const size_t lut_only = P.has_cam ? cam_lut_bytes((unsigned)r->M) : 16;        // scratch of the modular-multiply steps
-    size_t lut_bytes = lut_only + (size_t)P.cam_ctl_local[1];                      // + tables of folded multiply runs
-    P.xm_off = 0;
-    P.dbg = (uint32_t)tn.fuse_dbg & 0xffu;
-    {   // which tile a workgroup takes (fuse_stream_tile): memory-bound radix-8 passes (Hadamard sweeps, the tolerance mode's fast
-        // rounds) put the XCD number on tile-number bits 3-5 -- one XCD then stores 2^3 neighbouring runs back to back (n = 30
-        // sweep -6 %, n = 28 tolerance inverse QFT -1.6 %); the exact phase walk (FP64-bound) measures the same either way and
-        // keeps t = b (profiles/r05_streams.txt)
-        const bool membound = P.dg_slim == 2 && !P.gen;
-        long sl = tn.fuse_streams_log2 >= 0 ? tn.fuse_streams_log2 : (membound ? 3 : 0);
-        long pos1 = tn.fuse_streams_pos >= 0 ? tn.fuse_streams_pos : (membound ? 4 : 0);
-        sl = std::min<long>(std::min<long>(sl, 15), (long)(n - P.T));
-        P.dbg = (P.dbg & 0xfffu) | ((uint32_t)sl << 12) | (((uint32_t)pos1 & 31u) << 16);
-    }
-    if ((P.dg_cnt || P.dg_slim == 2) && !P.has_cam) { lut_bytes = 16; P.cam_ctl_local[3] = 16; }       // tolerance-mode pass without multiplies: no scratch
-    if (P.dg_slim == 3) {                 // the exact walk on 8 amplitudes per thread (k_fused_x8): the tile, then the records' outside-tile masks
-        if (P.T < 10 || P.T > 12 || P.has_cam || P.gen > 1 || P.zskip || !tn.fuse_ldsdma) { set_error("radix-8 exact pass: unsupported shape (T = %u)", P.T); return QCX_UNKNOWN_ERROR; }
-        P.xm_off = 0;
-        size_t lds8 = ((size_t)16 << P.T) + 8 * ((size_t)P.xm_cnt + 66);
-        if (P.gen) { P.gen_lds_off = (uint32_t)((8 * ((size_t)P.xm_cnt + 66) + 15) & ~(size_t)15); lds8 = ((size_t)16 << P.T) + P.gen_lds_off + 2 * 1024 * sizeof(unsigned short); }
-        const unsigned grid8 = grid_for(ntiles, 1, tn.fuse_x8_cap);
-#define QCX_X8_LAUNCH(B, TTv) do { \
-        if (P.gen) hipLaunchKernelGGL((k_fused_x8<B, TTv, true>), dim3(grid8), dim3(B), lds8, r->stream, amp_in, amp_out, n, P, d_ops, ntiles, d_ops); \
-        else hipLaunchKernelGGL((k_fused_x8<B, TTv, false>), dim3(grid8), dim3(B), lds8, r->stream, amp_in, amp_out, n, P, d_ops, ntiles, d_ops); } while (0)
-        switch (P.T) {
-        case 12: QCX_X8_LAUNCH(512, 12); break;
-        case 11: QCX_X8_LAUNCH(256, 11); break;
-        default: QCX_X8_LAUNCH(128, 10); break;
-        }
-#undef QCX_X8_LAUNCH
-        HIP_TRY(hipGetLastError());
-        return QCX_NO_ERROR;
-    }
-    if (P.xm_cnt && !P.dg_slim) {                                                  // + the records' outside-tile masks (phase runs)
-        P.xm_off = (uint32_t)((lut_bytes + 7) & ~(size_t)7);
-        lut_bytes = P.xm_off + 8 * ((size_t)P.xm_cnt + 66);          // padded: lanes look up to 64 entries past a run
-    }
-    P.dg_lds_off = 0;
-    if (P.dg_cnt) {                                                                // + tolerance mode: E_out slots and G tables of the merged diagonals
-        P.dg_lds_off = (uint32_t)((lut_bytes + 15) & ~(size_t)15);
-        lut_bytes = P.dg_lds_off + 16 * (size_t)P.dg_cnt * 49;
-    }
-    P.gen_lds_off = 0;
-    if (P.gen) {                                                                   // + the generated fill's slot tables (2 x 1024 entries of 2 B; 2 x 512 for the radix-8 kernel, whose two workgroups per CU have no room for more)
-        P.gen_lds_off = (uint32_t)((lut_bytes + 15) & ~(size_t)15);
-        lut_bytes = P.gen_lds_off + 2 * (P.dg_slim == 2 ? 512 : 1024) * sizeof(unsigned short);
-    }
-    if (P.gen >= 2) {                     // the generated first pass by columns (K6g; 3: of a compact chain): populated columns + the records' masks in LDS
-        P.xm_off = 0;
-        size_t lds_cols = (size_t)P.zpad * QCX_COL_STRIDE * sizeof(amp_t) + 8 * ((size_t)P.xm_cnt + 66);
-        if (P.dg_cnt) {                                            // tolerance mode: E_out slots and G tables of the merged diagonals
-            P.dg_lds_off = (uint32_t)((8 * ((size_t)P.xm_cnt + 66) + 15) & ~(size_t)15);
-            lds_cols = (size_t)P.zpad * QCX_COL_STRIDE * sizeof(amp_t) + P.dg_lds_off + 16 * (size_t)P.dg_cnt * 49;
-        }
-        P.gen_lds_off = (uint32_t)((lds_cols - (size_t)P.zpad * QCX_COL_STRIDE * sizeof(amp_t) + 15) & ~(size_t)15);   // the residue -> column table of a compact chain
-        lds_cols = (size_t)P.zpad * QCX_COL_STRIDE * sizeof(amp_t) + P.gen_lds_off + (P.gen == 3 ? P.gen_tab_bytes : 0);
+#define REFUSE(...) do { snprintf(L.err, sizeof L.err, __VA_ARGS__); return QCX_UNKNOWN_ERROR; } while (0)
+    if (!I.xp_on && (I.chained != 0) != (I.buffers_differ != 0)) REFUSE("fused pass: chained flag and buffers disagree");
+    if (I.xp_on && !pass_expanding_store_ok(I, tn)) REFUSE("expanding store on a pass that is not a k_fused_x8 pass");
+    if (!I.tables_cover) REFUSE("fused pass: the addressing tables do not cover the %u tile-number bits", I.n - I.T);
+    const unsigned T = I.T;
+    const uint64_t ntiles = (uint64_t)1 << (I.n - T);
+    const bool tol = I.dg_cnt != 0, gen = I.gen != 0, cam = I.has_cam != 0, ldsdma = tn.fuse_ldsdma != 0;
+
+    // which kernel, with how many workgroups (each walks its tiles)
+    long cap = tn.fuse_grid_cap;
+    L.waves = 0;
+    if (I.dg_slim == 3) {                 // the exact walk on 8 amplitudes per thread (k_fused_x8)
+        if (T < 10 || T > 12 || cam || I.gen > 1 || I.zskip || !ldsdma) REFUSE("radix-8 exact pass: unsupported shape (T = %u)", T);
+        L.block = 512u >> (12 - T);
+        L.kernel = pass_kernel(PK_k_fused_x8, L.block, T, gen, false);
+        cap = tn.fuse_x8_cap;
+    } else if (I.gen >= 2) {              // the generated first pass by columns (K6g; 3: of a compact chain)
         // (four waves; one wave per column -- six for the orbit of N = 21 -- is slower: 5.3 against 3.8 ms at n = 30, the extra waves idle through generation and store)
         // ... while a launch that does not fill the chip (<= 1024 tiles: n <= 22 behind a six-residue front) is a latency chain per tile,
         // which more waves shorten: attempts at n = 16 .. 22 take 88-127 us with eight waves against 97-138 with four
         // (profiles/r05_attempts_cols_waves.txt).  fuse_cols_waves = 0: chosen here.
-        const unsigned waves = tn.fuse_cols_waves <= 0 ? (ntiles <= 1024 ? 8u : 4u) : (unsigned)std::min<long>(8, std::max<long>(4, tn.fuse_cols_waves));
-        const unsigned gridc = grid_for(ntiles, 1, tn.fuse_cols_cap);
-        if (P.dg_cnt) hipLaunchKernelGGL((k_gen_cols<6, true>), dim3(gridc), dim3(64 * waves), lds_cols, r->stream, amp_out, n, P, d_ops, ntiles, d_ops);
-        else hipLaunchKernelGGL((k_gen_cols<6, false>), dim3(gridc), dim3(64 * waves), lds_cols, r->stream, amp_out, n, P, d_ops, ntiles, d_ops);
-        HIP_TRY(hipGetLastError());
-        return QCX_NO_ERROR;
-    }
-    const size_t lds = ((size_t)16 << P.T) + lut_bytes;
-    // 4 amplitudes per thread (all loads of a tile in flight at once, few registers): block = 2^T / 4
-#define QCX_FUSE_LAUNCH(B, TTv) do { \
-        if (P.cam_ctl_local[0] && tn.fuse_ldsdma && tn.fuse_rounds_occ >= 6 && launch_rounds_kernel<B, TTv>((int)tn.fuse_rounds_occ, (int)tn.fuse_tol_occ, grid, lds, r->stream, amp_in, amp_out, n, P, d_ops, ntiles)) { \
-        } else if (P.chained) { set_error("chained pass without a rounds kernel"); return QCX_UNKNOWN_ERROR; \
-        } else if (tn.fuse_ldsdma) hipLaunchKernelGGL((k_fused<B, TTv, true>), dim3(grid), dim3(B), lds, r->stream, amp_in, n, P, d_ops, ntiles, d_ops); \
-        else hipLaunchKernelGGL((k_fused<B, TTv, false>), dim3(grid), dim3(B), lds, r->stream, amp_in, n, P, d_ops, ntiles, d_ops); } while (0)
-    if (P.dg_slim == 2) {                 // tolerance mode, radix-8 fast rounds only
-        if (P.T != 12) { set_error("radix-8 pass on a tile of 2^%u amplitudes", P.T); return QCX_UNKNOWN_ERROR; }
-        if (P.dg_cnt && !P.gen && tn.fuse_x8t) {              // round 5: the hand-written round on the k_fused_x8 shell (K6x-t)
-            P.dg_lds_off = 0;
-            const size_t lds8 = ((size_t)16 << P.T) + 16 * (size_t)P.dg_cnt * 49;
-            hipLaunchKernelGGL((k_fused_x8<512, 12, false, true>), dim3(grid_for(ntiles, 1, tn.fuse_x8_cap)), dim3(512), lds8, r->stream, amp_in, amp_out, n, P, d_ops, ntiles, d_ops);
-            HIP_TRY(hipGetLastError());
-            return QCX_NO_ERROR;
+        L.waves = tn.fuse_cols_waves <= 0 ? (ntiles <= 1024 ? 8u : 4u) : (unsigned)std::min<long>(8, std::max<long>(4, tn.fuse_cols_waves));
+        L.block = 64 * L.waves;
+        L.kernel = pass_kernel(PK_k_gen_cols, 6, tol);
+        cap = tn.fuse_cols_cap;
+    } else if (I.dg_slim == 2) {          // tolerance mode, radix-8 fast rounds only
+        if (T != 12) REFUSE("radix-8 pass on a tile of 2^%u amplitudes", T);
+        L.block = 512;
+        if (tol && !gen && tn.fuse_x8t) {                     // round 5: the hand-written round on the k_fused_x8 shell (K6x-t)
+            L.kernel = pass_kernel(PK_k_fused_x8, 512, 12, false, true);
+            cap = tn.fuse_x8_cap;
+        } else {
+            // (a few workgroups per CU that walk the tiles: 2048 workgroups 6.3 ms, 24576 7.0 ms, one per tile 8.3 ms at n = 28)
+            // (the Hadamard-only exact form likes more of them: n = 30 sweep 23.5 ms with 8192, 23.9 with 3072)
+            L.kernel = pass_kernel(PK_k_fused_q3, 512, 12, 4, !tol, gen);
+            cap = tol ? tn.fuse_q3_cap : tn.fuse_q3_cap_exact;
         }
-        // (a few workgroups per CU that walk the tiles: 2048 workgroups 6.3 ms, 24576 7.0 ms, one per tile 8.3 ms at n = 28)
-        // (the Hadamard-only exact form likes more of them: n = 30 sweep 23.5 ms with 8192, 23.9 with 3072)
-        const unsigned grid3 = grid_for(ntiles, 1, P.dg_cnt ? tn.fuse_q3_cap : tn.fuse_q3_cap_exact);
-        if (P.gen) {
-            if (P.dg_cnt) hipLaunchKernelGGL((k_fused_q3<512, 12, 4, false, true>), dim3(grid3), dim3(512), lds, r->stream, amp_in, amp_out, n, P, d_ops, ntiles);
-            else hipLaunchKernelGGL((k_fused_q3<512, 12, 4, true, true>), dim3(grid3), dim3(512), lds, r->stream, amp_in, amp_out, n, P, d_ops, ntiles);
-        }
-        else if (P.dg_cnt) hipLaunchKernelGGL((k_fused_q3<512, 12, 4, false>), dim3(grid3), dim3(512), lds, r->stream, amp_in, amp_out, n, P, d_ops, ntiles);
-        else hipLaunchKernelGGL((k_fused_q3<512, 12, 4, true>), dim3(grid3), dim3(512), lds, r->stream, amp_in, amp_out, n, P, d_ops, ntiles);
-        HIP_TRY(hipGetLastError());
-        return QCX_NO_ERROR;
+    } else if (T >= 10 && T <= 12 && I.rounds_form && ldsdma && tn.fuse_rounds_occ >= 6) {       // the rounds-only kernel
+        const int slim = tol ? (I.dg_slim ? 2 : 1) : 0;
+        const int occ = slim == 2 ? (tn.fuse_tol_occ >= 8 ? 8 : 6) : slim == 1 ? 6 : (tn.fuse_rounds_occ >= 7 ? 7 : 6);
+        L.block = 1u << (T - 2);
+        L.kernel = pass_kernel(PK_k_fused_rounds, L.block, T, occ, cam && !gen, slim, gen);
+    } else if (T >= 9 && T <= 12) {       // the general kernel works in place only
+        if (I.chained) REFUSE("chained pass without a rounds kernel");
+        L.block = T == 9 ? 256u : 1u << (T - 2);
+        L.kernel = pass_kernel(PK_k_fused, L.block, T, ldsdma);
+    } else {
+        L.block = T >= 5 && T <= 8 ? 64 : 256;
+        L.kernel = pass_kernel(PK_k_fused, L.block, T >= 5 && T <= 8 ? T : 0, false);
     }
-    switch (P.T) {
-    case 12: QCX_FUSE_LAUNCH(1024, 12); break;
-    case 11: QCX_FUSE_LAUNCH(512, 11); break;
-    case 10: QCX_FUSE_LAUNCH(256, 10); break;
-    case 9:  QCX_FUSE_LAUNCH(256, 9); break;
-    // registers of the reference's own sizes (n = 5 ... 8: the whole state is one tile): one wave, everything known at compile time
-    // (the generic kernel below took 60 us for the 13 gates of the C = 15, L = 3, M = 4 circuit; these take ~10)
-    case 8:  hipLaunchKernelGGL((k_fused<64, 8, false>), dim3(grid), dim3(64), lds, r->stream, amp_in, n, P, d_ops, ntiles, d_ops); break;
-    case 7:  hipLaunchKernelGGL((k_fused<64, 7, false>), dim3(grid), dim3(64), lds, r->stream, amp_in, n, P, d_ops, ntiles, d_ops); break;
-    case 6:  hipLaunchKernelGGL((k_fused<64, 6, false>), dim3(grid), dim3(64), lds, r->stream, amp_in, n, P, d_ops, ntiles, d_ops); break;
-    case 5:  hipLaunchKernelGGL((k_fused<64, 5, false>), dim3(grid), dim3(64), lds, r->stream, amp_in, n, P, d_ops, ntiles, d_ops); break;
-    default: hipLaunchKernelGGL((k_fused<256, 0, false>), dim3(grid), dim3(256), lds, r->stream, amp_in, n, P, d_ops, ntiles, d_ops); break;
+    L.grid = grid_for(ntiles, 1, cap);
+
+    // the LDS layout that kernel indexes
+    const PassFamily fam = pass_kernel_family(L.kernel);
+    LdsAreas A{fam == PK_k_gen_cols ? (size_t)I.zpad * QCX_COL_STRIDE * sizeof(amp_t) : (size_t)16 << T};
+    L.xm_off = L.dg_lds_off = L.gen_lds_off = 0;
+    L.table_lds_off = (int32_t)lds_scratch_bytes(cam, I.M);
+    if (fam == PK_k_fused_x8) {           // the tile, then the exact walk's masks or the tolerance round's diagonals
+        if (I.dg_slim == 3) L.xm_off = A.add(lds_mask_bytes(I.xm_cnt), 8);
+        else L.dg_lds_off = A.add(lds_diag_bytes(I.dg_cnt), 16);
+        if (gen) L.gen_lds_off = A.add(lds_gen_bytes(I.dg_slim), 16);
+    } else if (fam == PK_k_gen_cols) {    // populated columns + the records' masks
+        L.xm_off = A.add(lds_mask_bytes(I.xm_cnt), 8);
+        if (tol) L.dg_lds_off = A.add(lds_diag_bytes(I.dg_cnt), 16);
+        L.gen_lds_off = A.add(I.gen == 3 ? I.gen_tab_bytes : 0, 16);       // the residue -> column table of a compact chain
+    } else {                              // multiply scratch, tables of folded multiply runs, then whatever the pass holds
+        const bool no_scratch = (tol || I.dg_slim == 2) && !cam;            // tolerance-mode pass without multiplies: 16 bytes, no tables
+        A.add(lds_scratch_bytes(cam, I.M), 1);
+        A.add(no_scratch ? 0 : I.table_bytes, 1);
+        if (I.xm_cnt && !I.dg_slim) L.xm_off = A.add(lds_mask_bytes(I.xm_cnt), 8);
+        if (tol) L.dg_lds_off = A.add(lds_diag_bytes(I.dg_cnt), 16);
+        if (gen) L.gen_lds_off = A.add(lds_gen_bytes(I.dg_slim), 16);
     }
-#undef QCX_FUSE_LAUNCH
+    L.lds = A.front + A.behind;
+
+    // which tile a workgroup takes (fuse_stream_tile): memory-bound radix-8 passes (Hadamard sweeps, the tolerance mode's fast
+    // rounds) put the XCD number on tile-number bits 3-5 -- one XCD then stores 2^3 neighbouring runs back to back (n = 30
+    // sweep -6 %, n = 28 tolerance inverse QFT -1.6 %); the exact phase walk (FP64-bound) measures the same either way and
+    // keeps t = b (profiles/r05_streams.txt)
+    const bool membound = I.dg_slim == 2 && !gen;
+    long sl = tn.fuse_streams_log2 >= 0 ? tn.fuse_streams_log2 : (membound ? 3 : 0);
+    const long pos1 = tn.fuse_streams_pos >= 0 ? tn.fuse_streams_pos : (membound ? 4 : 0);
+    sl = std::min<long>(std::min<long>(sl, 15), (long)(I.n - T));
+    L.dbg = ((uint32_t)tn.fuse_dbg & 0xffu) | ((uint32_t)sl << 12) | (((uint32_t)pos1 & 31u) << 16);
+    return QCX_NO_ERROR;
+#undef REFUSE
+}
+
+// Could this pass store the real register of a compact chain itself (FusePass::xp_on)?  The expanding store exists in
+// k_fused_x8<512, 12> only, not generated -- exact walk or tolerance round -- and under the exact walk's conditions (no
+// multiplies, no zskip, LDS-DMA) for both.  Asked of the pass as it would run without it, in place.
+static bool pass_expanding_store_ok(qcx_pass_launch_in I, const Tune &tn)
+{
+    PassLaunch L;
+    I.xp_on = 0; I.buffers_differ = I.chained; I.tables_cover = 1;
+    if (I.T > I.n || I.has_cam || I.zskip || !tn.fuse_ldsdma || pass_launch_plan(I, tn, L) != QCX_NO_ERROR) return false;
+    return L.kernel == pass_kernel(PK_k_fused_x8, 512, 12, false, false) || L.kernel == pass_kernel(PK_k_fused_x8, 512, 12, false, true);
+}
+
+// amp_in / amp_out: the buffer the pass reads / writes (the same for a pass that works in place; a chained pass goes from one of
+// the register's two buffers to the other)
+static int launch_pass(qcx_register *r, const Tune &tn, const FusePass &P_in, const FuseOp *d_ops, amp_t *amp_in, amp_t *amp_out)
+{
+    const unsigned n = r->n;
+    PassLaunch L;
+    if (pass_launch_plan(pass_launch_in(P_in, n, (unsigned)r->M, amp_in != amp_out), tn, L) != QCX_NO_ERROR) { set_error("%s", L.err); return QCX_UNKNOWN_ERROR; }
+    FusePass P = P_in;
+    P.xm_off = L.xm_off; P.dg_lds_off = L.dg_lds_off; P.gen_lds_off = L.gen_lds_off; P.cam_ctl_local[3] = L.table_lds_off; P.dbg = L.dbg;
+    const uint64_t ntiles = (uint64_t)1 << (n - P.T);
+    switch (L.kernel) {
+#define X(NAME, ...) case pass_kernel(PK_##NAME, __VA_ARGS__): hipLaunchKernelGGL((NAME<__VA_ARGS__>), dim3(L.grid), dim3(L.block), L.lds, r->stream, QCX_ARGS_##NAME); break;
+    QCX_PASS_KERNELS(X)
+#undef X
+    default: set_error("fused pass: no such kernel"); return QCX_UNKNOWN_ERROR;
+    }
     HIP_TRY(hipGetLastError());
     return QCX_NO_ERROR;
 }
@@ -966,8 +993,9 @@ static void fuse_plan(const qcx_register *r, const Tune &tn, const std::vector<Q
         act.P.has_cam = sh.n_other ? 1u : 0u;
         act.P.c = sh.c; act.P.nh = (uint32_t)sh.hbits.size(); act.P.T = sh.c + act.P.nh;
         // (the table area sits behind the modular-multiply scratch; a pass without multiplies carries none: with M >= 12 its 8 KiB
-        //  pushed the 2^10-tile phase passes over the LDS budget of the rounds form and onto the general kernel: 24 ms against 7)
-        act.P.cam_ctl_local[3] = (int32_t)(sh.n_other ? cam_lut_bytes((unsigned)r->M) : 16);
+        //  pushed the 2^10-tile phase passes over the LDS budget of the rounds form and onto the general kernel: 24 ms against 7
+        //  -- cam_ctl_local[3], its offset: with the rest of the LDS layout, at the launch: pass_launch_plan)
+        const size_t scratch = lds_scratch_bytes(sh.n_other != 0, (unsigned)r->M);
         for (unsigned j = 0; j < act.P.nh; j++) act.P.hbit[j] = (uint8_t)sh.hbits[j];
         std::vector<FuseOp> legacy;
         bool rounds = tn.fuse_rounds && act.P.T >= 10 && (act.P.T <= 12 || (act.P.T == 13 && sh.want_q3 && !tol && sh.n_ph == 0));
@@ -1001,15 +1029,15 @@ static void fuse_plan(const qcx_register *r, const Tune &tn, const std::vector<Q
                 keep_diags = !pass_diags.empty();
             }
             const size_t nrec = all_ops.size() - act.op_off;
-            size_t lds = 2 * ((size_t)16 << act.P.T) + (size_t)act.P.cam_ctl_local[3] + blob.size() + 64 + 8 * (nrec + 66);
+            size_t lds = 2 * ((size_t)16 << act.P.T) + scratch + blob.size() + 64 + lds_mask_bytes(nrec);
             size_t limit = (size_t)160 * 1024 / (act.P.T >= 12 ? 1 : act.P.T == 11 ? 2 : 4);
-            if (act.P.T == 13) lds = ((size_t)16 << 13) + 64 + 8 * (nrec + 66);          // one tile per CU
+            if (act.P.T == 13) lds = ((size_t)16 << 13) + 64 + lds_mask_bytes(nrec);          // one tile per CU
             if (keep_diags) {            // tolerance mode: what the workgroup really needs; two of them must fit a CU
-                lds = ((size_t)16 << act.P.T) + (sh.n_other ? (size_t)act.P.cam_ctl_local[3] : 16) + blob.size() + 64 + 8 * (nrec + 66) + 16 * 49 * pass_diags.size();
+                lds = ((size_t)16 << act.P.T) + scratch + blob.size() + 64 + lds_mask_bytes(nrec) + lds_diag_bytes(pass_diags.size());
                 limit = (size_t)80 * 1024;
             }
             if (sh.want_x8) {            // one tile + the records' masks; two workgroups of 2^12 (four of 2^11, eight of 2^10) per CU
-                lds = ((size_t)16 << act.P.T) + 8 * (nrec + 66);
+                lds = ((size_t)16 << act.P.T) + lds_mask_bytes(nrec);
                 limit = (size_t)160 * 1024 / (act.P.T == 12 ? 2 : act.P.T == 11 ? 4 : 8);
             }
             if (lds > limit) {
@@ -1734,7 +1762,7 @@ static int launch_actions(qcx_register *v, GateQueue *gq, const Tune &tn, const 
         const FuseAction &act = acts[ai];
         if (!act.fused) { QCX_TRY(launch_standalone(v, (*gates)[act.gate])); continue; }
         amp_t *out = (last_out && ai + 1 == count) ? last_out : (act.P.chained ? v->scratch : v->amp);
-        QCX_TRY(launch_pass(v, tn, act.P, gq->d_ops + act.op_off, act.nopipe != 0, v->amp, out));
+        QCX_TRY(launch_pass(v, tn, act.P, gq->d_ops + act.op_off, v->amp, out));
         if (out == v->scratch) std::swap(v->amp, v->scratch);
         if (act.P.chained) gq->chained_passes++;
         gq->passes_launched++;
@@ -1844,7 +1872,7 @@ static bool compact_chain_plan(const qcx_register *r, const GateQueue *gq, const
     // Round 5: when the chain's last pass is a k_fused_x8 pass whose tile holds the column bits, that pass can store the REAL
     // register itself (FusePass::xp_on) -- k_expand_compact's extra read and write of the compact form (8.6 of its 21.5 GB at
     // n = 30, M = 5) disappear.  (The last pass of a plan always stores the identity layout.)
-    if (tn.fuse_expand_fused && cp.acts.size() > 1 && cp.acts.back().fused && pass_is_x8(cp.acts.back().P, tn) && M <= 9 && cb <= 4) {
+    if (tn.fuse_expand_fused && cp.acts.size() > 1 && cp.acts.back().fused && pass_expanding_store_ok(pass_launch_in(cp.acts.back().P, L + cb, cb, false), tn) && M <= 9 && cb <= 4) {
         cp.Pxp = cp.acts.back().P;
         cp.xp = xp_setup(cp.Pxp, M, cb, cp.orbit);
     }

@@ -15,7 +15,12 @@ def bits(a):
 
 
 TUNE_KEYS = ("fuse_T", "fuse_c", "fuse_rounds", "fuse_camruns", "fuse_T_phase", "fuse_c_phase", "fuse_phase_ratio", "fuse_tol_T", "fuse_q3",
-             "fuse_x8", "fuse_x8_T", "fuse_x8_c", "fuse_x8_map", "fuse_x8_min_tiles_log2")
+             "fuse_x8", "fuse_x8_T", "fuse_x8_c", "fuse_x8_map", "fuse_x8_min_tiles_log2", "fuse_x8t")
+
+
+def kernels(actions):
+    """the kernel instantiation that would run each fused pass (qcx_plan_action.kernel)"""
+    return [a.kernel.decode() for a in actions if a.fused]
 
 
 @pytest.fixture()
@@ -113,6 +118,8 @@ def test_plan_of_the_n28_iqft(qc, tune_guard):
     assert len(descs) == 406 and [a.fused for a in actions] == [1, 1, 1]
     assert sum(a.ngates for a in actions) == 406
     assert [(a.T, a.c, a.nopipe) for a in actions] == [(12, 4, 1), (12, 4, 1), (12, 4, 1)]
+    assert kernels(actions) == ["k_fused_x8<512, 12, false, false>"] * 3
+    assert all((a.grid, a.block) == (65536, 512) and a.lds_bytes == (16 << 12) + 8 * (a.rec_cnt + 66) for a in actions)
     hot = [[a.hbit[j] for j in range(a.nh)] for a in actions]
     assert hot[0] == list(range(20, 28)) and hot[1] == list(range(12, 20)) and hot[2] == list(range(4, 12))
     for a in actions:
@@ -127,6 +134,7 @@ def test_plan_of_the_n28_iqft(qc, tune_guard):
     actions, recs, nrec = qc.fusion_plan(n, 0, descs)
     assert [a.fused for a in actions] == [1, 1, 1, 1]
     assert [(a.T, a.c, a.nopipe) for a in actions] == [(10, 4, 1), (10, 4, 1), (10, 4, 1), (11, 4, 0)]
+    assert kernels(actions) == ["k_fused_rounds<256, 10, 7, false, 0, false>"] * 3 + ["k_fused_rounds<512, 11, 7, false, 0, false>"]
     hot = [[a.hbit[j] for j in range(a.nh)] for a in actions]
     assert hot[0] == [22, 23, 24, 25, 26, 27] and hot[1] == [16, 17, 18, 19, 20, 21] and hot[2] == [10, 11, 12, 13, 14, 15]
     for a in actions:
@@ -153,6 +161,9 @@ def test_radix8_exact_rounds_on_the_iqft_schedule(qc, ob, tune_guard, n, M, tune
     actions, recs, nrec = qc.fusion_plan(n, M, descs)
     kinds = {recs[a.rec_off + k].type & 0xFF for a in actions if a.fused for k in range(a.nops)}
     assert emu.FUSE_ROUND8 in kinds
+    for a in actions:
+        if a.fused and any((recs[a.rec_off + k].type & 0xFF) == emu.FUSE_ROUND8 for k in range(a.nops)):
+            assert a.kernel.decode() == f"k_fused_x8<{512 >> (12 - a.T)}, {a.T}, false, false>" and a.block == 512 >> (12 - a.T)
     state = ob.random_state(n, 9)
     want = state.copy()
     oracle_run(ob, want, n, M, 1, steps)
@@ -339,7 +350,7 @@ def test_tolerance_mode_random_programs(qc, ob, tune_guard, seed):
 
 def test_tolerance_mode_plan_of_the_n28_iqft(qc, tune_guard):
     """config 3 in tolerance mode: 28 H + 378 phases -> THREE passes of radix-8 fast rounds on 2^12 tiles (8 hot bits each,
-    k_fused_q3), 27 diagonals; with the radix-8 form off: four passes of radix-4 fast rounds on 2^10 tiles"""
+    the round on the k_fused_x8 shell, k_fused_q3 with fuse_x8t = 0), 27 diagonals; with the radix-8 form off: four passes of radix-4 fast rounds on 2^10 tiles"""
     n = 28
     descs = iqft_descs(qc, n, 0)
     actions, recs, nrec = qc.fusion_plan(n, 0, descs, mode=2)
@@ -349,11 +360,16 @@ def test_tolerance_mode_plan_of_the_n28_iqft(qc, tune_guard):
     for a in actions:
         kinds = {recs[a.rec_off + k].type & 0xFF for k in range(0, a.nops, 2)}
         assert kinds == {emu.FUSE_QROUND3}, kinds
-    qc.tune(fuse_q3=0)
+    assert kernels(actions) == ["k_fused_x8<512, 12, false, true>"] * 3          # the hand-written round on the k_fused_x8 shell (fuse_x8t)
+    assert all(a.lds_bytes == (16 << 12) + 16 * 49 * a.diag_cnt for a in actions)
+    qc.tune(fuse_x8t=0)
+    assert kernels(qc.fusion_plan(n, 0, descs, mode=2)[0]) == ["k_fused_q3<512, 12, 4, false, false>"] * 3
+    qc.tune(fuse_x8t=1, fuse_q3=0)
     actions, recs, nrec = qc.fusion_plan(n, 0, descs, mode=2)
     assert [(a.T, a.c) for a in actions] == [(10, 4)] * 4 and sum(a.diag_cnt for a in actions) == 27
     for a in actions:
         assert {recs[a.rec_off + k].type & 0xFF for k in range(0, a.nops, 2)} == {emu.FUSE_QROUND}
+    assert kernels(actions) == ["k_fused_rounds<256, 10, 6, false, 2, false>"] * 4
 
 
 @pytest.mark.parametrize("n,M", [(12, 0), (12, 3), (20, 0), (21, 5)])
@@ -367,6 +383,11 @@ def test_tolerance_mode_radix8_rounds(qc, ob, tune_guard, n, M):
     assert max_delta(state, want) <= TOL
     q3 = [a for a in acts if a.fused and (recs[a.rec_off].type & 0xFF) == emu.FUSE_QROUND3]
     assert len(q3) == (n - max(M, 4) + 7) // 8, [(a.T, a.c) for a in acts]
+    assert kernels(q3) == ["k_fused_x8<512, 12, false, true>"] * len(q3)
+    qc.tune(fuse_x8t=0)
+    acts0, recs0, _ = qc.fusion_plan(n, M, descs, mode=2)
+    q30 = [a for a in acts0 if a.fused and (recs0[a.rec_off].type & 0xFF) == emu.FUSE_QROUND3]
+    assert len(q30) == len(q3) and kernels(q30) == ["k_fused_q3<512, 12, 4, false, false>"] * len(q3)
 
 
 def test_mode_1_plan_is_unchanged_by_the_tolerance_code(qc, ob, tune_guard):
@@ -393,9 +414,12 @@ def test_hadamard_sweep_takes_the_exact_radix8_form(qc, ob, tune_guard, n, mode)
     assert np.array_equal(bits(state), bits(want))
     fused = [a for a in acts if a.fused]
     assert fused and all((recs[a.rec_off].type & 0xFF) == emu.FUSE_QROUND3 and a.diag_cnt == 0 and (a.T, a.c) == (12, 3) for a in fused)
+    assert kernels(acts) == ["k_fused_q3<512, 12, 4, true, false>"] * len(fused)
+    assert all((a.grid, a.block, a.lds_bytes) == (1 << (n - 12), 512, (16 << 12) + 16) for a in fused)       # one workgroup per tile (fuse_q3_cap_exact)
     qc.tune(fuse_q3=0)
     acts, recs, _ = qc.fusion_plan(n, 0, descs, mode=mode)
     assert all((recs[a.rec_off].type & 0xFF) == emu.FUSE_ROUND for a in acts if a.fused)
+    assert kernels(acts) == ["k_fused_rounds<1024, 12, 7, false, 0, false>"] * len(kernels(acts))
 
 
 @pytest.mark.parametrize("seed", range(6))
