@@ -320,6 +320,35 @@ unsigned qcx_pauli_batch_width(void);   /* W: the most terms one read of the sta
  * 2 = a pending basis state (no kernel), 3 = a compact result expanded first; state_reads = the passes that read amplitudes:
  * one per term, or per pass of the batch call (0 for a basis state) */
 int  qcx_expectation_last_stats(qcx_register *reg, unsigned *source, unsigned long *state_reads);
+/* The reduced density matrix of the qubits [first_qubit, first_qubit + num_qubits), the others traced out, exactly, from one read
+ * of the state (no reference counterpart; tests/rdm_ref.py restates it in numpy and IS the definition).  rho holds
+ * 2 * 4^num_qubits doubles, row-major, (re, im) per entry, row v and column w in 0 .. 2^num_qubits - 1:
+ *   rho[v][w] = sum over r of amp[r, v] * conj(amp[r, w]),
+ * r running over the values of the n - num_qubits qubits outside the range, amp[r, v] the amplitude whose range bits are v and
+ * whose other bits are r.  first_qubit is bit 0 of v (the LSB convention of this library, as qcx_two_qubit_gate's kron(B, A)).
+ * The leaves are qcx_pauli_expectation's arithmetic: for v < w, a = amp[r, v], b = amp[r, w], every fl() one binary64 rounding,
+ * no FMA,
+ *   re-leaf = fl(0.0 + fl(fl(a.re*b.re) + fl(a.im*b.im))),   im-leaf = fl(0.0 + fl(fl(a.im*b.re) - fl(a.re*b.im)));
+ * for v = w the re-leaf is the same expression -- qcx_marginal_probabilities' p_i -- and the imaginary part of a diagonal entry is
+ * +0.0 by contract, not computed.  Each computed component (re or im) is the marginal's ONE PAIRWISE TREE over its leaves, over
+ * the summed bits s_0 < s_1 < ... (every bit outside the range), lowest first: tests/marginal_ref.py's tree for the same
+ * (first_qubit, num_qubits).  The lower triangle is the conjugate of the upper one: rho[w][v].re = rho[v][w].re,
+ * rho[w][v].im = fl(0.0 - rho[v][w].im), so that a zero stays +0.  Inf and NaN propagate by IEEE rules in the computed
+ * components; a result is never -0; num_qubits = 0 gives the 1 x 1 matrix (norm^2, +0).  Hence rho[v][v].re is
+ * qcx_marginal_probabilities(reg, first_qubit, num_qubits)[v] bit for bit, and for one qubit q on a finite state 2 rho[0][1].re
+ * and -2 rho[0][1].im are qcx_pauli_expectation's values of X_q and Y_q (up to the sign of a zero).
+ * The state is read once, every amplitude once, wherever the range lies (K16, DESIGN s4.5j; stage plan: qcx_plan.h).
+ * The state, and every lazy form of it, is left exactly as it was, and nothing is written to the state: queued gates are flushed
+ * first; a pending basis state k with no gate queued is answered on the host (no kernel): (1, +0) at [v_k][v_k], v_k the range
+ * value of k, +0 everywhere else; a circuit's compact result stays compact and is read from the expanded state (the register's
+ * buffer gets it first); a register flagged non-finite keeps its flag and needs nothing special.
+ * Checked in this order, before anything runs: NULL reg or rho: QCX_BAD_ARGUMENTS; a sharded register: QCX_UNSUPPORTED, nothing
+ * touched; first_qubit + num_qubits > n: QCX_BAD_QUBIT; num_qubits > qcx_rdm_max_qubits(): QCX_UNSUPPORTED. */
+int  qcx_reduced_density_matrix(qcx_register *reg, unsigned first_qubit, unsigned num_qubits, double *rho);
+unsigned qcx_rdm_max_qubits(void);   /* the widest range one call serves; a build constant, >= 4 */
+/* the last qcx_reduced_density_matrix call on this register: source 0 = the register, 2 = a pending basis state (no kernel),
+ * 3 = a compact result expanded first; state_reads = the passes that read amplitudes: 1, or 0 for a basis state */
+int  qcx_rdm_last_stats(qcx_register *reg, unsigned *source, unsigned long *state_reads);
 
 /* ---- state access (replaces gsl_vector_complex_get/set uses, T:7-37) ------- */
 int  qcx_state_read(qcx_register *reg, unsigned long first, unsigned long count, double *out_re_im);

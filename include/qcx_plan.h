@@ -122,6 +122,29 @@ int  qcx_marginal_plan_compact(unsigned n, unsigned M, unsigned first, unsigned 
  * qcx_pauli_batch_width().  width = 0, a NULL npasses, or NULL arrays with nterms > 0: QCX_BAD_ARGUMENTS. */
 int  qcx_pauli_batch_plan(unsigned long nterms, const uint64_t *x_masks, unsigned width,
                           unsigned long *pass_of_term /* [nterms] */, unsigned long *npasses);
+
+/* The stage plan of qcx_reduced_density_matrix (include/qcx.h; K16, DESIGN s4.5j), on the host.  The 4^num computed components
+ * (row v * 2^num + w, v <= w: Re rho[v][w]; row w * 2^num + v, v < w: Im rho[v][w]) are each the marginal's pairwise tree over
+ * the bits outside [first, first + num).  Stage 0 reads the state once and sums, for every row, the sum_bits lowest summed
+ * qubits (sum_mask, as qubit numbers: all of them below 12 qubits, else the 12 - num that share a unit of 2^12 amplitudes with the
+ * range plus group_bits = min(n - 21, 4) more from 22 qubits on, a workgroup adding the roots of 2^group_bits units); its output is rows x row_stride doubles,
+ * row-major, the column = the rest_bits summed qubits left, in ascending order.  stages[0 .. *n_stages) are the stages behind it:
+ * ordinary marginal stages (kind 1) over that array as one input of rest_bits + 2 num index bits with the row number as the kept
+ * high bits, so that all rows go through each launch together; *n_stages = 0 when stage 0 leaves nothing to sum.  Non-final
+ * outputs lie back to back in the call's device scratch, stage 0's first (out_offset counts from the scratch's start):
+ * `scratch` doubles in all, at most (1 + 2^-11) 2^(n + 2 num - 12 - group_bits) -- from 25 qubits on 2^(2 num - 17) (1 + 2^-11)
+ * of the state's doubles, 32 MiB for four qubits of 30 --, and none for n <= 12.  stages[] must hold QCX_MARGINAL_MAX_STAGES entries.  first + num > n: QCX_BAD_QUBIT; num >
+ * qcx_rdm_max_qubits(): QCX_UNSUPPORTED. */
+typedef struct {
+    uint64_t sum_mask;          /* the qubits stage 0 sums */
+    unsigned sum_bits;          /* ... their number */
+    unsigned group_bits;        /* ... of which a workgroup sums this many across consecutive units of 2^12 amplitudes */
+    unsigned rest_bits;         /* summed qubits left behind stage 0 */
+    unsigned rows;              /* 4^num */
+    uint64_t row_stride;        /* 2^rest_bits: stage 0 writes component k of unit u to [k * row_stride + u] */
+    uint64_t scratch;           /* doubles of all non-final outputs */
+} qcx_rdm_stage0;
+int  qcx_rdm_plan(unsigned n, unsigned first, unsigned num, qcx_rdm_stage0 *stage0, qcx_marginal_stage *stages, unsigned *n_stages);
 #ifdef __cplusplus
 }
 #endif

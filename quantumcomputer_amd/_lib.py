@@ -80,6 +80,10 @@ SIGNATURES = {
     "qcx_pauli_batch_width": (_u, []),
     "qcx_pauli_batch_plan": (_i, [_ul, _p, _u, _p, C.POINTER(_ul)]),
     "qcx_expectation_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
+    "qcx_reduced_density_matrix": (_i, [_p, _u, _u, _p]),
+    "qcx_rdm_max_qubits": (_u, []),
+    "qcx_rdm_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
+    "qcx_rdm_plan": (_i, [_u, _u, _u, _p, _p, C.POINTER(_u)]),
     "qcx_marginal_plan": (_i, [_u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_marginal_plan_compact": (_i, [_u, _u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_state_read": (_i, [_p, _ul, _ul, _p]),
@@ -226,6 +230,25 @@ def marginal_plan(n, first, num, M=None):
         st = lib().qcx_marginal_plan_compact(n, M, first, num, C.cast(arr, C.c_void_p), C.byref(ns))
     check(st, "qcx_marginal_plan")
     return [arr[i] for i in range(ns.value)]
+
+
+class RdmStage0(C.Structure):
+    """qcx_rdm_stage0 (include/qcx_plan.h): the first stage of a reduced density matrix's plan"""
+    _fields_ = [("sum_mask", _u64), ("sum_bits", _u), ("group_bits", _u), ("rest_bits", _u), ("rows", _u), ("row_stride", _u64), ("scratch", _u64)]
+
+
+def rdm_max_qubits():
+    """the widest range Register.reduced_density_matrix serves (qcx_rdm_max_qubits)"""
+    return int(lib().qcx_rdm_max_qubits())
+
+
+def rdm_plan(n, first, num):
+    """The stage plan of qcx_reduced_density_matrix (host code, no GPU needed): (RdmStage0, the list of MarginalStage behind it)."""
+    s0 = RdmStage0()
+    arr = (MarginalStage * MARGINAL_MAX_STAGES)()
+    ns = C.c_uint(0)
+    check(lib().qcx_rdm_plan(n, first, num, C.byref(s0), C.cast(arr, C.c_void_p), C.byref(ns)), "qcx_rdm_plan")
+    return s0, [arr[i] for i in range(ns.value)]
 
 
 def pauli_batch_width():

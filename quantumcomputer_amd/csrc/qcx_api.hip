@@ -1241,6 +1241,41 @@ extern "C" int qcx_marginal_plan_compact(unsigned n, unsigned M, unsigned first,
     return marginal_plan_from(2, labels, (((uint64_t)1) << M) - 1u, first, num, stages, n_stages);
 }
 
+// ---- K16: the stage plan of a reduced density matrix (include/qcx_plan.h, DESIGN s4.5j) -----------------------------------------
+// Stage 0 (k_rdm_leaves / k_rdm_small) sums the lowest summed qubits of every component: all of them below 12 qubits, else the
+// 12 - num that share a unit of 2^12 amplitudes with the range and, from 22 qubits on, min(n - 21, 4) more: a workgroup adds the
+// roots of that many consecutive units itself (at least 2^9 groups stay: two workgroups a CU).  Behind it the rows x 2^rest_bits partials are ONE marginal input
+// whose kept bits are the row number, on top: the marginal's own planner cuts the rest of the tree.
+extern "C" unsigned qcx_rdm_max_qubits(void) { return QCX_RDM_MAX_QUBITS; }
+
+extern "C" int qcx_rdm_plan(unsigned n, unsigned first, unsigned num, qcx_rdm_stage0 *s0, qcx_marginal_stage *stages, unsigned *n_stages)
+{
+    if (!s0 || !stages || !n_stages) return QCX_BAD_ARGUMENTS;
+    if (n < 1 || n > 40 || (uint64_t)first + num > n) return QCX_BAD_QUBIT;
+    if (num > QCX_RDM_MAX_QUBITS) return QCX_UNSUPPORTED;
+    memset(s0, 0, sizeof *s0);
+    s0->group_bits = n > 21 ? std::min(n - 21u, (unsigned)QCX_RDM_MAX_GROUP_BITS) : 0u;
+    s0->sum_bits = std::min(n, 12u) - num + s0->group_bits;
+    s0->rest_bits = n - num - s0->sum_bits;
+    for (unsigned q = 0, k = 0; q < n && k < s0->sum_bits; q++)
+        if (q < first || q >= first + num) { s0->sum_mask |= (uint64_t)1 << q; k++; }
+    s0->rows = 1u << (2u * num);
+    s0->row_stride = ((uint64_t)1) << s0->rest_bits;
+    *n_stages = 0;
+    if (s0->rest_bits == 0) return QCX_NO_ERROR;                     // stage 0 writes the components themselves
+    const unsigned m = s0->rest_bits + 2u * num;
+    std::vector<unsigned> labels(m);
+    for (unsigned b = 0; b < m; b++) labels[b] = b;
+    QCX_TRY(marginal_plan_from(1, labels, 0, s0->rest_bits, 2u * num, stages, n_stages));
+    s0->scratch = (uint64_t)s0->rows << s0->rest_bits;
+    for (unsigned i = 0; i < *n_stages; i++)
+        if (!stages[i].final_stage) {
+            stages[i].out_offset += (uint64_t)s0->rows << s0->rest_bits;
+            s0->scratch = std::max<uint64_t>(s0->scratch, stages[i].out_offset + (((uint64_t)1) << stages[i].out_bits));
+        }
+    return QCX_NO_ERROR;
+}
+
 // the kernel's parameters of one planned stage (tile-local bits, tree levels, output bits, tile-number segments)
 static void marginal_params(const qcx_marginal_stage &S, MargParams *P)
 {
@@ -1314,6 +1349,8 @@ struct qcx_register {
     unsigned long marg_reads;   // ... and the passes of it that read amplitudes
     unsigned   exp_source;      // the last pauli_expectation(_sum) call: 0 register, 2 basis (no kernel), 3 compact expanded first
     unsigned long exp_reads;    // ... and the passes of it that read amplitudes (one per term)
+    unsigned   rdm_source;      // the last reduced_density_matrix call: 0 register, 2 basis (no kernel), 3 compact expanded first
+    unsigned long rdm_reads;    // ... and the passes of it that read amplitudes (1, or 0 for a basis state)
     unsigned   coll_source;     // the last measure_qubits / postselect call: 0 register, 2 basis (no kernel), 3 compact expanded first
     unsigned long coll_reads, coll_writes;   // ... the marginal's reads behind its probabilities, and collapse passes launched (0 or 1)
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
@@ -2655,6 +2692,102 @@ extern "C" int qcx_expectation_last_stats(qcx_register *r, unsigned *source, uns
     if (!r) return QCX_BAD_ARGUMENTS;
     if (source) *source = r->exp_source;
     if (state_reads) *state_reads = r->exp_reads;
+    return QCX_NO_ERROR;
+}
+
+// ---- K16: the reduced density matrix of bits [first, first + num) (include/qcx.h, DESIGN s4.5j) -----------------------------------
+// Stage 0 reads the state in r->amp once and writes every component's partial roots; the planned marginal stages take all rows
+// through each launch; the 4^num components come back in one copy.
+static int rdm_launch(qcx_register *r, unsigned first, unsigned num, double *comps)
+{
+    qcx_rdm_stage0 s0;
+    qcx_marginal_stage st[QCX_MARGINAL_MAX_STAGES];
+    unsigned ns = 0;
+    QCX_TRY(qcx_rdm_plan(r->n, first, num, &s0, st, &ns));
+    QCX_TRY(marg_reserve(r, (size_t)s0.scratch + s0.rows));
+    double *const out = r->marg_buf + s0.scratch;
+    double *const dst0 = ns ? r->marg_buf : out;
+    const uint64_t stride0 = ns ? s0.row_stride : 1, ngroups = s0.row_stride;
+    const unsigned grid = (unsigned)std::min<uint64_t>(ngroups, 2048), ug = s0.group_bits;
+    const amp_t *amp = (const amp_t *)r->amp;
+    if (r->n < 12)
+        hipLaunchKernelGGL(k_rdm_small, dim3(1), dim3(256), 0, r->stream, amp, dst0, r->n, first, num);
+    else {
+        // EXCH: the range begins below the 12 - num summed bits of a unit, so a unit is 2^12 consecutive amplitudes
+        const bool exch = first < 12u - num;
+#define QCX_RDM_LAUNCH(NUM) \
+        do { \
+            if (exch) hipLaunchKernelGGL((k_rdm_leaves<NUM, true>), dim3(grid), dim3(256), 0, r->stream, amp, dst0, stride0, ngroups, ug, first); \
+            else hipLaunchKernelGGL((k_rdm_leaves<NUM, false>), dim3(grid), dim3(256), 0, r->stream, amp, dst0, stride0, ngroups, ug, first); \
+        } while (0)
+        switch (num) {
+        case 0: QCX_RDM_LAUNCH(0); break;
+        case 1: QCX_RDM_LAUNCH(1); break;
+        case 2: QCX_RDM_LAUNCH(2); break;
+        case 3: QCX_RDM_LAUNCH(3); break;
+        default: QCX_RDM_LAUNCH(4); break;
+        }
+#undef QCX_RDM_LAUNCH
+    }
+    HIP_TRY(hipGetLastError());
+    for (unsigned i = 0; i < ns; i++) {
+        MargParams P;
+        marginal_params(st[i], &P);
+        P.src = i == 0 ? r->marg_buf : r->marg_buf + st[i - 1].out_offset;
+        P.dst = st[i].final_stage ? out : r->marg_buf + st[i].out_offset;
+        P.bad = nullptr;
+        hipLaunchKernelGGL(k_marginal<MARG_DBL>, dim3((unsigned)std::min<uint64_t>(P.ntiles, 2048)), dim3(256), 0, r->stream, P);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(comps, out, s0.rows * sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_reduced_density_matrix(qcx_register *r, unsigned first, unsigned num, double *rho)
+{
+    if (!r || !rho) return QCX_BAD_ARGUMENTS;
+    if (r->sh) return QCX_UNSUPPORTED;
+    if ((uint64_t)first + num > r->n) return QCX_BAD_QUBIT;
+    if (num > QCX_RDM_MAX_QUBITS) return QCX_UNSUPPORTED;
+    r->rdm_source = 0; r->rdm_reads = 0;
+    const unsigned nv = 1u << num;
+    if (basis_only(r)) {
+        // amplitude 1 at basis_index: the projector on its range value -- no kernel, the state stays unwritten
+        const unsigned v = (unsigned)((r->basis_index >> first) & (nv - 1u));
+        for (unsigned i = 0; i < 2u * nv * nv; i++) rho[i] = 0.0;
+        rho[2u * (v * nv + v)] = 1.0;
+        r->rdm_source = 2;
+        return QCX_NO_ERROR;
+    }
+    QCX_TRY(settle_for_read(r));
+    if (r->compact_pending) {
+        // as a Pauli string's value: the register's buffer (stale while the state is compact) gets the expanded state, and the
+        // compact form stays what later calls see
+        QCX_TRY(launch_expand_compact(r->compact_amp, r->amp, r->n, r->compact_E, r->stream));
+        r->rdm_source = 3;
+    }
+    double comps[1u << (2 * QCX_RDM_MAX_QUBITS)];
+    QCX_TRY(rdm_launch(r, first, num, comps));
+    r->rdm_reads = 1;
+    // row v nv + w, v <= w, holds Re rho[v][w], row w nv + v its imaginary part; the lower triangle is the conjugate
+    for (unsigned v = 0; v < nv; v++) {
+        rho[2u * (v * nv + v)] = comps[v * nv + v];
+        rho[2u * (v * nv + v) + 1u] = 0.0;
+        for (unsigned w = v + 1u; w < nv; w++) {
+            const double re = comps[v * nv + w], im = comps[w * nv + v];
+            rho[2u * (v * nv + w)] = re; rho[2u * (v * nv + w) + 1u] = im;
+            rho[2u * (w * nv + v)] = re; rho[2u * (w * nv + v) + 1u] = 0.0 - im;
+        }
+    }
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_rdm_last_stats(qcx_register *r, unsigned *source, unsigned long *state_reads)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (source) *source = r->rdm_source;
+    if (state_reads) *state_reads = r->rdm_reads;
     return QCX_NO_ERROR;
 }
 

@@ -4865,4 +4865,199 @@ __global__ __launch_bounds__(256) void k_pauli_rot(amp_t *__restrict__ amp, uint
     }
 }
 
+// ---------------------------------------------------------------------------
+// K16  the first stage of a qubit range's reduced density matrix (qcx_reduced_density_matrix, DESIGN s4.5j; tests/rdm_ref.py is
+// the definition).  The range is [first, first + NUM), NV = 2^NUM its values; with a = amp[r, v], b = amp[r, w] (r = the bits
+// outside the range, squeezed) the components are ROWS of an NV x NV table of doubles:
+//     row v * NV + w, v <= w:  the real part, leaf  a.re b.re + a.im b.im           (v == w: the marginal's |a|^2)
+//     row w * NV + v, v <  w:  the imaginary part of rho[v][w], leaf  a.im b.re - a.re b.im
+// every product and sum rounded on its own (no FMA), and each row is K10's pairwise tree over r, lowest summed bit first.  A
+// leaf's "0.0 +" waits until the unit's root, as in K14b: with signed-zero leaves a node differs from the canonical tree only
+// where it is a zero of the other sign, and 0.0 + root is the same +0.
+// A UNIT of work is 2^12 amplitudes: the range's NUM bits and the S = 12 - NUM lowest summed bits.  Those are the index bits
+// [0, 12) when the range begins below S (EXCH), else the bits [0, S) and the range, unit u filling the bits between and above
+// (whole runs of 2^S >= 256 amplitudes either way: a wave instruction reads 1 KiB).  A workgroup takes 2^ug CONSECUTIVE units, a
+// GROUP -- ug more summed bits, the lowest that are left --, and thread k < NR adds their roots of row k as the tree does: a
+// binary counter of partial sums (stack[l] = the sum of a finished block of 2^l units, joined with the next block of its size as
+// soon as that is complete; unit i closes the blocks of its trailing one bits), so only a group's root leaves the kernel.
+// Group g's root of row k goes to dst[k * row_stride + g], g = the summed bits left, in ascending order; the later stages are
+// k_marginal<MARG_DBL> launches over all rows at once (the row number = kept high bits).
+// Thread tid holds, after the loads (EXCH: after the unit's amplitudes changed hands through LDS once, padded as K14b's),
+// x[v * C + c] = amp[r = tid + 256 c, v] for every v and the C = 16 / NV values of c: r's bits 0-5 are the lane, 6-7 the wave,
+// 8.. are c.  It forms its NR * C = 2^(NUM + 4) leaves in groups of at most 64 and reduces a group over the lanes -- r's bits
+// 0 - 5, in that order -- by HALVING: at level l a lane keeps the half of its values that bit l of its number selects, hands the
+// other half to lane ^ 2^l and adds what it receives (IEEE addition commutes), so after the group's levels a lane holds one
+// value, the wave's sum of the group's component number bit-reverse(lane).  That is 63 exchanges for 64 components where a
+// butterfly per component would take 384, and no per-thread running sum.  Then one double per wave, component and c through LDS
+// (ws), ONE barrier per unit, and thread k < NR forms row k: (w0 + w1) + (w2 + w3) per c -- r's bits 6, 7 --, then the tree over
+// c -- r's bits 8 and up.  FULL tiles only (n >= 12): nothing in a unit's path is guarded, and the next unit's loads go out
+// before the leaves are formed.  Nothing is written but dst.
+// k_rdm_small is the one partial unit of a register below 12 qubits: the state in LDS, the leaves of as many rows as fit 2^12
+// doubles at a time, K14's tree levels on them.
+// ---------------------------------------------------------------------------
+#define QCX_RDM_MAX_QUBITS 4
+#define QCX_RDM_MAX_GROUP_BITS 4
+
+__device__ __forceinline__ double rdm_xor_lane(double v, unsigned lvl)
+{
+    if (lvl == 0) return pauli_dpp<PAULI_DPP_XOR1>(v);
+    if (lvl == 1) return pauli_dpp<PAULI_DPP_XOR2>(v);
+    return __shfl_xor(v, 1 << lvl);
+}
+
+template <int NUM, bool EXCH>
+__global__ __launch_bounds__(256) void k_rdm_leaves(const amp_t *__restrict__ amp, double *__restrict__ dst, uint64_t row_stride,
+                                                    uint64_t ngroups, unsigned ug, unsigned first)
+{
+    static_assert(NUM >= 0 && NUM <= QCX_RDM_MAX_QUBITS, "a thread's 16 elements hold every value of the range");
+    constexpr unsigned EPT = 16u, NV = 1u << NUM, NR = NV * NV, S = 12u - NUM, C = EPT / NV;
+    constexpr unsigned NVAL = NR * C, GROUP = NVAL < 64u ? NVAL : 64u, NG = NVAL / GROUP;
+    constexpr unsigned HL = GROUP == 64u ? 6u : (GROUP == 32u ? 5u : 4u);      // halving levels of a group
+    static_assert((1u << HL) == GROUP, "a group is 16, 32 or 64 values");
+    __shared__ __attribute__((aligned(16))) amp_t sa[EXCH ? 256u * 17u : 1u];
+    __shared__ double ws[4u * NVAL];                                 // [wave][c * NR + row]
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t lowm = EXCH ? 0u : (((uint64_t)1) << (first - S)) - 1u;
+    auto amp_pos = [](unsigned e) { return e + (e >> 4); };
+    // the component a lane holds after a group's levels: bit l of the lane picked bit HL - 1 - l of the index
+    unsigned held = 0;
+#pragma unroll
+    for (unsigned l = 0; l < HL; l++) held |= ((lane >> l) & 1u) << (HL - 1u - l);
+    amp_t a[EPT];
+    auto load = [&](uint64_t u) {
+        const uint64_t base = EXCH ? u << 12 : (((u & lowm) << S) | ((u >> (first - S)) << (first + NUM)));
+        const amp_t *p = amp + base + tid;
+#pragma unroll
+        for (unsigned j = 0; j < EPT; j++) {
+            // element tid + 256 j of the unit, in memory order
+            const uint64_t o = EXCH ? 256u * j : (uint64_t)((256u * j) & ((1u << S) - 1u)) | ((uint64_t)(j >> (S - 8u)) << first);
+            a[j] = __builtin_nontemporal_load(p + o);
+        }
+    };
+    // (the counter's partial sums of row k are thread k's own words in LDS: in registers they cost the two-qubit exchange
+    // shape its second workgroup on a CU)
+    __shared__ double stack[QCX_RDM_MAX_GROUP_BITS * NR];
+    uint64_t g = blockIdx.x;
+    unsigned ui = 0;                                                 // unit ui of group g
+    if (g < ngroups) load(g << ug);
+    while (g < ngroups) {
+        const uint64_t g_next = ui + 1u == (1u << ug) ? g + gridDim.x : g;
+        const unsigned ui_next = ui + 1u == (1u << ug) ? 0u : ui + 1u;
+        const bool more = g_next < ngroups;
+        const uint64_t u_next = (g_next << ug) + ui_next;
+        amp_t x[EPT];
+        if constexpr (EXCH) {
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++) sa[amp_pos(tid + 256u * j)] = a[j];
+            __syncthreads();
+            if (more) load(u_next);
+            const unsigned fm = (1u << first) - 1u;
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++) {
+                const unsigned ep = tid + 256u * j, r = ep & ((1u << S) - 1u), v = ep >> S;
+                x[j] = sa[amp_pos((r & fm) | (v << first) | ((r >> first) << (first + NUM)))];
+            }
+        } else {
+#pragma unroll
+            for (unsigned j = 0; j < EPT; j++) x[j] = a[j];
+            if (more) load(u_next);
+        }
+#pragma unroll
+        for (unsigned gr = 0; gr < NG; gr++) {
+            double v[GROUP];
+#pragma unroll
+            for (unsigned i = 0; i < GROUP; i++) {
+                const unsigned I = gr * GROUP + i, c = I / NR, row = I % NR, rv = row / NV, rw = row % NV;
+                if (rv <= rw) {
+                    const amp_t p = x[rv * C + c], q = x[rw * C + c];
+                    v[i] = p.x * q.x + p.y * q.y;
+                } else {
+                    const amp_t p = x[rw * C + c], q = x[rv * C + c];
+                    v[i] = p.y * q.x - p.x * q.y;
+                }
+            }
+#pragma unroll
+            for (unsigned l = 0; l < HL; l++) {
+                const unsigned half = GROUP >> (l + 1u);
+                const bool up = ((lane >> l) & 1u) != 0;
+#pragma unroll
+                for (unsigned i = 0; i < half; i++) {
+                    const double keep = up ? v[i + half] : v[i], send = up ? v[i] : v[i + half];
+                    v[i] = keep + rdm_xor_lane(send, l);
+                }
+            }
+#pragma unroll
+            for (unsigned l = HL; l < 6u; l++) v[0] = v[0] + rdm_xor_lane(v[0], l);
+            if ((lane >> HL) == 0) ws[wave * NVAL + gr * GROUP + held] = v[0];
+        }
+        __syncthreads();
+        if (tid < NR) {
+            double s[C];
+#pragma unroll
+            for (unsigned c = 0; c < C; c++) {
+                const double *w = ws + c * NR + tid;
+                s[c] = (w[0] + w[NVAL]) + (w[2u * NVAL] + w[3u * NVAL]);
+            }
+#pragma unroll
+            for (unsigned len = C; len > 1u; len >>= 1)
+#pragma unroll
+                for (unsigned i = 0; i < len / 2u; i++) s[i] = s[2u * i] + s[2u * i + 1u];
+            // the unit's root joins the group's tree (ui is the same for all threads)
+            double root = 0.0 + s[0];
+            bool carry = true;
+#pragma unroll
+            for (unsigned l = 0; l < QCX_RDM_MAX_GROUP_BITS; l++)
+                if (carry && l < ug) {
+                    if ((ui >> l) & 1u) root = stack[l * NR + tid] + root;
+                    else { stack[l * NR + tid] = root; carry = false; }
+                }
+            if (carry) dst[tid * row_stride + g] = root;             // (every bit of ui set: the group's last unit)
+        }
+        // (EXCH: the next unit writes sa, which all have read, and ws only behind its own first barrier)
+        if constexpr (!EXCH) __syncthreads();
+        g = g_next; ui = ui_next;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rdm_small(const amp_t *__restrict__ amp, double *__restrict__ dst, unsigned n, unsigned first,
+                                                   unsigned num)
+{
+    __shared__ amp_t sa[2048];
+    __shared__ double red[4096];
+    const unsigned tid = threadIdx.x, nel = 1u << n, S = n - num, NV = 1u << num, fm = (1u << first) - 1u;
+    for (unsigned e = tid; e < nel; e += 256u) sa[e] = amp[e];
+    __syncthreads();
+    const unsigned total = (NV * NV) << S, batch = total < 4096u ? total : 4096u;      // (a batch holds whole rows: S <= 11)
+    for (unsigned b0 = 0; b0 < total; b0 += batch) {
+        for (unsigned k = tid; k < batch; k += 256u) {
+            const unsigned row = (b0 + k) >> S, r = (b0 + k) & ((1u << S) - 1u), rv = row >> num, rw = row & (NV - 1u);
+            const unsigned base = (r & fm) | ((r >> first) << (first + num));
+            const amp_t p = sa[base | ((rv <= rw ? rv : rw) << first)], q = sa[base | ((rv <= rw ? rw : rv) << first)];
+            red[k] = rv <= rw ? p.x * q.x + p.y * q.y : p.y * q.x - p.x * q.y;
+        }
+        __syncthreads();
+        // the tree levels of every row of the batch, lowest summed bit first; in place (read all, barrier, write all)
+        unsigned sz = batch;
+        for (unsigned h = 0; h < S; h++) {
+            const unsigned half = sz >> 1;
+            double v[8];
+#pragma unroll
+            for (unsigned m = 0; m < 8u; m++) {
+                const unsigned k = tid + 256u * m;
+                if (k < half) v[m] = red[2u * k] + red[2u * k + 1u];
+            }
+            __syncthreads();
+#pragma unroll
+            for (unsigned m = 0; m < 8u; m++) {
+                const unsigned k = tid + 256u * m;
+                if (k < half) red[k] = v[m];
+            }
+            __syncthreads();
+            sz = half;
+        }
+        for (unsigned k = tid; k < sz; k += 256u) dst[(b0 >> S) + k] = 0.0 + red[k];
+        __syncthreads();
+    }
+}
+
 }  // namespace qcx

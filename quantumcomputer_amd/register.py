@@ -284,6 +284,36 @@ class Register:
         check(lib().qcx_expectation_last_stats(self._h, C.byref(src), C.byref(reads)), "qcx_expectation_last_stats")
         return src.value, reads.value
 
+    def reduced_density_matrix(self, first, num):
+        """The reduced density matrix of qubits [first, first + num), the others traced out: complex128[2^num, 2^num], exactly,
+        from one read of the state, which stays as it was (include/qcx.h: qcx_reduced_density_matrix; the pinned arithmetic is
+        restated in tests/rdm_ref.py).  Qubit `first` is bit 0 of the row and column index; num <= rdm_max_qubits()."""
+        first, num = int(first), int(num)
+        if first < 0 or num < 0:
+            raise ValueError("reduced_density_matrix: first and num must be >= 0")
+        dim = 1 << num if num <= _lib.rdm_max_qubits() else 1          # (a wider range: the call refuses, QCX_UNSUPPORTED)
+        out = np.empty((dim, dim), dtype=np.complex128)
+        check(lib().qcx_reduced_density_matrix(self._h, first, num, out.ctypes.data_as(C.c_void_p)), "qcx_reduced_density_matrix")
+        return out
+
+    def rdm_stats(self):
+        """(source, state reads) of the last reduced_density_matrix call on this register: source 0 = the register, 2 = a pending
+        basis state (no kernel), 3 = a compact circuit result expanded first; state reads: 1, or 0 for a basis state"""
+        src, reads = C.c_uint(0), C.c_ulong(0)
+        check(lib().qcx_rdm_last_stats(self._h, C.byref(src), C.byref(reads)), "qcx_rdm_last_stats")
+        return src.value, reads.value
+
+    def expectation_matrix(self, first, O):
+        """Tr(rho O) as a Python complex, for any 2^num x 2^num matrix O on the qubits [first, first + num) (qubit `first` = bit 0
+        of O's index): <psi|O|psi> of an observable that need not be a Pauli string.  rho is reduced_density_matrix(first, num),
+        pinned bit for bit; the product over it is ordinary numpy on the host and is NOT pinned."""
+        O = np.asarray(O, dtype=np.complex128)
+        dim = O.shape[0] if O.ndim == 2 else 0
+        if O.ndim != 2 or O.shape[1] != dim or dim < 1 or dim & (dim - 1):
+            raise ValueError("expectation_matrix: O must be a 2^num x 2^num matrix")
+        rho = self.reduced_density_matrix(first, dim.bit_length() - 1)
+        return complex(np.sum(rho * O.T))
+
     def set_fusion(self, enable=True):
         """Fused LDS-tile passes (bit-identical results).  True/1: every gate call is queued; False/0 (default): only
         the whole-circuit calls (inverse_QFT, quantum_computation) run as fused passes; -1: strictly one kernel launch
@@ -520,6 +550,21 @@ def measure_qubits(reg, first, num, rng_or_r, strict=True):
 def postselect_qubits(reg, first, num, outcome, strict=True):
     """Collapse `reg` onto `outcome` of the qubits [first, first + num): the probability it had (Register.postselect)."""
     return reg.postselect(first, num, outcome, strict=strict)
+
+
+def purity(rho):
+    """Re Tr rho^2 of a matrix Register.reduced_density_matrix returned: 1 for a pure reduced state, 2^-num for the maximally
+    mixed one (ordinary numpy, not pinned)"""
+    rho = np.asarray(rho, dtype=np.complex128)
+    return float(np.real(np.sum(rho * rho.T)))
+
+
+def von_neumann_entropy(rho, base=2):
+    """-Tr rho log rho of a matrix Register.reduced_density_matrix returned, in units of log `base` (bits by default), from
+    numpy.linalg.eigvalsh; eigenvalues <= 0 are dropped (ordinary numpy, not pinned)"""
+    ev = np.linalg.eigvalsh(np.asarray(rho, dtype=np.complex128))
+    ev = ev[ev > 0]
+    return float(-np.sum(ev * np.log(ev)) / np.log(base))
 
 
 def omega_distribution(reg):
