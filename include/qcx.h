@@ -27,6 +27,9 @@
  *   - one state buffer, updated in place; swap_states is a no-op.
  * All gate calls are asynchronous on the register's HIP stream; read-back,
  * measurement and qcx_synchronize() wait.
+ * Threads: distinct registers may be used from distinct threads at the same time (the per-device scratch is locked);
+ *   one register is used by one thread at a time -- the caller serialises calls on the same handle;
+ *   the launch knobs (qcx_tune_set) are process-wide: do not change them while another thread is inside the library.
  */
 #ifndef QCX_H
 #define QCX_H

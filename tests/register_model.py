@@ -8,12 +8,17 @@ range collapse, tests/pauli_ref.py / pauli_rotation_ref.py for the Pauli calls -
 bit-for-bit expectation for the same calls on the GPU, whatever lazy form (queue, pending basis state, compact result, owed zero
 pass, strict mode, a handed-out buffer pointer, a caller's stream) the library keeps the state in between them.
 
-The generator has two vocabularies.  Seeds below NSEEDS_V1 draw from the calls up to the matrix gates; their op lists are frozen
-(tests/golden/sequence_digests.json: whatever is added here must leave them as they are).  The seeds from NSEEDS_V1 on add
+The generator has three vocabularies.  Seeds below NSEEDS_V1 draw from the calls up to the matrix gates; their op lists are frozen
+(tests/golden/sequence_digests.json: whatever is added here must leave them as they are).  The seeds NSEEDS_V1 .. NSEEDS - 1 add
 expect / expect_sum / prot (the Pauli calls), devptr (a read through qcx_device_pointer, after which the register works in
 place for the rest of its life) and stream (qcx_register_set_stream: a caller's non-blocking stream, or the own one again).
 
-A third family, generate_sharded (seeds 0 .. NSEEDS_SH - 1 of its own, at the end of this file), draws sequences for a SHARDED
+A third vocabulary (seeds NSEEDS .. NSEEDS_V3 - 1) adds the two newest observers: expect_batch (qcx_pauli_expectation_batch, the
+terms that share an x_mask in one read of the state) and rdm (qcx_reduced_density_matrix).  Its seeds also draw the launch knobs
+of the fused engine (KNOBS_FUSED), so that every call of the vocabulary meets a state that just left a chained pass, a generated
+front or a compact chain under other than the default knobs.
+
+A further family, generate_sharded (seeds 0 .. NSEEDS_SH - 1 of its own, at the end of this file), draws sequences for a SHARDED
 register (qcx_register_create_sharded): the same model -- a sharded register promises the same bits for the calls it supports --
 with the calls it refuses (QCX_UNSUPPORTED, nothing touched) as refused ops, and relays / selfcheck / stats ops the model does
 nothing for.  tests/test_sharded_sequences_dry.py replays them on a dry-run register, tests/test_gpu_sharded_sequences.py on the GPU.
@@ -28,6 +33,7 @@ import pauli_rotation_ref
 import two_qubit_ref
 from collapse_ref import collapse_ref, measure_ref
 from marginal_ref import marginal_ref
+from rdm_ref import rdm_ref
 
 NO_ERROR, BAD_ARGUMENTS, BAD_QUBIT, UNSUPPORTED = 0, 2, 6, 7
 THREADS = 8
@@ -129,6 +135,33 @@ def sum_terms(n, seed, k):
     return terms
 
 
+BATCH_WIDTH = 32                          # qcx_pauli_batch_width(): the most terms one read of the state serves
+RDM_MAX = 4                               # qcx_rdm_max_qubits() (tests/test_gpu_api_sequences.py checks both against the library)
+
+
+def batch_terms(n, seed, k):
+    """the k terms (coeff, x_mask, z_mask) of an expect_batch op.  One seed in two draws them as sum_terms does (every term its
+    own x_mask, some of them equal by chance); the others share ONE x_mask -- of any of draw_masks' three shapes -- with
+    z_masks of their own, two of them equal when k >= 2: k = 40 of those are more than BATCH_WIDTH and take a second read"""
+    rs = np.random.RandomState(seed)
+    if rs.randint(0, 2):
+        return sum_terms(n, int(rs.randint(1, 1 << 30)), k)
+    x, _ = draw_masks(rs, n)
+    terms = [(float(rs.uniform(-2.0, 2.0)), x, x if rs.randint(0, 4) == 0 else int(rs.randint(0, 1 << n))) for _ in range(k)]
+    if k >= 2:
+        terms[-1] = (terms[-1][0],) + terms[0][1:]
+    if k >= 3:
+        j = int(rs.randint(0, k))
+        terms[j] = (0.0,) + terms[j][1:]
+    return terms
+
+
+def rdm_shape(n, first, num):
+    """0, 1, 2: which kernel form a reduced density matrix takes: k_rdm_small (n < 12), k_rdm_leaves with the range beginning
+    below the 12 - num summed bits of a unit, k_rdm_leaves with the range at or above them"""
+    return 0 if n < 12 else 1 if first < 12 - num else 2
+
+
 # ---- the model --------------------------------------------------------------------------------------------------------------
 
 class RegisterModel:
@@ -213,6 +246,14 @@ class RegisterModel:
         total, values = pauli_ref.pauli_sum_ref(self.a, self.n, terms)
         return total, np.array(values, dtype=np.float64)
 
+    def expectation_batch(self, terms):
+        """the same definition as expectation_sum: how the terms share reads of the state changes no bit"""
+        return self.expectation_sum(terms)
+
+    def reduced_density_matrix(self, first, num):
+        """float64[2^num, 2^num, 2]: (re, im)"""
+        return rdm_ref(self.a, self.n, first, num)
+
     def pauli_rotation(self, x_mask, z_mask, theta):
         self.a = pauli_rotation_ref.apply(self.a, self.n, x_mask, z_mask, theta)
 
@@ -231,11 +272,13 @@ FOLLOWING = ("reset", "fill", "write", "read", "h", "cphase", "camodc", "iqft", 
              "sample", "marginal", "measure_qubits", "postselect", "total", "norm2", "save", "load", "flush", "sync", "fusion")
 # the second vocabulary (seeds NSEEDS_V1 .. NSEEDS - 1): the Pauli calls, the handed-out buffer pointer, the caller's stream
 FOLLOWING_V2 = FOLLOWING + ("expect", "expect_sum", "prot", "devptr", "stream")
+# the third vocabulary (seeds NSEEDS .. NSEEDS_V3 - 1): the batched Pauli sum and the reduced density matrix
+FOLLOWING_V3 = FOLLOWING_V2 + ("expect_batch", "rdm")
 SETTING = ("reset", "measure_state", "fill", "write_full_negzero", "write_partial", "write_nonfinite", "collapse", "compact",
            "queued_mode1", "queued_behind_basis", "load")
 QUEUED = ("h", "cphase", "camodc", "iqft", "qcomp")
 # calls that leave a lazily pending basis state pending (answered from the basis index, or refused before anything runs)
-QUIET_FOR_PENDING = ("sample", "marginal", "stats", "measure_qubits", "postselect", "refused", "expect", "expect_sum")
+QUIET_FOR_PENDING = ("sample", "marginal", "stats", "measure_qubits", "postselect", "refused", "expect", "expect_sum", "expect_batch", "rdm")
 
 
 def apply_to_model(m, op):
@@ -269,6 +312,8 @@ def apply_to_model(m, op):
     elif k == "stats": pass
     elif k == "expect": return m.expectation(op[1], op[2])
     elif k == "expect_sum": return m.expectation_sum(sum_terms(m.n, op[1], op[2]))
+    elif k == "expect_batch": return m.expectation_batch(batch_terms(m.n, op[1], op[2]))
+    elif k == "rdm": return (m.reduced_density_matrix(op[1], op[2]), m.marginal(op[1], op[2]))
     elif k == "prot": m.pauli_rotation(op[1], op[2], op[3])
     elif k == "devptr": return m.read(op[1], op[2])
     elif k == "stream": pass
@@ -290,7 +335,8 @@ def apply_to_model(m, op):
 # ---- the generator -----------------------------------------------------------------------------------------------------------
 
 NSEEDS_V1, NSEEDS = 64, 128              # seeds < NSEEDS_V1: vocabulary 1, frozen (tests/golden/sequence_digests.json); the others: 2
-SMALL_V1 = 24                             # the same for the small sequences of generate(.., small=True)
+NSEEDS_V3 = NSEEDS + 64                   # seeds NSEEDS .. NSEEDS_V3 - 1: vocabulary 3, frozen like the others
+SMALL_V1 = 24                             # the same for the small sequences of generate(.., small=True): 24 of every vocabulary
 # (L, M, C, a); n = 6 .. 14, M = 0 and n < 9 (partial tiles in several kernels) included
 SHAPES = [(8, 4, 15, 7), (9, 5, 21, 2), (8, 5, 21, 2), (6, 0, 1, 1), (10, 0, 1, 1), (2, 4, 15, 7), (3, 4, 15, 7), (4, 4, 15, 7),
           (5, 5, 21, 2), (13, 0, 1, 1), (7, 6, 35, 2), (10, 4, 15, 7), (4, 5, 21, 2), (8, 0, 1, 1)]
@@ -304,13 +350,26 @@ KNOBS_N9 = [dict(h_variant=1, h_ppt=2, h_streams_log2=3), dict(h_variant=2, h_wa
 KNOBS_ANY = [dict(collapse_upt=8), dict(collapse_perm=0), dict(collapse_grid_cap=1), dict(collapse_grid_cap=3, collapse_upt=8)]
 # vocabulary 2 adds K15's grid cap, at values that do not divide the number of units a rotation walks
 KNOBS_V2 = [dict(prot_grid_cap=1), dict(prot_grid_cap=3)]
+# vocabulary 3 adds the launch knobs of the fused engine, at the values tests/test_gpu_fuzz.py draws: chained passes from n = 13
+# on (the default begins at n = 20), the walk on 8 amplitudes per thread from one tile on or not at all, smaller and larger
+# tiles, no generated front, no column form of it, a compact result that is expanded at once, k_expand_compact in place of the
+# expanding store, no plan cache, the record scan of the measurement from 2^10 amplitudes on.  Drawn only for registers of
+# n >= max(M + 6, 10), the range the fuzz test uses
+KNOBS_FUSED = [dict(fuse_chain_min_n=13), dict(fuse_chain_min_n=13, fuse_chain_dir=0), dict(fuse_chain_min_n=13, fuse_chain_dir=1),
+               dict(fuse_x8_min_tiles_log2=0), dict(fuse_x8=0), dict(fuse_T=10), dict(fuse_T=12, fuse_c=3), dict(fuse_gen=0),
+               dict(fuse_gen_cols=0), dict(fuse_compact_lazy=0), dict(fuse_expand_fused=0), dict(fuse_plan_cache=0),
+               dict(meas_min_log2=10, meas_block_log=8), dict(meas_min_log2=10, meas_fast=0)]
+# without these two no flush runs as a compact chain (compact_chain_plan, csrc/qcx_fuse.inc.h), which run_ops asserts on the
+# compact seeds
+ENDS_COMPACT_CHAINS = ("fuse_gen", "fuse_gen_cols")
 
 
 class Config:
     def __init__(self, seed, small=False):
         rs = np.random.RandomState(7919 * seed + 13)
         self.seed, self.small = seed, small
-        self.vocab = 1 if seed < (SMALL_V1 if small else NSEEDS_V1) else 2
+        v1, v2 = (SMALL_V1, 2 * SMALL_V1) if small else (NSEEDS_V1, NSEEDS)
+        self.vocab = 1 if seed < v1 else 2 if seed < v2 else 3
         self.compact = (not small) and seed % 8 == 5
         if small:
             shapes = [SMALL_SHAPES[seed % len(SMALL_SHAPES)]]
@@ -325,8 +384,14 @@ class Config:
         self.modes = [self.mode] + [int(rs.choice([-1, 0, 1])) for _ in shapes[1:]]      # the start mode of every register
         self.knobs = {}
         if not small and seed % 3 == 1:
-            pool = KNOBS_ANY + (KNOBS_V2 if self.vocab == 2 else []) + (KNOBS_N9 if min(s[0] + s[1] for s in shapes) >= 9 else [])
+            pool = KNOBS_ANY + (KNOBS_V2 if self.vocab >= 2 else []) + (KNOBS_N9 if min(s[0] + s[1] for s in shapes) >= 9 else [])
             for i in rs.choice(len(pool), 3, replace=False):
+                self.knobs.update(pool[int(i)])
+        # vocabulary 3, two seeds in three: the fused engine's knobs (seed % 3 == 1: one dict on top of the per-gate knobs;
+        # seed % 3 == 2: two of them); seed % 3 == 0 runs under the defaults
+        if self.vocab == 3 and not small and seed % 3 and all(L + M >= max(M + 6, 10) for L, M, _, _ in shapes):
+            pool = [d for d in KNOBS_FUSED if not (self.compact and any(k in ENDS_COMPACT_CHAINS for k in d))]
+            for i in rs.choice(len(pool), seed % 3, replace=False):
                 self.knobs.update(pool[int(i)])
 
     def __repr__(self):
@@ -347,11 +412,11 @@ def pair_is_legal(s, f, shape, compact):
 
 
 def seeds_of(vocab):
-    return range(NSEEDS_V1) if vocab == 1 else range(NSEEDS_V1, NSEEDS)
+    return range(NSEEDS_V1) if vocab == 1 else range(NSEEDS_V1, NSEEDS) if vocab == 2 else range(NSEEDS, NSEEDS_V3)
 
 
 def following_of(vocab):
-    return FOLLOWING if vocab == 1 else FOLLOWING_V2
+    return FOLLOWING if vocab == 1 else FOLLOWING_V2 if vocab == 2 else FOLLOWING_V3
 
 
 def _schedule(vocab):
@@ -509,6 +574,8 @@ class _Gen:
         if f == "expect": return ("expect", *draw_masks(rs, n))
         if f == "expect_sum": return ("expect_sum", self.seed(), int(rs.choice([0, 1, 3, 6])))
         if f == "prot": return ("prot", *draw_masks(rs, n), self.theta())
+        if f == "expect_batch": return ("expect_batch", self.seed(), int(rs.choice([0, 1, 3, 6, 6, 40])))
+        if f == "rdm": return ("rdm", *self.rdm_range())
         if f == "devptr":
             if rs.randint(0, 3) == 0:
                 return ("devptr", 0, self.dim)
@@ -516,6 +583,17 @@ class _Gen:
             return ("devptr", first, int(rs.randint(1, min(self.dim - first, 2000) + 1)))
         if f == "stream": return ("stream", int(rs.randint(0, 2)))
         raise ValueError(f)
+
+    def rdm_range(self):
+        """(first, num) with num = 0 .. RDM_MAX; on a register of n >= 12 one draw in two begins below bit 12 - num and the other
+        at or above it (rdm_shape: the two forms of k_rdm_leaves)"""
+        rs, n = self.rs, self.n
+        num = int(rs.randint(0, min(RDM_MAX, n) + 1))
+        if n < 12:
+            return int(rs.randint(0, n - num + 1)), num
+        if rs.randint(0, 2):
+            return int(rs.randint(0, 12 - num)), num
+        return int(rs.randint(12 - num, n - num + 1)), num
 
     def theta(self):
         """uniform in (-7, 7); one draw in six is 0.0, pi, 2 pi or -0.0 (the two zeros leave the state's bits as they are)"""
@@ -531,19 +609,33 @@ class _Gen:
         self.emit(("prot", *draw_masks(self.rs, self.n), self.theta()))
         self.emit(("prot", x, z, self.theta()))
         self.emit(("expect", x, z) if self.rs.randint(0, 2) else ("expect_sum", self.seed(), int(self.rs.choice([1, 3, 6]))))
+        if self.vocab == 3:                     # the same state through the batched sum and the density matrix, either first
+            tail = [("expect_batch", self.seed(), int(self.rs.choice([3, 6, 40]))), ("rdm", *self.rdm_range())]
+            for op in tail[::-1] if self.rs.randint(0, 2) else tail:
+                self.emit(op)
 
     def quiet(self):
         """a call that leaves every lazy form as it is (the issue's "non-flushing" calls)"""
-        c = int(self.rs.randint(0, 3 if self.vocab == 1 else 4))
+        c = int(self.rs.randint(0, {1: 3, 2: 4, 3: 6}[self.vocab]))
         if c == 0: return ("sample", self.seed(), int(self.rs.choice([1, 4, 9])))
         if c == 1: return ("marginal", *self.a_range(self.M))
         if c == 3: return ("expect", *draw_masks(self.rs, self.n))
+        if c == 4: return ("expect_batch", self.seed(), int(self.rs.choice([1, 3, 6])))
+        if c == 5: return ("rdm", *self.rdm_range())
         return ("stats",)
 
     def refused(self):
         """a call the library must refuse with the state untouched: (inner op, status)"""
         rs, n = self.rs, self.n
-        c = int(rs.randint(0, 4 if self.vocab == 1 else 6))
+        c = int(rs.randint(0, {1: 4, 2: 6, 3: 8}[self.vocab]))
+        if c == 6:                                                           # a density matrix past the register, or wider than the call serves
+            if n > RDM_MAX and rs.randint(0, 2):
+                return ("rdm", int(rs.randint(0, n - RDM_MAX)), RDM_MAX + 1), UNSUPPORTED
+            num = int(rs.randint(1, RDM_MAX + 3))                            # (past the register is looked at first: RDM_MAX + 1 and + 2 too)
+            return ("rdm", int(rs.randint(max(0, n - num + 1), n + 2)), num), BAD_QUBIT
+        if c == 7:                                                           # a batch with ONE mask that reaches bit n: nothing runs
+            k = int(rs.choice([1, 3, 6, 40]))
+            return ("expect_batch", self.seed(), k, int(rs.randint(0, k)), str(rs.choice(["x", "z"]))), BAD_QUBIT
         if c >= 4:                                                           # the Pauli calls: a mask that reaches bit n, an angle that is not finite
             x, z = draw_masks(rs, n)
             k = int(rs.randint(0, 3))
@@ -689,7 +781,7 @@ class _Gen:
         if rs.randint(0, 12) == 0:
             self.underflow()
             return
-        if self.vocab == 2 and rs.randint(0, 8) == 0:
+        if self.vocab >= 2 and rs.randint(0, 8) == 0:
             self.pauli()
             return
         f = self.following[int(rs.randint(0, len(self.following)))]
@@ -727,7 +819,7 @@ def generate(ob, seed, small=False, length=None):
             g.refuse()
         if rs.randint(0, 10) < 2:
             g.extra()
-        if cfg.vocab == 2 and rs.randint(0, 10) < (5 if g.m.holds_nonfinite() else 1):    # (often where the state is not finite:
+        if cfg.vocab >= 2 and rs.randint(0, 10) < (5 if g.m.holds_nonfinite() else 1):    # (often where the state is not finite:
             g.pauli()                                                                       #  the strict register's Pauli calls)
     while len(g.ops) < 40:
         g.extra()
@@ -747,7 +839,8 @@ def generate(ob, seed, small=False, length=None):
 # ---- what a list of ops reaches (judged on the list alone) ---------------------------------------------------------------------
 
 def is_quiet(op, M, vocab=1):
-    return op[0] in ("sample", "stats") or (op[0] == "marginal" and op[1] >= M) or (vocab == 2 and op[0] == "expect")
+    return (op[0] in ("sample", "stats") or (op[0] == "marginal" and op[1] >= M) or (vocab in (2, 3) and op[0] == "expect")
+            or (vocab == 3 and op[0] in ("expect_batch", "rdm")))
 
 
 def compact_shape(shape):

@@ -5,10 +5,12 @@ entry point settles it in its own way; the files of the single features check ea
 this one checks chains of them.  Everything a call returns is compared bit for bit (NaN matching NaN) with the model; full
 reads are rare, so that the lazy forms live long.
 
-Two vocabularies: the seeds below register_model.NSEEDS_V1 draw from the calls up to the matrix gates and are frozen
+Three vocabularies: the seeds below register_model.NSEEDS_V1 draw from the calls up to the matrix gates and are frozen
 (tests/golden/sequence_digests.json); the others add the Pauli calls (expectation, expectation_sum, pauli_rotation), reads
 through qcx_device_pointer (after which the register works in place for the rest of its life) and qcx_register_set_stream with
 a non-blocking stream of PyTorch's, which is not ordered with the null stream the way the register's own stream is.
+The seeds from register_model.NSEEDS on add the batched Pauli sum (expectation_batch) and the reduced density matrix, and run
+under launch knobs of the fused engine as well (register_model.KNOBS_FUSED).  The replaying itself is tests/sequence_replay.py.
 
 One seed alone:  QCX_SEQ_CASE=<seed> [QCX_SEQ_OPS=<k>] python -m pytest tests/test_gpu_api_sequences.py -m gpu -q -s -k random
 (a failure prints the seed, the index of the failing op and the ops up to it as a Python literal)."""
@@ -19,36 +21,12 @@ import numpy as np
 import pytest
 
 import register_model as rm
+from sequence_replay import apply_to_register, bits, compact_chains, compact_measures, compare, run_ops
+from sequence_replay import same, status_of  # noqa: F401  (tests/test_gpu_sharded_sequences.py takes them from here)
 
 pytestmark = pytest.mark.gpu
 
-KNOB_KEYS = sorted({k for d in rm.KNOBS_N9 + rm.KNOBS_ANY + rm.KNOBS_V2 for k in d})
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(got, want, what):
-    """bitwise, NaN matching NaN"""
-    got, want = np.asarray(got, dtype=np.float64).reshape(-1), np.asarray(want, dtype=np.float64).reshape(-1)
-    assert got.shape == want.shape, what
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), f"{what}: NaN positions differ at {np.flatnonzero(gn != wn)[:6]}"
-    bad = np.flatnonzero(bits(got[~gn]) != bits(want[~wn]))
-    assert bad.size == 0, f"{what}: {bad.size} values differ, first at {bad[:4]}: {got[~gn][bad[:4]]} vs {want[~wn][bad[:4]]}"
-
-
-def compact_measures(qc, reg):
-    v = C.c_ulong(0)
-    assert qc.lib().qcx_compact_measure_stats(reg._h, C.byref(v)) == 0
-    return int(v.value)
-
-
-def compact_chains(qc, reg):
-    v = C.c_ulong(0)
-    assert qc.lib().qcx_compact_stats(reg._h, C.byref(v)) == 0
-    return int(v.value)
+KNOB_KEYS = sorted({k for d in rm.KNOBS_N9 + rm.KNOBS_ANY + rm.KNOBS_V2 + rm.KNOBS_FUSED for k in d})
 
 
 def measure_last_stats(qc):
@@ -61,199 +39,6 @@ def chain_stats(qc, reg):
     v = C.c_ulong(0)
     assert qc.lib().qcx_chain_stats(reg._h, C.byref(v)) == 0
     return int(v.value)
-
-
-_hip_memcpy = None
-
-
-def hip_memcpy():
-    """hipMemcpy of the HIP runtime this process already holds (quantumcomputer_amd/_lib.py arranges that there is one): looked
-    up in the process image, or, where the runtime was not loaded into the global scope, in the one copy that is mapped"""
-    global _hip_memcpy
-    if _hip_memcpy is None:
-        try:
-            fn = C.CDLL(None).hipMemcpy
-        except AttributeError:
-            with open("/proc/self/maps") as f:
-                mapped = sorted({line.split()[-1] for line in f if "libamdhip64.so" in line})
-            assert len(mapped) == 1, f"one HIP runtime per process, mapped are {mapped}"
-            fn = C.CDLL(mapped[0]).hipMemcpy
-        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        _hip_memcpy = fn
-    return _hip_memcpy
-
-
-def read_through_pointer(reg, first, count, ctx):
-    """`count` amplitudes from qcx_device_pointer() + 16 * first, copied by the caller; the pointer never changes"""
-    assert 0 <= first and 0 < count and first + count <= reg.num_states
-    ptr = reg.device_pointer()
-    assert ptr, "qcx_device_pointer returned null"
-    assert ctx.setdefault("pointer", ptr) == ptr, f"the buffer that was handed out as {ctx['pointer']:#x} is now {ptr:#x}"
-    reg.synchronize()
-    out = np.empty(2 * count, dtype=np.float64)
-    st = hip_memcpy()(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr + 16 * first), 16 * count, 2)      # hipMemcpyDeviceToHost
-    assert st == 0, f"hipMemcpy: error {st}"
-    return out
-
-
-def set_stream(reg, on, ctx):
-    """on: the register works on ONE non-blocking stream of PyTorch's, alive until the register is closed; off: on its own"""
-    if on:
-        if "stream" not in ctx:
-            import torch
-            ctx["stream"] = torch.cuda.Stream()
-        reg.set_stream(ctx["stream"].cuda_stream)
-    else:
-        reg.set_stream(0)
-
-
-def status_of(qc, call):
-    try:
-        call()
-    except qc.QcxError as e:
-        return e.status
-    return rm.NO_ERROR
-
-
-def apply_to_register(qc, reg, op, path_of, ctx):
-    """one op on the GPU register; returns what the call returns, in the form register_model.apply_to_model gives.  ctx: a dict
-    per register that lives until the register is closed (the handed-out pointer, the caller's stream)"""
-    k = op[0]
-    if k == "reset": qc.reset_register(reg)
-    elif k == "fill": reg.fill_random(op[1])
-    elif k == "write": reg.write(rm.window_data(reg.num_states, op[2], op[3], op[4]), op[1])
-    elif k == "read": return reg.read(op[1], op[2])
-    elif k == "h": qc.hadamard_gate(op[1], reg)
-    elif k == "cphase": qc.c_phase_shift_gate(op[1], op[2], op[3], reg)
-    elif k == "camodc": qc.c_amodc_gate(op[1], op[2], op[3], reg)
-    elif k == "iqft": qc.inverse_QFT(reg)
-    elif k == "qcomp": qc.quantum_computation(op[1], op[2], reg)
-    elif k == "u1": qc.one_qubit_gate(op[1], rm.matrix_data(2, op[2]), reg)
-    elif k == "cu1": qc.c_one_qubit_gate(op[1], op[2], rm.matrix_data(2, op[3]), reg)
-    elif k == "u2": qc.two_qubit_gate(op[1], op[2], rm.matrix_data(4, op[3]), reg)
-    elif k == "cu2": qc.c_two_qubit_gate(op[1], op[2], op[3], rm.matrix_data(4, op[4]), reg)
-    elif k == "measure": return qc.measure_state(reg, op[1])
-    elif k == "sample": return qc.sample_states(reg, rm.sample_draws(op[1], op[2]))
-    elif k == "marginal": return reg.marginal(op[1], op[2])
-    elif k == "measure_qubits": return reg.measure_qubits(op[1], op[2], op[3], strict=False)
-    elif k == "postselect": return reg.postselect(op[1], op[2], op[3], strict=False)
-    elif k == "total": return reg.total_probability()
-    elif k == "norm2": return reg.norm2()
-    elif k == "save": reg.save(path_of(op[1]))
-    elif k == "load": reg.load(path_of(op[1]))
-    elif k == "flush": reg.flush()
-    elif k == "sync": reg.synchronize()
-    elif k == "fusion": reg.set_fusion(op[1])
-    elif k == "stats":
-        reg.fusion_stats(); reg.marginal_stats(); reg.sample_stats(); reg.collapse_stats(); compact_measures(qc, reg)
-        reg.expectation_stats()
-    elif k == "expect": return reg.expectation((op[1], op[2]))
-    elif k == "expect_sum": return reg.expectation_sum([(c, (x, z)) for c, x, z in rm.sum_terms(reg.num_qubits, op[1], op[2])])
-    elif k == "prot": qc.pauli_rotation((op[1], op[2]), op[3], reg)
-    elif k == "devptr": return read_through_pointer(reg, op[1], op[2], ctx)
-    elif k == "stream": set_stream(reg, op[1], ctx)
-    elif k == "refused":
-        inner = op[1]
-        j = inner[0]
-        if j == "postselect":
-            p, st = reg.postselect(inner[1], inner[2], inner[3], strict=False)
-            return (p, st) if inner[3] < (1 << inner[2]) and inner[1] + inner[2] <= reg.num_qubits else st
-        if j == "h": return status_of(qc, lambda: qc.hadamard_gate(inner[1], reg))
-        if j == "marginal": return status_of(qc, lambda: reg.marginal(inner[1], inner[2]))
-        if j == "cphase": return status_of(qc, lambda: qc.c_phase_shift_gate(inner[1], inner[2], inner[3], reg))
-        if j == "u1": return status_of(qc, lambda: qc.one_qubit_gate(inner[1], rm.matrix_data(2, inner[2]), reg))
-        if j == "u1x": return status_of(qc, lambda: qc.one_qubit_gate(inner[1], rm.matrix_data(2, inner[2], ulp=True), reg))
-        if j == "expect":                                                  # (through the library: pauli_masks would raise first)
-            v = C.c_double(0.0)
-            return qc.lib().qcx_pauli_expectation(reg._h, inner[1], inner[2], C.byref(v))
-        if j == "prot": return qc.lib().qcx_pauli_rotation(inner[1], inner[2], float(inner[3]), reg._h)
-        if j == "u2x": return status_of(qc, lambda: qc.two_qubit_gate(inner[1], inner[2], rm.matrix_data(4, inner[3], ulp=True), reg))
-        raise ValueError(f"unknown refused op {op!r}")
-    else:
-        raise ValueError(f"unknown op {op!r}")
-    return None
-
-
-def compare(op, got, want):
-    k = op[0]
-    if k in ("read", "marginal", "devptr"):
-        same(got, want, k)
-    elif k == "expect":
-        same([got], [want], "expectation")
-    elif k == "expect_sum":
-        same([got[0]], [want[0]], "the terms' sum")
-        same(got[1], want[1], "the values of the terms")
-    elif k in ("measure",):
-        assert got == want, f"index {got} != {want}"
-    elif k == "sample":
-        assert np.array_equal(got, want), f"indices {got.tolist()} != {want.tolist()}"
-    elif k == "measure_qubits":
-        assert (got[0], got[2]) == (want[0], want[2]), f"(outcome, status) {(got[0], got[2])} != {(want[0], want[2])}"
-        same([got[1]], [want[1]], "probability")
-    elif k == "postselect":
-        assert got[1] == want[1], f"status {got[1]} != {want[1]}"
-        same([got[0]], [want[0]], "probability")
-    elif k == "total":
-        same([got], [want], "total_probability")
-    elif k == "norm2":
-        if want is not None:                                               # (a tree sum: not bit-defined; skipped on a non-finite state)
-            assert abs(got - want) < 1e-9, f"norm2 {got!r} vs {want!r}"
-    elif k == "refused":
-        if isinstance(want, tuple):
-            assert got[1] == want[1], f"status {got[1]} != {want[1]}"
-            same([got[0]], [want[0]], "probability")
-        else:
-            assert got == want, f"status {got} != {want}"
-    else:
-        assert got is None and want is None
-
-
-FLUSHES_NOTHING = ("reset", "fill", "stats", "refused") + rm.QUEUED      # (in mode 1: these leave a queued circuit queued, or drop it)
-
-
-def run_ops(qc, ob, shapes, modes, ops, tmp_path, header, compact=False):
-    """the ops on fresh registers and fresh models, everything returned compared; ends with a full read of every register.
-    compact: register 0 has a shape at which reset + quantum_computation must run as a compact chain (qcx_compact_stats moves:
-    with the call in mode 0, with the first call that flushes the queue in mode 1)"""
-    regs, models, ctxs = [], [], []
-    done = []
-    modes = list(modes)
-    owed = None                                 # the compact-chain count register 0 must show after its next flushing call
-    try:
-        for (L, M, Cn, a), mode in zip(shapes, modes):
-            reg = qc.Register(L, M)
-            reg.set_fusion(mode)
-            regs.append(reg)
-            ctxs.append({})
-            models.append(rm.RegisterModel(ob, L, M))
-        for i, (which, op) in enumerate(ops):
-            done.append((which, op))
-            try:
-                chains = compact_chains(qc, regs[0]) if compact and which == 0 else 0
-                got = apply_to_register(qc, regs[which], op, lambda slot: str(tmp_path / f"reg{which}_slot{slot}.qcx"), ctxs[which])
-                want = rm.apply_to_model(models[which], op)
-                compare(op, got, want)
-                if op[0] == "fusion":
-                    modes[which] = op[1]
-                if compact and which == 0:
-                    if owed is not None and op[0] not in FLUSHES_NOTHING:
-                        assert compact_chains(qc, regs[0]) == owed, f"the queued circuit did not run as a compact chain ({chains} chains before, {compact_chains(qc, regs[0])} now)"
-                    if owed is not None and op[0] != "stats":
-                        owed = None
-                    if op[0] == "qcomp" and len(done) > 1 and [o for w, o in done[:-1] if w == 0][-1:] == [("reset",)]:
-                        if modes[0] == 0:
-                            assert compact_chains(qc, regs[0]) == chains + 1, "reset + quantum_computation did not run as a compact chain"
-                        elif modes[0] == 1:
-                            owed = chains + 1
-                if i + 1 == len(ops):
-                    for w in range(len(regs)):
-                        same(regs[w].read(), models[w].a, f"the final state of register {w}")
-            except Exception as e:
-                raise AssertionError(f"{header}\nop {i} on register {which}: {op!r}\n{type(e).__name__}: {e}\nops = {done!r}") from e
-    finally:
-        for reg in regs:
-            reg.close()
-        ctxs.clear()                                # (the callers' streams go after the registers that worked on them)
 
 
 # ---- random sequences ----------------------------------------------------------------------------------------------------------
@@ -274,7 +59,7 @@ def one_seed(qc, ob, seed, tmp_path):
 ONLY = os.environ.get("QCX_SEQ_CASE")
 
 
-@pytest.mark.parametrize("seed", [int(ONLY)] if ONLY else range(rm.NSEEDS))
+@pytest.mark.parametrize("seed", [int(ONLY)] if ONLY else range(rm.NSEEDS_V3))
 def test_random_sequences_against_the_model(qc, ob, tmp_path, seed):
     one_seed(qc, ob, seed, tmp_path)
 
@@ -776,3 +561,203 @@ def test_random_sequence_gives_the_same_on_the_callers_stream(qc, ob, tmp_path):
     assert len(own) == len(callers)
     for a_, b_ in zip(own, callers):
         assert a_ == b_, f"{cfg!r}: op {a_[:2]} returned something else on the caller's stream\nops = {ops!r}"
+
+
+# ---- named chains: the batched Pauli sum and the reduced density matrix --------------------------------------------------------------
+
+def test_the_model_restates_the_librarys_limits(qc):
+    assert (rm.BATCH_WIDTH, rm.RDM_MAX) == (qc.pauli_batch_width(), qc.rdm_max_qubits())
+
+
+def shared_mask_seed(n, k, shape=None):
+    """a seed at which register_model.batch_terms(n, seed, k) draws k terms on ONE x_mask (of the given draw_masks shape)"""
+    for seed in range(1, 200):
+        xs = {x for _, x, _ in rm.batch_terms(n, seed, k)}
+        if len(xs) == 1 and (shape is None or rm.mask_shape(min(xs)) == shape):
+            return seed
+    raise AssertionError("no such seed below 200")
+
+
+def passes_of(qc, n, seed, k):
+    return qc.pauli_batch_plan([x for _, x, _ in rm.batch_terms(n, seed, k)])[1]
+
+
+def test_chain_compact_result_density_matrix_and_batch_keep_the_compact_form(qc, ob, tmp_path):
+    with Chain(qc, ob, 11, 5, 0, tmp_path) as c:
+        k0 = compact_chains(qc, c.reg)
+        c.do("reset"); c.do("qcomp", 21, 2)
+        assert compact_chains(qc, c.reg) == k0 + 1
+        m0 = compact_measures(qc, c.reg)
+        c.do("rdm", 2, 3)                                                 # expanded into the register's stale buffer ...
+        assert c.reg.rdm_stats() == (3, 1)
+        seed = shared_mask_seed(c.n, 40)
+        got = c.do("expect_batch", seed, 40)
+        assert got[3] == (3, 2), "more terms on one x_mask than a read serves: two reads, of the expanded compact result"
+        c.do("marginal", 1, 3)                                            # inside the M register: borrows marg_buf after both did
+        assert c.reg.marginal_stats() == (3, 1)
+        c.do("rdm", 12, 4)                                                # the range above a unit's summed bits
+        assert c.reg.rdm_stats() == (3, 1)
+        got = c.do("expect_batch", 29, 6)
+        assert got[3] == (3, passes_of(qc, c.n, 29, 6))
+        assert compact_measures(qc, c.reg) == m0
+        c.do("measure", 0.61)                                             # ... and the compact form is still what is scanned
+        assert compact_measures(qc, c.reg) == m0 + 1
+        c.do("rdm", 9, 4)                                                 # the pending basis state
+        assert c.reg.rdm_stats() == (2, 0)
+        c.state()
+
+
+def test_chain_pending_basis_state_answers_density_matrix_and_batch_on_the_host(qc, ob, tmp_path):
+    with Chain(qc, ob, 9, 5, 0, tmp_path) as c:
+        for start in ("reset", "measure"):
+            if start == "reset":
+                c.do("reset")
+            else:
+                c.do("fill", 5)
+                assert popcount(c.do("measure", 0.61)) >= 3, "the chain wants a basis state with several bits set"
+            for first, num in [(0, 0), (0, 4), (3, 3), (7, 4), (10, 4), (13, 1)]:
+                rho = c.do("rdm", first, num)
+                assert c.reg.rdm_stats() == (2, 0), "a basis state's density matrix is answered on the host"
+                assert np.count_nonzero(rho) == 1 and rho.sum() == 1.0
+            for seed, k in [(shared_mask_seed(c.n, 40), 40), (17, 6), (3, 1)]:
+                got = c.do("expect_batch", seed, k)
+                assert got[3] == (2, 0) and set(np.abs(got[1]).tolist()) <= {0.0, 1.0}
+            c.do("marginal", 3, 6)
+            assert c.reg.marginal_stats() == (2, 0), "neither call wrote the basis state: it is still pending"
+            c.do("sample", 4, 3)
+            c.do("h", 12)
+            c.do("rdm", 10, 4)
+            assert c.reg.rdm_stats() == (0, 1)
+            c.state()
+
+
+def test_chain_mode_1_queue_is_run_by_density_matrix_and_by_batch(qc, ob, tmp_path):
+    with Chain(qc, ob, 9, 5, 1, tmp_path) as c:
+        c.do("fill", 7)
+        c.do("flush")
+        s0 = c.reg.fusion_stats()
+        c.do("h", 3); c.do("cphase", 4, 9, 0.3); c.do("h", 13)
+        assert c.reg.fusion_stats() == s0, "mode 1 queues the gates"
+        c.do("rdm", 2, 3)                                                 # an observer: the queue runs first
+        s1 = c.reg.fusion_stats()
+        assert s1 != s0 and c.reg.rdm_stats() == (0, 1)
+        c.do("h", 6); c.do("cphase", 6, 2, 0.8)
+        assert c.reg.fusion_stats() == s1
+        got = c.do("expect_batch", 11, 6)
+        s2 = c.reg.fusion_stats()
+        assert s2 != s1 and got[3] == (0, passes_of(qc, c.n, 11, 6))
+        c.do("h", 0); c.do("camodc", 21, 4, 9)
+        c.do("rdm", 11, 3)                                                # the range at and above bit 12 - num
+        assert c.reg.fusion_stats() != s2
+        got = c.do("expect_batch", 5, 0)                                  # no terms: nothing runs, nothing is flushed
+        assert bits([got[0]])[0] == 0 and len(got[1]) == 0
+        c.state()
+
+
+def test_chain_owed_negative_zeros_are_still_owed_after_density_matrix_and_batch(qc, ob, tmp_path):
+    with Chain(qc, ob, 7, 4, 0, tmp_path) as c:
+        c.do("write", 0, c.dim, 31, "negzero")
+        c.do("rdm", 4, 4)
+        c.do("expect_batch", shared_mask_seed(c.n, 40), 40)
+        c.do("rdm", 0, 2)
+        got = c.do("read", 0, c.dim)                                      # the -0 are still there
+        assert np.count_nonzero((got == 0) & np.signbit(got)) > 100
+        c.do("cphase", 10, 0, 0.4)                                        # canonicalises every amplitude, touched or not
+        assert not np.any((c.m.a == 0) & np.signbit(c.m.a))
+        c.state()
+        c.do("write", 0, c.dim, 32, "negzero")
+        c.do("expect_batch", 8, 3)
+        c.do("rdm", 7, 4)
+        c.do("cu1", 3, 8, 2)
+        c.state()
+
+
+def test_chain_non_finite_register_stays_strict_through_density_matrix_and_batch(qc, ob, tmp_path):
+    with Chain(qc, ob, 8, 4, 0, tmp_path) as c:
+        c.do("fill", 3)
+        c.do("write", 700, 64, 21, "inf")
+        rho = c.do("rdm", 8, 4)                                           # whatever the definition gives
+        assert not np.all(np.isfinite(rho))
+        got = c.do("expect_batch", shared_mask_seed(c.n, 40), 40)
+        assert not np.isfinite(got[0])
+        c.do("rdm", 2, 2)
+        c.do("h", 7)                                                      # still the strict gate: the oracle's products, NaN / Inf included
+        c.do("read", 600, 300)
+        got = c.do("postselect", 0, 0, 0)                                 # the total is not finite: refused, state kept
+        assert got[1] == rm.BAD_ARGUMENTS
+        c.do("cphase", 2, 11, 0.9)
+        c.do("fill", 9)
+        assert np.all(np.isfinite(c.do("rdm", 8, 4)))
+        c.state()
+
+
+def test_chain_density_matrix_and_batch_behind_the_handed_out_pointer_on_a_callers_stream(qc, ob, tmp_path):
+    with Chain(qc, ob, 9, 5, 0, tmp_path) as c:
+        c.do("stream", 1)
+        c.do("fill", 3)
+        c.do("devptr", 0, 64)                                             # in place from here on
+        c.do("h", 13)
+        c.do("rdm", 10, 4)
+        c.do("write", 1000, 300, 6, "negzero")
+        got = c.do("expect_batch", shared_mask_seed(c.n, 40, 2), 40)      # pairs of tiles
+        assert got[3] == (0, 2)
+        c.do("prot", 0x2011, 0x0013, 0.8)
+        c.do("rdm", 0, 4)
+        c.do("devptr", 900, 500)
+        c.do("fusion", 1)
+        c.do("h", 4); c.do("cphase", 4, 11, 0.3)
+        c.do("expect_batch", 21, 6)
+        c.do("stream", 0)
+        c.do("h", 2)
+        c.do("rdm", 8, 4)
+        c.do("reset")
+        c.do("rdm", 0, 1)
+        assert c.reg.rdm_stats() == (2, 0)
+        c.do("devptr", 0, c.dim)
+
+
+# marginal, density matrix and batch all borrow one scratch area of the register (marg_buf, grown by marg_reserve): sizes that
+# grow and shrink; (first, num) of a marginal go up to its 2^12 outcomes, far more than the few rows of a density matrix
+INTERLEAVED = [("marginal", 0, 1), ("rdm", 0, 4), ("marginal", 0, 12), ("rdm", 5, 1), ("marginal", 3, 2), ("rdm", 9, 4),
+               ("expect_batch", 7, 40), ("marginal", 2, 9), ("rdm", 0, 0), ("marginal", 0, 0), ("rdm", 10, 4), ("marginal", 1, 12),
+               ("expect_batch", 9, 6), ("rdm", 3, 3), ("marginal", 8, 5), ("rdm", 8, 4)]
+
+
+def test_chain_marginal_density_matrix_marginal_growing_and_shrinking_on_one_register(qc, ob, tmp_path):
+    with Chain(qc, ob, 9, 5, 0, tmp_path) as c:
+        c.do("fill", 12)
+        for op in INTERLEAVED:
+            c.do(*op)
+            if op[0] == "rdm":
+                assert c.reg.rdm_stats() == (0, 1)
+        c.do("h", 5)
+        for op in INTERLEAVED[::-1]:
+            c.do(*op)
+        c.state()
+
+
+def test_chain_marginal_density_matrix_marginal_alternating_between_two_registers(qc, ob, tmp_path):
+    small = [(k, min(f, 4), min(v, 4)) if k != "expect_batch" else (k, f, v) for k, f, v in INTERLEAVED]      # ranges that fit n = 9
+    with Chain(qc, ob, 9, 5, 0, tmp_path, "a") as a, Chain(qc, ob, 9, 0, 1, tmp_path, "b") as b:
+        a.do("fill", 12); b.do("fill", 13)
+        b.do("h", 3); b.do("cphase", 2, 7, 0.4)                           # queued in mode 1
+        for k, op in enumerate(INTERLEAVED):
+            a.do(*op)
+            b.do(*small[(k + 5) % len(small)])
+            if k == 7:
+                a.do("postselect", 2, 3, int(np.argmax(a.m.marginal(2, 3))))
+                b.do("h", 8)
+        a.state(); b.state()
+
+
+def test_chain_forty_terms_on_one_x_mask_take_two_reads(qc, ob, tmp_path):
+    for L, M, shape in ((6, 0, 1), (9, 5, 0), (9, 5, 1), (9, 5, 2)):       # a partial unit; a diagonal string, one tile, pairs of tiles
+        with Chain(qc, ob, L, M, 0, tmp_path) as c:
+            c.do("fill", 21 + shape)
+            seed = shared_mask_seed(c.n, 40, shape)
+            assert passes_of(qc, c.n, seed, 40) == 2
+            got = c.do("expect_batch", seed, 40)
+            assert got[3] == (0, 2), f"expectation_stats() {got[3]}"
+            got = c.do("expect_batch", shared_mask_seed(c.n, 6, shape), 6)
+            assert got[3] == (0, 1)
+            c.state()

@@ -168,6 +168,32 @@ def test_small_registers_single_wave(qc, ob, n):
     check_sample(qc, ob, n, a, thresholds(a, rs, 4))
 
 
+def test_more_shots_than_one_batch(qc):
+    """2^20 + 3 shots: the draws go to the device a batch of 2^20 at a time, so the last three are a second batch.  On the
+    uniform superposition of n = 12 every partial sum is exact (k / 4096), so the reference needs no scan: the first index whose
+    partial sum is >= r among all but the last, else the last index (numpy's searchsorted)"""
+    n, shots = 12, (1 << 20) + 3
+    dim = 1 << n
+    a = np.zeros(2 * dim); a[0::2] = 2.0 ** (-n / 2)
+    cum = np.arange(1, dim, dtype=np.float64) / dim                 # the partial sums behind the indices 0 .. dim - 2
+    assert np.array_equal(cum, np.cumsum(np.full(dim, a[0] * a[0]))[:-1]), "exact partial sums"
+    rs = np.random.RandomState(5)
+    r = rs.uniform(0.0, 1.0, shots)
+    edges = np.array([0.0, 1.0, 1.5, 1e-300, -0.25, 0.5, np.nextafter(0.5, 0.0), np.nextafter(0.5, 1.0), cum[0], cum[-1],
+                      np.nextafter(cum[-1], 1.0), np.nextafter(cum[-1], 0.0), 1777.0 / dim])
+    r[rs.choice(1 << 20, edges.size, replace=False)] = edges        # in the first batch ...
+    r[-3:] = [np.nextafter(0.5, 1.0), 1777.0 / dim, 1.0]            # ... and as the whole of the second
+    want = np.minimum(np.searchsorted(cum, r, side="left"), dim - 1).astype(np.uint64)
+    with qc.Register(n, 0) as reg:
+        reg.write(a)
+        got = qc.sample_states(reg, r)
+        assert reg.sample_stats() == (1, 0), reg.sample_stats()
+        assert np.array_equal(bits(reg.read()), bits(a)), "the state changed"
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, f"{bad.size} shots differ, first (shot, r, got, want): {[(int(i), r[i], int(got[i]), int(want[i])) for i in bad[:6]]}"
+    assert got[-3:].tolist() == [dim // 2, 1776, dim - 1] and len(set(got.tolist())) == dim, "every index is hit, the second batch included"
+
+
 def test_state_untouched_and_measure_afterwards(qc, ob):
     n = 20
     rs = np.random.RandomState(1)

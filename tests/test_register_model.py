@@ -8,7 +8,9 @@
     three times over that vocabulary's seeds with nothing but quiet calls in between, judged on the op lists alone; the op lists
     of vocabulary 1 are the committed ones (tests/golden/sequence_digests.json); the Pauli calls of vocabulary 2 are not vacuous
     (masks of all three unit shapes, Y letters, values other than 0, non-finite states, rotations that change the state); the op
-    lists of vocabulary 2 are pinned as well.
+    lists of vocabulary 2 are pinned as well.  The same for vocabulary 3: its pairs, its op lists, batches whose terms share an
+    x_mask and take a second read, density matrices of every width in all three kernel forms, and fused-engine knobs on
+    registers large enough for them.
 (c) the sharded family (register_model.generate_sharded): every legal pair of its own setting and following kinds at least three
     times, every refused entry point, every shard count and shape list; its op lists are the committed ones."""
 import hashlib
@@ -106,6 +108,14 @@ class Replay:
             P = np.kron(Y if xb and zb else X if xb else Z if zb else I, P)
         return P
 
+    def rdm(self, first, num):
+        """rho[v, w] = sum over the other bits of amp[.., v, ..] conj(amp[.., w, ..]): interleaved (re, im) like rdm_ref"""
+        x = self.v.reshape(1 << (self.n - first - num), 1 << num, 1 << first)
+        rho = np.einsum("hvl,hwl->vw", x, np.conj(x))
+        out = np.empty(rho.shape + (2,), dtype=LD)
+        out[..., 0], out[..., 1] = rho.real, rho.imag
+        return out
+
     def expect(self, x_mask, z_mask):
         return (np.conj(self.v) @ (self.pauli(x_mask, z_mask) @ self.v)).real
 
@@ -136,9 +146,9 @@ def replay_seed(ob, seed, bound):
     m, x = rm.RegisterModel(ob, L, M), Replay(L, M)
     worst = 0.0
 
-    def near(got, want, what):
+    def near(got, want, what, scale=1.0):
         nonlocal worst
-        d = float(np.max(np.abs(np.asarray(got, dtype=LD) - np.asarray(want, dtype=LD)))) if np.size(got) else 0.0
+        d = float(np.max(np.abs(np.asarray(got, dtype=LD) - np.asarray(want, dtype=LD)))) / scale if np.size(got) else 0.0
         worst = max(worst, d)
         assert d <= bound, f"{cfg} op {i} {op!r}: {what} off by {d:.3e}\nops = {[o for _, o in ops[:i + 1]]!r}"
 
@@ -168,11 +178,16 @@ def replay_seed(ob, seed, bound):
         elif k == "cu2": x.gate(rm.matrix_data(4, op[4]), [op[2], op[3]], control=op[1])
         elif k == "prot": x.prot(op[1], op[2], op[3])
         elif k == "expect": near(got, x.expect(op[1], op[2]), "expectation")
-        elif k == "expect_sum":
-            terms = rm.sum_terms(m.n, op[1], op[2])
+        elif k == "rdm":
+            near(got[0], x.rdm(op[1], op[2]), "reduced density matrix")
+            near(got[1], x.marginal(op[1], op[2]), "marginal")
+        elif k in ("expect_sum", "expect_batch"):
+            terms = (rm.sum_terms if k == "expect_sum" else rm.batch_terms)(m.n, op[1], op[2])
             values = [x.expect(xm, zm) for _, xm, zm in terms]
             near(got[1], values, "the values of the terms")
-            near(got[0], sum((LD(c) * v for (c, _, _), v in zip(terms, values)), LD(0)), "the terms' sum")
+            # (the error of a sum grows at most linearly with its terms: the bound is that of the six terms an expect_sum op has at
+            #  most, times k / 6 for the longer batches)
+            near(got[0], sum((LD(c) * v for (c, _, _), v in zip(terms, values)), LD(0)), "the terms' sum", max(1.0, len(terms) / 6.0))
         elif k in ("read", "devptr"): near(got, x.interleaved()[2 * op[1]:2 * (op[1] + op[2])], "window")
         elif k == "marginal": near(got, x.marginal(op[1], op[2]), "marginal")
         elif k in ("total", "norm2"): near(got, x.probs().sum(), k)
@@ -218,6 +233,13 @@ SMALL_SEEDS_V2 = range(rm.SMALL_V1, 2 * rm.SMALL_V1)
 MEASURED_V2, BOUND_V2 = 9.688e-16, 16 * 9.688e-16
 
 
+# SMALL_SEEDS_V3, the small sequences of vocabulary 3, are held to vocabulary 2's bound: an entry of a density matrix is a sum of
+# up to 64 products of two amplitudes, as a Pauli value is, and the sum of a batch of k terms is held to k / 6 times the bound of
+# a sum of six (replay_seed)
+SMALL_SEEDS_V3 = range(2 * rm.SMALL_V1, 3 * rm.SMALL_V1)
+BOUND_V3 = BOUND_V2
+
+
 def test_model_against_long_double_linear_algebra(ob):
     assert all(rm.Config(seed, small=True).vocab == 1 for seed in SMALL_SEEDS)
     worst = max(replay_seed(ob, seed, BOUND) for seed in SMALL_SEEDS)
@@ -234,9 +256,19 @@ def test_model_of_vocabulary_2_against_long_double_linear_algebra(ob):
     assert worst <= BOUND_V2
 
 
+def test_model_of_vocabulary_3_against_long_double_linear_algebra(ob):
+    assert all(rm.Config(seed, small=True).vocab == 3 for seed in SMALL_SEEDS_V3)
+    kinds = {op[0] for seed in SMALL_SEEDS_V3 for _, op in rm.generate(ob, seed, small=True, length=30)[1]}
+    assert {"expect_batch", "rdm", "expect", "expect_sum", "prot", "devptr", "stream"} <= kinds
+    worst = max(replay_seed(ob, seed, BOUND_V3) for seed in SMALL_SEEDS_V3)
+    print(f"largest deviation of the model from the long-double replay, vocabulary 3: {worst:.3e} (bound {BOUND_V3:.3e})")
+    assert worst <= BOUND_V3
+
+
 def test_replay_notices_a_wrongly_composed_model(ob):
     """the replay is not vacuous: a model with the two-qubit gate's qubits swapped, or a postselect that does not scale, fails it;
-    so do, on the sequences of vocabulary 2, an expectation with x_mask and z_mask swapped and a rotation by -theta"""
+    so do, on the sequences of vocabulary 2, an expectation with x_mask and z_mask swapped and a rotation by -theta, and on
+    those of vocabulary 3 a density matrix that is transposed and a batch that answers its terms in reverse order"""
     class Swapped(rm.RegisterModel):
         def two_qubit_gate(self, q0, q1, U): super().two_qubit_gate(q1, q0, U)
 
@@ -253,7 +285,15 @@ def test_replay_notices_a_wrongly_composed_model(ob):
     class Backwards(rm.RegisterModel):
         def pauli_rotation(self, x_mask, z_mask, theta): super().pauli_rotation(x_mask, z_mask, -theta)
 
-    for broken, seeds, bound in ((Swapped, SMALL_SEEDS, BOUND), (Unscaled, SMALL_SEEDS, BOUND),
+    class Transposed(rm.RegisterModel):
+        def reduced_density_matrix(self, first, num): return np.swapaxes(super().reduced_density_matrix(first, num), 0, 1)
+
+    class Reversed(rm.RegisterModel):
+        def expectation_batch(self, terms):
+            total, values = super().expectation_batch(terms)
+            return total, values[::-1]
+
+    for broken, seeds, bound in ((Transposed, SMALL_SEEDS_V3, BOUND_V3), (Reversed, SMALL_SEEDS_V3, BOUND_V3), (Swapped, SMALL_SEEDS, BOUND), (Unscaled, SMALL_SEEDS, BOUND),
                                  (MasksSwapped, SMALL_SEEDS_V2, BOUND_V2), (Backwards, SMALL_SEEDS_V2, BOUND_V2)):
         real, rm.RegisterModel = rm.RegisterModel, broken
         try:
@@ -277,7 +317,7 @@ def generated(ob, seed):
 
 
 def test_generator_reaches_every_pair(ob):
-    for vocab in (1, 2):
+    for vocab in (1, 2, 3):
         pairs_of_vocabulary(ob, vocab)
 
 
@@ -307,10 +347,10 @@ def pairs_of_vocabulary(ob, vocab):
     print("calls: " + ", ".join(f"{k} {calls.get(k, 0)}" for k in following))
     short = [(p, total.get(p, 0)) for p in legal if total.get(p, 0) < 3]
     assert not short, f"pairs reached fewer than 3 times: {short}"
-    # all but (write of an Inf/NaN, norm2) and, in vocabulary 2, (compact, devptr)
-    assert len(legal) == len(rm.SETTING) * len(following) - vocab
-    assert (len(rm.SETTING), len(following)) == ((11, 25) if vocab == 1 else (11, 30))
-    assert 40 <= min(lengths) and max(lengths) <= (90 if vocab == 1 else 140), lengths      # (a circuit front alone is L + a few calls)
+    # all but (write of an Inf/NaN, norm2) and, from vocabulary 2 on, (compact, devptr)
+    assert len(legal) == len(rm.SETTING) * len(following) - min(vocab, 2)
+    assert (len(rm.SETTING), len(following)) == (11, {1: 25, 2: 30, 3: 32}[vocab])
+    assert 40 <= min(lengths) and max(lengths) <= {1: 90, 2: 140, 3: 150}[vocab], lengths   # (a circuit front alone is L + a few calls)
 
 
 def test_vocabulary_1_generates_the_committed_op_lists(ob):
@@ -356,6 +396,79 @@ def test_pauli_calls_of_vocabulary_2_are_not_vacuous(ob):
     assert 10 * ex["nonfinite"] >= ex["n"], "at least a tenth fall on a non-finite state"
     assert 10 * pr["changed"] >= 9 * pr["n"], "at least 90 % of the prot ops change the bits of the state"
     assert min(ex["shape"]) >= 20 and min(pr["shape"]) >= 20, "each of the three unit shapes in >= 20 expect and >= 20 prot ops"
+
+
+def test_new_calls_of_vocabulary_3_are_not_vacuous(ob):
+    """on the model alone, over the seeds of vocabulary 3: what the expect_batch and rdm ops meet, which refused forms occur and
+    which knobs the seeds run under"""
+    eb = dict(n=0, shared=0, two_reads=0, nonzero=0, nonfinite=0, shape=[0, 0, 0], k={})
+    rd = dict(n=0, offdiag=0, nonfinite=0, shape=[0, 0, 0], num=[0] * (rm.RDM_MAX + 1))
+    refused, drawn, plain = {}, set(), []
+    for seed in rm.seeds_of(3):
+        cfg, ops = generated(ob, seed)
+        assert cfg.vocab == 3
+        fused = {k: v for k, v in cfg.knobs.items() if k.startswith(("fuse_", "meas_"))}
+        if fused:
+            assert seed % 3 and all(L + M >= max(M + 6, 10) for L, M, _, _ in cfg.shapes), cfg
+            assert not (cfg.compact and set(fused) & set(rm.ENDS_COMPACT_CHAINS)), cfg
+            drawn |= {i for i, d in enumerate(rm.KNOBS_FUSED) if all(fused.get(k) == v for k, v in d.items())}
+        if not cfg.knobs:
+            plain.append(seed)
+        models = [rm.RegisterModel(ob, L, M) for L, M, _, _ in cfg.shapes]
+        for which, op in ops:
+            m = models[which]
+            bad = m.holds_nonfinite()
+            got = rm.apply_to_model(m, op)
+            if op[0] == "expect_batch":
+                terms = rm.batch_terms(m.n, op[1], op[2])
+                xs = [x for _, x, _ in terms]
+                eb["n"] += 1
+                eb["k"][op[2]] = eb["k"].get(op[2], 0) + 1
+                eb["shared"] += len(terms) >= 2 and len(set(xs)) == 1
+                eb["two_reads"] += any(xs.count(x) > rm.BATCH_WIDTH for x in set(xs))
+                eb["nonzero"] += got[0] != 0
+                eb["nonfinite"] += bad
+                for x in set(xs):
+                    eb["shape"][rm.mask_shape(x)] += 1
+                assert np.array_equal(got[1].view(np.uint64), m.expectation_sum(terms)[1].view(np.uint64))
+            elif op[0] == "rdm":
+                rho, P = got
+                rd["n"] += 1
+                rd["num"][op[2]] += 1
+                rd["shape"][rm.rdm_shape(m.n, op[1], op[2])] += 1
+                rd["offdiag"] += bool(np.any(rho[~np.eye(1 << op[2], dtype=bool)] != 0))
+                rd["nonfinite"] += bad
+                assert rho.shape == (1 << op[2], 1 << op[2], 2) and P.shape == (1 << op[2],)
+            elif op[0] == "refused" and op[1][0] in ("rdm", "expect_batch"):
+                refused[(op[1][0], op[2])] = refused.get((op[1][0], op[2]), 0) + 1
+                if op[1][0] == "rdm":
+                    past = op[1][1] + op[1][2] > m.n
+                    assert op[2] == (rm.BAD_QUBIT if past else rm.UNSUPPORTED) and (past or op[1][2] > rm.RDM_MAX), op
+    print(f"expect_batch: {eb}\nrdm: {rd}\nrefused: {refused}\nfused-engine knob dicts drawn: {sorted(drawn)}; seeds without knobs: {plain}")
+    assert 3 * eb["shared"] >= eb["n"], "at least a third of the batches have two or more terms that all share one x_mask"
+    assert eb["two_reads"] >= 10, "batches with more than BATCH_WIDTH terms on one x_mask: a second read of the state"
+    assert set(eb["k"]) == {0, 1, 3, 6, 40} and eb["k"][0] >= 3 and min(v for k, v in eb["k"].items() if k) >= 10
+    assert 2 * eb["nonzero"] >= eb["n"] and 20 * eb["nonfinite"] >= eb["n"]
+    assert min(eb["shape"]) >= 20 and min(rd["shape"]) >= 20, "every mask shape and every form of the density-matrix kernel >= 20 times"
+    assert min(rd["num"]) >= 20, "every width 0 .. RDM_MAX at least 20 times"
+    assert 2 * rd["offdiag"] >= rd["n"] - rd["num"][0] and 20 * rd["nonfinite"] >= rd["n"]
+    assert all(refused.get(key, 0) >= 3 for key in (("rdm", rm.BAD_QUBIT), ("rdm", rm.UNSUPPORTED), ("expect_batch", rm.BAD_QUBIT))), refused
+    assert drawn == set(range(len(rm.KNOBS_FUSED))), "every dict of KNOBS_FUSED is drawn by some seed"
+    # what tests/test_gpu_concurrent_callers.py picks from: seeds that run under the default knobs
+    assert any(len(rm.Config(s).shapes) == 1 and not rm.Config(s).compact for s in plain) and len(plain) >= 16
+
+
+def test_vocabulary_3_generates_the_committed_op_lists(ob):
+    """the seeds NSEEDS .. NSEEDS_V3 - 1 and the small seeds 2 SMALL_V1 .. 3 SMALL_V1 - 1 are frozen like the others"""
+    golden = golden_digests()
+    assert sorted(golden["big_v3"], key=int) == [str(s) for s in rm.seeds_of(3)]
+    assert sorted(golden["small_v3"], key=int) == [str(s) for s in SMALL_SEEDS_V3]
+    drifted = [s for s in rm.seeds_of(3) if digest(generated(ob, s)[1]) != golden["big_v3"][str(s)]]
+    drifted += [("small", s) for s in SMALL_SEEDS_V3 if digest(rm.generate(ob, s, small=True, length=30)[1]) != golden["small_v3"][str(s)]]
+    assert not drifted, f"the op lists of these vocabulary-3 seeds changed: {drifted}"
+    # the digest covers the op lists; the knobs a seed runs under are part of what the GPU asserts, so they are pinned too
+    knobs = hashlib.sha256(repr([sorted(rm.Config(s).knobs.items()) for s in rm.seeds_of(3)]).encode()).hexdigest()
+    assert knobs == golden["knobs_v3"], "the knobs of the vocabulary-3 seeds changed"
 
 
 def test_generator_is_deterministic(ob):
