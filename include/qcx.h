@@ -84,7 +84,7 @@ int  qcx_M_size(const qcx_register *reg);
  * M_size > 12 works like on one GPU (the modular multiply then runs in place through a per-device staging buffer instead of
  * LDS tiles; M_size <= 26).  Not available on a sharded register: qcx_register_set_stream, qcx_device_pointer (NULL),
  * the event pool, qcx_one_qubit_gate / qcx_c_one_qubit_gate, qcx_two_qubit_gate / qcx_c_two_qubit_gate,
- * qcx_pauli_rotation (QCX_UNSUPPORTED). */
+ * qcx_pauli_rotation, qcx_pauli_rotation_batch (QCX_UNSUPPORTED). */
 int  qcx_register_create_sharded(int L_size, int M_size, unsigned nshards, const int *devices, qcx_register **out);
 int  qcx_spread_devices(unsigned nshards, int visible_devices /* <= 0: ask HIP */, int *devices_out /* [nshards] */);
 int  qcx_sharded_selfcheck(qcx_register *reg);             /* the pre-flight exchange check on demand */
@@ -184,6 +184,28 @@ int  qcx_c_two_qubit_gate(unsigned c_qubit_num, unsigned qubit0, unsigned qubit1
  * NULL reg or a theta that is not finite: QCX_BAD_ARGUMENTS; a mask bit at or above n: QCX_BAD_QUBIT; a sharded register:
  * QCX_UNSUPPORTED, nothing touched. */
 int  qcx_pauli_rotation(uint64_t x_mask, uint64_t z_mask, double theta, qcx_register *reg);
+/* A list of rotations -- a Trotter step -- in as few passes over the state as locality allows (K15b, DESIGN s4.5k).  The state
+ * afterwards is, bit for bit, what the loop  for k: qcx_pauli_rotation(x_masks[k], z_masks[k], thetas[k], reg)  leaves, for any
+ * list in any order, on finite and non-finite registers: each term has its own (c, s) = qcx_polar(fl(theta / 2)) and
+ * qcx_pauli_rotation's arithmetic; theta = 0 still runs; no term is merged, reordered or skipped.  The terms need not commute.
+ * The passes: a run of consecutive terms whose partners i ^ x_mask all stay inside one tile of 2^12 amplitudes -- index bits
+ * 0-7 plus four more bits chosen from the strings themselves -- is applied in order while the tile sits in registers, one read
+ * and one write of the state for up to W = qcx_pauli_rotation_batch_width() terms; Z letters never constrain a pass.  A term
+ * with more than four X or Y letters on qubits 8 and up is a pass of its own, qcx_pauli_rotation's.
+ * qcx_pauli_rotation_batch_plan in qcx_plan.h is the rule on its own; qcx_rotation_batch_last_stats reports the last call's
+ * passes and how many of them were such single wide terms.
+ * Everything else is qcx_pauli_rotation's contract: asynchronous, never queued, flushes what is pending in every fusion mode,
+ * not counted by qcx_fusion_stats, exact in mode 2; a register flagged non-finite keeps its flag and runs the same kernels.
+ * Checked in this order, before anything runs: NULL reg, or a NULL array with nterms > 0: QCX_BAD_ARGUMENTS; a theta that is not
+ * finite: QCX_BAD_ARGUMENTS, qcx_last_error() names the term; a mask bit at or above n: QCX_BAD_QUBIT; a sharded register:
+ * QCX_UNSUPPORTED -- nothing touched in any of these cases.  nterms = 0: QCX_NO_ERROR, nothing is launched and queued gates stay
+ * queued. */
+int  qcx_pauli_rotation_batch(qcx_register *reg, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks,
+                              const double *thetas);
+unsigned qcx_pauli_rotation_batch_width(void);   /* W: the most terms one pass applies; a build constant, 8 <= W <= 64 */
+/* the last qcx_pauli_rotation_batch call on this register that passed its checks: passes = the plan's npasses (kernel launches:
+ * reads and writes of the state), wide_terms = those of them that are one wide term */
+int  qcx_rotation_batch_last_stats(qcx_register *reg, unsigned long *passes, unsigned long *wide_terms);
 int  qcx_swap_states(qcx_register *reg);                                           /* Q:242-249: no-op */
 /* host-side gate schedules */
 int  qcx_inverse_QFT(qcx_register *reg);                                           /* Q:678-690 */

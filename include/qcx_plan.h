@@ -123,6 +123,22 @@ int  qcx_marginal_plan_compact(unsigned n, unsigned M, unsigned first, unsigned 
 int  qcx_pauli_batch_plan(unsigned long nterms, const uint64_t *x_masks, unsigned width,
                           unsigned long *pass_of_term /* [nterms] */, unsigned long *npasses);
 
+/* The passes of qcx_pauli_rotation_batch (include/qcx.h; K15b, DESIGN s4.5k) over n qubits, on the host.  For term k let hx_k be
+ * the bits of x_masks[k] at positions >= 8; the term is WIDE when popcount(hx_k) > 4.  Walk the terms in order; at most one pass
+ * is open, with a hot set H and a term count:
+ *   a wide term closes the open pass and is a pass of its own (kind 1: the qcx_pauli_rotation launch, hot mask 0);
+ *   any other term joins the open pass if count < width and popcount(H | hx_k) <= 4, otherwise the open pass closes and the term
+ *   opens a new one with H = hx_k (kind 0);
+ *   on closing, H is padded with the lowest qubits of [8, n) not yet in it, up to min(4, max(n, 8) - 8) bits.
+ * A kind-0 pass's tile is qubits 0-7 plus H: the whole register for n <= 12 (no term is wide, only `width` splits passes), and
+ * for n >= 13 one tile per value of the other n - 12 bits.  pass_of_term[k] is term k's pass (non-decreasing), *npasses their
+ * number, pass_kind[p] and pass_hot[p] pass p's kind and hot mask (all three arrays hold nterms entries).  The library calls it
+ * with width = qcx_pauli_rotation_batch_width().  width = 0, n = 0 or n > 40, a NULL npasses, or a NULL array with nterms > 0:
+ * QCX_BAD_ARGUMENTS; an x_mask bit at or above n: QCX_BAD_QUBIT. */
+int  qcx_pauli_rotation_batch_plan(unsigned n, unsigned long nterms, const uint64_t *x_masks, unsigned width,
+                                   unsigned long *pass_of_term /* [nterms] */, unsigned long *npasses,
+                                   unsigned *pass_kind /* [nterms] */, uint64_t *pass_hot /* [nterms] */);
+
 /* The stage plan of qcx_reduced_density_matrix (include/qcx.h; K16, DESIGN s4.5j), on the host.  The 4^num computed components
  * (row v * 2^num + w, v <= w: Re rho[v][w]; row w * 2^num + v, v < w: Im rho[v][w]) are each the marginal's pairwise tree over
  * the bits outside [first, first + num).  Stage 0 reads the state once and sums, for every row, the sum_bits lowest summed

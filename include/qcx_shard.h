@@ -35,6 +35,13 @@ int  qcx_shard_two_qubit(void *amp, unsigned n_local, unsigned q0, unsigned q1, 
 /* exp(-i theta/2 P) of the Pauli string (x_mask, z_mask) over the local bits (qcx.h: qcx_pauli_rotation), the launch alone:
  * c and s are cos and sin of theta / 2 (qcx_polar).  Not used by the sharded hosts. */
 int  qcx_shard_pauli_rotation(void *amp, unsigned n_local, uint64_t x_mask, uint64_t z_mask, double c, double s, void *stream);
+/* ONE pass of qcx_pauli_rotation_batch (qcx.h), the launch alone: the nterms rotations (x_masks[k], z_masks[k]) with cs[k], ss[k] =
+ * cos and sin of theta_k / 2, in order, over the tiles of local bits 0-7 and hot_mask.  1 <= nterms <=
+ * qcx_pauli_rotation_batch_width(); hot_mask is what qcx_pauli_rotation_batch_plan gives a pass: min(4, max(n_local, 8) - 8) bits of
+ * [8, n_local) that cover every term's x bits at and above 8, else QCX_BAD_ARGUMENTS.  The arrays are read before the call
+ * returns.  Not used by the sharded hosts. */
+int  qcx_shard_pauli_rotation_run(void *amp, unsigned n_local, uint64_t hot_mask, unsigned nterms, const uint64_t *x_masks,
+                                  const uint64_t *z_masks, const double *cs, const double *ss, void *stream);
 /* multiply by (cos_t + i sin_t) every amplitude whose local index has all bits of
  * `mask_local` set; mask_local has 0, 1 or 2 bits (global control bits that are 1
  * simply drop out of the mask; a global bit that is 0 means: do not call). */

@@ -55,6 +55,10 @@ SIGNATURES = {
     "qcx_two_qubit_gate": (_i, [_u, _u, _p, _p]),
     "qcx_c_two_qubit_gate": (_i, [_u, _u, _u, _p, _p]),
     "qcx_pauli_rotation": (_i, [_u64, _u64, _d, _p]),
+    "qcx_pauli_rotation_batch": (_i, [_p, _ul, _p, _p, _p]),
+    "qcx_pauli_rotation_batch_width": (_u, []),
+    "qcx_rotation_batch_last_stats": (_i, [_p, C.POINTER(_ul), C.POINTER(_ul)]),
+    "qcx_pauli_rotation_batch_plan": (_i, [_u, _ul, _p, _u, _p, C.POINTER(_ul), _p, _p]),
     "qcx_swap_states": (_i, [_p]),
     "qcx_inverse_QFT": (_i, [_p]),
     "qcx_quantum_computation": (_i, [_u, _u, _i, _p]),
@@ -108,6 +112,7 @@ SIGNATURES = {
     "qcx_shard_one_qubit": (_i, [_p, _u, _u, _i, _p, _p]),
     "qcx_shard_two_qubit": (_i, [_p, _u, _u, _u, _i, _p, _p]),
     "qcx_shard_pauli_rotation": (_i, [_p, _u, _u64, _u64, _d, _d, _p]),
+    "qcx_shard_pauli_rotation_run": (_i, [_p, _u, _u64, _u, _p, _p, _p, _p, _p]),
     "qcx_shard_phase": (_i, [_p, _u, _u64, _d, _d, _p]),
     "qcx_shard_camodc": (_i, [_p, _u, _u, _u, _u, _i, _p]),
     "qcx_shard_swap_bits": (_i, [_p, _p, _u, _u, C.POINTER(_u), C.POINTER(_u), _p]),
@@ -267,6 +272,27 @@ def pauli_batch_plan(x_masks, width=None):
     check(lib().qcx_pauli_batch_plan(xs.size, ptr(xs), pauli_batch_width() if width is None else int(width), ptr(out), C.byref(np_)),
           "qcx_pauli_batch_plan")
     return [int(v) for v in out], int(np_.value)
+
+
+def pauli_rotation_batch_width():
+    """W: the most terms one pass of pauli_rotation_batch applies (qcx_pauli_rotation_batch_width)"""
+    return int(lib().qcx_pauli_rotation_batch_width())
+
+
+def pauli_rotation_batch_plan(terms, n, width=None):
+    """The passes of pauli_rotation_batch over n qubits (host code, no GPU needed; include/qcx_plan.h:
+    qcx_pauli_rotation_batch_plan): (pass_of_term, passes) for terms = [(pauli, theta), ...] in order, passes = [(kind, hot_mask),
+    ...] -- kind 0: a run of terms over the tile of qubits 0-7 and hot_mask, kind 1: one wide term on its own; width=None: the
+    library's W."""
+    import numpy as np
+    n = int(n)
+    xs = np.array([pauli_masks(p, n)[0] for p, _ in terms], dtype=np.uint64)
+    pass_of, kind, hot = np.zeros(xs.size, dtype=np.uint64), np.zeros(xs.size, dtype=np.uint32), np.zeros(xs.size, dtype=np.uint64)
+    np_ = C.c_ulong(0)
+    ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if xs.size else (lambda a: None)
+    check(lib().qcx_pauli_rotation_batch_plan(n, xs.size, ptr(xs), pauli_rotation_batch_width() if width is None else int(width),
+                                              ptr(pass_of), C.byref(np_), ptr(kind), ptr(hot)), "qcx_pauli_rotation_batch_plan")
+    return [int(v) for v in pass_of], [(int(kind[p]), int(hot[p])) for p in range(np_.value)]
 
 
 def fusion_plan(n_local, M, descs, mode=1):

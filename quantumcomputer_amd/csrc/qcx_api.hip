@@ -749,6 +749,106 @@ extern "C" int qcx_shard_pauli_rotation(void *amp, unsigned n_local, uint64_t x_
     return launch_status("pauli rotation");
 }
 
+// ---- K15b: a run of rotations in one pass (qcx_pauli_rotation_batch) -----------------------------------------------------------
+extern "C" unsigned qcx_pauli_rotation_batch_width(void) { return QCX_PROT_RUN_W; }
+
+// a mask's bits at and above 8: what a term asks of a pass's hot set
+static inline uint64_t prot_hx(uint64_t x_mask) { return x_mask & ~(uint64_t)0xFF; }
+
+// The passes of qcx_pauli_rotation_batch (include/qcx_plan.h states the rule): at most one pass is open; a wide term (more than
+// four x bits at or above 8) closes it and is a pass of its own, any other joins it while it holds fewer than `width` terms and
+// the hot set stays within four bits; a closing pass pads its hot set with the lowest qubits of [8, n) not in it.
+extern "C" int qcx_pauli_rotation_batch_plan(unsigned n, unsigned long nterms, const uint64_t *x_masks, unsigned width,
+                                             unsigned long *pass_of_term, unsigned long *npasses, unsigned *pass_kind, uint64_t *pass_hot)
+{
+    if (!npasses || width == 0 || n == 0 || n > 40 || (nterms && (!x_masks || !pass_of_term || !pass_kind || !pass_hot))) return QCX_BAD_ARGUMENTS;
+    for (unsigned long k = 0; k < nterms; k++)
+        if (x_masks[k] >> n) return QCX_BAD_QUBIT;
+    const unsigned nhot = std::min(4u, std::max(n, 8u) - 8u);
+    unsigned long np = 0;
+    bool open = false;
+    uint64_t H = 0;
+    unsigned count = 0;
+    auto close = [&]() {
+        for (unsigned q = 8; q < n && (unsigned)__builtin_popcountll(H) < nhot; q++) H |= (uint64_t)1 << q;
+        pass_kind[np] = 0; pass_hot[np] = H;
+        np++; open = false;
+    };
+    for (unsigned long k = 0; k < nterms; k++) {
+        const uint64_t hx = prot_hx(x_masks[k]);
+        if (__builtin_popcountll(hx) > 4) {
+            if (open) close();
+            pass_kind[np] = 1; pass_hot[np] = 0;
+            pass_of_term[k] = np++;
+            continue;
+        }
+        if (open && !(count < width && __builtin_popcountll(H | hx) <= 4)) close();
+        if (!open) { open = true; H = 0; count = 0; }
+        H |= hx; count++;
+        pass_of_term[k] = np;
+    }
+    if (open) close();
+    *npasses = np;
+    return QCX_NO_ERROR;
+}
+
+// One pass, the launch alone: the nterms <= W rotations (x_masks, z_masks, cs, ss)[0 .. nterms) in order, over the tile of index
+// bits 0-7 and hot_mask.  hot_mask must be what the plan gives a pass: min(4, max(n, 8) - 8) bits of [8, n), covering every
+// term's x bits at and above 8 (else QCX_BAD_ARGUMENTS: nothing outside the tile can be reached).
+extern "C" int qcx_shard_pauli_rotation_run(void *amp, unsigned n_local, uint64_t hot_mask, unsigned nterms, const uint64_t *x_masks,
+                                            const uint64_t *z_masks, const double *cs, const double *ss, void *stream)
+{
+    if (!amp || n_local == 0 || n_local > 40 || nterms == 0 || nterms > QCX_PROT_RUN_W || !x_masks || !z_masks || !cs || !ss) return QCX_BAD_ARGUMENTS;
+    for (unsigned k = 0; k < nterms; k++)
+        if ((x_masks[k] | z_masks[k]) >> n_local) return QCX_BAD_QUBIT;
+    const unsigned nhot = std::min(4u, std::max(n_local, 8u) - 8u);
+    if ((hot_mask & 0xFF) || (hot_mask >> n_local) || (unsigned)__builtin_popcountll(hot_mask) != nhot) {
+        set_error("pauli rotation run: hot mask %#llx is not %u bits of [8, %u)", (unsigned long long)hot_mask, nhot, n_local);
+        return QCX_BAD_ARGUMENTS;
+    }
+    unsigned hpos[4], nh = 0;
+    for (unsigned q = 8; q < n_local; q++)
+        if (hot_mask >> q & 1u) hpos[nh++] = q;
+    for (unsigned q = 8; nh < 4; q++)                               // (n < 12: the tile-local bits that do not exist keep their own place)
+        if (!(hot_mask >> q & 1u)) hpos[nh++] = q;
+    std::sort(hpos, hpos + 4);
+    auto local = [&](uint64_t m) {                                  // the tile's bits of a mask, squeezed: 0-7, then the hot bits
+        unsigned v = (unsigned)m & 255u;
+        for (unsigned b = 0; b < 4; b++) v |= (unsigned)(m >> hpos[b] & 1u) << (8u + b);
+        return v;
+    };
+    PRotRun run = {};
+    bool diag = true;
+    for (unsigned k = 0; k < nterms; k++) {
+        const uint64_t x = x_masks[k], z = z_masks[k];
+        if (prot_hx(x) & ~hot_mask) {
+            set_error("pauli rotation run: term %u's x_mask %#llx leaves the tile of hot mask %#llx", k, (unsigned long long)x, (unsigned long long)hot_mask);
+            return QCX_BAD_ARGUMENTS;
+        }
+        const unsigned g = (unsigned)__builtin_popcountll(x & z) & 3u, x_loc = local(x), z_loc = local(z);
+        const double c = cs[k], s = ss[k];
+        unsigned odd = 0;
+        for (unsigned j = 0; j < 16; j++) {
+            odd |= (unsigned)(__builtin_popcount(j & (z_loc >> 8)) & 1) << j;
+            odd |= (unsigned)((__builtin_popcount((j ^ (x_loc >> 8)) & (z_loc >> 8)) + __builtin_popcount(x_loc & z_loc & 255u)) & 1) << (16u + j);
+        }
+        run.t[k].z_mask = z;
+        run.t[k].R = {c, 0.0, g == 1 ? s : (g == 3 ? -s : 0.0), g == 0 ? -s : (g == 2 ? s : 0.0)};      // (qcx_shard_pauli_rotation's)
+        run.t[k].loc = x_loc | z_loc << 12 | g << 24;
+        run.t[k].odd = odd;
+        diag = diag && x_loc == 0;
+    }
+    const bool full = n_local >= 12;
+    const uint64_t nunits = full ? ((uint64_t)1) << (n_local - 12) : 1;
+    const unsigned grid = grid_for(nunits, 1, tune_now().prot_grid_cap, 256);
+    const unsigned hot = hpos[0] | hpos[1] << 8 | hpos[2] << 16 | hpos[3] << 24;
+#define QCX_PROT_RUN(DIAG, FULL) hipLaunchKernelGGL((k_prot_run<DIAG, FULL>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (amp_t *)amp, nunits, n_local, hot, nterms, run)
+    if (full) { if (diag) QCX_PROT_RUN(true, true); else QCX_PROT_RUN(false, true); }
+    else      { if (diag) QCX_PROT_RUN(true, false); else QCX_PROT_RUN(false, false); }
+#undef QCX_PROT_RUN
+    return launch_status("pauli rotation run");
+}
+
 static unsigned gcd_u32(unsigned a, unsigned b) { while (b) { unsigned t = a % b; a = b; b = t; } return a; }
 
 // modular inverse of a mod m (gcd(a, m) == 1, m >= 1); 0 when m == 1
@@ -1353,6 +1453,7 @@ struct qcx_register {
     unsigned long rdm_reads;    // ... and the passes of it that read amplitudes (1, or 0 for a basis state)
     unsigned   coll_source;     // the last measure_qubits / postselect call: 0 register, 2 basis (no kernel), 3 compact expanded first
     unsigned long coll_reads, coll_writes;   // ... the marginal's reads behind its probabilities, and collapse passes launched (0 or 1)
+    unsigned long rotb_passes, rotb_wide;    // the last pauli_rotation_batch call: its passes, and those of them that are one wide term (K15)
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
 };
 
@@ -2138,6 +2239,51 @@ extern "C" int qcx_pauli_rotation(uint64_t x_mask, uint64_t z_mask, double theta
     double c, s;
     qcx_polar(theta / 2.0, &c, &s);
     return qcx_shard_pauli_rotation(r->amp, r->n, x_mask, z_mask, c, s, r->stream);
+}
+
+// A list of rotations, in order, as the passes of qcx_pauli_rotation_batch_plan: a run of terms whose partners stay inside one
+// tile is one k_prot_run launch (K15b), a wide term its own k_pauli_rot launch.  Every term is K15's arithmetic with its own
+// (c, s) = polar(theta / 2), so the state is what the loop of qcx_pauli_rotation leaves; everything else is that call's sequence.
+extern "C" int qcx_pauli_rotation_batch(qcx_register *r, unsigned long nterms, const uint64_t *x_masks, const uint64_t *z_masks,
+                                        const double *thetas)
+{
+    if (!r || (nterms && (!x_masks || !z_masks || !thetas))) return QCX_BAD_ARGUMENTS;
+    for (unsigned long k = 0; k < nterms; k++)
+        if (!std::isfinite(thetas[k])) { set_error("pauli_rotation_batch: theta of term %lu is %g", k, thetas[k]); return QCX_BAD_ARGUMENTS; }
+    for (unsigned long k = 0; k < nterms; k++)
+        if ((x_masks[k] | z_masks[k]) >> r->n) {
+            set_error("pauli_rotation_batch: term %lu's masks %#llx / %#llx reach past the %u qubits", k, (unsigned long long)x_masks[k],
+                      (unsigned long long)z_masks[k], r->n);
+            return QCX_BAD_QUBIT;
+        }
+    if (r->sh) { set_error("pauli_rotation_batch: not available on a sharded register"); return QCX_UNSUPPORTED; }
+    r->rotb_passes = 0; r->rotb_wide = 0;
+    if (nterms == 0) return QCX_NO_ERROR;
+    std::vector<unsigned long> pass_of(nterms);
+    std::vector<unsigned> kind(nterms);
+    std::vector<uint64_t> hot(nterms);
+    unsigned long np = 0;
+    QCX_TRY(qcx_pauli_rotation_batch_plan(r->n, nterms, x_masks, QCX_PROT_RUN_W, pass_of.data(), &np, kind.data(), hot.data()));
+    QCX_TRY(unqueued_gate(r, "pauli_rotation_batch", true));
+    double cs[QCX_PROT_RUN_W], ss[QCX_PROT_RUN_W];
+    for (unsigned long k = 0; k < nterms;) {
+        const unsigned long p = pass_of[k];
+        unsigned cnt = 0;
+        while (k + cnt < nterms && pass_of[k + cnt] == p) { qcx_polar(thetas[k + cnt] / 2.0, &cs[cnt], &ss[cnt]); cnt++; }
+        if (kind[p] == 1) { QCX_TRY(qcx_shard_pauli_rotation(r->amp, r->n, x_masks[k], z_masks[k], cs[0], ss[0], r->stream)); r->rotb_wide++; }
+        else QCX_TRY(qcx_shard_pauli_rotation_run(r->amp, r->n, hot[p], cnt, x_masks + k, z_masks + k, cs, ss, r->stream));
+        r->rotb_passes++;
+        k += cnt;
+    }
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_rotation_batch_last_stats(qcx_register *r, unsigned long *passes, unsigned long *wide_terms)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (passes) *passes = r->rotb_passes;
+    if (wide_terms) *wide_terms = r->rotb_wide;
+    return QCX_NO_ERROR;
 }
 
 extern "C" int qcx_c_amodc_gate(unsigned C, unsigned long long atox, unsigned c, qcx_register *r)

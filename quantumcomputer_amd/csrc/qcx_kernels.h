@@ -4866,6 +4866,121 @@ __global__ __launch_bounds__(256) void k_pauli_rot(amp_t *__restrict__ amp, uint
 }
 
 // ---------------------------------------------------------------------------
+// K15b  a RUN of K15's rotations in one read and one write of the state (qcx_pauli_rotation_batch, DESIGN s4.5k): up to
+// QCX_PROT_RUN_W consecutive terms of a list whose partners i ^ x_mask all stay inside one tile of 2^12 amplitudes, applied in
+// the order given while the tile sits in registers -- term by term K15's arithmetic (prot_diag / prot_row), so the state
+// afterwards is, bit for bit, what one k_pauli_rot launch per term leaves.  Terms need not commute: only locality is used.
+// The tile is NOT the 12 lowest index bits: it is bits 0-7 plus the pass's four HOT bits hot[0] < .. < hot[3], any in [8, n)
+// (qcx_pauli_rotation_batch_plan chooses them from the strings).  Thread tid holds the tile-local elements e = tid + 256 j, j < 16,
+// for all terms; element e of unit u is index base(u) + tid + off(j): off(j) deposits j's four bits at the hot bits (uniform),
+// base(u) deposits u into the n - 12 bits that are left, so a wave instruction still moves one whole run of 2^8 amplitudes'
+// quarter, 1 KiB.  Units are disjoint index sets: in place is safe.  The deposit is monotone, so tile-local order is index order.
+// A term arrives as a record in the kernel arguments (uniform index: scalar loads, no table in memory), its masks already
+// tile-local:
+//     loc = x_loc | z_loc << 12 | g << 24   (x_loc, z_loc: bits 0-7 of the mask, and its hot bits at 8-11)
+//     odd: bit j = par(j & (z_loc >> 8)), the thread's own element; bit 16 + j = par((e ^ x_loc) & z_loc) - par(tid & z_loc),
+//          its partner's -- the entry's sign goes by the PARTNER's index, as K15's podd
+//     popcount(i & z_mask) mod 2 = par(base(u) & z_mask) + par(tid & z_loc) + bit j of odd
+//   x_loc == 0  prot_diag on the 16 registers: no LDS, no barrier
+//   else        own elements to LDS (64 KiB), barrier, the partner read back from e ^ x_loc, prot_row with first = the highest
+//               bit of x_loc is clear in e; a barrier before the next term's writes.  Where x_loc has hot bits only, the partner
+//               is the thread's own element j ^ (x_loc >> 8) and nothing leaves the registers (the same prot_row: the same bits)
+// DIAG: the pass has no exchange term, and the kernel no LDS at all.  FULL as in K15: !FULL is the one partial tile of n < 12
+// (hot = 8 .. 11, elements at or above 2^n guarded).
+// ---------------------------------------------------------------------------
+#define QCX_PROT_RUN_W 32
+struct PRotTerm {
+    uint64_t z_mask;
+    PRot     R;
+    uint32_t loc, odd;
+};
+struct PRotRun { PRotTerm t[QCX_PROT_RUN_W]; };
+
+// v with its sign bit flipped where bit 31 of sgn is set: "neg ? -v : v" for every v (a zero's and a NaN's sign included), as
+// one 32-bit XOR, so that a sign put together from uniform and per-lane parts costs no compare and no select
+__device__ __forceinline__ double prot_flip(double v, unsigned sgn)
+{
+    return __hiloint2double(__double2hiint(v) ^ (int)sgn, __double2loint(v));
+}
+
+template <bool DIAG, bool FULL>
+__global__ __launch_bounds__(256) void k_prot_run(amp_t *__restrict__ amp, uint64_t nunits, unsigned n, unsigned hot, unsigned nterms,
+                                                  PRotRun run)
+{
+    constexpr unsigned EPT = 16u;
+    __shared__ amp_t sa[DIAG ? 1 : 4096];
+    const unsigned tid = threadIdx.x;
+    const unsigned h0 = hot & 255u, h1 = (hot >> 8) & 255u, h2 = (hot >> 16) & 255u, h3 = hot >> 24;
+    const unsigned nel = FULL ? 4096u : 1u << n;
+    auto off = [&](unsigned j) {
+        return ((uint64_t)(j & 1u) << h0) | ((uint64_t)((j >> 1) & 1u) << h1) | ((uint64_t)((j >> 2) & 1u) << h2) | ((uint64_t)(j >> 3) << h3);
+    };
+    for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
+        const uint64_t base = insert_zero(insert_zero(insert_zero(insert_zero(u << 8, h0), h1), h2), h3);
+        amp_t a[EPT];
+#pragma unroll
+        for (unsigned j = 0; j < EPT; j++)
+            if (FULL || tid + 256u * j < nel) a[j] = __builtin_nontemporal_load(amp + (base | off(j)) + tid);      // (a uniform address + the lane)
+            else a[j] = amp_t{0.0, 0.0};                             // (never stored; the in-thread exchange moves it about)
+#pragma unroll 1
+        for (unsigned k = 0; k < nterms; k++) {
+            const PRot R = run.t[k].R;
+            const unsigned loc = run.t[k].loc, odd = run.t[k].odd;
+            const unsigned x_loc = loc & 0xFFFu, z_loc = (loc >> 12) & 0xFFFu;
+            // signs as words with bit 31 alone: the unit's and the lane's share of the parity here, element j's from `odd` (uniform)
+            const unsigned parw = ((unsigned)__popcll(base & run.t[k].z_mask) + (unsigned)__popc(tid & z_loc)) << 31;
+            auto oddw = [&](unsigned bit) { return ((odd >> bit) & 1u) << 31; };
+            if (DIAG || x_loc == 0) {
+                const double ei = prot_flip(R.ei, parw);
+#pragma unroll
+                for (unsigned j = 0; j < EPT; j++)
+                    if (FULL || tid + 256u * j < nel) a[j] = prot_diag({R.c, R.zr, R.er, prot_flip(ei, oddw(j))}, false, a[j]);
+            } else {
+                const bool godd = ((loc >> 24) & 1u) != 0;
+                const unsigned mr = godd ? 0x80000000u : 0u, mi = mr ^ 0x80000000u;      // the entry's non-zero component carries the sign
+                const double er = prot_flip(R.er, parw & mr), ei = prot_flip(R.ei, parw & mi);
+                const unsigned hbit = 1u << (31u - (unsigned)__clz((int)x_loc));
+                if ((x_loc & 255u) == 0) {
+                    // the partner is one of the thread's own elements, j ^ (x_loc >> 8): b = a so permuted, one uniform step
+                    // per hot bit of x_loc, and neither LDS nor a barrier
+                    amp_t b[EPT];
+#pragma unroll
+                    for (unsigned j = 0; j < EPT; j++) b[j] = a[j];
+#pragma unroll
+                    for (unsigned t = 0; t < 4; t++)
+                        if ((x_loc >> (8u + t)) & 1u) {
+#pragma unroll
+                            for (unsigned j = 0; j < EPT; j++)
+                                if (!((j >> t) & 1u)) { const amp_t v = b[j]; b[j] = b[j | (1u << t)]; b[j | (1u << t)] = v; }
+                        }
+#pragma unroll
+                    for (unsigned j = 0; j < EPT; j++)
+                        if (FULL || tid + 256u * j < nel) {
+                            const unsigned w = oddw(16u + j);
+                            a[j] = prot_row({R.c, R.zr, prot_flip(er, w & mr), prot_flip(ei, w & mi)}, godd, false, ((256u * j) & hbit) == 0, a[j], b[j]);
+                        }
+                    continue;
+                }
+#pragma unroll
+                for (unsigned j = 0; j < EPT; j++)
+                    if (FULL || tid + 256u * j < nel) sa[tid + 256u * j] = a[j];
+                __syncthreads();
+#pragma unroll
+                for (unsigned j = 0; j < EPT; j++)
+                    if (FULL || tid + 256u * j < nel) {
+                        const unsigned e = tid + 256u * j, w = oddw(16u + j);
+                        a[j] = prot_row({R.c, R.zr, prot_flip(er, w & mr), prot_flip(ei, w & mi)}, godd, false, (e & hbit) == 0, a[j], sa[e ^ x_loc]);
+                    }
+                __syncthreads();
+            }
+        }
+#pragma unroll
+        for (unsigned j = 0; j < EPT; j++)
+            if (FULL || tid + 256u * j < nel) __builtin_nontemporal_store(a[j], amp + (base | off(j)) + tid);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // K16  the first stage of a qubit range's reduced density matrix (qcx_reduced_density_matrix, DESIGN s4.5j; tests/rdm_ref.py is
 // the definition).  The range is [first, first + NUM), NV = 2^NUM its values; with a = amp[r, v], b = amp[r, w] (r = the bits
 // outside the range, squeezed) the components are ROWS of an NV x NV table of doubles:

@@ -303,6 +303,13 @@ class Register:
         check(lib().qcx_rdm_last_stats(self._h, C.byref(src), C.byref(reads)), "qcx_rdm_last_stats")
         return src.value, reads.value
 
+    def rotation_batch_stats(self):
+        """(passes, wide terms) of the last pauli_rotation_batch call on this register: the passes over the state it ran (the
+        plan's: pauli_rotation_batch_plan), and those of them that were one wide term on its own"""
+        passes, wide = C.c_ulong(0), C.c_ulong(0)
+        check(lib().qcx_rotation_batch_last_stats(self._h, C.byref(passes), C.byref(wide)), "qcx_rotation_batch_last_stats")
+        return passes.value, wide.value
+
     def expectation_matrix(self, first, O):
         """Tr(rho O) as a Python complex, for any 2^num x 2^num matrix O on the qubits [first, first + num) (qubit `first` = bit 0
         of O's index): <psi|O|psi> of an observable that need not be a Pauli string.  rho is reduced_density_matrix(first, num),
@@ -442,6 +449,21 @@ def pauli_rotation(pauli, theta, reg):
     takes -- a str such as "XIZY" (character k = qubit k), a dict {qubit: 'X' | 'Y' | 'Z' | 'I'}, or an (x_mask, z_mask) pair."""
     x, z = _lib.pauli_masks(pauli, reg.num_qubits)
     check(lib().qcx_pauli_rotation(x, z, float(theta), reg._h), "pauli_rotation")
+
+
+def pauli_rotation_batch(terms, reg):
+    """Apply the rotations terms = [(pauli, theta), ...] in order -- a Trotter step -- in as few passes over the state as locality
+    allows: bit for bit the state that pauli_rotation(pauli, theta, reg) term by term leaves (include/qcx.h:
+    qcx_pauli_rotation_batch).  `pauli` as for pauli_rotation; pauli_rotation_batch_plan(terms, n) gives the passes and
+    reg.rotation_batch_stats() what the last call ran."""
+    terms = list(terms)
+    k = len(terms)
+    masks = [_lib.pauli_masks(p, reg.num_qubits) for p, _ in terms]
+    xs = np.array([m[0] for m in masks], dtype=np.uint64)
+    zs = np.array([m[1] for m in masks], dtype=np.uint64)
+    th = np.array([float(t) for _, t in terms], dtype=np.float64)
+    ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if k else (lambda a: None)
+    check(lib().qcx_pauli_rotation_batch(reg._h, k, ptr(xs), ptr(zs), ptr(th)), "pauli_rotation_batch")
 
 
 def controlled(U2):
