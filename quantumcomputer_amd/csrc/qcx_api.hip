@@ -1428,8 +1428,10 @@ struct qcx_register {
     int        no_chain;        // the buffer pointer was handed out (qcx_device_pointer) or no second buffer fits: passes work in place
     int        nonfinite;       // the caller wrote a component that is not finite (or >= 2^500): every gate runs as a STRICT pass (K9: the
                                 // mat-vec's own products, identity rows included) until a reset, a fill or a measurement replaces the state
-    int        zeros_dirty;     // the caller wrote amplitudes (qcx_state_write / _load): they may hold -0, which the reference's gates would
-                                // canonicalise (Q:393-413); one k_canon_zeros pass runs before the next gate
+    int        zeros_dirty;     // 1: the caller wrote amplitudes (qcx_state_write / _load): they may hold -0, which the reference's gates would
+                                // canonicalise (Q:393-413); one k_canon_zeros pass runs before the next gate.  2: a tolerance-mode flush
+                                // ran merged diagonals, which leave -0 as well (plan_has_diagonals, qcx_fuse.inc.h): the same pass, but
+                                // not before another tolerance-mode flush
     int        fusion;          // 1: every gate call is queued (fused passes, qcx_fuse.inc.h); 0: only the whole-circuit entry points; -1: nothing
     int        composite;       // > 0 while a whole-circuit entry point is queueing its gates
     struct GateQueue *queue;
@@ -1962,6 +1964,13 @@ extern "C" int qcx_chain_stats(qcx_register *r, unsigned long *chained_passes)
 {
     if (!r || !chained_passes) return QCX_BAD_ARGUMENTS;
     *chained_passes = (!r->sh && r->queue) ? r->queue->chained_passes : 0;
+    return QCX_NO_ERROR;
+}
+// ... fused passes that carried merged diagonals (tolerance mode: a flush without one ran the exact interpreter throughout)
+extern "C" int qcx_diag_stats(qcx_register *r, unsigned long *diag_passes)
+{
+    if (!r || !diag_passes) return QCX_BAD_ARGUMENTS;
+    *diag_passes = (!r->sh && r->queue) ? r->queue->diag_passes : 0;
     return QCX_NO_ERROR;
 }
 extern "C" int qcx_gen_stats(qcx_register *r, unsigned long *generated_fronts)

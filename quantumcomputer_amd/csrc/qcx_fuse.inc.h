@@ -93,7 +93,7 @@ struct GateQueue {
     size_t   d_cap = 0;
     FuseOp  *h_ops = nullptr;       // pinned staging
     size_t   h_cap = 0;
-    unsigned long passes_launched = 0, gates_fused = 0, chained_passes = 0, gen_fronts = 0, gen_cols = 0, compact_chains = 0, expanding_stores = 0;
+    unsigned long passes_launched = 0, gates_fused = 0, chained_passes = 0, diag_passes = 0, gen_fronts = 0, gen_cols = 0, compact_chains = 0, expanding_stores = 0;
     hipEvent_t ev;                  // recorded after the last kernel of a flush: guards the record buffers
     bool     ev_valid = false;
     // the LAST pass of a compact chain that was asked to stay compact (qcx_register::compact_pending == 2): not launched yet.
@@ -1765,6 +1765,7 @@ static int launch_actions(qcx_register *v, GateQueue *gq, const Tune &tn, const 
         QCX_TRY(launch_pass(v, tn, act.P, gq->d_ops + act.op_off, v->amp, out));
         if (out == v->scratch) std::swap(v->amp, v->scratch);
         if (act.P.chained) gq->chained_passes++;
+        if (act.P.dg_cnt) gq->diag_passes++;
         gq->passes_launched++;
         gq->gates_fused += act.ngates;
     }
@@ -1879,6 +1880,17 @@ static bool compact_chain_plan(const qcx_register *r, const GateQueue *gq, const
     return true;
 }
 
+// does a plan hold a pass with merged diagonals?  The tolerance kernels multiply by a merged diagonal F as one complex product
+// without the exact kernels' trailing + 0.0: an amplitude (+0, +0) times F with Re F < 0 comes out with a -0 component.  A flush
+// that ran such a pass therefore leaves the zero pass of K0c OWED (zeros_dirty = 2), as a write of the caller's does: observers see
+// the state as it is, the next exact gate canonicalises first.  Another tolerance-mode flush does not (fuse_flush): it promises
+// no bits, and a canonicalising pass between two of them would cost a tenth of an n = 28 inverse QFT.
+static bool plan_has_diagonals(const std::vector<FuseAction> &acts)
+{
+    for (const FuseAction &a : acts) if (a.fused && a.P.dg_cnt) return true;
+    return false;
+}
+
 // The launching half.  keep: leave the result in its compact form (r->compact_pending; measure_state reads it there, everything
 // else expands it first).  *done = false: not applicable, nothing was launched -- but no_chain may be set: no room for the second buffer.
 static int compact_chain(qcx_register *r, GateQueue *gq, const Tune &tn, const BasisFront &Bf, size_t kfront, const std::vector<QGate> &gates, bool keep, bool *done)
@@ -1910,7 +1922,7 @@ static int compact_chain(qcx_register *r, GateQueue *gq, const Tune &tn, const B
         if (!keep) QCX_TRY(expand_pending(r));
     }
     r->basis_pending = 0;
-    r->zeros_dirty = 0;
+    r->zeros_dirty = plan_has_diagonals(cp.acts) ? 2 : 0;
     r->fronts++;
     gq->gen_fronts++; gq->gen_cols++; gq->compact_chains++;
     gq->gates_fused += kfront;
@@ -1952,7 +1964,9 @@ static int fuse_flush(qcx_register *r, bool keep_compact = false)
         }
     }
     if (!gq || gq->gates.empty()) return QCX_NO_ERROR;
-    if (r->own_stream && !gen_try) QCX_TRY(canon_if_dirty(r));      // gates are about to run on a state the caller wrote (a shard view: its host's business)
+    // gates are about to run on a state the caller wrote (a shard view: its host's business); what a tolerance-mode flush left owed
+    // stays owed through the next one
+    if (r->own_stream && !gen_try && !(r->zeros_dirty == 2 && r->fusion == 2)) QCX_TRY(canon_if_dirty(r));
     std::vector<QGate> gates;
     gates.swap(gq->gates);                       // the queue is empty from here on (re-entrancy safe)
     if (gen_try) {                               // the whole flush on a compact copy of the state, when the front allows it
@@ -2020,6 +2034,7 @@ static int fuse_flush(qcx_register *r, bool keep_compact = false)
     if (!hit && plan_cache_store(gq, key, acts, all_ops)) { gq->pc.gen_built = gen_built; gq->pc.gen2 = gen2; }
     QCX_TRY(plan_records_resident(r, gq, hit, all_ops, tn));
     QCX_TRY(launch_actions(r, gq, tn, acts.data(), acts.size(), &gates));
+    if (plan_has_diagonals(acts)) r->zeros_dirty = 2;
     if (hit ? !gq->pc.all_ops.empty() : !all_ops.empty()) QCX_TRY(mark_records_in_use(gq, r->stream));
     return QCX_NO_ERROR;
 }

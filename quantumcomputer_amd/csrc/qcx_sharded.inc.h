@@ -70,7 +70,8 @@ struct ShardSet {
     unsigned long selfchecks = 0;                 // pre-flight checks this register has passed (qcx_sharded_selfchecks)
     bool     staged = false;                      // no peer access between some of the devices (or QCX_SHARD_FORCE_STAGED=1): a trade packs into the
                                                   // shard's OWN spare buffer and the chunks travel by hipMemcpyPeerAsync (no peer stores, no relays)
-    bool     zeros_dirty = false;                 // the caller wrote amplitudes: one k_canon_zeros pass per shard before the next gate (Q:393-413)
+    int      zeros_dirty = 0;                     // 1: the caller wrote amplitudes: one k_canon_zeros pass per shard before the next gate (Q:393-413);
+                                                  // 2: a tolerance-mode flush ran (its merged diagonals leave -0, K6t): the same pass, before the next EXACT gate
     ShardSet *comp = nullptr;                     // the COMPANION register of compact circuits (sh_compact): L + cb qubits on the same devices, created on first use
     unsigned long compact_circuits = 0, compact_measures = 0;
     // round 5: the result of a compact circuit STAYS on the companion until something other than measure_state looks at the state
@@ -706,7 +707,18 @@ static int sh_expand_pending(ShardSet *sh)
     return QCX_NO_ERROR;
 }
 
+static int sh_flush_queue(ShardSet *sh, bool keep_compact);
+
+// the queue in tolerance mode leaves the zero pass owed (qcx_register::zeros_dirty == 2), whatever path the flush takes
 static int sh_flush(ShardSet *sh, bool keep_compact)
+{
+    const bool tol = sh->fusion == 2 && !sh->queue.empty() && !sh->dry;
+    const int st = sh_flush_queue(sh, keep_compact);
+    if (tol && st == QCX_NO_ERROR) sh->zeros_dirty = 2;
+    return st;
+}
+
+static int sh_flush_queue(ShardSet *sh, bool keep_compact)
 {
     if (sh->comp_pending) {                       // an earlier flush left the state on the companion register
         if (keep_compact && sh->queue.empty() && !sh->basis_pending) return QCX_NO_ERROR;
@@ -720,8 +732,8 @@ static int sh_flush(ShardSet *sh, bool keep_compact)
     }
     if (sh->basis_pending) QCX_TRY(sh_materialize_basis(sh));
     if (sh->queue.empty()) return QCX_NO_ERROR;
-    if (sh->zeros_dirty) {
-        sh->zeros_dirty = false;
+    if (sh->zeros_dirty && !(sh->zeros_dirty == 2 && sh->fusion == 2)) {       // (another tolerance-mode flush: its -0 stay owed)
+        sh->zeros_dirty = 0;
         if (!sh->dry) for (unsigned r = 0; r < sh->W; r++) { SH_DEV(sh, r); QCX_TRY(qcx_shard_canon_zeros(sh->buf[sh->cur][r], sh->n_local, sh->st[r])); }
     }
     std::vector<SGate> q;

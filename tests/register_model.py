@@ -23,6 +23,9 @@ register (qcx_register_create_sharded): the same model -- a sharded register pro
 with the calls it refuses (QCX_UNSUPPORTED, nothing touched) as refused ops, and relays / selfcheck / stats ops the model does
 nothing for.  tests/test_sharded_sequences_dry.py replays them on a dry-run register, tests/test_gpu_sharded_sequences.py on the GPU.
 
+One op no generator above draws: prot_batch (qcx_pauli_rotation_batch, terms from rotation_terms), which the model applies as the
+loop of the single rotation; tests/tolerance_twin.py deals it out behind the tolerance mode.
+
 An op is a tuple of a name and plain numbers / strings, so that a failing sequence prints as a Python literal and replays:
 written data and matrices are regenerated from the seed inside the op (window_data, matrix_data).  Host only."""
 import numpy as np
@@ -154,6 +157,18 @@ def batch_terms(n, seed, k):
         j = int(rs.randint(0, k))
         terms[j] = (0.0,) + terms[j][1:]
     return terms
+
+
+ROTATION_THETAS = [0.0, float(np.pi), -0.7, 7.5, 0.3]     # tests/test_gpu_pauli_rotation_batch.THETAS (tests/test_tolerance_twin.py holds them equal)
+
+
+def rotation_terms(n, seed, k):
+    """the k terms ((x_mask, z_mask), theta) of a prot_batch op, in the order the call applies them: masks as draw_masks gives
+    them (all three unit shapes, so that a list of 40 closes passes by the width, by a fifth hot bit and by a wide term), thetas
+    the ones the direct test of qcx_pauli_rotation_batch cycles through, from a start the seed picks"""
+    rs = np.random.RandomState(seed)
+    shift = int(rs.randint(0, len(ROTATION_THETAS)))
+    return [(draw_masks(rs, n), ROTATION_THETAS[(j + shift) % len(ROTATION_THETAS)]) for j in range(k)]
 
 
 def rdm_shape(n, first, num):
@@ -315,6 +330,9 @@ def apply_to_model(m, op):
     elif k == "expect_batch": return m.expectation_batch(batch_terms(m.n, op[1], op[2]))
     elif k == "rdm": return (m.reduced_density_matrix(op[1], op[2]), m.marginal(op[1], op[2]))
     elif k == "prot": m.pauli_rotation(op[1], op[2], op[3])
+    elif k == "prot_batch":                                                 # (qcx_pauli_rotation_batch promises the bits of the loop)
+        for (x, z), theta in rotation_terms(m.n, op[1], op[2]):
+            m.pauli_rotation(x, z, theta)
     elif k == "devptr": return m.read(op[1], op[2])
     elif k == "stream": pass
     elif k in ("relays", "selfcheck"): pass                                 # (a sharded register's; no amplitude changes)

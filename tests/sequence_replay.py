@@ -35,6 +35,13 @@ def compact_chains(qc, reg):
     return int(v.value)
 
 
+def diagonal_passes(qc, reg):
+    """fused passes so far that carried merged diagonals (the tolerance mode's arithmetic; the others ran the exact interpreter)"""
+    v = C.c_ulong(0)
+    assert qc.lib().qcx_diag_stats(reg._h, C.byref(v)) == 0
+    return int(v.value)
+
+
 _hip_memcpy = None
 
 
@@ -138,6 +145,11 @@ def apply_to_register(qc, reg, op, path_of, ctx):
         rho = reg.reduced_density_matrix(op[1], op[2])
         return np.ascontiguousarray(rho).view(np.float64).reshape(rho.shape + (2,))       # (re, im) pairs, as rdm_ref gives them
     elif k == "prot": qc.pauli_rotation((op[1], op[2]), op[3], reg)
+    elif k == "prot_batch":
+        terms = rm.rotation_terms(reg.num_qubits, op[1], op[2])
+        qc.pauli_rotation_batch(terms, reg)
+        passes = qc.pauli_rotation_batch_plan(terms, reg.num_qubits)[1]
+        return reg.rotation_batch_stats(), (len(passes), sum(kind for kind, _ in passes))       # (what ran, what the plan says)
     elif k == "devptr": return read_through_pointer(reg, op[1], op[2], ctx)
     elif k == "stream": set_stream(reg, op[1], ctx)
     elif k == "refused":
@@ -209,6 +221,8 @@ def compare(op, got, want):
     elif k == "norm2":
         if want is not None:                                               # (a tree sum: not bit-defined; skipped on a non-finite state)
             assert abs(got - want) < 1e-9, f"norm2 {got!r} vs {want!r}"
+    elif k == "prot_batch":
+        assert want is None and got[0] == got[1], f"rotation_batch_stats() {got[0]}, the plan's (passes, wide terms) {got[1]}"
     elif k == "refused":
         if isinstance(want, tuple):
             assert got[1] == want[1], f"status {got[1]} != {want[1]}"
