@@ -1020,8 +1020,9 @@ static void fuse_plan(const qcx_register *r, const Tune &tn, const std::vector<Q
                 all_ops.resize(act.op_off); return 1;
             }
             act.P.dg_slim = sh.want_x8 ? 3u : sh.want_q3 ? 2u : (keep_diags && !kept.empty() && generic_rounds == 0) ? 1u : 0u;     // every round is a fast round (2: radix 8); 3: the exact walk on 8 amplitudes per thread
-            act.P.tol_scale = 1.0;
-            if (sh.want_q3) for (size_t k = 0; k < sh.n_h; k++) act.P.tol_scale *= QCX_SQRT1_2;
+            // (1/sqrt 2)^n_h: the even part is a power of two, exact.  (A product of n_h rounded factors is 1 ulp high for every even
+            // n_h >= 2 -- M_SQRT1_2^2 rounds to 0.5 (1 + 2^-52) -- which left the n = 28 inverse QFT of |0> 3 ulps off, the oracle 1.)
+            act.P.tol_scale = sh.want_q3 ? std::ldexp((sh.n_h & 1) ? QCX_SQRT1_2 : 1.0, -(int)(sh.n_h / 2)) : 1.0;
             if (keep_diags) {
                 std::vector<unsigned> kd;
                 for (unsigned os : kept) kd.push_back(pass_diags[os]);

@@ -1541,7 +1541,7 @@ struct FusePass {
                                 // bit 0 skip the gates, bit 1 skip the stores, bit 2 skip the tile fill -- results are then wrong by design
     uint32_t dg_cnt, dg_rec_off;// tolerance mode: merged diagonals of the pass (0 = none), record offset of their table area in ops
     uint32_t dg_lds_off, dg_slim;// byte offset of their LDS area behind the lut; 1: every round of the pass is a fast round; 2: radix-8 fast rounds
-    double   tol_scale;         // radix-8 passes: M_SQRT1_2 ^ (Hadamards of the pass), applied once when a tile is stored
+    double   tol_scale;         // radix-8 passes: (1/sqrt 2) ^ (Hadamards of the pass) -- the exact power of two, times M_SQRT1_2 for an odd count -- applied once when a tile is stored
     // General tile addressing (round 4).  A pass reads the tile whose local bit j is PHYSICAL index bit in_pos[j] of the input
     // buffer (ascending in j: in_pos[j] = j for the first c) and stores it where the pass's output layout puts those bits --
     // in place on the identity layout (the default: out = in), or OUT OF PLACE into the second buffer under another

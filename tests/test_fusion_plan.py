@@ -7,7 +7,9 @@ import math
 import numpy as np
 import pytest
 
+import exact_ref as er
 import fuse_emulator as emu
+import tolerance_cases as tc
 
 
 def bits(a):
@@ -257,6 +259,8 @@ def test_long_phase_runs_are_cut_at_64_gates(qc, ob, tune_guard, count):
 
 # ---- tolerance mode (qcx_set_fusion(reg, 2)): merged diagonals, NOT bit-exact -----------------------------------------
 TOL = 1e-12       # max |delta amplitude| against the oracle on these n <= 14 circuits (north_star allows 1e-10)
+# ... and, beside it, the criterion of tests/exact_ref.py: the planner's real tables (E_out, G0, G1, G2, kc / ks), applied by the
+# emulator, leave a state as close to an extended-precision truth as the oracle's own is (within exact_ref.MARGIN, both norms)
 
 
 def shor_descs(qc, Cn, L, M, a):
@@ -288,6 +292,9 @@ def test_tolerance_mode_iqft_merges_every_run_into_one_diagonal(qc, ob, tune_gua
     ob.iqft(want, n, M)
     tot = emu.run_plan(state, n, M, descs, acts, recs, ob)
     assert max_delta(state, want) <= TOL
+    cw, truth, _ = tc.iqft_case(ob, n, M, 11)
+    assert np.array_equal(bits(cw), bits(want))
+    er.assert_as_accurate_as_oracle(state, want, truth, f"iQFT n={n} M={M} T{T}c{c}")
     assert not np.array_equal(bits(state), bits(want)) or L < 3          # it really is the other arithmetic
     # every H but the last is followed by a run of phases sharing its qubit: one diagonal each (a diagonal that lands in a
     # round of another shape gets its phases back; a lone last H may run stand-alone)
@@ -306,6 +313,9 @@ def test_tolerance_mode_shor_circuit(qc, ob, tune_guard, Cn, L, M, a):
     ob.quantum_computation(want, n, M, Cn, a)
     tot = emu.run_plan(state, n, M, descs, acts, recs, ob)
     assert max_delta(state, want) <= TOL and tot["diags"] >= L - 3
+    cw, truth, _ = tc.shor_case(ob, Cn, L, M, a)
+    assert np.array_equal(bits(cw), bits(want))
+    er.assert_as_accurate_as_oracle(state, want, truth, f"Shor {Cn}/{L}/{M}")
     # the measurement distribution is untouched at this level: same cumulative probabilities to 1e-12
     p0 = np.cumsum(state[0::2] ** 2 + state[1::2] ** 2); p1 = np.cumsum(want[0::2] ** 2 + want[1::2] ** 2)
     assert np.max(np.abs(p0 - p1)) < 1e-12
@@ -343,9 +353,11 @@ def test_tolerance_mode_random_programs(qc, ob, tune_guard, seed):
     acts, recs, _ = qc.fusion_plan(n, M, descs, mode=2)
     state = ob.fill_random(n, seed)
     want = state.copy()
+    truth = er.truth(state, n, M, steps, Cn=Cn)
     oracle_run(ob, want, n, M, Cn, steps)
     emu.run_plan(state, n, M, descs, acts, recs, ob)
     assert max_delta(state, want) <= TOL, (n, M, T, c)
+    er.assert_as_accurate_as_oracle(state, want, truth, f"program {seed}: n={n} M={M} T{T}c{c}")
 
 
 def test_tolerance_mode_plan_of_the_n28_iqft(qc, tune_guard):
@@ -381,6 +393,10 @@ def test_tolerance_mode_radix8_rounds(qc, ob, tune_guard, n, M):
     want = state.copy(); ob.iqft(want, n, M)
     tot = emu.run_plan(state, n, M, descs, acts, recs, ob)
     assert max_delta(state, want) <= TOL
+    if n <= tc.RADIX8_TRUTH_MAX_N:
+        cw, truth, _ = tc.iqft_case(ob, n, M, 5)
+        assert np.array_equal(bits(cw), bits(want))
+        er.assert_as_accurate_as_oracle(state, want, truth, f"radix-8 rounds, iQFT n={n} M={M}")
     q3 = [a for a in acts if a.fused and (recs[a.rec_off].type & 0xFF) == emu.FUSE_QROUND3]
     assert len(q3) == (n - max(M, 4) + 7) // 8, [(a.T, a.c) for a in acts]
     assert kernels(q3) == ["k_fused_x8<512, 12, false, true>"] * len(q3)
@@ -388,6 +404,62 @@ def test_tolerance_mode_radix8_rounds(qc, ob, tune_guard, n, M):
     acts0, recs0, _ = qc.fusion_plan(n, M, descs, mode=2)
     q30 = [a for a in acts0 if a.fused and (recs0[a.rec_off].type & 0xFF) == emu.FUSE_QROUND3]
     assert len(q30) == len(q3) and kernels(q30) == ["k_fused_q3<512, 12, 4, false, false>"] * len(q3)
+
+
+def steps_descs(qc, steps):
+    out = []
+    for s in steps:
+        if s[0] == "h":
+            out.append((0, s[1], 0, 0.0, 0.0, 0, 0))
+        else:
+            c, sn = qc.polar(s[3])
+            out.append((1, 0, (1 << s[1]) | (1 << s[2]), c, sn, 0, 0))
+    return out
+
+
+def diag_tables_used(act, recs, slot):
+    """(G0, G1, G2 hold a factor, E_out has a field) for one merged diagonal of a pass, read from its table area"""
+    import struct
+    raw = b"".join(bytes(memoryview(recs[act.rec_off + act.diag_rec_off + k]).cast("B")) for k in range(act.rec_cnt - act.diag_rec_off))
+    area = np.frombuffer(raw, dtype=np.complex128)
+    nd = act.diag_cnt
+    G = area[3 * nd + 48 * slot: 3 * nd + 48 * (slot + 1)]
+    present = struct.unpack("<8I", area[3 * slot: 3 * slot + 2].tobytes())[5]
+    return tuple(bool(np.any(G[16 * g: 16 * g + 16] != 1.0)) for g in range(3)) + (present != 0,)
+
+
+@pytest.fixture()
+def edge_guard(qc):
+    old = {k: qc.lib().qcx_tune_get(k.encode()) for k in tc.EDGE_KNOB_KEYS}
+    yield
+    qc.tune(**old)
+
+
+@pytest.mark.parametrize("knobs", tc.EDGE_KNOBS, ids=tc.EDGE_KNOB_IDS)
+def test_tolerance_mode_run_merge_edges(qc, ob, edge_guard, knobs):
+    """tolerance_cases.edge_steps: one run on the top qubit of a 13-qubit register whose three factors come from G0, G2 and E_out
+    (pinned here for the 2^12 tiles; the library's own defaults, as the GPU test runs it).  The whole state and each factor's
+    half-space against the truth: a wrong entry in one table is not diluted by the rest"""
+    qc.tune(**knobs)
+    steps = tc.edge_steps()
+    descs = steps_descs(qc, steps)
+    acts, recs, _ = qc.fusion_plan(tc.EDGE_N, 0, descs, mode=2)
+    carrying = [a for a in acts if a.fused and a.diag_cnt]
+    assert len(carrying) == 1 and carrying[0].diag_cnt == 1, "the run stays merged, in one pass"
+    if knobs.get("fuse_q3", 1):
+        a = carrying[0]
+        assert len(acts) == 1 and a.T == 12 and list(a.tl[:12]) == [0, 1, 2, 3] + list(range(5, 13))
+        assert a.kernel.decode() == ("k_fused_q3<512, 12, 4, false, false>" if knobs.get("fuse_x8t", 1) == 0 else "k_fused_x8<512, 12, false, true>")
+    if carrying[0].T == 12:
+        assert diag_tables_used(carrying[0], recs, 0) == (True, False, True, True), "one factor each in G0, G2 and E_out"
+    want, truth, _ = tc.edge_case(ob)
+    state = ob.fill_random(tc.EDGE_N, tc.EDGE_SEED)
+    tot = emu.run_plan(state, tc.EDGE_N, 0, descs, acts, recs, ob)
+    assert tot["diags"] == 1 and max_delta(state, want) <= TOL
+    assert not np.array_equal(bits(state), bits(want))
+    er.assert_as_accurate_as_oracle(state, want, truth, f"edges {knobs}")
+    for name, where in tc.edge_half_spaces().items():
+        er.assert_as_accurate_as_oracle(state, want, truth, f"edges {knobs}: the half-space of the {name} factor", where=where)
 
 
 def test_mode_1_plan_is_unchanged_by_the_tolerance_code(qc, ob, tune_guard):
@@ -494,6 +566,7 @@ def test_chained_plans_reproduce_the_oracle(qc, ob, chain_guard, n, M, Cn, mode)
         dd, ss = random_program(rs, n, M, Cn, 120)
         programs.append((f"random{trial}", fill_polar(qc, dd, ss), ss))
     total_chained = 0
+    truths = {}
     for name, descs, steps in programs:
         # (fuse_chain_dir: which side of a chained pass is the gathered one -- stores (0), reads (1), by the kind of chain (-1))
         for tune in (dict(), dict(fuse_T=10, fuse_c=4, fuse_chain_dir=0), dict(fuse_T=12, fuse_c=3, fuse_chain_dir=1), dict(fuse_chain_dir=1),
@@ -505,11 +578,14 @@ def test_chained_plans_reproduce_the_oracle(qc, ob, chain_guard, n, M, Cn, mode)
             state = ob.random_state(n, 3)
             want = state.copy()
             oracle_run(ob, want, n, M, Cn, steps)
+            if mode == 2 and name not in truths:                      # one truth per program: the five knob sets share the input
+                truths[name] = er.truth(state, n, M, steps, Cn=Cn)
             emu.run_plan(state, n, M, descs, actions, recs, ob)
             if mode == 1:
                 assert np.array_equal(bits(state), bits(want)), (name, tune)
             else:
                 assert float(np.max(np.abs(state - want))) <= 1e-12, (name, tune)
+                er.assert_as_accurate_as_oracle(state, want, truths[name], f"chained {name} n={n} M={M} {tune}")
     assert total_chained >= 6, "the planner never chained anything"
 
 
@@ -617,6 +693,9 @@ def test_compact_register_premise(qc, ob, chain_guard, C, L, M, a, mode):
         assert np.array_equal(bits(got), bits(want))
     else:
         assert float(np.max(np.abs(got - want))) <= 1e-12
+        cw, truth, _ = tc.shor_case(ob, C, L, M, a)
+        assert np.array_equal(bits(cw), bits(want))
+        er.assert_as_accurate_as_oracle(got, want, truth, f"compact chain, Shor {C}/{L}/{M}")
     assert not np.any(cc[(np.arange(1 << nv) & ((1 << cb) - 1)) >= len(orbit)]), "unused columns stay zero"
 
 

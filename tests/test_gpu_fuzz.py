@@ -9,9 +9,12 @@ import time
 import numpy as np
 import pytest
 
+import exact_ref as er
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-12
+TRUTH_MAX_N = 20                                    # mode-2 cases up to here carry an extended-precision truth beside the oracle's state
 KNOBS = ("fuse_T", "fuse_c", "fuse_x8", "fuse_x8_min_tiles_log2", "fuse_chain", "fuse_chain_min_n", "fuse_chain_dir", "fuse_compact",
          "fuse_compact_lazy", "fuse_expand_fused", "fuse_gen", "fuse_gen_cols", "fuse_plan_cache", "meas_parallel", "meas_min_log2", "meas_block_log", "meas_fast")
 
@@ -20,7 +23,7 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def same(got, want, mode, what):
+def same(got, want, mode, what, truth=None):
     if mode == 3:                                   # poisoned states: NaN wherever the oracle has one, everything else bit for bit
         gn, wn = np.isnan(got), np.isnan(want)
         assert np.array_equal(gn, wn), f"{what}: NaN pattern differs at {np.nonzero(gn != wn)[0][:6]}"
@@ -30,6 +33,8 @@ def same(got, want, mode, what):
     if mode == 2:
         err = float(np.max(np.abs(got - want)))
         assert err <= TOL, f"{what}: max |delta| {err:.3e}"
+        if truth is not None:                       # as accurate against the truth as the oracle's own state (tests/exact_ref.py)
+            er.assert_as_accurate_as_oracle(got, want, truth, what)
     else:
         bad = np.nonzero(bits(got) != bits(want))[0]
         assert bad.size == 0, f"{what}: {bad.size} doubles differ, first at {int(bad[0])}: {got[bad[0]]!r} vs {want[bad[0]]!r}"
@@ -51,7 +56,9 @@ def gate_mix(rs, n, M, Cn, length, lo, phase_bias):
     return prog
 
 
-def apply(qc, ob, reg, want, n, M, Cn, prog, threads=8):
+def apply(qc, ob, reg, want, n, M, Cn, prog, threads=8, truth=None):
+    if truth is not None:
+        er.advance(truth, n, M, prog, Cn)
     for g in prog:
         if g[0] == "h":
             qc.hadamard_gate(g[1], reg); ob.hadamard(want, n, g[1], threads)
@@ -92,6 +99,8 @@ def one_case(qc, ob, seed):
         prog0 = gate_mix(rs, n, M, Cn, int(rs.randint(20, 260)), 0, float(rs.choice([0.3, 0.6, 0.9])))
         tail2 = gate_mix(rs, n, M, Cn, int(rs.randint(10, 200)), M, float(rs.choice([0.5, 0.8, 0.95])))
         for rep_i in range(reps):
+            truth = None
+            tracked = mode == 2 and not poisoned and n <= TRUTH_MAX_N
             if kind == 0 and poisoned:                      # the same on a state with Inf / NaN / overflow-prone components: strict gates (K9)
                 want = ob.random_state(n, (seed + rep_i) & 0xFFFF)
                 for w_ in rs.choice(2 << n, size=int(rs.randint(1, 5)), replace=False):
@@ -101,26 +110,32 @@ def one_case(qc, ob, seed):
             elif kind == 0:                                 # a random program on a random dense state
                 sd = (seed + 977 * rep_i) & 0xFFFF
                 want = ob.fill_random(n, sd); reg.fill_random(sd)
-                apply(qc, ob, reg, want, n, M, Cn, prog0)
+                truth = er.widen(want) if tracked else None
+                apply(qc, ob, reg, want, n, M, Cn, prog0, truth=truth)
             else:                                           # behind a reset: the circuit front, then the inverse QFT (1) or a random tail on the L register (2)
                 want = np.zeros(2 << n); ob.reset(want, n)
+                truth = er.widen(want) if tracked else None
                 qc.reset_register(reg)
                 if kind == 1:
                     qc.quantum_computation(Cn, a, reg); ob.quantum_computation(want, n, M, Cn, a, threads=8)
+                    if tracked:
+                        er.advance(truth, n, M, er.qcomp_steps(Cn, a, L, M))
                 else:
                     for l in range(M, n):
                         qc.hadamard_gate(l, reg); ob.hadamard(want, n, l, 8)
                     x = a % Cn
                     for l in range(M, n):
                         qc.c_amodc_gate(Cn, x, l, reg); ob.camodc(want, n, M, Cn, x, l, 8); x = (x * x) % Cn
-                    apply(qc, ob, reg, want, n, M, Cn, tail2)
+                    if tracked:
+                        er.advance(truth, n, M, er.qcomp_steps(Cn, a, L, M)[:2 * L])
+                    apply(qc, ob, reg, want, n, M, Cn, tail2, truth=truth)
             # observers, in random order; each must see the reference's state
             for obs in rs.permutation(["read", "norm", "window", "measure", "more"])[:int(rs.randint(1, 5))]:
                 cmp_mode = 3 if poisoned else mode
                 if poisoned and obs in ("norm", "more"):
                     continue                                # (norm of a NaN state; "more" would run on a collapsed or still poisoned state: covered by the next case)
                 if obs == "read":
-                    same(reg.read(), want, cmp_mode, tag + " read")
+                    same(reg.read(), want, cmp_mode, tag + " read", truth)
                 elif obs == "norm":
                     # (two different summation orders -- the oracle's is the sequential one: 1.1e-11 apart at n = 25 -- so this observer
                     #  only checks that the flush it triggers leaves the right state behind; the reads do the comparing)
@@ -128,7 +143,7 @@ def one_case(qc, ob, seed):
                 elif obs == "window":
                     s = int(rs.randint(0, (1 << n) - 64)); cnt = int(rs.randint(1, min(1 << n, 5000) - 63))
                     cnt = min(cnt, (1 << n) - s)
-                    same(reg.read(s, cnt), want[2 * s:2 * (s + cnt)], cmp_mode, tag + " window")
+                    same(reg.read(s, cnt), want[2 * s:2 * (s + cnt)], cmp_mode, tag + " window", None if truth is None else truth[s:s + cnt])
                 elif obs == "measure":
                     r = float(rs.uniform(0, 1)) if rs.randint(0, 4) else float(rs.choice([0.0, 1.0, 1e-9, 0.999999999]))
                     got = qc.measure_state(reg, r)
@@ -138,14 +153,15 @@ def one_case(qc, ob, seed):
                         lo, hi = int(np.searchsorted(cum, r - 1e-9)), int(np.searchsorted(cum, r + 1e-9))
                         assert (r <= 0.0 and got == 0) or lo <= got <= max(hi, lo) or got == (1 << n) - 1, tag + f" measure r={r!r}: {got} not in [{lo}, {hi}]"
                         want[:] = 0.0; want[2 * got] = 1.0
+                        truth = er.widen(want) if truth is not None else None
                     else:
                         assert got == ob.measure(want, n, r), tag + f" measure r={r!r}"
                     same(reg.read(), want, 0, tag + " collapsed state")
                     poisoned = False                            # the collapse replaced the state
                 else:
                     prog = gate_mix(rs, n, M, Cn, int(rs.randint(1, 60)), 0, 0.6)
-                    apply(qc, ob, reg, want, n, M, Cn, prog)
-                    same(reg.read(), want, mode, tag + " more gates")
+                    apply(qc, ob, reg, want, n, M, Cn, prog, truth=truth)
+                    same(reg.read(), want, mode, tag + " more gates", truth)
     return scale
 
 

@@ -8,6 +8,9 @@ import threading
 import numpy as np
 import pytest
 
+import exact_ref as er
+import tolerance_cases as tc
+
 pytestmark = pytest.mark.gpu
 
 
@@ -185,6 +188,10 @@ def test_virtual_ranks_shor_and_measurement(ob, world, fusion):
         if fusion == 2:                                 # tolerance mode per shard: rounding-level differences only
             d = np.asarray(state) - want
             assert float(np.max(np.hypot(d[0::2], d[1::2]))) <= 1e-12 and abs(nrm - 1.0) < 1e-12 and idx == widx
+            # ... and as accurate against an extended-precision truth as the oracle's own state is (tests/exact_ref.py)
+            cw, truth, _ = tc.shor_case(ob, Cn, L, M, a)
+            assert np.array_equal(bits(cw), bits(want))
+            er.assert_as_accurate_as_oracle(state, want, truth, f"world {world}: the gathered mode-2 state")
             continue
         assert np.array_equal(bits(state), bits(want))
         assert abs(nrm - 1.0) < 1e-12

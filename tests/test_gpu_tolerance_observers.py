@@ -13,6 +13,7 @@ import time
 import numpy as np
 import pytest
 
+import exact_ref as er
 import register_model as rm
 import sequence_replay as sr
 import tolerance_twin as tt
@@ -104,7 +105,7 @@ def test_four_threads_in_tolerance_mode(qc, ob, tmp_path, sched):
         follower = next(ops for _, g, ops in sched[(kind, shape)] if g == f)
         prefix, near = tt.prefix_ops(kind, shape), tt.oracle_state(ob, kind, shape)[0]
         twin = tt.run_twin(qc, shape, prefix, tmp_path)
-        tt.check_twin(twin, near, prefix, shape)
+        tt.check_twin(twin, near, prefix, shape, tt.truth_of(ob, shape, prefix))
         ops = tt.pair_ops(shape, follower)
         jobs.append((kind, shape, f, prefix, ops, twin) + tt.expectations(ob, shape, twin[0], ops))
     assert any(rm.compact_shape(j[1]) and j[5][2] == 1 for j in jobs), "one pair behind a compact chain"
@@ -145,7 +146,9 @@ def test_chain_compact_result_marginal_collapse_then_the_exact_inverse_qft(qc, o
         qc.quantum_computation(Cn, a, reg)
 
     S = twin_state(qc, L, M, work)
-    assert tt.max_delta(S, tt.oracle_state(ob, "shor", rm.COMPACT_SHAPES[0])[0]) <= tt.TOL
+    near = tt.oracle_state(ob, "shor", rm.COMPACT_SHAPES[0])[0]
+    assert tt.max_delta(S, near) <= tt.TOL
+    er.assert_as_accurate_as_oracle(S, near, tt.truth_of(ob, rm.COMPACT_SHAPES[0], tt.prefix_ops("shor", rm.COMPACT_SHAPES[0])), "the compact chain's state")
     with Chain(qc, ob, L, M, 2, tmp_path) as c:
         k0 = sr.compact_chains(qc, c.reg)
         work(c.reg, c.ctx)
@@ -173,6 +176,7 @@ def test_chain_inverse_qft_queued_behind_the_handed_out_pointer_on_a_callers_str
     S = twin_state(qc, L, M, work)
     want = ob.fill_random(L + M, 3); ob.iqft(want, L + M, M, 8)
     assert tt.max_delta(S, want) <= tt.TOL and not np.array_equal(sr.bits(S), sr.bits(want))
+    er.assert_as_accurate_as_oracle(S, want, tt.truth_from(ob.fill_random(L + M, 3), L + M, M, [("iqft",)]), "the inverse QFT run in place")
     with Chain(qc, ob, L, M, 2, tmp_path) as c:
         p0 = chain_stats(qc, c.reg)
         work(c.reg, c.ctx)
@@ -232,16 +236,17 @@ def test_chain_sparse_state_controlled_gates_meet_the_zeros_mode_2_left(qc, ob, 
 
     S = twin_state(qc, L, M, work)
     if state == "sparse":
-        near = tt.oracle_state(ob, "sparse", shape)[0]
+        near, truth = tt.oracle_state(ob, "sparse", shape)[0], tt.truth_of(ob, shape, prefix)
     else:
         m = rm.RegisterModel(ob, L, M)
         m.write(zero_half(n, 41))
         for op in gates:
             rm.apply_to_model(m, op)
-        near = m.a
+        near, truth = m.a, tt.truth_from(zero_half(n, 41), n, M, gates)
         assert not S[0::4].any() and not S[1::4].any(), "the control-clear half of qubit 0 holds nothing but zeros"
         assert tt.negative_zeros(S[0::4]) + tt.negative_zeros(S[1::4]) > 50, "the chain must make -0 where the next gate does not act"
     assert tt.max_delta(S, near) <= tt.TOL and not np.array_equal(sr.bits(S), sr.bits(near))
+    er.assert_as_accurate_as_oracle(S, near, truth, f"{state}: the mode-2 state")
     print(f"{state}: the mode-2 state holds {tt.negative_zeros(S)} components that are -0")
     with Chain(qc, ob, L, M, 2, tmp_path) as c:
         work(c.reg, c.ctx)
@@ -302,6 +307,7 @@ def test_sharded_register_owes_the_zero_pass_after_a_tolerance_flush(qc, ob, sha
     for op in gates:
         rm.apply_to_model(m, op)
     assert tt.max_delta(S, m.a) <= tt.TOL and not np.array_equal(sr.bits(S), sr.bits(m.a))
+    er.assert_as_accurate_as_oracle(S, m.a, tt.truth_from(zero_half(n, 43), n, M, gates), f"{shards} shards: the mode-2 state")
     assert tt.negative_zeros(S) > 50, "the chain must make -0"
     m.a = S.copy()
     m.c_phase_shift_gate(9, 1, 0.4)

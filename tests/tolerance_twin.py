@@ -8,7 +8,9 @@ other call is defined bit for bit as a function of the state it is given.  So th
 same mode-2 work is the exact reference: a RegisterModel whose state is set to S must return, and be left with, the very bits the
 subject register gives for the follower -- whatever lazy form (a queue planned with merged diagonals, a compact chain, a chained
 result in the second buffer, a deferred expanding store) the subject held when the follower arrived.  No tolerance enters but
-the one of the mode itself, which only keeps a pair from being vacuous (S is within 1e-12 of the oracle and differs from it in bits).
+the one of the mode itself, which only keeps a pair from being vacuous (S is within 1e-12 of the oracle and differs from it in bits)
+-- and S itself is held to the criterion of tests/exact_ref.py: against an extended-precision truth of the prefix's gates it is as
+accurate as the oracle's state is (truth_of, check_twin).
 
 A mode-2 pass may leave -0 behind (an amplitude (+0, +0) times a merged diagonal F with Re F < 0 <= Im F has the real part
 (-0) - (+0) = -0), so a flush that ran merged diagonals owes the zero pass like a state the caller wrote: observers see S as it
@@ -18,6 +20,7 @@ acts on half of the state only, and the model's gates -- the reference's, which 
 Host only: imports no GPU code itself."""
 import numpy as np
 
+import exact_ref as er
 import register_model as rm
 import sequence_replay as sr
 
@@ -118,6 +121,40 @@ def oracle_state(ob, kind, shape):
         m.a.setflags(write=False)
         _ORACLE[key] = (m.a, returned)
     return _ORACLE[key]
+
+
+GATE_OPS = ("h", "cphase", "camodc", "iqft", "qcomp")
+
+
+def gate_steps(n, M, ops):
+    """the gate ops of a prefix in the step form of exact_ref"""
+    steps = []
+    for op in ops:
+        k = op[0]
+        if k == "h": steps.append(("h", op[1]))
+        elif k == "cphase": steps.append(("p", op[1], op[2], op[3]))
+        elif k == "camodc": steps.append(("c", op[1], op[2], op[3]))
+        elif k == "iqft": steps += er.iqft_steps(n, M)
+        elif k == "qcomp": steps += er.qcomp_steps(op[1], op[2], n - M, M)
+        else: raise AssertionError(f"{op!r} is no gate")
+    return steps
+
+
+def truth_from(start, n, M, ops):
+    """the extended-precision truth (exact_ref.truth) of the gate ops of a prefix, applied to the pairs `start`"""
+    return er.truth(start, n, M, gate_steps(n, M, ops))
+
+
+def truth_of(ob, shape, prefix):
+    """the truth of a prefix, computed once: the calls in front of its first gate (fill, write, reset, a measurement's collapse) make
+    the input on the host model, exactly; everything behind must be a gate"""
+    def make():
+        m = rm.RegisterModel(ob, shape[0], shape[1])
+        k = 0
+        while k < len(prefix) and prefix[k][0] not in GATE_OPS:
+            rm.apply_to_model(m, prefix[k]); k += 1
+        return truth_from(m.a, shape[0] + shape[1], shape[1], prefix[k:])
+    return er.cached(("twin", tuple(shape), repr(prefix)), make)
 
 
 # ---- followers ---------------------------------------------------------------------------------------------------------------
@@ -253,15 +290,18 @@ def dense_input(prefix):
     return prefix[0][0] in ("fill", "write") and not any(op[0] == "measure" for op in prefix)
 
 
-def check_twin(twin, near, prefix, shape):
+def check_twin(twin, near, prefix, shape, truth=None):
     """What keeps a pair from being vacuous, as far as the twin shows it.  The planner keeps a run of phases merged only in a pass
     that can carry the diagonal (rounds form, its tables within the LDS budget, not the by-columns pass of an ordinary chain);
     elsewhere it puts the phases back and the pass is the exact interpreter's.  So the library's own count of passes with merged
     diagonals says what the bits must show: none -- the oracle's bits, exactly; some, on random dense amplitudes -- other bits.
-    (On a basis state or a circuit's periodic state the merged products can round as the single ones do: nothing is asked.)"""
+    (On a basis state or a circuit's periodic state the merged products can round as the single ones do: nothing is asked.)
+    truth: exact_ref's, of the prefix -- S must be as accurate against it as the oracle's state `near` is."""
     S, stats, chains, _ = twin
     err = max_delta(S, near)
     assert err <= TOL, f"the mode-2 state is {err:.3e} from the oracle's"
+    if truth is not None:
+        er.assert_as_accurate_as_oracle(S, near, truth, "the mode-2 state S")
     assert holds_a_merged_run(prefix), "a prefix without a run of phases on one control says nothing about mode 2"
     equal = np.array_equal(sr.bits(S), sr.bits(near))
     if stats[2] == 0:
@@ -350,7 +390,7 @@ def run_pair(qc, ob, shape, knobs, prefix, follower, tmp_path, near=None, kind=N
     try:
         qc.tune(**knobs)
         twin = run_twin(qc, shape, prefix, tmp_path)
-        check_twin(twin, near, prefix, shape)
+        check_twin(twin, near, prefix, shape, truth_of(ob, shape, prefix))
         ops = pair_ops(shape, follower)
         wants, final = expectations(ob, shape, twin[0], ops)
         assert negative_zeros(final) == 0, "the model's gate leaves canonical zeros"
