@@ -7,7 +7,8 @@ QCX_TEST_NMAX qubits (default 32 = 64 GiB; 33 = 128 GiB still has room for the s
 * `qcx_inverse_QFT` through the default fused path on basis states -- windows bit for bit against the oracle's per-index
   evaluation (orc_basis_iqft_window, pinned to the whole-state oracle in tests/test_oracle_pinning.py);
 * Shor N = 21 (M = 5, L = NMAX - 5): the front windows against the oracle's closed form, then the whole circuit -- norm, the
-  measured index the same through two runs of the scan that share no binade guess (record sizes 2^11 and 2^8), the period visible in omega;
+  measured index the same through two runs of the scan that share no binade guess (record sizes 2^11 and 2^8 -- 2^9 at n = 34,
+  where the library raises a smaller one; the record counts of the two runs are asserted to differ), the period visible in omega;
 * a fused Hadamard sweep applied twice (identity within rounding), norm kept;
 * measure_state on a dense random state: the same index from both record sizes for r over the whole range.
 
@@ -36,15 +37,48 @@ def chain_stats(qc, reg):
     return int(v.value)
 
 
-def scan(qc, reg, n, r):
-    """the measurement scan without the collapse (qcx_shard_measure_scan on the register's buffer): the index measure_state
-    would return for the draw r.  (Taking the device pointer pins the register to passes in place from then on.)"""
+def effective_block_log(n, forced):
+    """the record size (log2) the scan of a 2^n register runs with when meas_block_log = forced: the library keeps it within
+    8 .. 11 and RAISES one that is too small for the register -- k_meas_onepass takes four records per 256-thread workgroup and a
+    launch holds fewer than 2^32 threads (meas_launch in csrc/qcx_api.hip)"""
+    blog = min(max(forced, 8), 11)
+    while blog < 11 and ((((1 << n) + (1 << blog) - 1 >> blog) + 3) // 4) * 256 > 0xFFFFFFFF:
+        blog += 1
+    return blog
+
+
+def block_logs(n):
+    """the two record sizes of the cross-check: 2^11, and the smallest the register allows (2^8 up to n = 33) -- or, were that
+    raised all the way to 2^11, one step above it, which the record-count assertion then reports: two runs of one record size are
+    one run compared with itself"""
+    low = effective_block_log(n, 8)
+    return 11, (low if low != 11 else low + 1)
+
+
+def scan(qc, reg, n, r, block_log):
+    """the measurement scan without the collapse (qcx_shard_measure_scan on the register's buffer) with meas_block_log =
+    block_log: (the index measure_state would return for the draw r, the number of records the scan ran over, as the scan itself
+    counted them).  (Taking the device pointer pins the register to passes in place from then on.)"""
     found, index, cum = C.c_int(0), C.c_uint64(0), C.c_double(0.0)
+    slow, records = C.c_uint(0), C.c_uint(0)
     reg.flush()
+    qc.tune(meas_block_log=block_log)
     st = qc.lib().qcx_shard_measure_scan(reg.device_pointer(), n, 0, (1 << n) - 1, 0.0, float(r), C.byref(found), C.byref(index),
                                          C.byref(cum), None)
     assert st == 0
-    return int(index.value) if found.value else (1 << n) - 1
+    assert qc.lib().qcx_measure_last_stats(C.byref(slow), C.byref(records)) == 0
+    assert records.value == (1 << n) + (1 << effective_block_log(n, block_log)) - 1 >> effective_block_log(n, block_log), \
+        (block_log, records.value)                             # (a clamp this module does not know of fails here)
+    return (int(index.value) if found.value else (1 << n) - 1), int(records.value)
+
+
+def scan_both(qc, reg, n, r):
+    """the scan with both record sizes: the two indices, from runs that did NOT use the same number of records"""
+    high, low = block_logs(n)
+    i1, n1 = scan(qc, reg, n, r, high)          # two runs of the scan that share no binade guess: other records,
+    i0, n0 = scan(qc, reg, n, r, low)           # other look-back groups
+    assert n1 != n0, (r, n1, n0)
+    return i1, i0
 
 
 @pytest.fixture
@@ -92,10 +126,7 @@ def test_shor_front_and_whole_circuit(qc, ob, tune_guard):
         assert abs(reg.norm2() - 1.0) < 1e-11
         picks = []
         for r in (0.0, 1e-7, 0.25, 0.5, 0.77, 0.999999, 1.0):
-            qc.tune(meas_block_log=11)          # two runs of the scan that share no binade guess: other records,
-            i1 = scan(qc, reg, n, r)          # other look-back groups
-            qc.tune(meas_block_log=8)
-            i0 = scan(qc, reg, n, r)
+            i1, i0 = scan_both(qc, reg, n, r)
             assert i1 == i0, (r, i1, i0)
             picks.append(i1)
         # period 6: omega of every drawn index sits next to a multiple of 1/6
@@ -139,10 +170,7 @@ def test_measure_dense_random_state_both_scans(qc, tune_guard):
         last = -1
         for f in (0.0, 1e-9, 0.1, 0.5, 0.9, 0.999999999, 1.0, 1.5):
             r = f * tot
-            qc.tune(meas_block_log=11)
-            i1 = scan(qc, reg, n, r)
-            qc.tune(meas_block_log=8)
-            i0 = scan(qc, reg, n, r)
+            i1, i0 = scan_both(qc, reg, n, r)
             assert i1 == i0, (f, i1, i0)
             assert i1 >= last                                  # the cumulative sum is monotone in r
             last = i1
