@@ -84,7 +84,7 @@ int  qcx_M_size(const qcx_register *reg);
  * M_size > 12 works like on one GPU (the modular multiply then runs in place through a per-device staging buffer instead of
  * LDS tiles; M_size <= 26).  Not available on a sharded register: qcx_register_set_stream, qcx_device_pointer (NULL),
  * the event pool, qcx_one_qubit_gate / qcx_c_one_qubit_gate, qcx_two_qubit_gate / qcx_c_two_qubit_gate,
- * qcx_pauli_rotation, qcx_pauli_rotation_batch (QCX_UNSUPPORTED). */
+ * qcx_pauli_rotation, qcx_pauli_rotation_batch, qcx_gate_batch (QCX_UNSUPPORTED). */
 int  qcx_register_create_sharded(int L_size, int M_size, unsigned nshards, const int *devices, qcx_register **out);
 int  qcx_spread_devices(unsigned nshards, int visible_devices /* <= 0: ask HIP */, int *devices_out /* [nshards] */);
 int  qcx_sharded_selfcheck(qcx_register *reg);             /* the pre-flight exchange check on demand */
@@ -206,6 +206,36 @@ unsigned qcx_pauli_rotation_batch_width(void);   /* W: the most terms one pass a
 /* the last qcx_pauli_rotation_batch call on this register that passed its checks: passes = the plan's npasses (kernel launches:
  * reads and writes of the state), wide_terms = those of them that are one wide term */
 int  qcx_rotation_batch_last_stats(qcx_register *reg, unsigned long *passes, unsigned long *wide_terms);
+/* A list of one- and two-qubit gates -- a circuit layer -- in as few passes over the state as locality allows (K12b / K13b, DESIGN
+ * s4.5l).  Gate k is qcx_one_qubit_gate(qubit0, u) (ntargets = 1, control < 0), qcx_c_one_qubit_gate(control, qubit0, u),
+ * qcx_two_qubit_gate(qubit0, qubit1, u) (ntargets = 2) or qcx_c_two_qubit_gate(control, qubit0, qubit1, u), and the state
+ * afterwards is, bit for bit, what the loop of those calls leaves: for any list in any order, on finite and non-finite registers,
+ * zero signs included.  No gate is merged, reordered, skipped or special-cased; exact zeros in a matrix are multiplied out; with
+ * qubit0 > qubit1 the matrix is taken as P u P exactly as qcx_two_qubit_gate takes it.
+ * The passes: a run of consecutive gates whose targets all lie inside one tile of 2^12 amplitudes -- index bits 0-7 plus four more
+ * bits chosen from the gates' targets -- is applied in order while the tile sits in registers, one read and one write of the
+ * state.  A one-target gate costs 1 unit of a pass's W = qcx_gate_batch_width(), a two-target gate 4; controls never constrain a
+ * pass.  qcx_gate_batch_plan in qcx_plan.h is the rule on its own; qcx_gate_batch_last_stats reports what the last call ran.
+ * Everything else is qcx_one_qubit_gate's contract: asynchronous, never queued, flushes what is pending in every fusion mode, not
+ * counted by qcx_fusion_stats, exact in mode 2; a -0 the caller wrote is canonicalised before the first launch.  A register
+ * flagged non-finite keeps its flag and runs the list gate by gate through those calls' own paths (passes = ngates).
+ * Checked in this order, before anything runs: NULL reg, or NULL gates with ngates > 0: QCX_BAD_ARGUMENTS; an ntargets that is
+ * not 1 or 2: QCX_BAD_ARGUMENTS, qcx_last_error() names the gate; a matrix component (the first 8, or all 32) that is not finite
+ * or above 1 in absolute value: QCX_BAD_ARGUMENTS, the message names gate and component; a qubit or control at or above n, or two
+ * of a gate's qubits equal: QCX_BAD_QUBIT, the message names the gate; a sharded register: QCX_UNSUPPORTED -- nothing touched in
+ * any of these cases.  ngates = 0: QCX_NO_ERROR, nothing is launched and queued gates stay queued. */
+typedef struct qcx_gate {
+    unsigned ntargets;        /* 1: u holds 8 doubles (qcx_one_qubit_gate's layout); 2: 32 doubles (qcx_two_qubit_gate's) */
+    int      control;         /* < 0: none */
+    unsigned qubit0, qubit1;  /* qubit1 ignored when ntargets == 1 */
+    double   u[32];
+} qcx_gate;
+int  qcx_gate_batch(qcx_register *reg, unsigned long ngates, const qcx_gate *gates);
+unsigned qcx_gate_batch_width(void);             /* W, in units: a build constant */
+/* the last qcx_gate_batch call on this register that passed its checks: passes = kernel launches (reads and writes of the state;
+ * the plan's npasses, or ngates on a register flagged non-finite), lds_gates = the gates of those passes with a target on
+ * qubits 0-7, which exchange between threads -- through LDS, or inside the wave (the others never leave the thread's registers) */
+int  qcx_gate_batch_last_stats(qcx_register *reg, unsigned long *passes, unsigned long *lds_gates);
 int  qcx_swap_states(qcx_register *reg);                                           /* Q:242-249: no-op */
 /* host-side gate schedules */
 int  qcx_inverse_QFT(qcx_register *reg);                                           /* Q:678-690 */

@@ -139,6 +139,22 @@ int  qcx_pauli_rotation_batch_plan(unsigned n, unsigned long nterms, const uint6
                                    unsigned long *pass_of_term /* [nterms] */, unsigned long *npasses,
                                    unsigned *pass_kind /* [nterms] */, uint64_t *pass_hot /* [nterms] */);
 
+/* The passes of qcx_gate_batch (include/qcx.h; K12b / K13b, DESIGN s4.5l) over n qubits, on the host: qcx_pauli_rotation_batch_plan's
+ * walk.  Gate k has its target qubits as the bits of target_masks[k] (controls do not count) and costs units[k]: 1 with one target,
+ * 4 with two, the size of its record.  hx_k is target_masks[k]'s bits at positions >= 8 (at most two).  Walk the gates in order;
+ * at most one pass is open, with a hot set H and the units used:
+ *   a gate joins the open pass if used + units[k] <= width and popcount(H | hx_k) <= 4, otherwise the open pass closes and the
+ *   gate opens a new one with H = hx_k.  A gate always fits an empty pass, whatever `width` is (width = 1 places a two-target gate
+ *   in a pass of its own);
+ *   on closing, H is padded with the lowest qubits of [8, n) not yet in it, up to min(4, max(n, 8) - 8) bits.
+ * A pass's tile is qubits 0-7 plus H: the whole register for n <= 12 (only `width` splits passes), and for n >= 13 one tile per
+ * value of the other n - 12 bits.  pass_of_gate[k] is gate k's pass (non-decreasing), *npasses their number, pass_hot[p] pass p's
+ * hot mask (both arrays hold ngates entries).  The library calls it with width = qcx_gate_batch_width().  width = 0, n = 0 or
+ * n > 40, a NULL npasses, a NULL array with ngates > 0, or a units[k] other than 1 or 4: QCX_BAD_ARGUMENTS; a target bit at or
+ * above n, or a number of target bits that is not 1 for 1 unit and 2 for 4: QCX_BAD_QUBIT. */
+int  qcx_gate_batch_plan(unsigned n, unsigned long ngates, const uint64_t *target_masks, const unsigned *units, unsigned width,
+                         unsigned long *pass_of_gate /* [ngates] */, unsigned long *npasses, uint64_t *pass_hot /* [ngates] */);
+
 /* The stage plan of qcx_reduced_density_matrix (include/qcx.h; K16, DESIGN s4.5j), on the host.  The 4^num computed components
  * (row v * 2^num + w, v <= w: Re rho[v][w]; row w * 2^num + v, v < w: Im rho[v][w]) are each the marginal's pairwise tree over
  * the bits outside [first, first + num).  Stage 0 reads the state once and sums, for every row, the sum_bits lowest summed

@@ -42,6 +42,13 @@ int  qcx_shard_pauli_rotation(void *amp, unsigned n_local, uint64_t x_mask, uint
  * returns.  Not used by the sharded hosts. */
 int  qcx_shard_pauli_rotation_run(void *amp, unsigned n_local, uint64_t hot_mask, unsigned nterms, const uint64_t *x_masks,
                                   const uint64_t *z_masks, const double *cs, const double *ss, void *stream);
+/* ONE pass of qcx_gate_batch (qcx.h), the launch alone: the ngates gates (qcx_gate records, their qubits local bits) in order, over
+ * the tiles of local bits 0-7 and hot_mask.  The gates' units (1 per one-target gate, 4 per two-target gate) must not exceed
+ * qcx_gate_batch_width(); hot_mask is what qcx_gate_batch_plan gives a pass: min(4, max(n_local, 8) - 8) bits of [8, n_local) that
+ * hold every gate's targets at and above 8, else QCX_BAD_ARGUMENTS -- nothing outside a tile can then be addressed.  Matrices are
+ * taken as given (not checked).  The records are read before the call returns.  Not used by the sharded hosts. */
+struct qcx_gate;
+int  qcx_shard_gate_run(void *amp, unsigned n_local, uint64_t hot_mask, unsigned ngates, const struct qcx_gate *gates, void *stream);
 /* multiply by (cos_t + i sin_t) every amplitude whose local index has all bits of
  * `mask_local` set; mask_local has 0, 1 or 2 bits (global control bits that are 1
  * simply drop out of the mask; a global bit that is 0 means: do not call). */

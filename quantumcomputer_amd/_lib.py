@@ -59,6 +59,10 @@ SIGNATURES = {
     "qcx_pauli_rotation_batch_width": (_u, []),
     "qcx_rotation_batch_last_stats": (_i, [_p, C.POINTER(_ul), C.POINTER(_ul)]),
     "qcx_pauli_rotation_batch_plan": (_i, [_u, _ul, _p, _u, _p, C.POINTER(_ul), _p, _p]),
+    "qcx_gate_batch": (_i, [_p, _ul, _p]),
+    "qcx_gate_batch_width": (_u, []),
+    "qcx_gate_batch_last_stats": (_i, [_p, C.POINTER(_ul), C.POINTER(_ul)]),
+    "qcx_gate_batch_plan": (_i, [_u, _ul, _p, _p, _u, _p, C.POINTER(_ul), _p]),
     "qcx_swap_states": (_i, [_p]),
     "qcx_inverse_QFT": (_i, [_p]),
     "qcx_quantum_computation": (_i, [_u, _u, _i, _p]),
@@ -113,6 +117,7 @@ SIGNATURES = {
     "qcx_shard_two_qubit": (_i, [_p, _u, _u, _u, _i, _p, _p]),
     "qcx_shard_pauli_rotation": (_i, [_p, _u, _u64, _u64, _d, _d, _p]),
     "qcx_shard_pauli_rotation_run": (_i, [_p, _u, _u64, _u, _p, _p, _p, _p, _p]),
+    "qcx_shard_gate_run": (_i, [_p, _u, _u64, _u, _p, _p]),
     "qcx_shard_phase": (_i, [_p, _u, _u64, _d, _d, _p]),
     "qcx_shard_camodc": (_i, [_p, _u, _u, _u, _u, _i, _p]),
     "qcx_shard_swap_bits": (_i, [_p, _p, _u, _u, C.POINTER(_u), C.POINTER(_u), _p]),
@@ -294,6 +299,49 @@ def pauli_rotation_batch_plan(terms, n, width=None):
     check(lib().qcx_pauli_rotation_batch_plan(n, xs.size, ptr(xs), pauli_rotation_batch_width() if width is None else int(width),
                                               ptr(pass_of), C.byref(np_), ptr(kind), ptr(hot)), "qcx_pauli_rotation_batch_plan")
     return [int(v) for v in pass_of], [(int(kind[p]), int(hot[p])) for p in range(np_.value)]
+
+
+class Gate(C.Structure):
+    """qcx_gate (include/qcx.h): one record of qcx_gate_batch"""
+    _fields_ = [("ntargets", _u), ("control", _i), ("qubit0", _u), ("qubit1", _u), ("u", _d * 32)]
+
+
+def gate_targets(entry):
+    """(targets, control) of one gate_batch entry (U, targets) or (U, targets, control): targets as a 1- or 2-tuple of ints,
+    control an int or None"""
+    if len(entry) not in (2, 3):
+        raise ValueError(f"a gate is (U, targets) or (U, targets, control), not {len(entry)} items")
+    t = entry[1]
+    t = (int(t),) if not hasattr(t, "__len__") else tuple(int(q) for q in t)
+    if len(t) not in (1, 2):
+        raise ValueError(f"a gate has one or two targets, not {len(t)}")
+    c = entry[2] if len(entry) == 3 else None
+    return t, (None if c is None else int(c))
+
+
+def gate_batch_width():
+    """W: the units one pass of gate_batch holds -- 1 per one-target gate, 4 per two-target gate (qcx_gate_batch_width)"""
+    return int(lib().qcx_gate_batch_width())
+
+
+def gate_batch_plan(gates, n, width=None):
+    """The passes of gate_batch over n qubits (host code, no GPU needed; include/qcx_plan.h: qcx_gate_batch_plan):
+    (pass_of_gate, hot_masks) for gates = [(U, targets) or (U, targets, control), ...] in order (U is not looked at) -- pass p is a
+    run of gates over the tile of qubits 0-7 and hot_masks[p]; width=None: the library's W."""
+    import numpy as np
+    n = int(n)
+    ts = [gate_targets(g)[0] for g in gates]
+    for t in ts:
+        if min(t) < 0 or max(t) >= 64:
+            raise ValueError(f"targets {t} are not qubits")
+    masks = np.array([sum(1 << q for q in set(t)) for t in ts], dtype=np.uint64)
+    units = np.array([1 if len(t) == 1 else 4 for t in ts], dtype=np.uint32)
+    pass_of, hot = np.zeros(masks.size, dtype=np.uint64), np.zeros(masks.size, dtype=np.uint64)
+    np_ = C.c_ulong(0)
+    ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if masks.size else (lambda a: None)
+    check(lib().qcx_gate_batch_plan(n, masks.size, ptr(masks), ptr(units), gate_batch_width() if width is None else int(width),
+                                    ptr(pass_of), C.byref(np_), ptr(hot)), "qcx_gate_batch_plan")
+    return [int(v) for v in pass_of], [int(hot[p]) for p in range(np_.value)]
 
 
 def fusion_plan(n_local, M, descs, mode=1):

@@ -849,6 +849,115 @@ extern "C" int qcx_shard_pauli_rotation_run(void *amp, unsigned n_local, uint64_
     return launch_status("pauli rotation run");
 }
 
+// ---- K12b / K13b: a run of one- and two-qubit gates in one pass (qcx_gate_batch) ------------------------------------------------
+extern "C" unsigned qcx_gate_batch_width(void) { return QCX_GATE_RUN_W; }
+
+// The passes of qcx_gate_batch (include/qcx_plan.h states the rule): qcx_pauli_rotation_batch_plan's walk with a budget in units
+// instead of a term count, and no wide gate -- two targets never ask for more than two hot bits.  A gate always fits an empty pass.
+extern "C" int qcx_gate_batch_plan(unsigned n, unsigned long ngates, const uint64_t *target_masks, const unsigned *units, unsigned width,
+                                   unsigned long *pass_of_gate, unsigned long *npasses, uint64_t *pass_hot)
+{
+    if (!npasses || width == 0 || n == 0 || n > 40 || (ngates && (!target_masks || !units || !pass_of_gate || !pass_hot))) return QCX_BAD_ARGUMENTS;
+    for (unsigned long k = 0; k < ngates; k++)
+        if (units[k] != 1 && units[k] != 4) return QCX_BAD_ARGUMENTS;
+    for (unsigned long k = 0; k < ngates; k++)
+        if ((target_masks[k] >> n) || (unsigned)__builtin_popcountll(target_masks[k]) != (units[k] == 1 ? 1u : 2u)) return QCX_BAD_QUBIT;
+    const unsigned nhot = std::min(4u, std::max(n, 8u) - 8u);
+    unsigned long np = 0;
+    bool open = false;
+    uint64_t H = 0;
+    unsigned long used = 0;
+    auto close = [&]() {
+        for (unsigned q = 8; q < n && (unsigned)__builtin_popcountll(H) < nhot; q++) H |= (uint64_t)1 << q;
+        pass_hot[np] = H;
+        np++; open = false;
+    };
+    for (unsigned long k = 0; k < ngates; k++) {
+        const uint64_t hx = prot_hx(target_masks[k]);
+        if (open && !(used + units[k] <= width && __builtin_popcountll(H | hx) <= 4)) close();
+        if (!open) { open = true; H = 0; used = 0; }
+        H |= hx; used += units[k];
+        pass_of_gate[k] = np;
+    }
+    if (open) close();
+    *npasses = np;
+    return QCX_NO_ERROR;
+}
+
+// a gate's qubits against n: in range and distinct (the matrix is not looked at)
+static bool gate_qubits_ok(const qcx_gate &g, unsigned n)
+{
+    if (g.qubit0 >= n) return false;
+    if (g.ntargets == 2 && (g.qubit1 >= n || g.qubit1 == g.qubit0)) return false;
+    if (g.control >= 0 && ((unsigned)g.control >= n || (unsigned)g.control == g.qubit0 || (g.ntargets == 2 && (unsigned)g.control == g.qubit1))) return false;
+    return true;
+}
+
+static inline uint64_t gate_targets(const qcx_gate &g)
+{
+    return ((uint64_t)1 << g.qubit0) | (g.ntargets == 2 ? (uint64_t)1 << g.qubit1 : 0);
+}
+
+// One pass, the launch alone: the gates in order over the tile of index bits 0-7 and hot_mask.  hot_mask must be what the plan
+// gives a pass and hold every gate's targets at and above 8 (else QCX_BAD_ARGUMENTS: nothing outside the tile can be reached).
+extern "C" int qcx_shard_gate_run(void *amp, unsigned n_local, uint64_t hot_mask, unsigned ngates, const struct qcx_gate *gates, void *stream)
+{
+    if (!amp || n_local == 0 || n_local > 40 || ngates == 0 || ngates > QCX_GATE_RUN_W || !gates) return QCX_BAD_ARGUMENTS;
+    unsigned units = 0;
+    for (unsigned k = 0; k < ngates; k++) {
+        if (gates[k].ntargets != 1 && gates[k].ntargets != 2) return QCX_BAD_ARGUMENTS;
+        units += gates[k].ntargets == 2 ? 4u : 1u;
+    }
+    if (units > QCX_GATE_RUN_W) { set_error("gate run: %u units are more than the %u of one pass", units, (unsigned)QCX_GATE_RUN_W); return QCX_BAD_ARGUMENTS; }
+    for (unsigned k = 0; k < ngates; k++)
+        if (!gate_qubits_ok(gates[k], n_local)) return QCX_BAD_QUBIT;
+    const unsigned nhot = std::min(4u, std::max(n_local, 8u) - 8u);
+    if ((hot_mask & 0xFF) || (hot_mask >> n_local) || (unsigned)__builtin_popcountll(hot_mask) != nhot) {
+        set_error("gate run: hot mask %#llx is not %u bits of [8, %u)", (unsigned long long)hot_mask, nhot, n_local);
+        return QCX_BAD_ARGUMENTS;
+    }
+    unsigned hpos[4], nh = 0;
+    for (unsigned q = 8; q < n_local; q++)
+        if (hot_mask >> q & 1u) hpos[nh++] = q;
+    for (unsigned q = 8; nh < 4; q++)                               // (n < 12: the tile-local bits that do not exist keep their own place)
+        if (!(hot_mask >> q & 1u)) hpos[nh++] = q;
+    std::sort(hpos, hpos + 4);
+    auto local = [&](unsigned q) -> unsigned {                      // a qubit's tile-local position, 255: not in the tile
+        if (q < 8) return q;
+        for (unsigned b = 0; b < 4; b++)
+            if (hpos[b] == q) return 8u + b;
+        return 255u;
+    };
+    GateRun run = {};
+    bool lds = false;
+    unsigned at = 0;
+    for (unsigned k = 0; k < ngates; k++) {
+        const qcx_gate &g = gates[k];
+        if (prot_hx(gate_targets(g)) & ~hot_mask) {
+            set_error("gate run: gate %u's targets %#llx leave the tile of hot mask %#llx", k, (unsigned long long)gate_targets(g), (unsigned long long)hot_mask);
+            return QCX_BAD_ARGUMENTS;
+        }
+        const bool two = g.ntargets == 2;
+        const unsigned lo = two && g.qubit1 < g.qubit0 ? g.qubit1 : g.qubit0, hi = two ? (g.qubit0 ^ g.qubit1 ^ lo) : 0u;
+        const uint64_t p0 = local(lo), p1 = two ? local(hi) : 0u;   // (the deposit is monotone: lo < hi stays p0 < p1)
+        const uint64_t cloc = g.control >= 0 ? local((unsigned)g.control) : 255u, cfull = g.control >= 0 ? (unsigned)g.control : 255u;
+        run.w[at] = p0 | p1 << 8 | cloc << 16 | cfull << 24 | (uint64_t)g.ntargets << 32;
+        if (two) { const U4Mat U = u4_ascending(g.qubit0, g.qubit1, g.u); memcpy(&run.w[at + 2], U.m, sizeof U.m); }
+        else memcpy(&run.w[at + 2], g.u, 8 * sizeof(double));
+        at += two ? 4u * QCX_GATE_UNIT : QCX_GATE_UNIT;
+        lds = lds || lo < 8;
+    }
+    const bool full = n_local >= 12;
+    const uint64_t nunits = full ? ((uint64_t)1) << (n_local - 12) : 1;
+    const unsigned grid = grid_for(nunits, 1, tune_now().prot_grid_cap, 256);
+    const unsigned hot = hpos[0] | hpos[1] << 8 | hpos[2] << 16 | hpos[3] << 24;
+#define QCX_GATE_RUN(LDS, FULL) hipLaunchKernelGGL((k_gate_run<LDS, FULL>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (amp_t *)amp, nunits, n_local, hot, ngates, run)
+    if (full) { if (lds) QCX_GATE_RUN(true, true); else QCX_GATE_RUN(false, true); }
+    else      { if (lds) QCX_GATE_RUN(true, false); else QCX_GATE_RUN(false, false); }
+#undef QCX_GATE_RUN
+    return launch_status("gate run");
+}
+
 static unsigned gcd_u32(unsigned a, unsigned b) { while (b) { unsigned t = a % b; a = b; b = t; } return a; }
 
 // modular inverse of a mod m (gcd(a, m) == 1, m >= 1); 0 when m == 1
@@ -1456,6 +1565,7 @@ struct qcx_register {
     unsigned   coll_source;     // the last measure_qubits / postselect call: 0 register, 2 basis (no kernel), 3 compact expanded first
     unsigned long coll_reads, coll_writes;   // ... the marginal's reads behind its probabilities, and collapse passes launched (0 or 1)
     unsigned long rotb_passes, rotb_wide;    // the last pauli_rotation_batch call: its passes, and those of them that are one wide term (K15)
+    unsigned long gateb_passes, gateb_lds;   // the last gate_batch call: its passes, and the gates in them that exchanged through LDS (K12b / K13b)
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
 };
 
@@ -2292,6 +2402,67 @@ extern "C" int qcx_rotation_batch_last_stats(qcx_register *r, unsigned long *pas
     if (!r) return QCX_BAD_ARGUMENTS;
     if (passes) *passes = r->rotb_passes;
     if (wide_terms) *wide_terms = r->rotb_wide;
+    return QCX_NO_ERROR;
+}
+
+// A list of one- and two-qubit gates, in order, as the passes of qcx_gate_batch_plan: a run of gates whose targets lie inside one
+// tile is one k_gate_run launch (K12b / K13b).  Every output amplitude is its own row of K12's / K13's arithmetic, so the state is
+// what the loop of the four gate calls leaves; everything else is one_qubit_gate()'s sequence.  A register flagged non-finite
+// runs that loop itself: its controlled gates need the strict kernels, which rewrite the control-clear amplitudes too.
+extern "C" int qcx_gate_batch(qcx_register *r, unsigned long ngates, const qcx_gate *gates)
+{
+    if (!r || (ngates && !gates)) return QCX_BAD_ARGUMENTS;
+    for (unsigned long k = 0; k < ngates; k++)
+        if (gates[k].ntargets != 1 && gates[k].ntargets != 2) { set_error("gate_batch: gate %lu has %u targets (1 or 2)", k, gates[k].ntargets); return QCX_BAD_ARGUMENTS; }
+    for (unsigned long k = 0; k < ngates; k++)
+        for (int c = 0, nc = gates[k].ntargets == 2 ? 32 : 8; c < nc; c++)
+            if (!(fabs(gates[k].u[c]) <= 1.0)) {
+                set_error("gate_batch: gate %lu's matrix component %d is %g (each must be finite with |.| <= 1)", k, c, gates[k].u[c]);
+                return QCX_BAD_ARGUMENTS;
+            }
+    for (unsigned long k = 0; k < ngates; k++)
+        if (!gate_qubits_ok(gates[k], r->n)) {
+            set_error("gate_batch: gate %lu's qubits (control %d, qubit0 %u, qubit1 %u with %u targets) are not distinct qubits of the %u", k,
+                      gates[k].control, gates[k].qubit0, gates[k].qubit1, gates[k].ntargets, r->n);
+            return QCX_BAD_QUBIT;
+        }
+    if (r->sh) { set_error("gate_batch: not available on a sharded register"); return QCX_UNSUPPORTED; }
+    r->gateb_passes = 0; r->gateb_lds = 0;
+    if (ngates == 0) return QCX_NO_ERROR;
+    std::vector<uint64_t> masks(ngates), hot(ngates);
+    std::vector<unsigned> units(ngates);
+    std::vector<unsigned long> pass_of(ngates);
+    for (unsigned long k = 0; k < ngates; k++) { masks[k] = gate_targets(gates[k]); units[k] = gates[k].ntargets == 2 ? 4u : 1u; }
+    unsigned long np = 0;
+    QCX_TRY(qcx_gate_batch_plan(r->n, ngates, masks.data(), units.data(), QCX_GATE_RUN_W, pass_of.data(), &np, hot.data()));
+    QCX_TRY(unqueued_gate(r, "gate_batch", false));
+    if (r->nonfinite) {
+        for (unsigned long k = 0; k < ngates; k++) {
+            const qcx_gate &g = gates[k];
+            if (g.ntargets == 2) QCX_TRY(two_qubit_gate(g.control < 0 ? -1 : g.control, g.qubit0, g.qubit1, g.u, r, "gate_batch"));
+            else QCX_TRY(one_qubit_gate(g.control < 0 ? -1 : g.control, g.qubit0, g.u, r, "gate_batch"));
+            r->gateb_passes++;
+        }
+        return QCX_NO_ERROR;
+    }
+    for (unsigned long k = 0; k < ngates;) {
+        const unsigned long p = pass_of[k];
+        unsigned cnt = 0;
+        while (k + cnt < ngates && pass_of[k + cnt] == p) cnt++;
+        QCX_TRY(qcx_shard_gate_run(r->amp, r->n, hot[p], cnt, gates + k, r->stream));
+        for (unsigned c = 0; c < cnt; c++)
+            if (masks[k + c] & 0xFF) r->gateb_lds++;
+        r->gateb_passes++;
+        k += cnt;
+    }
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_gate_batch_last_stats(qcx_register *r, unsigned long *passes, unsigned long *lds_gates)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (passes) *passes = r->gateb_passes;
+    if (lds_gates) *lds_gates = r->gateb_lds;
     return QCX_NO_ERROR;
 }
 

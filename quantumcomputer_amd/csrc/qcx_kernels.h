@@ -4981,6 +4981,177 @@ __global__ __launch_bounds__(256) void k_prot_run(amp_t *__restrict__ amp, uint6
 }
 
 // ---------------------------------------------------------------------------
+// K12b / K13b  a RUN of K12's and K13's gates in one read and one write of the state (qcx_gate_batch, DESIGN s4.5l): consecutive
+// gates of a list whose targets all lie inside one tile of 2^12 amplitudes, applied in the order given while the tile sits in
+// registers.  Every output amplitude is its own row of the pinned arithmetic (u_row / u4_row: q_row over q_mul, columns in
+// ascending index order), which lane computes a row changes no bit, so the state afterwards is what one launch per gate leaves.
+// Tile, elements and addressing are k_prot_run's: bits 0-7 plus the pass's four hot bits, thread tid holds e = tid + 256 j,
+// j < 16, index base(u) | off(j) | tid.
+// The records travel in the kernel arguments in UNITS of 80 bytes and are read at a uniform running offset (scalar loads, no table
+// in memory, nothing indexed at run time).  A record is a 16-byte header and the matrix: a one-target gate is 1 unit (UMat's 8
+// doubles), a two-target gate 4 units (U4Mat's 32 doubles, already P u P where qubit0 > qubit1: 272 of the 320 bytes used).
+//     header word 0:  p0 | p1 << 8 | cloc << 16 | cfull << 24 | ntargets << 32
+//         p0 (< p1): the targets' tile-local positions (0-7 themselves, 8 + k = hot bit k)
+//         cfull: the control as a bit of the full index, 255 = none; cloc: its tile-local position, 255 = not in the tile
+//   control  an amplitude whose control bit is clear keeps the bits it has.  In the unit's base bits: the gate is skipped for
+//            the whole unit; on a hot bit: skipped by j; in bits 0-7: a per-lane select (every lane still reaches the barriers)
+//   all targets hot   the pair / quad is the thread's own registers: u_butterfly / u4_quad, no LDS, no barrier.  Two targets are
+//            first brought to j's bits 0 and 1 by uniform register swaps (and back afterwards), so one copy of the quad code serves
+//   one target in 0-5 the partner sits in the same wave: an xor-shuffle (k_u_wave's way), no LDS write and no barrier; the row as below
+//   a target in 0-7   (any other) own elements to LDS (64 KiB), barrier, the pair's / quad's members read back in ascending order, the row of
+//            the thread's own element chosen with selects (one target: (u00, u01) or (u10, u11) by its target bit; two: row
+//            lb + 2 hb), a barrier before the next gate's writes
+// LDS = false: every gate of the pass has hot targets only, and the kernel no LDS at all.  FULL as in K15b.
+// ---------------------------------------------------------------------------
+#define QCX_GATE_RUN_W 40                                  /* units in one pass: 3200 of the 4096 bytes of kernel arguments */
+#define QCX_GATE_UNIT 10                                   /* 64-bit words in a unit */
+struct GateRun { uint64_t w[QCX_GATE_RUN_W * QCX_GATE_UNIT]; };
+
+// a[j] <-> a[j with bits BL and BH exchanged], for the j whose two bits differ: a uniform permutation of the thread's registers
+#define QCX_GATE_SWAP(BL, BH)                                                                                   \
+    _Pragma("unroll") for (unsigned j = 0; j < EPT; j++)                                                        \
+        if (((j >> (BL)) & 1u) && !((j >> (BH)) & 1u)) {                                                        \
+            const amp_t v = a[j]; a[j] = a[j ^ (1u << (BL)) ^ (1u << (BH))]; a[j ^ (1u << (BL)) ^ (1u << (BH))] = v; \
+        }
+
+template <bool LDS, bool FULL>
+__global__ __launch_bounds__(256) void k_gate_run(amp_t *__restrict__ amp, uint64_t nunits, unsigned n, unsigned hot, unsigned ngates,
+                                                  GateRun run)
+{
+    constexpr unsigned EPT = 16u;
+    __shared__ amp_t sa[LDS ? 4096 : 1];
+    const unsigned tid = threadIdx.x;
+    const unsigned h0 = hot & 255u, h1 = (hot >> 8) & 255u, h2 = (hot >> 16) & 255u, h3 = hot >> 24;
+    const unsigned nel = FULL ? 4096u : 1u << n;
+    auto off = [&](unsigned j) {
+        return ((uint64_t)(j & 1u) << h0) | ((uint64_t)((j >> 1) & 1u) << h1) | ((uint64_t)((j >> 2) & 1u) << h2) | ((uint64_t)(j >> 3) << h3);
+    };
+    auto mat = [&](unsigned at) { return __longlong_as_double((long long)run.w[at]); };
+    auto pick = [](bool c, amp_t x, amp_t y) { return c ? x : y; };
+    for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
+        const uint64_t base = insert_zero(insert_zero(insert_zero(insert_zero(u << 8, h0), h1), h2), h3);
+        amp_t a[EPT];
+#pragma unroll
+        for (unsigned j = 0; j < EPT; j++)
+            if (FULL || tid + 256u * j < nel) a[j] = __builtin_nontemporal_load(amp + (base | off(j)) + tid);
+            else a[j] = amp_t{0.0, 0.0};                             // (never stored)
+        unsigned at = 0;
+#pragma unroll 1
+        for (unsigned k = 0; k < ngates; k++) {
+            const uint64_t hdr = run.w[at];
+            const unsigned g = at + 2u, nt = (unsigned)(hdr >> 32);
+            at += nt == 2u ? 4u * QCX_GATE_UNIT : QCX_GATE_UNIT;
+            const unsigned p0 = (unsigned)hdr & 255u, p1 = (unsigned)(hdr >> 8) & 255u, cloc = (unsigned)(hdr >> 16) & 255u, cfull = (unsigned)(hdr >> 24) & 255u;
+            if (cfull != 255u && cloc == 255u && !((base >> cfull) & 1u)) continue;      // a control in the base bits, clear: not this unit
+            const unsigned cl = cloc < 8u ? 1u << cloc : 0u;                              // the control among the lane's bits ...
+            unsigned ch = (cloc >= 8u && cloc < 12u) ? 1u << (cloc - 8u) : 0u;            // ... or among j's
+            const bool lane_ok = (tid & cl) == cl;
+            if (nt != 2u) {
+                const UMat U = {mat(g), mat(g + 1), mat(g + 2), mat(g + 3), mat(g + 4), mat(g + 5), mat(g + 6), mat(g + 7)};
+                if (!LDS || p0 >= 8u) {
+#pragma unroll
+                    for (unsigned t = 0; t < 4; t++)
+                        if (p0 == 8u + t) {
+#pragma unroll
+                            for (unsigned j = 0; j < EPT; j++)
+                                if (!((j >> t) & 1u) && (j & ch) == ch) {
+                                    amp_t x = a[j], y = a[j | (1u << t)];
+                                    u_butterfly(U, x, y);
+                                    a[j] = pick(lane_ok, x, a[j]); a[j | (1u << t)] = pick(lane_ok, y, a[j | (1u << t)]);
+                                }
+                        }
+                } else if constexpr (LDS) {
+                    const bool upper = (tid >> p0) & 1u;
+                    const double m0r = upper ? U.r10 : U.r00, m0i = upper ? U.i10 : U.i00;
+                    const double m1r = upper ? U.r11 : U.r01, m1i = upper ? U.i11 : U.i01;
+                    const unsigned bit = 1u << p0;
+                    if (p0 < 6u) {
+                        // the partner sits in the same wave: an xor-shuffle, neither an LDS write nor a barrier (k_u_wave's way).  Every
+                        // lane shuffles, also one past a partial tile: its value is never used
+#pragma unroll
+                        for (unsigned j = 0; j < EPT; j++)
+                            if ((j & ch) == ch) {
+                                const amp_t o = shfl_xor_amp(a[j], (int)bit);
+                                a[j] = pick(lane_ok, u_row(m0r, m0i, m1r, m1i, pick(upper, o, a[j]), pick(upper, a[j], o)), a[j]);
+                            }
+                        continue;
+                    }
+#pragma unroll
+                    for (unsigned j = 0; j < EPT; j++)
+                        if (FULL || tid + 256u * j < nel) sa[tid + 256u * j] = a[j];
+                    __syncthreads();
+#pragma unroll
+                    for (unsigned j = 0; j < EPT; j++)
+                        if ((FULL || tid + 256u * j < nel) && (j & ch) == ch) {
+                            const amp_t o = sa[(tid + 256u * j) ^ bit];
+                            a[j] = pick(lane_ok, u_row(m0r, m0i, m1r, m1i, pick(upper, o, a[j]), pick(upper, a[j], o)), a[j]);
+                        }
+                    __syncthreads();
+                }
+            } else {
+                U4Mat U;
+#pragma unroll
+                for (unsigned c = 0; c < 32; c++) U.m[c] = mat(g + c);
+                if (!LDS || p0 >= 8u) {
+                    const unsigned t0 = p0 - 8u, t1 = p1 - 8u;       // t0 < t1: to j's bits 0 and 1
+                    auto swapbits = [](unsigned v, unsigned x, unsigned y) { const unsigned d = ((v >> x) ^ (v >> y)) & 1u; return v ^ (d << x) ^ (d << y); };
+                    ch = swapbits(swapbits(ch, 0u, t0 & 3u), 1u, t1 & 3u);
+                    if (t0 == 1u) { QCX_GATE_SWAP(0, 1) }
+                    if (t0 == 2u) { QCX_GATE_SWAP(0, 2) }
+                    if (t1 == 2u) { QCX_GATE_SWAP(1, 2) }
+                    if (t1 == 3u) { QCX_GATE_SWAP(1, 3) }
+                    if (t0 < t1 && t1 < 4u) {
+#pragma unroll
+                        for (unsigned j = 0; j < EPT; j += 4)
+                            if ((j & ch) == ch) {
+                                amp_t x0 = a[j], x1 = a[j + 1], x2 = a[j + 2], x3 = a[j + 3];
+                                u4_quad(U, x0, x1, x2, x3);
+                                a[j] = pick(lane_ok, x0, a[j]); a[j + 1] = pick(lane_ok, x1, a[j + 1]);
+                                a[j + 2] = pick(lane_ok, x2, a[j + 2]); a[j + 3] = pick(lane_ok, x3, a[j + 3]);
+                            }
+                    }
+                    if (t1 == 3u) { QCX_GATE_SWAP(1, 3) }
+                    if (t1 == 2u) { QCX_GATE_SWAP(1, 2) }
+                    if (t0 == 2u) { QCX_GATE_SWAP(0, 2) }
+                    if (t0 == 1u) { QCX_GATE_SWAP(0, 1) }
+                } else if constexpr (LDS) {
+                    const bool lb = (tid >> p0) & 1u;
+                    const U4Row R0 = u4_row_sel(U, lb, false), R1 = u4_row_sel(U, lb, true);      // the rows of hb = 0 and of hb = 1
+                    auto row = [&](bool hb) {
+                        return U4Row{hb ? R1.r0 : R0.r0, hb ? R1.i0 : R0.i0, hb ? R1.r1 : R0.r1, hb ? R1.i1 : R0.i1,
+                                     hb ? R1.r2 : R0.r2, hb ? R1.i2 : R0.i2, hb ? R1.r3 : R0.r3, hb ? R1.i3 : R0.i3};
+                    };
+                    const unsigned lob = 1u << p0, hib = 1u << p1;
+#pragma unroll
+                    for (unsigned j = 0; j < EPT; j++)
+                        if (FULL || tid + 256u * j < nel) sa[tid + 256u * j] = a[j];
+                    __syncthreads();
+                    auto quad = [&](const U4Row &R, unsigned j) {
+                        const unsigned e0 = (tid + 256u * j) & ~(lob | hib);
+                        a[j] = pick(lane_ok, u4_row(R, sa[e0], sa[e0 | lob], sa[e0 | hib], sa[e0 | lob | hib]), a[j]);
+                    };
+                    if (p1 < 8u) {                                   // hb is the lane's
+                        const U4Row R = row((tid >> p1) & 1u);
+#pragma unroll
+                        for (unsigned j = 0; j < EPT; j++)
+                            if ((FULL || tid + 256u * j < nel) && (j & ch) == ch) quad(R, j);
+                    } else {                                         // hb is j's: uniform
+#pragma unroll
+                        for (unsigned j = 0; j < EPT; j++)
+                            if ((FULL || tid + 256u * j < nel) && (j & ch) == ch) quad(row((j >> (p1 - 8u)) & 1u), j);
+                    }
+                    __syncthreads();
+                }
+            }
+        }
+#pragma unroll
+        for (unsigned j = 0; j < EPT; j++)
+            if (FULL || tid + 256u * j < nel) __builtin_nontemporal_store(a[j], amp + (base | off(j)) + tid);
+    }
+}
+#undef QCX_GATE_SWAP
+
+// ---------------------------------------------------------------------------
 // K16  the first stage of a qubit range's reduced density matrix (qcx_reduced_density_matrix, DESIGN s4.5j; tests/rdm_ref.py is
 // the definition).  The range is [first, first + NUM), NV = 2^NUM its values; with a = amp[r, v], b = amp[r, w] (r = the bits
 // outside the range, squeezed) the components are ROWS of an NV x NV table of doubles:

@@ -310,6 +310,14 @@ class Register:
         check(lib().qcx_rotation_batch_last_stats(self._h, C.byref(passes), C.byref(wide)), "qcx_rotation_batch_last_stats")
         return passes.value, wide.value
 
+    def gate_batch_stats(self):
+        """(passes, low-target gates) of the last gate_batch call on this register: the passes over the state it ran (the plan's:
+        gate_batch_plan; the number of gates on a register flagged non-finite), and the gates in them with a target on qubits 0-7,
+        which exchange between threads"""
+        passes, lds = C.c_ulong(0), C.c_ulong(0)
+        check(lib().qcx_gate_batch_last_stats(self._h, C.byref(passes), C.byref(lds)), "qcx_gate_batch_last_stats")
+        return passes.value, lds.value
+
     def expectation_matrix(self, first, O):
         """Tr(rho O) as a Python complex, for any 2^num x 2^num matrix O on the qubits [first, first + num) (qubit `first` = bit 0
         of O's index): <psi|O|psi> of an observable that need not be a Pauli string.  rho is reduced_density_matrix(first, num),
@@ -441,6 +449,25 @@ def c_two_qubit_gate(c_qubit_num, qubit0, qubit1, U, reg):
     """two_qubit_gate on the amplitudes whose qubit `c_qubit_num` reads 1 (include/qcx.h: qcx_c_two_qubit_gate)"""
     u = _matrix32(U)
     check(lib().qcx_c_two_qubit_gate(int(c_qubit_num), int(qubit0), int(qubit1), u.ctypes.data_as(C.c_void_p), reg._h), "c_two_qubit_gate")
+
+
+def gate_batch(gates, reg):
+    """Apply gates = [(U, targets) or (U, targets, control), ...] in order -- a circuit layer -- in as few passes over the state as
+    locality allows: bit for bit the state that one_qubit_gate / c_one_qubit_gate / two_qubit_gate / c_two_qubit_gate gate by
+    gate leave (include/qcx.h: qcx_gate_batch).  `targets` is a qubit or a 1- or 2-tuple (qubit0, qubit1); U is 2x2 for one target
+    and 4x4 (or the 32 doubles) for two, as those calls take it.  gate_batch_plan(gates, n) gives the passes and
+    reg.gate_batch_stats() what the last call ran."""
+    gates = list(gates)
+    recs = (_lib.Gate * max(len(gates), 1))()
+    for rec, g in zip(recs, gates):
+        t, c = _lib.gate_targets(g)
+        for q in t + (() if c is None else (c,)):
+            if not 0 <= q < 2 ** 31:
+                raise ValueError(f"{q} is not a qubit")
+        u = _matrix8(g[0]) if len(t) == 1 else _matrix32(g[0])
+        rec.ntargets, rec.control, rec.qubit0, rec.qubit1 = len(t), (-1 if c is None else c), t[0], (t[1] if len(t) == 2 else 0)
+        rec.u[:u.size] = u.tolist()
+    check(lib().qcx_gate_batch(reg._h, len(gates), C.cast(recs, C.c_void_p) if gates else None), "gate_batch")
 
 
 def pauli_rotation(pauli, theta, reg):
