@@ -84,7 +84,7 @@ int  qcx_M_size(const qcx_register *reg);
  * M_size > 12 works like on one GPU (the modular multiply then runs in place through a per-device staging buffer instead of
  * LDS tiles; M_size <= 26).  Not available on a sharded register: qcx_register_set_stream, qcx_device_pointer (NULL),
  * the event pool, qcx_one_qubit_gate / qcx_c_one_qubit_gate, qcx_two_qubit_gate / qcx_c_two_qubit_gate,
- * qcx_pauli_rotation, qcx_pauli_rotation_batch, qcx_gate_batch (QCX_UNSUPPORTED). */
+ * qcx_mc_one_qubit_gate / qcx_mc_two_qubit_gate, qcx_pauli_rotation, qcx_pauli_rotation_batch, qcx_gate_batch (QCX_UNSUPPORTED). */
 int  qcx_register_create_sharded(int L_size, int M_size, unsigned nshards, const int *devices, qcx_register **out);
 int  qcx_spread_devices(unsigned nshards, int visible_devices /* <= 0: ask HIP */, int *devices_out /* [nshards] */);
 int  qcx_sharded_selfcheck(qcx_register *reg);             /* the pre-flight exchange check on demand */
@@ -160,6 +160,30 @@ int  qcx_c_one_qubit_gate(unsigned c_qubit_num, unsigned qubit_num, const double
  * name distinct qubits); a sharded register: QCX_UNSUPPORTED, nothing touched. */
 int  qcx_two_qubit_gate(unsigned qubit0, unsigned qubit1, const double *u, qcx_register *reg);
 int  qcx_c_two_qubit_gate(unsigned c_qubit_num, unsigned qubit0, unsigned qubit1, const double *u, qcx_register *reg);
+/* A one- or two-qubit gate under any set of control qubits, of either polarity (no reference counterpart; tests/mc_gate_ref.py
+ * restates it in numpy and IS the definition; K17, DESIGN s4.5m).
+ *   ctrl_mask = the set of control qubits, ctrl_values (a subset of ctrl_mask) = the value each control must have: a set bit is
+ *   an ordinary control, a clear bit a negative one (the gate fires where that qubit reads 0).
+ *   The gate acts on the pairs (quads) whose index satisfies (i & ctrl_mask) == ctrl_values, and there it is, operation for
+ *   operation, qcx_one_qubit_gate's (qcx_two_qubit_gate's) arithmetic: the same u layout, the same P u P rule for
+ *   qubit0 > qubit1, every fl() one binary64 rounding, no FMA, exact zeros multiplied out.  Every other amplitude takes the
+ *   reference's identity row, exactly as for qcx_c_one_qubit_gate -- on a finite state without -0 the value unchanged, so those
+ *   amplitudes are not touched (with k controls at bit >= 3 only 2^-k of the state is read); a register flagged non-finite has
+ *   them rewritten by a strict pass.  A Toffoli is X under two controls, a Fredkin SWAP under one, a Grover oracle Z under n - 1.
+ *   So, bit for bit: ctrl_mask == 0 gives the plain gates; a mask of one bit, set in ctrl_values, gives qcx_c_one_qubit_gate /
+ *   qcx_c_two_qubit_gate; diag(1, qcx_polar(theta)) under one positive control gives qcx_c_phase_shift_gate; and
+ *   (ctrl_mask, qubit0, qubit1, V) gives the bits of (ctrl_mask, qubit1, qubit0, P V P).
+ * Everything else is qcx_one_qubit_gate's contract: the matrix is applied as given; asynchronous, on the register's stream; in
+ * every fusion mode the call flushes what is pending and launches its own kernel, never enters the queue, is not counted by
+ * qcx_fusion_stats, stays exact in mode 2; a -0 the caller wrote is canonicalised first.  ctrl_mask == 0 and one positive
+ * control ARE the calls above (the same kernels and launches) unless the knob mc_generic is 1.  qcx_mc_gate_plan in qcx_plan.h
+ * is the launch rule on its own.
+ * Checked in this order, before anything runs and with nothing touched: NULL reg or u: QCX_BAD_ARGUMENTS; a matrix component
+ * that is not finite or above 1 in absolute value: QCX_BAD_ARGUMENTS (the message names it); ctrl_values & ~ctrl_mask != 0:
+ * QCX_BAD_ARGUMENTS; a target >= n, two targets equal, a mask bit at or above n or on a target: QCX_BAD_QUBIT; a sharded
+ * register: QCX_UNSUPPORTED. */
+int  qcx_mc_one_qubit_gate(uint64_t ctrl_mask, uint64_t ctrl_values, unsigned qubit_num, const double *u, qcx_register *reg);
+int  qcx_mc_two_qubit_gate(uint64_t ctrl_mask, uint64_t ctrl_values, unsigned qubit0, unsigned qubit1, const double *u, qcx_register *reg);
 /* The rotation about a Pauli string, exp(-i theta/2 P) = cos(theta/2) I - i sin(theta/2) P, in ONE read and one write of the
  * state for any string (no reference counterpart; the matrix applied as the reference's mat-vec applies every gate, Q:393-413;
  * tests/pauli_rotation_ref.py restates it in numpy and IS the definition).  The string is qcx_pauli_expectation's pair of masks:

@@ -177,6 +177,45 @@ typedef struct {
     uint64_t scratch;           /* doubles of all non-final outputs */
 } qcx_rdm_stage0;
 int  qcx_rdm_plan(unsigned n, unsigned first, unsigned num, qcx_rdm_stage0 *stage0, qcx_marginal_stage *stages, unsigned *n_stages);
+
+/* The launch of qcx_mc_one_qubit_gate / qcx_mc_two_qubit_gate (include/qcx.h; K17, DESIGN s4.5m) on a register of n qubits, on the
+ * host, under the knobs of the moment; the library launches from this very function.  ntargets = 1 (qubit1 ignored) or 2.
+ * Work item p of `count` stands for the index
+ *     i(p) = deposit(p) | or_const,
+ * deposit = p's bits moved, in order, into the positions outside the squeezed runs [run_pos[k], run_pos[k] + run_len[k]),
+ * k < nruns, ascending; squeezed are the controls at bit >= 3 (or_const = those of them that are positive) and the targets
+ * that live in registers, so count = 2^(n - squeezed positions).  A lane acts when (i & low_mask) == low_values (controls below
+ * bit 3); with store_all the lanes that do not act store the bits they read (whole lines go back).  Forms:
+ *   QCX_MC_PAIR       one target, squeezed; a lane owns the pair (i, i | 2^q).  Target >= 3 and no control below 3
+ *   QCX_MC_LINE_PAIR  the same with a predicate: a control below 3, target >= 3
+ *   QCX_MC_LINE_SHFL  one target below 3, not squeezed: a lane owns i, the partner comes by xor-shuffle
+ *   QCX_MC_QUAD       two targets, both squeezed; a lane owns the quad
+ *   QCX_MC_LINES2     lo or a control below 3: ns = 2, 1 or 0 of the targets sit below bit 6 of the lane numbering and are
+ *                     shuffled (xor masks shfl_lo, shfl_hi), the others are squeezed; ns = 0 is the quad with a predicate
+ * The shuffle forms need whole waves: with count < 64, n < 9, or the knob ph_lines = 0 (two targets: also u2_variant = 1) the
+ * call takes QCX_MC_PAIR / QCX_MC_QUAD with EVERY control squeezed (low_mask = 0), which is correct for any bit positions.
+ * One work item per thread, block = 64 (one wave), grid = ceil(count / 64) capped where HIP caps it (the kernels stride);
+ * glog / slog: the stream-interleaved tile order.  nt: nontemporal accesses -- no squeezed position below 3 and the knob on:
+ * ph_nt for one target, u2_nt for two, the knobs K12 and K13 read.
+ * NULL out, ntargets not 1 or 2, n = 0 or n > 40, ctrl_values outside ctrl_mask: QCX_BAD_ARGUMENTS; a target >= n, equal targets,
+ * a mask bit at or above n or on a target: QCX_BAD_QUBIT; more than QCX_MC_MAX_RUNS runs (n > 34 only): QCX_UNSUPPORTED. */
+#define QCX_MC_MAX_RUNS 17
+enum { QCX_MC_PAIR = 0, QCX_MC_LINE_PAIR = 1, QCX_MC_LINE_SHFL = 2, QCX_MC_QUAD = 3, QCX_MC_LINES2 = 4 };
+typedef struct {
+    unsigned form, ns;              /* ns: QCX_MC_LINES2 only */
+    uint64_t count;
+    unsigned nruns;
+    unsigned char run_pos[QCX_MC_MAX_RUNS], run_len[QCX_MC_MAX_RUNS];
+    uint64_t or_const;
+    unsigned low_mask, low_values, store_all;
+    unsigned shfl_lo, shfl_hi;
+    unsigned nt;
+    unsigned grid, block, items_per_thread;
+    unsigned glog, slog;
+    char     kernel[48];            /* the instantiation as a kernel trace spells it, e.g. "k_mcu2_lines<1, true>" */
+} qcx_mc_plan;
+int  qcx_mc_gate_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, unsigned ntargets, unsigned qubit0, unsigned qubit1,
+                      qcx_mc_plan *out);
 #ifdef __cplusplus
 }
 #endif

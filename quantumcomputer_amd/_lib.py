@@ -54,6 +54,8 @@ SIGNATURES = {
     "qcx_c_one_qubit_gate": (_i, [_u, _u, _p, _p]),
     "qcx_two_qubit_gate": (_i, [_u, _u, _p, _p]),
     "qcx_c_two_qubit_gate": (_i, [_u, _u, _u, _p, _p]),
+    "qcx_mc_one_qubit_gate": (_i, [_u64, _u64, _u, _p, _p]),
+    "qcx_mc_two_qubit_gate": (_i, [_u64, _u64, _u, _u, _p, _p]),
     "qcx_pauli_rotation": (_i, [_u64, _u64, _d, _p]),
     "qcx_pauli_rotation_batch": (_i, [_p, _ul, _p, _p, _p]),
     "qcx_pauli_rotation_batch_width": (_u, []),
@@ -92,6 +94,7 @@ SIGNATURES = {
     "qcx_rdm_max_qubits": (_u, []),
     "qcx_rdm_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
     "qcx_rdm_plan": (_i, [_u, _u, _u, _p, _p, C.POINTER(_u)]),
+    "qcx_mc_gate_plan": (_i, [_u, _u64, _u64, _u, _u, _u, _p]),
     "qcx_marginal_plan": (_i, [_u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_marginal_plan_compact": (_i, [_u, _u, _u, _u, _p, C.POINTER(_u)]),
     "qcx_state_read": (_i, [_p, _ul, _ul, _p]),
@@ -260,6 +263,27 @@ def rdm_plan(n, first, num):
     ns = C.c_uint(0)
     check(lib().qcx_rdm_plan(n, first, num, C.byref(s0), C.cast(arr, C.c_void_p), C.byref(ns)), "qcx_rdm_plan")
     return s0, [arr[i] for i in range(ns.value)]
+
+
+MC_MAX_RUNS = 17            # QCX_MC_MAX_RUNS (include/qcx_plan.h)
+MC_PAIR, MC_LINE_PAIR, MC_LINE_SHFL, MC_QUAD, MC_LINES2 = range(5)
+
+
+class McPlan(C.Structure):
+    """qcx_mc_plan (include/qcx_plan.h): the launch of a gate under a control mask"""
+    _fields_ = [("form", _u), ("ns", _u), ("count", _u64), ("nruns", _u), ("run_pos", C.c_ubyte * MC_MAX_RUNS),
+                ("run_len", C.c_ubyte * MC_MAX_RUNS), ("or_const", _u64), ("low_mask", _u), ("low_values", _u), ("store_all", _u),
+                ("shfl_lo", _u), ("shfl_hi", _u), ("nt", _u), ("grid", _u), ("block", _u), ("items_per_thread", _u),
+                ("glog", _u), ("slog", _u), ("kernel", C.c_char * 48)]
+
+
+def mc_gate_plan(n, ctrl_mask, ctrl_values, targets):
+    """What mc_one_qubit_gate / mc_two_qubit_gate would launch on n qubits under the knobs of the moment (host code, no GPU
+    needed; include/qcx_plan.h: qcx_mc_gate_plan): (status, McPlan).  targets: a 1- or 2-tuple (qubit0[, qubit1])."""
+    t = tuple(int(q) for q in targets)
+    pl = McPlan()
+    st = lib().qcx_mc_gate_plan(int(n), int(ctrl_mask), int(ctrl_values), len(t), t[0], t[1] if len(t) > 1 else 0, C.byref(pl))
+    return st, pl
 
 
 def pauli_batch_width():

@@ -169,7 +169,8 @@ extern "C" int qcx_set_device(int device) { HIP_TRY(hipSetDevice(device)); retur
     X(u2_nt, 1)                   /* K13: nontemporal accesses (only where a wave instruction covers whole 128-B lines, as in K12) */ \
     X(u2_streams_log2, -1)        /* K13: -1 = plain gate: the Hadamard plan's streams for hi; controlled: the phase gate's rule.  Both are guesses taken */ \
                                   /* over from kernels with two address streams, not four; tools/time_two_qubit_gate.py is there to measure them */ \
-    X(prot_grid_cap, 2048)        /* K15 (k_pauli_rot): workgroups, each walks its units (tiles, or pairs of tiles) with this stride; 0 = one unit each */
+    X(prot_grid_cap, 2048)        /* K15 (k_pauli_rot): workgroups, each walks its units (tiles, or pairs of tiles) with this stride; 0 = one unit each */ \
+    X(mc_generic, 0)              /* K17 (gates under a control mask): 1 = no control and one positive control run K17's kernels too (0: K12's / K13's launches; the tests compare the two bit for bit) */
 struct Tune {
 #define X(name, value) long name = value;
     QCX_TUNABLES(X)
@@ -707,6 +708,110 @@ extern "C" int qcx_shard_two_qubit(void *amp, unsigned n_local, unsigned q0, uns
         else         { if (ntq) launch_u2_quad<true, true>(a, lo, hi, c, U, namps >> 3, want, st);  else launch_u2_quad<false, true>(a, lo, hi, c, U, namps >> 3, want, st); }
     }
     return launch_status("two-qubit gate");
+}
+
+// ---- K17: a one- or two-qubit gate under a control mask (include/qcx_plan.h states the rule, DESIGN s4.5m) ------------------------
+// The ONE place that decides the form, the numbering and the launch geometry; mc_launch() below launches what it returns.
+static int mc_gate_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q0, unsigned q1, qcx_mc_plan *out)
+{
+    if (!out || (ntargets != 1 && ntargets != 2) || n == 0 || n > 40) return QCX_BAD_ARGUMENTS;
+    if (cvals & ~cmask) { set_error("mc gate: ctrl_values %#llx has bits outside ctrl_mask %#llx", (unsigned long long)cvals, (unsigned long long)cmask); return QCX_BAD_ARGUMENTS; }
+    if (q0 >= n || (ntargets == 2 && (q1 >= n || q1 == q0))) return QCX_BAD_QUBIT;
+    const uint64_t tmask = ((uint64_t)1 << q0) | (ntargets == 2 ? (uint64_t)1 << q1 : 0);
+    if ((cmask >> n) != 0 || (cmask & tmask) != 0) return QCX_BAD_QUBIT;
+    memset(out, 0, sizeof *out);
+    const unsigned lo = ntargets == 2 && q1 < q0 ? q1 : q0, hi = ntargets == 2 ? (q0 < q1 ? q1 : q0) : q0;
+    const uint64_t high = cmask & ~(uint64_t)7;
+    const unsigned low = (unsigned)cmask & 7u;
+    // the forms that keep whole lines: a target or a control inside a 128-B line, registers of 2^9 amplitudes or more
+    bool lines = (lo < 3 || low != 0) && n >= 9 && t.ph_lines != 0 && (ntargets == 1 || t.u2_variant == 0);
+    uint64_t squeezed = 0;
+    unsigned form = 0, ns = 0, plo = 0, phi = 0;
+    if (lines) {
+        squeezed = high;
+        if (ntargets == 1) {
+            if (lo >= 3) squeezed |= tmask;
+            form = lo < 3 ? QCX_MC_LINE_SHFL : QCX_MC_LINE_PAIR;
+        } else {
+            // where each target sits in the lane numbering once the high controls are squeezed out (lo in registers puts hi there too)
+            plo = lo - (unsigned)__builtin_popcountll(high & (((uint64_t)1 << lo) - 1));
+            phi = hi - (unsigned)__builtin_popcountll(high & (((uint64_t)1 << hi) - 1));
+            if (plo >= 6) squeezed |= (uint64_t)1 << lo;
+            if (phi >= 6) squeezed |= (uint64_t)1 << hi;
+            ns = (plo < 6 ? 1u : 0u) + (phi < 6 ? 1u : 0u);
+            form = QCX_MC_LINES2;
+        }
+        // the shuffle forms need whole waves: below 64 work items the pair / quad form (its traffic is irrelevant at that size)
+        if ((n - (unsigned)__builtin_popcountll(squeezed)) < 6) lines = false;
+    }
+    if (!lines) {
+        squeezed = cmask | tmask;
+        form = ntargets == 1 ? QCX_MC_PAIR : QCX_MC_QUAD;
+        ns = 0;
+    }
+    out->form = form; out->ns = ns;
+    out->count = (uint64_t)1 << (n - (unsigned)__builtin_popcountll(squeezed));
+    for (unsigned b = 0; b < n;) {
+        if (!((squeezed >> b) & 1u)) { b++; continue; }
+        unsigned len = 1;
+        while (b + len < n && ((squeezed >> (b + len)) & 1u)) len++;
+        if (out->nruns == QCX_MC_MAX_RUNS) { set_error("mc gate: more than %d runs of squeezed positions", QCX_MC_MAX_RUNS); return QCX_UNSUPPORTED; }
+        out->run_pos[out->nruns] = (unsigned char)b; out->run_len[out->nruns] = (unsigned char)len; out->nruns++;
+        b += len;
+    }
+    out->or_const = cvals & squeezed;
+    if (lines) { out->low_mask = low; out->low_values = (unsigned)cvals & 7u; out->store_all = (low & 3u) ? 1 : 0; }
+    if (form == QCX_MC_LINES2 && ns >= 1) out->shfl_lo = 1u << plo;
+    if (form == QCX_MC_LINES2 && ns == 2) out->shfl_hi = 1u << phi;
+    // nontemporal only where a wave instruction covers whole 128-B lines
+    out->nt = ((ntargets == 1 ? t.ph_nt : t.u2_nt) != 0 && (squeezed & 7u) == 0) ? 1 : 0;      // (K12's knob, K13's knob)
+    out->block = 64; out->items_per_thread = 1;
+    out->grid = grid_for(out->count, 64, 0, 64);
+    long want = ntargets == 1 ? t.ph_streams_log2 : t.u2_streams_log2;
+    if (want < 0) want = (squeezed & 255u) == 0 ? 1 : 2;             // the phase gate's rule: 1 when the lowest squeezed bit is >= 8
+    stream_map(out->grid, (uint64_t)out->grid * 64, out->count, want, &out->glog, &out->slog);
+    const char *b = out->nt ? "true" : "false";
+    if (form == QCX_MC_LINE_SHFL) snprintf(out->kernel, sizeof out->kernel, "k_mcu_shfl<%s>", b);
+    else if (ntargets == 1)       snprintf(out->kernel, sizeof out->kernel, "k_mcu_pair<%s>", b);
+    else if (ns == 0)             snprintf(out->kernel, sizeof out->kernel, "k_mcu2_quad<%s>", b);
+    else                          snprintf(out->kernel, sizeof out->kernel, "k_mcu2_lines<%u, %s>", ns, b);
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_mc_gate_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, unsigned ntargets, unsigned qubit0, unsigned qubit1,
+                                qcx_mc_plan *out)
+{
+    return mc_gate_plan(tune_now(), n, ctrl_mask, ctrl_values, ntargets, qubit0, qubit1, out);
+}
+
+// launches what the plan says (u: the caller's 8 or 32 doubles)
+static int mc_launch(amp_t *a, unsigned n, uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q0, unsigned q1, const double *u, hipStream_t st)
+{
+    qcx_mc_plan pl;
+    QCX_TRY(mc_gate_plan(tune_now(), n, cmask, cvals, ntargets, q0, q1, &pl));
+    static_assert(MC_MAP_RUNS == QCX_MC_MAX_RUNS, "McMap holds the runs of a qcx_mc_plan");
+    McMap M; memset(&M, 0, sizeof M);
+    M.nruns = pl.nruns; M.orc = pl.or_const;
+    for (unsigned k = 0; k < pl.nruns; k++) M.run[k] = (uint32_t)pl.run_pos[k] | ((uint32_t)pl.run_len[k] << 8);
+    const dim3 grid(pl.grid), block(pl.block);
+    const int sa = (int)pl.store_all;
+    if (ntargets == 1) {
+        const UMat U = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]};
+#define QCX_MC1(K) do { if (pl.nt) hipLaunchKernelGGL((K<true>), grid, block, 0, st, a, q0, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog); \
+                        else       hipLaunchKernelGGL((K<false>), grid, block, 0, st, a, q0, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog); } while (0)
+        if (pl.form == QCX_MC_LINE_SHFL) QCX_MC1(k_mcu_shfl); else QCX_MC1(k_mcu_pair);
+#undef QCX_MC1
+    } else {
+        const U4Mat U = u4_ascending(q0, q1, u);
+        const unsigned lo = q0 < q1 ? q0 : q1, hi = q0 < q1 ? q1 : q0;
+#define QCX_MC2(NS, NT) hipLaunchKernelGGL((k_mcu2_lines<NS, NT>), grid, block, 0, st, a, lo, hi, pl.shfl_lo, pl.shfl_hi, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog)
+        if (pl.form == QCX_MC_LINES2 && pl.ns == 2)      { if (pl.nt) QCX_MC2(2, true); else QCX_MC2(2, false); }
+        else if (pl.form == QCX_MC_LINES2 && pl.ns == 1) { if (pl.nt) QCX_MC2(1, true); else QCX_MC2(1, false); }
+        else if (pl.nt) hipLaunchKernelGGL((k_mcu2_quad<true>), grid, block, 0, st, a, lo, hi, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog);
+        else            hipLaunchKernelGGL((k_mcu2_quad<false>), grid, block, 0, st, a, lo, hi, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog);
+#undef QCX_MC2
+    }
+    return launch_status("mc gate");
 }
 
 // ---- K14 / K15: the units of work of a Pauli string (PauliTiles in qcx_kernels.h) ------------------------------------------------
@@ -2341,6 +2446,46 @@ extern "C" int qcx_c_two_qubit_gate(unsigned c, unsigned q0, unsigned q1, const 
 {
     if (r && c >= r->n) return QCX_BAD_QUBIT;         // (before the cast: a control >= 2^31 is a bad qubit, not "no control")
     return two_qubit_gate((int)c, q0, q1, u, r, "c_two_qubit_gate");
+}
+
+// A one- or two-qubit gate under a control mask (K17).  one_qubit_gate()'s sequence behind the checks of include/qcx.h, in their
+// order.  No control and one positive control ARE the calls above -- the same kernels and launches -- unless mc_generic is set.
+static int mc_gate(uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q0, unsigned q1, const double *u, qcx_register *r, const char *who)
+{
+    if (!r || !u) return QCX_BAD_ARGUMENTS;
+    QCX_TRY(check_matrix(who, u, ntargets == 1 ? 8 : 32));
+    if (cvals & ~cmask) { set_error("%s: ctrl_values %#llx has bits outside ctrl_mask %#llx", who, (unsigned long long)cvals, (unsigned long long)cmask); return QCX_BAD_ARGUMENTS; }
+    if (q0 >= r->n || (ntargets == 2 && (q1 >= r->n || q1 == q0))) return QCX_BAD_QUBIT;
+    const uint64_t tmask = ((uint64_t)1 << q0) | (ntargets == 2 ? (uint64_t)1 << q1 : 0);
+    if ((r->n < 64 && (cmask >> r->n) != 0) || (cmask & tmask) != 0) return QCX_BAD_QUBIT;
+    if (tune_now().mc_generic == 0 && (cmask == 0 || (cmask == cvals && (cmask & (cmask - 1)) == 0))) {
+        const int ctl = cmask ? (int)__builtin_ctzll(cmask) : -1;
+        return ntargets == 1 ? one_qubit_gate(ctl, q0, u, r, who) : two_qubit_gate(ctl, q0, q1, u, r, who);
+    }
+    QCX_TRY(unqueued_gate(r, who, false));
+    if (r->nonfinite) {
+        if (ntargets == 1) {
+            const UMat U = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]};
+            hipLaunchKernelGGL(k_strict_mcu, dim3(grid_for(r->dim >> 1, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, q0, cmask, cvals, U, 1.0, 0.0);
+        } else {
+            const U4Mat U = u4_ascending(q0, q1, u);
+            const unsigned lo = q0 < q1 ? q0 : q1, hi = q0 < q1 ? q1 : q0;
+            hipLaunchKernelGGL(k_strict_mcu2, dim3(grid_for(r->dim >> 2, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, lo, hi, cmask, cvals, U, 1.0, 0.0);
+        }
+        HIP_TRY(hipGetLastError());
+        return QCX_NO_ERROR;
+    }
+    return mc_launch(r->amp, r->n, cmask, cvals, ntargets, q0, q1, u, r->stream);
+}
+
+extern "C" int qcx_mc_one_qubit_gate(uint64_t ctrl_mask, uint64_t ctrl_values, unsigned q, const double *u, qcx_register *r)
+{
+    return mc_gate(ctrl_mask, ctrl_values, 1, q, 0, u, r, "mc_one_qubit_gate");
+}
+
+extern "C" int qcx_mc_two_qubit_gate(uint64_t ctrl_mask, uint64_t ctrl_values, unsigned q0, unsigned q1, const double *u, qcx_register *r)
+{
+    return mc_gate(ctrl_mask, ctrl_values, 2, q0, q1, u, r, "mc_two_qubit_gate");
 }
 
 // exp(-i theta/2 P) of the Pauli string (x_mask, z_mask).  one_qubit_gate()'s sequence: never queued, in any fusion mode; the

@@ -4734,6 +4734,158 @@ __global__ __launch_bounds__(256) void k_strict_cu2(amp_t *__restrict__ amp, uns
 }
 
 // ---------------------------------------------------------------------------
+// K17  a one- or two-qubit gate under any set of controls of either polarity (qcx_mc_one_qubit_gate / qcx_mc_two_qubit_gate,
+// DESIGN s4.5m): K12's and K13's rows on the pairs / quads whose index satisfies (i & ctrl_mask) == ctrl_values, nothing else
+// read.  The forms are K12a / K12c / K13a / K13b's with two generalisations, both decided on the host (qcx_mc_gate_plan):
+//   the numbering.  Every control at bit >= 3 and every target that lives in registers is squeezed out of the work numbering:
+//       index(p) = deposit(p) | orc,
+//       deposit = p's bits moved, in order, into the positions that are NOT squeezed; the squeezed positions come as ascending
+//       runs (position, length) in McMap, a by-value kernel argument -- no table in memory, nothing allocated; orc = the bits
+//       of the positive squeezed controls.  A deposit is bit-wise: deposit(base + lane) = deposit(base) | deposit(lane) for a
+//       tile base that is a multiple of 64, so the lane's part is formed once per kernel and the tile's part is wave-uniform
+//       (scalar) work; the loop over the runs has the same trip count in every lane.
+//   the predicate.  Controls below bit 3 leave every line touched: a lane hits when (i & lmask) == lvals (K12c / K13b's clow
+//       test with a mask and values); bits 0-2 of an index are the lane's, so the test is formed once per kernel too.  Lanes
+//       that miss keep their bits and, with store_all (a control at 16- or 32-B granularity), whole lines are stored back.
+// A workgroup is one wave, a tile 64 work items; stream-interleaved tile order as in k_phase.  The shuffle forms are launched
+// with a work count that is a multiple of 64 only (the host's rule), so no wave diverges around a shuffle.
+// ---------------------------------------------------------------------------
+constexpr unsigned MC_MAP_RUNS = 17;                       // QCX_MC_MAX_RUNS of include/qcx_plan.h (the host asserts that they agree)
+struct McMap { uint32_t run[MC_MAP_RUNS]; uint32_t nruns; uint64_t orc; };      // run = position | length << 8, ascending
+
+__device__ __forceinline__ uint64_t mc_deposit(const McMap &M, uint64_t p)
+{
+    uint64_t i = p;
+    for (unsigned k = 0; k < M.nruns; k++) {
+        const unsigned pos = M.run[k] & 255u, len = M.run[k] >> 8;
+        const uint64_t low = ((uint64_t)1 << pos) - 1;
+        i = ((i & ~low) << len) | (i & low);
+    }
+    return i;
+}
+
+// K17a  one target, the pair in two registers of a lane (K12a's shape; with lmask != 0 K12c's !LOWQ case).  The target is
+// squeezed out: count pairs.  Correct for any bit positions (the small-count fallback squeezes every control, lmask = 0).
+template <bool NT>
+__global__ __launch_bounds__(64) void k_mcu_pair(amp_t *__restrict__ amp, unsigned q, McMap M, unsigned lmask, unsigned lvals, int store_all,
+                                                 UMat U, uint64_t count, unsigned glog, unsigned slog)
+{
+    const uint64_t bit = (uint64_t)1 << q, step = (uint64_t)gridDim.x * 64u;
+    const uint64_t lane_i = mc_deposit(M, threadIdx.x) | M.orc;
+    const bool hit = ((unsigned)lane_i & lmask) == lvals;
+    for (uint64_t base = stream_tile(glog, slog) * 64u; base < count; base += step) {
+        if (base + threadIdx.x < count) {
+            const uint64_t i0 = mc_deposit(M, base) | lane_i;
+            amp_t a = ld<NT>(amp + i0), b = ld<NT>(amp + i0 + bit);
+            if (hit) u_butterfly(U, a, b);
+            if (hit || store_all) { st<NT>(amp + i0, a); st<NT>(amp + i0 + bit, b); }
+        }
+    }
+}
+
+// K17b  one target below bit 3: a lane owns one amplitude of every touched line, the partner arrives by xor-shuffle and every
+// lane computes its own row (K12c's LOWQ case).  count is a multiple of 64.
+template <bool NT>
+__global__ __launch_bounds__(64) void k_mcu_shfl(amp_t *__restrict__ amp, unsigned q, McMap M, unsigned lmask, unsigned lvals, int store_all,
+                                                 UMat U, uint64_t count, unsigned glog, unsigned slog)
+{
+    const uint64_t step = (uint64_t)gridDim.x * 64u;
+    const uint64_t lane_i = mc_deposit(M, threadIdx.x) | M.orc;      // (bits below 3 keep their place: lane ^ 2^q holds the partner)
+    const bool hit = ((unsigned)lane_i & lmask) == lvals, upper = (lane_i >> q) & 1u;
+    const double m0r = upper ? U.r10 : U.r00, m0i = upper ? U.i10 : U.i00, m1r = upper ? U.r11 : U.r01, m1i = upper ? U.i11 : U.i01;
+    for (uint64_t base = stream_tile(glog, slog) * 64u; base < count; base += step) {
+        const uint64_t i = mc_deposit(M, base) | lane_i;
+        const amp_t v = ld<NT>(amp + i);
+        const amp_t o = shfl_xor_amp(v, 1 << q);
+        if (hit) st<NT>(amp + i, u_row(m0r, m0i, m1r, m1i, upper ? o : v, upper ? v : o));
+        else if (store_all) st<NT>(amp + i, v);
+    }
+}
+
+// K17c  two targets, the quad in four registers of a lane (K13a's shape; with lmask != 0 K13b's NS = 0).  Both targets are
+// squeezed out: count quads.  Correct for any bit positions (the small-count fallback squeezes every control, lmask = 0).
+template <bool NT>
+__global__ __launch_bounds__(64) void k_mcu2_quad(amp_t *__restrict__ amp, unsigned lo, unsigned hi, McMap M, unsigned lmask, unsigned lvals,
+                                                  int store_all, U4Mat U, uint64_t count, unsigned glog, unsigned slog)
+{
+    const uint64_t lob = (uint64_t)1 << lo, hib = (uint64_t)1 << hi, step = (uint64_t)gridDim.x * 64u;
+    const uint64_t lane_i = mc_deposit(M, threadIdx.x) | M.orc;
+    const bool hit = ((unsigned)lane_i & lmask) == lvals;
+    for (uint64_t base = stream_tile(glog, slog) * 64u; base < count; base += step) {
+        if (base + threadIdx.x < count) {
+            const uint64_t i = mc_deposit(M, base) | lane_i;
+            amp_t x0 = ld<NT>(amp + i), x1 = ld<NT>(amp + (i | lob)), x2 = ld<NT>(amp + (i | hib)), x3 = ld<NT>(amp + (i | lob | hib));
+            if (hit) u4_quad(U, x0, x1, x2, x3);
+            if (hit || store_all) { st<NT>(amp + i, x0); st<NT>(amp + (i | lob), x1); st<NT>(amp + (i | hib), x2); st<NT>(amp + (i | lob | hib), x3); }
+        }
+    }
+}
+
+// K17d  two targets, line forms (K13b's NS = 2 and NS = 1): NS targets sit below bit 6 of the LANE numbering and reach the lane
+// by xor-shuffle (mlo, mhi: the shuffle masks in lane numbering -- squeezing controls in 3 .. 5 moves the targets above them
+// down); the other target, if any, is squeezed out and lives in a second register.  The lane's own row comes from the bits of
+// its INDEX, the four amplitudes are fed in ascending index order.  count is a multiple of 64.
+template <int NS, bool NT>
+__global__ __launch_bounds__(64) void k_mcu2_lines(amp_t *__restrict__ amp, unsigned lo, unsigned hi, unsigned mlo, unsigned mhi, McMap M,
+                                                   unsigned lmask, unsigned lvals, int store_all, U4Mat U, uint64_t count, unsigned glog, unsigned slog)
+{
+    const uint64_t lob = (uint64_t)1 << lo, hib = (uint64_t)1 << hi, step = (uint64_t)gridDim.x * 64u;
+    const uint64_t lane_i = mc_deposit(M, threadIdx.x) | M.orc;      // (a target that is shuffled is a lane bit: its index bit is the lane's)
+    const bool hit = ((unsigned)lane_i & lmask) == lvals, lb = (lane_i & lob) != 0, hb = NS == 2 && (lane_i & hib) != 0;
+    for (uint64_t base = stream_tile(glog, slog) * 64u; base < count; base += step) {
+        const uint64_t i = mc_deposit(M, base) | lane_i;
+        if constexpr (NS == 2) {
+            const amp_t v = ld<NT>(amp + i);
+            const amp_t ol = shfl_xor_amp(v, (int)mlo), oh = shfl_xor_amp(v, (int)mhi), olh = shfl_xor_amp(ol, (int)mhi);
+            // a_j: bit lo = j & 1, bit hi = (own) ^ (j >> 1); then ascending order
+            const amp_t a0 = lb ? ol : v, a1 = lb ? v : ol, a2 = lb ? olh : oh, a3 = lb ? oh : olh;
+            if (hit) st<NT>(amp + i, u4_row(u4_row_sel(U, lb, hb), hb ? a2 : a0, hb ? a3 : a1, hb ? a0 : a2, hb ? a1 : a3));
+            else if (store_all) st<NT>(amp + i, v);
+        } else {                                               // (i has bit hi clear: squeezed out)
+            const amp_t v0 = ld<NT>(amp + i), v1 = ld<NT>(amp + (i | hib));
+            const amp_t o0 = shfl_xor_amp(v0, (int)mlo), o1 = shfl_xor_amp(v1, (int)mlo);
+            const amp_t x0 = lb ? o0 : v0, x1 = lb ? v0 : o0, x2 = lb ? o1 : v1, x3 = lb ? v1 : o1;
+            if (hit) {
+                st<NT>(amp + i, u4_row(u4_row_sel(U, lb, false), x0, x1, x2, x3));
+                st<NT>(amp + (i | hib), u4_row(u4_row_sel(U, lb, true), x0, x1, x2, x3));
+            } else if (store_all) { st<NT>(amp + i, v0); st<NT>(amp + (i | hib), v1); }
+        }
+    }
+}
+
+// K17s  the strict twins (K9's reason: a register that holds non-finite amplitudes): one plain pass over all pairs / quads, the
+// defined rows where the mask matches and the reference's identity row elsewhere; `one` and `z` are kernel arguments so that
+// no product is folded, as in k_strict_cu.
+__global__ __launch_bounds__(256) void k_strict_mcu(amp_t *__restrict__ amp, unsigned n, unsigned q, uint64_t cmask, uint64_t cvals, UMat U,
+                                                    double one, double z)
+{
+    const uint64_t half = (uint64_t)1 << (n - 1);
+    for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < half; p += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i0 = insert_zero(p, q), i1 = i0 | ((uint64_t)1 << q);
+        amp_t a = amp[i0], b = amp[i1];
+        if ((i0 & cmask) == cvals) u_butterfly(U, a, b);
+        else { a = q_row(q_mul(one, z, a)); b = q_row(q_mul(one, z, b)); }
+        amp[i0] = a; amp[i1] = b;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_strict_mcu2(amp_t *__restrict__ amp, unsigned n, unsigned lo, unsigned hi, uint64_t cmask, uint64_t cvals,
+                                                     U4Mat U, double one, double z)
+{
+    const uint64_t quads = (uint64_t)1 << (n - 2), lob = (uint64_t)1 << lo, hib = (uint64_t)1 << hi;
+    for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < quads; p += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i = insert_zero(insert_zero(p, lo), hi);
+        amp_t x[4] = {amp[i], amp[i | lob], amp[i | hib], amp[i | lob | hib]};
+        if ((i & cmask) == cvals) u4_quad(U, x[0], x[1], x[2], x[3]);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) x[k] = q_row(q_mul(one, z, x[k]));
+        }
+        amp[i] = x[0]; amp[i | lob] = x[1]; amp[i | hib] = x[2]; amp[i | lob | hib] = x[3];
+    }
+}
+
+// ---------------------------------------------------------------------------
 // K15  the rotation about a Pauli string, exp(-i theta/2 P) = cos(theta/2) I - i sin(theta/2) P, in place (qcx_pauli_rotation,
 // DESIGN s4.5i; tests/pauli_rotation_ref.py is the definition).  The string is K14's (x_mask, z_mask), g = popcount(x_mask &
 // z_mask) mod 4, (c, s) = polar(theta / 2).  The matrix has one or two entries per row and is applied as the reference's

@@ -451,6 +451,62 @@ def c_two_qubit_gate(c_qubit_num, qubit0, qubit1, U, reg):
     check(lib().qcx_c_two_qubit_gate(int(c_qubit_num), int(qubit0), int(qubit1), u.ctypes.data_as(C.c_void_p), reg._h), "c_two_qubit_gate")
 
 
+def _control_masks(controls, values):
+    """(ctrl_mask, ctrl_values) of the mc gates: controls = an iterable of qubit numbers or an int mask; values = None (all
+    positive), an int mask, or a {qubit: 0 | 1} dict"""
+    def qubit(q):
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= int(q) < 64:
+            raise ValueError(f"{q!r} is not a qubit")
+        return int(q)
+    if isinstance(controls, (int, np.integer)) and not isinstance(controls, bool):
+        mask = int(controls)
+        if not 0 <= mask < 2 ** 64:
+            raise ValueError(f"a control mask is a 64-bit set of qubits, not {controls!r}")
+    else:
+        try:
+            mask = 0
+            for q in controls:
+                mask |= 1 << qubit(q)
+        except TypeError:
+            raise ValueError(f"controls are an iterable of qubits or an int mask, not {controls!r}") from None
+    if values is None:
+        return mask, mask
+    if isinstance(values, dict):
+        vals = mask
+        for q, v in values.items():
+            if not (mask >> qubit(q)) & 1:
+                raise ValueError(f"values names qubit {q}, which is no control")
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in (0, 1):
+                raise ValueError(f"a control's value is 0 or 1, not {v!r}")
+            if not v:
+                vals &= ~(1 << int(q))
+        return mask, vals
+    if isinstance(values, (int, np.integer)) and not isinstance(values, bool):
+        vals = int(values)
+        if vals < 0 or vals & ~mask:
+            raise ValueError(f"values {vals:#x} has bits outside the controls {mask:#x}")
+        return mask, vals
+    raise ValueError(f"values is None, an int mask or a {{qubit: 0 | 1}} dict, not {values!r}")
+
+
+def mc_one_qubit_gate(controls, qubit_num, U, reg, values=None):
+    """one_qubit_gate on the amplitudes whose control qubits read their `values` (include/qcx.h: qcx_mc_one_qubit_gate): any
+    number of controls, positive or negative.  controls: an iterable of qubit numbers or an int mask; values: None = all
+    positive, an int mask (a subset of the controls: set = fires on 1), or a {qubit: 0 | 1} dict for the controls that differ
+    from 1.  mc_one_qubit_gate({c0, c1}, t, GATES["X"], reg) is a Toffoli."""
+    mask, vals = _control_masks(controls, values)
+    u = _matrix8(U)
+    check(lib().qcx_mc_one_qubit_gate(mask, vals, int(qubit_num), u.ctypes.data_as(C.c_void_p), reg._h), "mc_one_qubit_gate")
+
+
+def mc_two_qubit_gate(controls, qubit0, qubit1, U, reg, values=None):
+    """two_qubit_gate on the amplitudes whose control qubits read their `values` (include/qcx.h: qcx_mc_two_qubit_gate);
+    controls and values as for mc_one_qubit_gate.  mc_two_qubit_gate({c}, a, b, GATES2["SWAP"], reg) is a Fredkin."""
+    mask, vals = _control_masks(controls, values)
+    u = _matrix32(U)
+    check(lib().qcx_mc_two_qubit_gate(mask, vals, int(qubit0), int(qubit1), u.ctypes.data_as(C.c_void_p), reg._h), "mc_two_qubit_gate")
+
+
 def gate_batch(gates, reg):
     """Apply gates = [(U, targets) or (U, targets, control), ...] in order -- a circuit layer -- in as few passes over the state as
     locality allows: bit for bit the state that one_qubit_gate / c_one_qubit_gate / two_qubit_gate / c_two_qubit_gate gate by
