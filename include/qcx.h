@@ -260,6 +260,39 @@ unsigned qcx_gate_batch_width(void);             /* W, in units: a build constan
  * the plan's npasses, or ngates on a register flagged non-finite), lds_gates = the gates of those passes with a target on
  * qubits 0-7, which exchange between threads -- through LDS, or inside the wave (the others never leave the thread's registers) */
 int  qcx_gate_batch_last_stats(qcx_register *reg, unsigned long *passes, unsigned long *lds_gates);
+/* A diagonal operator on the qubit range [first_qubit, first_qubit + num_qubits) from a table, in ONE read and one write of the
+ * state (no reference counterpart; the matrix applied as the reference's mat-vec applies every gate, Q:393-413;
+ * tests/diagonal_ref.py restates it in numpy and IS the definition; K18, DESIGN s4.5n).  d holds 2^num_qubits entries as
+ * (re, im) pairs; entry k belongs to the amplitudes whose bits first_qubit .. first_qubit + num_qubits - 1 read k, qubit
+ * first_qubit being bit 0 of k.  For every index i, with m = d[k(i)] and x = amp[i], every fl() one binary64 rounding, no FMA:
+ *     new.re = fl(0.0 + fl(fl(m.re*x.re) - fl(m.im*x.im))),   new.im = fl(0.0 + fl(fl(m.re*x.im) + fl(m.im*x.re)))
+ *   Zero components are multiplied out (0 * Inf = NaN, as in the reference).  Every amplitude is rewritten: a result is never
+ *   -0, and an Inf or NaN stays in its own row, so a register flagged non-finite keeps its flag and runs the same kernel.
+ *   num_qubits = 0 is the global factor d[0] and still runs.
+ *   So, bit for bit: the table (c - is, c + is, ...) by parity gives qcx_pauli_rotation of a Z string; on finite states
+ *   diag(u00, u11) gives qcx_one_qubit_gate, a 4-entry table qcx_two_qubit_gate with that diagonal, (1, qcx_polar(theta)) at
+ *   entry 3 of a 2-qubit table qcx_c_phase_shift_gate, and -1 at the last entry of an n-qubit table Z under n - 1 controls.
+ * qcx_diagonal_gate takes the table from host memory: it is copied into the library's scratch before the call returns, so the
+ * caller may reuse d at once; num_qubits <= qcx_diagonal_host_max_qubits().  qcx_diagonal_gate_device takes 2^num_qubits complex
+ * doubles in memory of the register's device, for any num_qubits <= n (a full-register diagonal): the range must lie in device
+ * memory of that device and must not overlap the register's buffer (hipPointerGetAttributes and the address ranges), and the
+ * library scans it on the device for the rule below before use -- one read of the table, a 4-byte copy and a sync of the
+ * register's stream.  The caller guarantees that the table is complete when the call is made and stays unchanged until the
+ * register's stream has passed the call.
+ * Both are qcx_pauli_rotation's sequence: asynchronous, on the register's stream; flush queued gates, a pending basis state and
+ * a compact circuit result in every fusion mode; never enter the queue, are not counted by qcx_fusion_stats, stay exact in
+ * mode 2.  qcx_diagonal_plan in qcx_plan.h is the launch rule on its own; qcx_diagonal_last_stats reports the last call's form
+ * (QCX_DIAG_* of qcx_plan.h) and its table's entries.
+ * Checked in this order, before anything runs and with nothing touched: NULL reg or table: QCX_BAD_ARGUMENTS;
+ * first_qubit + num_qubits > n: QCX_BAD_QUBIT; host form: num_qubits above the maximum: QCX_BAD_ARGUMENTS (the message points
+ * to the device form); a component that is not finite or above 1 in absolute value: QCX_BAD_ARGUMENTS (host form: the message
+ * names entry and component); device form: a range that is not device memory of the register's device, or that overlaps the
+ * register: QCX_BAD_ARGUMENTS; a sharded register: QCX_UNSUPPORTED (the device form then checks the kind of memory only). */
+int  qcx_diagonal_gate(unsigned first_qubit, unsigned num_qubits, const double *d, qcx_register *reg);
+int  qcx_diagonal_gate_device(unsigned first_qubit, unsigned num_qubits, const void *d_device, qcx_register *reg);
+unsigned qcx_diagonal_host_max_qubits(void);     /* a build constant: 20 (a 16-MiB table) */
+/* the last qcx_diagonal_gate(_device) call on this register that passed its checks: form = the plan's, table_entries = 2^num_qubits */
+int  qcx_diagonal_last_stats(qcx_register *reg, unsigned *form, unsigned long *table_entries);
 int  qcx_swap_states(qcx_register *reg);                                           /* Q:242-249: no-op */
 /* host-side gate schedules */
 int  qcx_inverse_QFT(qcx_register *reg);                                           /* Q:678-690 */
@@ -270,6 +303,8 @@ int  qcx_quantum_computation(unsigned C, unsigned a, int intpow_mode, qcx_regist
 /* e^{i theta} as the reference's gsl_complex_polar(1.0, theta) yields it under gcc -O2 + glibc: one sincos()
  * call (Q:526).  Hosts that compute the phase factor themselves (qcx_shard_phase) must use this. */
 void qcx_polar(double theta, double *cos_out, double *sin_out);
+/* qcx_polar per element: out_re_im[2k], out_re_im[2k + 1] = cos, sin of thetas[k] -- a phase table for qcx_diagonal_gate */
+void qcx_polar_array(unsigned long count, const double *thetas, double *out_re_im);
 
 /* the reference's INT_POW macro (Q:158-159) exactly as x86-64 gcc evaluates it, 32-bit wrap included */
 unsigned qcx_ref_int_pow(double base, double power);

@@ -216,6 +216,34 @@ typedef struct {
 } qcx_mc_plan;
 int  qcx_mc_gate_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, unsigned ntargets, unsigned qubit0, unsigned qubit1,
                       qcx_mc_plan *out);
+
+/* The launch of qcx_diagonal_gate / qcx_diagonal_gate_device (include/qcx.h; K18, DESIGN s4.5n) for the range [first, first + num)
+ * of a register of n qubits, on the host, under the knobs of the moment; the library launches from this very function.
+ * A unit of work is a tile of the T = min(n, 12) lowest index bits, `units` = 2^(n - T) of them; workgroup b of `grid` takes the
+ * units b, b + grid, ...  Thread tid of the 256 owns the tile-local elements e = tid + 256 j, j < elems, that exist: e < 2^T
+ * (n < 12 is the one partial tile, full = 0).  The amplitude is i = (u << T) | e and its entry
+ *     k(i) = (i >> first) & kmask,   kmask = 2^num - 1,
+ * in 64 bits.  The forms say where a thread gets the entry from:
+ *   QCX_DIAG_TILE   num = 0 or first >= T: k depends on u alone -- one entry per tile, read once per tile
+ *   QCX_DIAG_GROUP  8 <= first < T: k depends on u and j, not on the lane -- at most 16 entries per tile, uniform reads
+ *   QCX_DIAG_LANE   first < 8: an entry per lane, out of a slice of the table of slice_entries = 2^(min(first + num, T) - first)
+ *                   entries per tile.  lds = 1: the slice is the same for every tile (first + num <= 12), the knob diag_lds is
+ *                   on, and the workgroup copies the 2^num entries into lds_bytes of LDS once; lds = 0: each lane reads its entry
+ *                   from memory.
+ * grid = min(units, the knob diag_grid_cap (0: no cap)), within what HIP takes; block = 256.
+ * NULL out, n = 0 or n > 40: QCX_BAD_ARGUMENTS; first + num > n: QCX_BAD_QUBIT. */
+enum { QCX_DIAG_TILE = 0, QCX_DIAG_GROUP = 1, QCX_DIAG_LANE = 2 };
+typedef struct {
+    unsigned form, full, lds;
+    unsigned T, first, num;
+    uint64_t kmask;
+    uint64_t units;
+    unsigned elems;                 /* 2^(T - 8), or 1 for T <= 8 */
+    uint64_t slice_entries;         /* table entries one tile reads (QCX_DIAG_TILE: 1) */
+    unsigned grid, block, lds_bytes;
+    char     kernel[48];            /* the instantiation as a kernel trace spells it, e.g. "k_diagonal<2, true, false>" */
+} qcx_diag_plan;
+int  qcx_diagonal_plan(unsigned n, unsigned first, unsigned num, qcx_diag_plan *out);
 #ifdef __cplusplus
 }
 #endif

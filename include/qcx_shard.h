@@ -49,6 +49,10 @@ int  qcx_shard_pauli_rotation_run(void *amp, unsigned n_local, uint64_t hot_mask
  * taken as given (not checked).  The records are read before the call returns.  Not used by the sharded hosts. */
 struct qcx_gate;
 int  qcx_shard_gate_run(void *amp, unsigned n_local, uint64_t hot_mask, unsigned ngates, const struct qcx_gate *gates, void *stream);
+/* the diagonal of local bits [first, first + num) from a table of 2^num complex doubles in DEVICE memory (qcx.h:
+ * qcx_diagonal_gate), the launch alone, as qcx_diagonal_plan (qcx_plan.h) says: the table is taken as given (not checked) and
+ * must stay unchanged until the stream has passed the launch.  Not used by the sharded hosts. */
+int  qcx_shard_diagonal(void *amp, unsigned n_local, unsigned first, unsigned num, const void *table_dev, void *stream);
 /* multiply by (cos_t + i sin_t) every amplitude whose local index has all bits of
  * `mask_local` set; mask_local has 0, 1 or 2 bits (global control bits that are 1
  * simply drop out of the mask; a global bit that is 0 means: do not call). */

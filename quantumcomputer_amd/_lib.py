@@ -65,6 +65,12 @@ SIGNATURES = {
     "qcx_gate_batch_width": (_u, []),
     "qcx_gate_batch_last_stats": (_i, [_p, C.POINTER(_ul), C.POINTER(_ul)]),
     "qcx_gate_batch_plan": (_i, [_u, _ul, _p, _p, _u, _p, C.POINTER(_ul), _p]),
+    "qcx_diagonal_gate": (_i, [_u, _u, _p, _p]),
+    "qcx_diagonal_gate_device": (_i, [_u, _u, _p, _p]),
+    "qcx_diagonal_host_max_qubits": (_u, []),
+    "qcx_diagonal_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
+    "qcx_diagonal_plan": (_i, [_u, _u, _u, _p]),
+    "qcx_polar_array": (None, [_ul, _p, _p]),
     "qcx_swap_states": (_i, [_p]),
     "qcx_inverse_QFT": (_i, [_p]),
     "qcx_quantum_computation": (_i, [_u, _u, _i, _p]),
@@ -121,6 +127,7 @@ SIGNATURES = {
     "qcx_shard_pauli_rotation": (_i, [_p, _u, _u64, _u64, _d, _d, _p]),
     "qcx_shard_pauli_rotation_run": (_i, [_p, _u, _u64, _u, _p, _p, _p, _p, _p]),
     "qcx_shard_gate_run": (_i, [_p, _u, _u64, _u, _p, _p]),
+    "qcx_shard_diagonal": (_i, [_p, _u, _u, _u, _p, _p]),
     "qcx_shard_phase": (_i, [_p, _u, _u64, _d, _d, _p]),
     "qcx_shard_camodc": (_i, [_p, _u, _u, _u, _u, _i, _p]),
     "qcx_shard_swap_bits": (_i, [_p, _p, _u, _u, C.POINTER(_u), C.POINTER(_u), _p]),
@@ -284,6 +291,28 @@ def mc_gate_plan(n, ctrl_mask, ctrl_values, targets):
     pl = McPlan()
     st = lib().qcx_mc_gate_plan(int(n), int(ctrl_mask), int(ctrl_values), len(t), t[0], t[1] if len(t) > 1 else 0, C.byref(pl))
     return st, pl
+
+
+DIAG_TILE, DIAG_GROUP, DIAG_LANE = range(3)        # QCX_DIAG_* (include/qcx_plan.h)
+
+
+class DiagPlan(C.Structure):
+    """qcx_diag_plan (include/qcx_plan.h): the launch of a diagonal on a qubit range"""
+    _fields_ = [("form", _u), ("full", _u), ("lds", _u), ("T", _u), ("first", _u), ("num", _u), ("kmask", _u64), ("units", _u64),
+                ("elems", _u), ("slice_entries", _u64), ("grid", _u), ("block", _u), ("lds_bytes", _u), ("kernel", C.c_char * 48)]
+
+
+def diagonal_plan(n, first, num):
+    """What diagonal_gate(first, num, ...) would launch on n qubits under the knobs of the moment (host code, no GPU needed;
+    include/qcx_plan.h: qcx_diagonal_plan): (status, DiagPlan)."""
+    pl = DiagPlan()
+    st = lib().qcx_diagonal_plan(int(n), int(first), int(num), C.byref(pl))
+    return st, pl
+
+
+def diagonal_host_max_qubits():
+    """the widest range diagonal_gate takes a host table for (qcx_diagonal_host_max_qubits); wider tables go in device memory"""
+    return int(lib().qcx_diagonal_host_max_qubits())
 
 
 def pauli_batch_width():

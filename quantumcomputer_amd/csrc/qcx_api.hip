@@ -170,6 +170,8 @@ extern "C" int qcx_set_device(int device) { HIP_TRY(hipSetDevice(device)); retur
     X(u2_streams_log2, -1)        /* K13: -1 = plain gate: the Hadamard plan's streams for hi; controlled: the phase gate's rule.  Both are guesses taken */ \
                                   /* over from kernels with two address streams, not four; tools/time_two_qubit_gate.py is there to measure them */ \
     X(prot_grid_cap, 2048)        /* K15 (k_pauli_rot): workgroups, each walks its units (tiles, or pairs of tiles) with this stride; 0 = one unit each */ \
+    X(diag_grid_cap, 2048)        /* K18 (k_diagonal): workgroups, each walks its tiles with this stride; 0 = one tile each */ \
+    X(diag_lds, 0)                /* K18: 1 = the per-lane form (first < 8) copies a table of first + num <= 12 into LDS once per workgroup; 0 = every lane reads its entry from memory (DESIGN s4.5n has both times) */ \
     X(mc_generic, 0)              /* K17 (gates under a control mask): 1 = no control and one positive control run K17's kernels too (0: K12's / K13's launches; the tests compare the two bit for bit) */
 struct Tune {
 #define X(name, value) long name = value;
@@ -852,6 +854,50 @@ extern "C" int qcx_shard_pauli_rotation(void *amp, unsigned n_local, uint64_t x_
         hipLaunchKernelGGL((k_pauli_rot<f.shape, f.full>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (amp_t *)amp, pu.nunits, pu.T, x_mask, z_mask, g, R);
     });
     return launch_status("pauli rotation");
+}
+
+// ---- K18: a diagonal on a qubit range from a table ------------------------------------------------------------------------------
+// the rule of include/qcx_plan.h, under one snapshot of the knobs
+static int diagonal_plan(const Tune &t, unsigned n, unsigned first, unsigned num, qcx_diag_plan *out)
+{
+    if (!out || n == 0 || n > 40) return QCX_BAD_ARGUMENTS;
+    if (first > n || num > n - first) return QCX_BAD_QUBIT;
+    memset(out, 0, sizeof *out);
+    const unsigned T = std::min(n, 12u);
+    out->T = T; out->first = first; out->num = num;
+    out->kmask = (((uint64_t)1) << num) - 1u;
+    out->units = ((uint64_t)1) << (n - T);
+    out->full = T == 12;
+    out->elems = T > 8 ? 1u << (T - 8) : 1u;
+    out->form = (num == 0 || first >= T) ? QCX_DIAG_TILE : (first >= 8 ? QCX_DIAG_GROUP : QCX_DIAG_LANE);
+    out->slice_entries = out->form == QCX_DIAG_TILE ? 1 : ((uint64_t)1) << (std::min(first + num, T) - first);
+    out->lds = out->form == QCX_DIAG_LANE && first + num <= 12 && t.diag_lds != 0;
+    out->lds_bytes = out->lds ? 16u << num : 0;
+    out->grid = grid_for(out->units, 1, t.diag_grid_cap, 256);
+    out->block = 256;
+    snprintf(out->kernel, sizeof out->kernel, "k_diagonal<%u, %s, %s>", out->form, out->full ? "true" : "false", out->lds ? "true" : "false");
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_diagonal_plan(unsigned n, unsigned first, unsigned num, qcx_diag_plan *out)
+{
+    return diagonal_plan(tune_now(), n, first, num, out);
+}
+
+extern "C" int qcx_shard_diagonal(void *amp, unsigned n_local, unsigned first, unsigned num, const void *table_dev, void *stream)
+{
+    if (!amp || !table_dev) return QCX_BAD_ARGUMENTS;
+    qcx_diag_plan pl;
+    QCX_TRY(diagonal_plan(tune_now(), n_local, first, num, &pl));
+    const dim3 grid(pl.grid), block(pl.block);
+#define QCX_DIAG(FORM, FULL, LDS) hipLaunchKernelGGL((k_diagonal<FORM, FULL, LDS>), grid, block, pl.lds_bytes, (hipStream_t)stream, \
+                                                     (amp_t *)amp, (const amp_t *)table_dev, pl.units, pl.T, pl.first, pl.kmask)
+    if (pl.form == QCX_DIAG_TILE)       { if (pl.full) QCX_DIAG(0, true, false); else QCX_DIAG(0, false, false); }
+    else if (pl.form == QCX_DIAG_GROUP) { if (pl.full) QCX_DIAG(1, true, false); else QCX_DIAG(1, false, false); }
+    else if (pl.lds)                    { if (pl.full) QCX_DIAG(2, true, true);  else QCX_DIAG(2, false, true); }
+    else                                { if (pl.full) QCX_DIAG(2, true, false); else QCX_DIAG(2, false, false); }
+#undef QCX_DIAG
+    return launch_status("diagonal gate");
 }
 
 // ---- K15b: a run of rotations in one pass (qcx_pauli_rotation_batch) -----------------------------------------------------------
@@ -1670,6 +1716,12 @@ struct qcx_register {
     unsigned   coll_source;     // the last measure_qubits / postselect call: 0 register, 2 basis (no kernel), 3 compact expanded first
     unsigned long coll_reads, coll_writes;   // ... the marginal's reads behind its probabilities, and collapse passes launched (0 or 1)
     unsigned long rotb_passes, rotb_wide;    // the last pauli_rotation_batch call: its passes, and those of them that are one wide term (K15)
+    unsigned   diag_form;       // the last diagonal_gate call: the plan's form ...
+    unsigned long diag_entries; // ... and its table's entries
+    amp_t     *diag_tab;        // K18, host form: the table on the device, and the pinned buffer it is copied through; one allocation
+    amp_t     *diag_stage;      // each, grown on demand.  diag_ev: the copy out of diag_stage has been passed by the stream
+    size_t     diag_cap;        // entries both hold
+    hipEvent_t diag_ev;
     unsigned long gateb_passes, gateb_lds;   // the last gate_batch call: its passes, and the gates in them that exchanged through LDS (K12b / K13b)
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
 };
@@ -1865,6 +1917,9 @@ extern "C" int qcx_register_destroy(qcx_register *r)
     (void)hipFree(r->amp);
     if (r->scratch) (void)hipFree(r->scratch);
     if (r->marg_buf) (void)hipFree(r->marg_buf);
+    if (r->diag_tab) (void)hipFree(r->diag_tab);
+    if (r->diag_stage) (void)hipHostFree(r->diag_stage);
+    if (r->diag_ev) (void)hipEventDestroy(r->diag_ev);
     free(r);
     return QCX_NO_ERROR;
 }
@@ -2547,6 +2602,122 @@ extern "C" int qcx_rotation_batch_last_stats(qcx_register *r, unsigned long *pas
     if (!r) return QCX_BAD_ARGUMENTS;
     if (passes) *passes = r->rotb_passes;
     if (wide_terms) *wide_terms = r->rotb_wide;
+    return QCX_NO_ERROR;
+}
+
+// ---- the diagonal of a qubit range from a table (K18) ---------------------------------------------------------------------------
+#define QCX_DIAG_HOST_MAX 20u
+extern "C" unsigned qcx_diagonal_host_max_qubits(void) { return QCX_DIAG_HOST_MAX; }
+
+extern "C" void qcx_polar_array(unsigned long count, const double *thetas, double *out_re_im)
+{
+    for (unsigned long k = 0; k < count; k++) qcx_polar(thetas[k], out_re_im + 2 * k, out_re_im + 2 * k + 1);
+}
+
+// behind the checks: qcx_pauli_rotation's sequence, then the launch the plan gives
+static int diagonal_run(qcx_register *r, const char *who, unsigned first, unsigned num, const amp_t *tab_dev)
+{
+    QCX_TRY(unqueued_gate(r, who, true));
+    qcx_diag_plan pl;
+    QCX_TRY(qcx_diagonal_plan(r->n, first, num, &pl));
+    r->diag_form = pl.form; r->diag_entries = (unsigned long)(pl.kmask + 1);
+    return qcx_shard_diagonal(r->amp, r->n, first, num, tab_dev, r->stream);
+}
+
+// The host form: the table goes through the register's pinned buffer into its device scratch, on the register's stream, so the
+// caller's array is free when the call returns and the kernel finds the table behind the copy.  The next call waits for that
+// copy (diag_ev) before it overwrites the pinned buffer; the device scratch is only ever touched in stream order.
+extern "C" int qcx_diagonal_gate(unsigned first, unsigned num, const double *d, qcx_register *r)
+{
+    if (!r || !d) return QCX_BAD_ARGUMENTS;
+    if (first > r->n || num > r->n - first) return QCX_BAD_QUBIT;
+    if (num > QCX_DIAG_HOST_MAX) {
+        set_error("diagonal_gate: a table over %u qubits is more than the host form takes (%u); build it on the device and call qcx_diagonal_gate_device", num, QCX_DIAG_HOST_MAX);
+        return QCX_BAD_ARGUMENTS;
+    }
+    const size_t entries = (size_t)1 << num;
+    for (size_t k = 0; k < 2 * entries; k++)
+        if (!(fabs(d[k]) <= 1.0)) {
+            set_error("diagonal_gate: entry %zu's %s part is %g (each component must be finite with |.| <= 1)", k >> 1, (k & 1) ? "imaginary" : "real", d[k]);
+            return QCX_BAD_ARGUMENTS;
+        }
+    if (r->sh) { set_error("diagonal_gate: not available on a sharded register"); return QCX_UNSUPPORTED; }
+    if (!r->diag_ev) HIP_TRY(hipEventCreateWithFlags(&r->diag_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(r->diag_ev));
+    if (r->diag_cap < entries) {
+        HIP_TRY(hipStreamSynchronize(r->stream));                 // (a kernel may still be reading the old table)
+        if (r->diag_tab) (void)hipFree(r->diag_tab);
+        if (r->diag_stage) (void)hipHostFree(r->diag_stage);
+        r->diag_tab = nullptr; r->diag_stage = nullptr; r->diag_cap = 0;
+        size_t cap = 4096;
+        while (cap < entries) cap <<= 1;
+        if (hipMalloc(&r->diag_tab, cap * sizeof(amp_t)) != hipSuccess) { (void)hipGetLastError(); r->diag_tab = nullptr; return QCX_INSUFFICIENT_MEMORY; }
+        if (hipHostMalloc(&r->diag_stage, cap * sizeof(amp_t)) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(r->diag_tab); r->diag_tab = nullptr; r->diag_stage = nullptr; return QCX_INSUFFICIENT_MEMORY;
+        }
+        r->diag_cap = cap;
+    }
+    memcpy(r->diag_stage, d, entries * sizeof(amp_t));
+    HIP_TRY(hipMemcpyAsync(r->diag_tab, r->diag_stage, entries * sizeof(amp_t), hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipEventRecord(r->diag_ev, r->stream));
+    return diagonal_run(r, "diagonal_gate", first, num, r->diag_tab);
+}
+
+// The device form: the caller's table in place.  Where it lies is checked on the host; what it holds, on the device, on the
+// register's stream (k_diag_scan, note_nonfinite's flag word and its one sync) -- before the flush, so a refusal touches nothing.
+extern "C" int qcx_diagonal_gate_device(unsigned first, unsigned num, const void *d_device, qcx_register *r)
+{
+    if (!r || !d_device) return QCX_BAD_ARGUMENTS;
+    if (first > r->n || num > r->n - first) return QCX_BAD_QUBIT;
+    const uint64_t entries = ((uint64_t)1) << num, bytes = entries * sizeof(amp_t);
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, d_device) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        set_error("diagonal_gate_device: the table at %p is not device memory", d_device);
+        return QCX_BAD_ARGUMENTS;
+    }
+    if (((uintptr_t)d_device & 15u) != 0) { set_error("diagonal_gate_device: the table at %p is not aligned to 16 bytes", d_device); return QCX_BAD_ARGUMENTS; }
+    void *base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)d_device) == hipSuccess) {
+        if ((uintptr_t)d_device + bytes > (uintptr_t)base + size) {
+            set_error("diagonal_gate_device: 2^%u entries from %p run past the end of their allocation", num, d_device);
+            return QCX_BAD_ARGUMENTS;
+        }
+    } else (void)hipGetLastError();
+    if (r->sh) { set_error("diagonal_gate_device: not available on a sharded register"); return QCX_UNSUPPORTED; }
+    hipPointerAttribute_t ra;
+    memset(&ra, 0, sizeof ra);
+    HIP_TRY(hipPointerGetAttributes(&ra, r->amp));
+    if (at.device != ra.device) {
+        set_error("diagonal_gate_device: the table lies on device %d, the register on device %d", at.device, ra.device);
+        return QCX_BAD_ARGUMENTS;
+    }
+    const uintptr_t t0 = (uintptr_t)d_device, t1 = t0 + bytes;
+    const auto overlaps = [&](const amp_t *p) { const uintptr_t a0 = (uintptr_t)p, a1 = a0 + (uintptr_t)(r->dim * sizeof(amp_t)); return p && t0 < a1 && a0 < t1; };
+    if (overlaps(r->amp) || overlaps(r->scratch)) { set_error("diagonal_gate_device: the table overlaps the register's buffer"); return QCX_BAD_ARGUMENTS; }
+    {
+        Workspace *w;
+        QCX_TRY(workspace(&w));
+        std::lock_guard<std::mutex> use(g_ws_use[w - g_ws]);
+        HIP_TRY(hipMemsetAsync(w->meas_stats, 0, sizeof(unsigned), r->stream));
+        hipLaunchKernelGGL(k_diag_scan, dim3(grid_for(entries, 256 * 8, 65536, 256)), dim3(256), 0, r->stream, (const amp_t *)d_device, entries, w->meas_stats);
+        HIP_TRY(hipGetLastError());
+        const unsigned keep = w->h_meas_stats[0];                // (note_nonfinite's use of the pinned word)
+        HIP_TRY(hipMemcpyAsync(w->h_meas_stats, w->meas_stats, sizeof(unsigned), hipMemcpyDeviceToHost, r->stream));
+        HIP_TRY(hipStreamSynchronize(r->stream));
+        const unsigned bad = w->h_meas_stats[0];
+        w->h_meas_stats[0] = keep;
+        if (bad) { set_error("diagonal_gate_device: the table holds a component that is not finite or exceeds 1 in absolute value"); return QCX_BAD_ARGUMENTS; }
+    }
+    return diagonal_run(r, "diagonal_gate_device", first, num, (const amp_t *)d_device);
+}
+
+extern "C" int qcx_diagonal_last_stats(qcx_register *r, unsigned *form, unsigned long *table_entries)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (form) *form = r->diag_form;
+    if (table_entries) *table_entries = r->diag_entries;
     return QCX_NO_ERROR;
 }
 

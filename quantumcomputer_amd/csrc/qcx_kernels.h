@@ -5498,4 +5498,76 @@ __global__ __launch_bounds__(256) void k_rdm_small(const amp_t *__restrict__ amp
     }
 }
 
+// ---------------------------------------------------------------------------
+// K18  a diagonal operator on the qubit range [first, first + num) from a table (qcx_diagonal_gate, DESIGN s4.5n;
+// tests/diagonal_ref.py is the definition): amp[i] = q_row(tab[k(i)] * amp[i]), k(i) = (i >> first) & kmask, kmask = 2^num - 1,
+// the product by q_mul (the pinned arithmetic), zero components multiplied out.  This is K15 SHAPE 0 with the entry taken from
+// memory instead of (c, -+s) by parity: the same tiles (T = min(n, 12) lowest index bits, a workgroup of 256 threads, element
+// e = tid + 256 j, j < 16), at most 8 amplitudes of a thread in flight, no barrier in the walk, nontemporal loads and stores of
+// the state; the table is read with ordinary loads (it is the one thing here that is used again).  Every amplitude is rewritten
+// as 0 + ..., so a result is never -0, and an Inf or NaN stays in its own row: there is no strict twin.
+// Where the entry comes from (qcx_diagonal_plan in include/qcx_plan.h is the rule; i = (u << T) | e throughout, in 64 bits):
+//   FORM 0  num == 0 or first >= T: one entry per tile, k = ((u << T) >> first) & kmask -- uniform, read once per tile
+//   FORM 1  8 <= first < T: the entry depends on j and the tile, not on the lane -- uniform addresses, at most 16 per tile
+//   FORM 2  first < 8: an entry per lane.  LDS: the tile's slice of the table is the same for every tile (first + num <= 12) and
+//           the workgroup copies its 2^num entries into LDS once; otherwise each lane reads tab[k(i)] itself, contiguous or
+//           broadcast 16-B reads that L2 serves
+// FULL as in K15: !FULL is the one partial tile of n < 12, where a thread owns the elements with tid + 256 j < 2^T.
+// ---------------------------------------------------------------------------
+template <int FORM, bool FULL, bool LDS>
+__global__ __launch_bounds__(256) void k_diagonal(amp_t *__restrict__ amp, const amp_t *__restrict__ tab, uint64_t nunits, unsigned T,
+                                                  unsigned first, uint64_t kmask)
+{
+    constexpr unsigned EPT = 16u, HALF = 8u;
+    static_assert(!LDS || FORM == 2, "only the per-lane form stages its slice");
+    extern __shared__ amp_t diag_sd[];
+    const unsigned tid = threadIdx.x;
+    unsigned nld = EPT;
+    if constexpr (!FULL) {
+        nld = 0;
+#pragma unroll
+        for (unsigned j = 0; j < EPT; j++)
+            if (tid + 256u * j < (1u << T)) nld = j + 1;
+    }
+    if constexpr (LDS) {
+        for (uint64_t k = tid; k <= kmask; k += 256u) diag_sd[k] = tab[k];
+        __syncthreads();
+    }
+    for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
+        const uint64_t base = u << T;
+        amp_t *pa = amp + base + tid;
+        amp_t m_tile = {0.0, 0.0};
+        if constexpr (FORM == 0) m_tile = tab[(base >> first) & kmask];
+#pragma unroll 1
+        for (unsigned h = 0; h < EPT; h += HALF) {
+            amp_t a[HALF], m[HALF];
+#pragma unroll
+            for (unsigned k = 0; k < HALF; k++)
+                if (FULL || h + k < nld) {
+                    a[k] = __builtin_nontemporal_load(pa + 256u * (h + k));
+                    if constexpr (FORM == 0) m[k] = m_tile;
+                    else if constexpr (FORM == 1) m[k] = tab[((base | (uint64_t)(256u * (h + k))) >> first) & kmask];
+                    else if constexpr (LDS) m[k] = diag_sd[((tid | (256u * (h + k))) >> first) & (unsigned)kmask];
+                    else m[k] = tab[((base | (uint64_t)(tid | (256u * (h + k)))) >> first) & kmask];
+                }
+#pragma unroll
+            for (unsigned k = 0; k < HALF; k++)
+                if (FULL || h + k < nld)
+                    __builtin_nontemporal_store(q_row(q_mul(m[k].x, m[k].y, a[k])), pa + 256u * (h + k));
+        }
+    }
+}
+
+// the matrices' rule for a table in device memory (qcx_diagonal_gate_device): does tab[0 .. count) hold a component that is not
+// finite or exceeds 1 in magnitude?  k_scan_nonfinite with that bound; one read of the table
+__global__ __launch_bounds__(256) void k_diag_scan(const amp_t *__restrict__ tab, uint64_t count, unsigned *flag)
+{
+    bool bad = false;
+    for (uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x; k < count; k += (uint64_t)gridDim.x * 256u) {
+        const amp_t v = tab[k];
+        bad |= !(fabs(v.x) <= 1.0) || !(fabs(v.y) <= 1.0);
+    }
+    if (__ballot(bad) && (threadIdx.x & 63u) == 0u) atomicOr(flag, 1u);
+}
+
 }  // namespace qcx

@@ -310,6 +310,13 @@ class Register:
         check(lib().qcx_rotation_batch_last_stats(self._h, C.byref(passes), C.byref(wide)), "qcx_rotation_batch_last_stats")
         return passes.value, wide.value
 
+    def diagonal_stats(self):
+        """(form, table entries) of the last diagonal_gate call on this register: the form of its launch (diagonal_plan's:
+        DIAG_TILE, DIAG_GROUP or DIAG_LANE) and the 2^num entries of its table"""
+        form, entries = C.c_uint(0), C.c_ulong(0)
+        check(lib().qcx_diagonal_last_stats(self._h, C.byref(form), C.byref(entries)), "qcx_diagonal_last_stats")
+        return form.value, entries.value
+
     def gate_batch_stats(self):
         """(passes, low-target gates) of the last gate_batch call on this register: the passes over the state it ran (the plan's:
         gate_batch_plan; the number of gates on a register flagged non-finite), and the gates in them with a target on qubits 0-7,
@@ -350,6 +357,7 @@ class Register:
 
     def synchronize(self):
         check(lib().qcx_synchronize(self._h), "qcx_synchronize")
+        self._diag_keep = []                        # (the stream has passed every diagonal_gate call: their device tables are free)
 
     def set_stream(self, hip_stream_ptr):
         check(lib().qcx_register_set_stream(self._h, C.c_void_p(hip_stream_ptr)), "qcx_register_set_stream")
@@ -547,6 +555,58 @@ def pauli_rotation_batch(terms, reg):
     th = np.array([float(t) for _, t in terms], dtype=np.float64)
     ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if k else (lambda a: None)
     check(lib().qcx_pauli_rotation_batch(reg._h, k, ptr(xs), ptr(zs), ptr(th)), "pauli_rotation_batch")
+
+
+def diagonal_gate(first, num, d, reg):
+    """Multiply every amplitude by the entry of the table d that its bits first .. first+num-1 select, qubit `first` being bit 0
+    of the entry's number, in one pass over the state (include/qcx.h: qcx_diagonal_gate; the pinned arithmetic is restated in
+    tests/diagonal_ref.py).  d is either
+      - anything numpy.asarray(d, complex) turns into 2^num values: the host form, copied before the call returns
+        (num <= diagonal_host_max_qubits()), or
+      - a table in the memory of the register's GPU, for any num <= n: an integer device address of 2^num complex128 values, or
+        an object with data_ptr() such as a torch tensor -- complex128, contiguous, 2^num elements, on a GPU.  The table must be
+        complete when the call is made: the stream that produced it must have been synchronised (torch.cuda.synchronize()).
+        It must stay unchanged until reg.synchronize(); the register keeps a reference to the object until then.
+    Every component must be finite with |.| <= 1; the table is applied as given, not checked for unit modulus."""
+    first, num = int(first), int(num)
+    if hasattr(d, "data_ptr") or isinstance(d, (int, np.integer)):
+        if hasattr(d, "data_ptr"):
+            if "complex128" not in str(getattr(d, "dtype", "")):
+                raise TypeError(f"a device table holds complex128 values, not {getattr(d, 'dtype', None)}")
+            if not d.is_contiguous():
+                raise ValueError("a device table must be contiguous")
+            if num < 0 or int(d.numel()) != 1 << num:
+                raise ValueError(f"a diagonal over {num} qubits has {1 << max(num, 0)} entries, not {int(d.numel())}")
+            if not getattr(d, "is_cuda", False):
+                raise ValueError("a table with data_ptr() must lie on a GPU; pass host values as an array")
+            address = int(d.data_ptr())
+        else:
+            address = int(d)
+        check(lib().qcx_diagonal_gate_device(first, num, C.c_void_p(address), reg._h), "diagonal_gate")
+        if not hasattr(reg, "_diag_keep"):
+            reg._diag_keep = []
+        reg._diag_keep.append(d)
+        return
+    t = np.ascontiguousarray(np.asarray(d, dtype=complex).reshape(-1))
+    if num < 0 or t.size != 1 << num:
+        raise ValueError(f"a diagonal over {num} qubits has {1 << max(num, 0)} entries, not {t.size}")
+    check(lib().qcx_diagonal_gate(first, num, t.view(np.float64).ctypes.data_as(C.c_void_p), reg._h), "diagonal_gate")
+
+
+def phase_table(angles):
+    """e^{i angle} for every angle, each through qcx_polar (one sincos, the factor c_phase_shift_gate uses): a complex128 array
+    for diagonal_gate, so that the table (1, 1, 1, e^{i theta}) on two qubits gives c_phase_shift_gate's bits"""
+    th = np.ascontiguousarray(np.asarray(angles, dtype=np.float64).reshape(-1))
+    out = np.empty(2 * th.size, dtype=np.float64)
+    if th.size:
+        lib().qcx_polar_array(th.size, th.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    return out.view(np.complex128)
+
+
+def diagonal_phase(first, num, angles, reg):
+    """diagonal_gate with the table phase_table(angles): amplitude i takes the phase e^{i angles[k(i)]} -- a QAOA cost layer is
+    diagonal_phase(0, n, -gamma * C, reg)"""
+    diagonal_gate(first, num, phase_table(angles), reg)
 
 
 def controlled(U2):
