@@ -1675,6 +1675,11 @@ extern "C" int qcx_measure_last_stats(unsigned *slow_blocks, unsigned *blocks)
 // ---------------------------------------------------------------------------
 // register (single-GPU handle): one in-place amplitude buffer in HBM
 // ---------------------------------------------------------------------------
+// What an observer's last call read (the *_last_stats getters): where the state came from, and the passes that read amplitudes.
+// SRC_COMPACT is the marginal's alone; SRC_EXPANDED: the compact result expanded into the register first, the compact form kept.
+enum { SRC_REGISTER = 0, SRC_COMPACT = 1, SRC_BASIS = 2 /* no kernel */, SRC_EXPANDED = 3 };
+struct ReadStats { unsigned source; unsigned long reads; };
+
 struct qcx_register {
     int        L, M;
     unsigned   n;
@@ -1707,14 +1712,9 @@ struct qcx_register {
     unsigned long samp_scans, samp_fallback;   // the last qcx_sample_states call: whole-state scans launched / shots a per-shot scan answered
     double    *marg_buf;        // K10 (qcx_marginal_probabilities): the stages' partials, the output and the `bad` word; its own buffer
     size_t     marg_cap;        // doubles marg_buf holds
-    unsigned   marg_source;     // the last marginal call: 0 register, 1 compact in place, 2 basis (no kernel), 3 compact expanded first
-    unsigned long marg_reads;   // ... and the passes of it that read amplitudes
-    unsigned   exp_source;      // the last pauli_expectation(_sum) call: 0 register, 2 basis (no kernel), 3 compact expanded first
-    unsigned long exp_reads;    // ... and the passes of it that read amplitudes (one per term)
-    unsigned   rdm_source;      // the last reduced_density_matrix call: 0 register, 2 basis (no kernel), 3 compact expanded first
-    unsigned long rdm_reads;    // ... and the passes of it that read amplitudes (1, or 0 for a basis state)
-    unsigned   coll_source;     // the last measure_qubits / postselect call: 0 register, 2 basis (no kernel), 3 compact expanded first
-    unsigned long coll_reads, coll_writes;   // ... the marginal's reads behind its probabilities, and collapse passes launched (0 or 1)
+    ReadStats  marg, exp, rdm;  // the last marginal / pauli_expectation(_sum, _batch) / reduced_density_matrix call
+    ReadStats  coll;            // the last measure_qubits / postselect call: the marginal's reads behind its probabilities ...
+    unsigned long coll_writes;  // ... and collapse passes launched (0 or 1)
     unsigned long rotb_passes, rotb_wide;    // the last pauli_rotation_batch call: its passes, and those of them that are one wide term (K15)
     unsigned   diag_form;       // the last diagonal_gate call: the plan's form ...
     unsigned long diag_entries; // ... and its table's entries
@@ -2323,21 +2323,34 @@ extern "C" int qcx_synchronize(qcx_register *r)
 }
 
 // ---- strict gates (K9): a register that was handed non-finite amplitudes -------------------------------------------------------
+// What a scan kernel ORs into the workspace's device flag word: the word cleared, launch(word) enqueued on the stream, its value
+// to *flag behind one sync.  The pinned word it is read through doubles as the last measurement scan's statistics: put back.
+template <typename Launch>
+static int scan_flag_word(hipStream_t stream, Launch launch, unsigned *flag)
+{
+    Workspace *w;
+    QCX_TRY(workspace(&w));
+    std::lock_guard<std::mutex> use(g_ws_use[w - g_ws]);
+    HIP_TRY(hipMemsetAsync(w->meas_stats, 0, sizeof(unsigned), stream));
+    launch(w->meas_stats);
+    HIP_TRY(hipGetLastError());
+    const unsigned keep = w->h_meas_stats[0];
+    HIP_TRY(hipMemcpyAsync(w->h_meas_stats, w->meas_stats, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *flag = w->h_meas_stats[0];
+    w->h_meas_stats[0] = keep;
+    return QCX_NO_ERROR;
+}
+
 // did the caller just write something that is not finite (or >= 2^500) into [first, first + count)?  (scanned on the device)
 static int note_nonfinite(qcx_register *r, uint64_t first, uint64_t count)
 {
     if (!count || r->nonfinite) return QCX_NO_ERROR;
-    Workspace *w;
-    QCX_TRY(workspace(&w));
-    std::lock_guard<std::mutex> use(g_ws_use[w - g_ws]);
-    HIP_TRY(hipMemsetAsync(w->meas_stats, 0, sizeof(unsigned), r->stream));
-    hipLaunchKernelGGL(k_scan_nonfinite, dim3(grid_for(count, 256 * 8, 65536, 256)), dim3(256), 0, r->stream, (const amp_t *)(r->amp + first), count, w->meas_stats);
-    HIP_TRY(hipGetLastError());
-    const unsigned keep = w->h_meas_stats[0];                // (the pinned word doubles as the last scan's statistics: put it back)
-    HIP_TRY(hipMemcpyAsync(w->h_meas_stats, w->meas_stats, sizeof(unsigned), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    if (w->h_meas_stats[0]) r->nonfinite = 1;
-    w->h_meas_stats[0] = keep;
+    unsigned found = 0;
+    QCX_TRY(scan_flag_word(r->stream, [&](unsigned *word) {
+        hipLaunchKernelGGL(k_scan_nonfinite, dim3(grid_for(count, 256 * 8, 65536, 256)), dim3(256), 0, r->stream, (const amp_t *)(r->amp + first), count, word);
+    }, &found));
+    if (found) r->nonfinite = 1;
     return QCX_NO_ERROR;
 }
 
@@ -2445,6 +2458,22 @@ static int unqueued_gate(qcx_register *r, const char *who, bool rewrites_all)
     return canon_if_dirty(r);
 }
 
+// A gate on 1 or 2 targets under the controls (cmask, cvals) as the STRICT pass of a register flagged non-finite (K9): one plain
+// pass over all pairs / quads, the two-qubit matrix permuted to lo < hi as every K13 kernel takes it.
+static int strict_controlled_gate(qcx_register *r, uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q0, unsigned q1, const double *u)
+{
+    if (ntargets == 1) {
+        const UMat U = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]};
+        hipLaunchKernelGGL(k_strict_mcu, dim3(grid_for(r->dim >> 1, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, q0, cmask, cvals, U, 1.0, 0.0);
+    } else {
+        const U4Mat U = u4_ascending(q0, q1, u);
+        const unsigned lo = q0 < q1 ? q0 : q1, hi = q0 < q1 ? q1 : q0;
+        hipLaunchKernelGGL(k_strict_mcu2, dim3(grid_for(r->dim >> 2, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, lo, hi, cmask, cvals, U, 1.0, 0.0);
+    }
+    HIP_TRY(hipGetLastError());
+    return QCX_NO_ERROR;
+}
+
 // Any one-qubit gate (ctl < 0: plain).  Never queued, in any fusion mode: the fused passes know H and phase only, so the call
 // flushes what is pending and launches its own kernel (K12); the fusion statistics do not count it.
 static int one_qubit_gate(int ctl, unsigned q, const double *u, qcx_register *r, const char *who)
@@ -2453,12 +2482,7 @@ static int one_qubit_gate(int ctl, unsigned q, const double *u, qcx_register *r,
     QCX_TRY(check_matrix(who, u, 8));
     if (q >= r->n || (ctl >= 0 && ((unsigned)ctl >= r->n || (unsigned)ctl == q))) return QCX_BAD_QUBIT;
     QCX_TRY(unqueued_gate(r, who, false));
-    if (r->nonfinite && ctl >= 0) {                   // (the plain kernels already are strict)
-        const UMat U = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]};
-        hipLaunchKernelGGL(k_strict_cu, dim3(grid_for(r->dim >> 1, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, q, (unsigned)ctl, U, 1.0, 0.0);
-        HIP_TRY(hipGetLastError());
-        return QCX_NO_ERROR;
-    }
+    if (r->nonfinite && ctl >= 0) return strict_controlled_gate(r, (uint64_t)1 << ctl, (uint64_t)1 << ctl, 1, q, 0, u);     // (the plain kernels already are strict)
     return qcx_shard_one_qubit(r->amp, r->n, q, ctl, u, r->stream);
 }
 
@@ -2482,13 +2506,7 @@ static int two_qubit_gate(int ctl, unsigned q0, unsigned q1, const double *u, qc
     if (q0 >= r->n || q1 >= r->n || q0 == q1) return QCX_BAD_QUBIT;
     if (ctl >= 0 && ((unsigned)ctl >= r->n || (unsigned)ctl == q0 || (unsigned)ctl == q1)) return QCX_BAD_QUBIT;
     QCX_TRY(unqueued_gate(r, who, false));
-    if (r->nonfinite && ctl >= 0) {                   // (the plain kernels already are strict)
-        const U4Mat U = u4_ascending(q0, q1, u);
-        const unsigned lo = q0 < q1 ? q0 : q1, hi = q0 < q1 ? q1 : q0;
-        hipLaunchKernelGGL(k_strict_cu2, dim3(grid_for(r->dim >> 2, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, lo, hi, (unsigned)ctl, U, 1.0, 0.0);
-        HIP_TRY(hipGetLastError());
-        return QCX_NO_ERROR;
-    }
+    if (r->nonfinite && ctl >= 0) return strict_controlled_gate(r, (uint64_t)1 << ctl, (uint64_t)1 << ctl, 2, q0, q1, u);   // (the plain kernels already are strict)
     return qcx_shard_two_qubit(r->amp, r->n, q0, q1, ctl, u, r->stream);
 }
 
@@ -2518,18 +2536,7 @@ static int mc_gate(uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q
         return ntargets == 1 ? one_qubit_gate(ctl, q0, u, r, who) : two_qubit_gate(ctl, q0, q1, u, r, who);
     }
     QCX_TRY(unqueued_gate(r, who, false));
-    if (r->nonfinite) {
-        if (ntargets == 1) {
-            const UMat U = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]};
-            hipLaunchKernelGGL(k_strict_mcu, dim3(grid_for(r->dim >> 1, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, q0, cmask, cvals, U, 1.0, 0.0);
-        } else {
-            const U4Mat U = u4_ascending(q0, q1, u);
-            const unsigned lo = q0 < q1 ? q0 : q1, hi = q0 < q1 ? q1 : q0;
-            hipLaunchKernelGGL(k_strict_mcu2, dim3(grid_for(r->dim >> 2, 256, 65536, 256)), dim3(256), 0, r->stream, r->amp, r->n, lo, hi, cmask, cvals, U, 1.0, 0.0);
-        }
-        HIP_TRY(hipGetLastError());
-        return QCX_NO_ERROR;
-    }
+    if (r->nonfinite) return strict_controlled_gate(r, cmask, cvals, ntargets, q0, q1, u);
     return mc_launch(r->amp, r->n, cmask, cvals, ntargets, q0, q1, u, r->stream);
 }
 
@@ -2541,6 +2548,20 @@ extern "C" int qcx_mc_one_qubit_gate(uint64_t ctrl_mask, uint64_t ctrl_values, u
 extern "C" int qcx_mc_two_qubit_gate(uint64_t ctrl_mask, uint64_t ctrl_values, unsigned q0, unsigned q1, const double *u, qcx_register *r)
 {
     return mc_gate(ctrl_mask, ctrl_values, 2, q0, q1, u, r, "mc_two_qubit_gate");
+}
+
+// The passes of a batch plan, in order: pass_of is non-decreasing over the items, a pass a run of equal values.  each(first item,
+// count, pass number) returns a status; the first that is not QCX_NO_ERROR ends the walk and is returned.
+template <typename Each>
+static int for_each_pass(const std::vector<unsigned long> &pass_of, Each each)
+{
+    for (unsigned long k = 0, n = pass_of.size(); k < n;) {
+        unsigned cnt = 1;
+        while (k + cnt < n && pass_of[k + cnt] == pass_of[k]) cnt++;
+        QCX_TRY(each(k, cnt, pass_of[k]));
+        k += cnt;
+    }
+    return QCX_NO_ERROR;
 }
 
 // exp(-i theta/2 P) of the Pauli string (x_mask, z_mask).  one_qubit_gate()'s sequence: never queued, in any fusion mode; the
@@ -2584,17 +2605,14 @@ extern "C" int qcx_pauli_rotation_batch(qcx_register *r, unsigned long nterms, c
     unsigned long np = 0;
     QCX_TRY(qcx_pauli_rotation_batch_plan(r->n, nterms, x_masks, QCX_PROT_RUN_W, pass_of.data(), &np, kind.data(), hot.data()));
     QCX_TRY(unqueued_gate(r, "pauli_rotation_batch", true));
-    double cs[QCX_PROT_RUN_W], ss[QCX_PROT_RUN_W];
-    for (unsigned long k = 0; k < nterms;) {
-        const unsigned long p = pass_of[k];
-        unsigned cnt = 0;
-        while (k + cnt < nterms && pass_of[k + cnt] == p) { qcx_polar(thetas[k + cnt] / 2.0, &cs[cnt], &ss[cnt]); cnt++; }
+    return for_each_pass(pass_of, [&](unsigned long k, unsigned cnt, unsigned long p) {
+        double cs[QCX_PROT_RUN_W], ss[QCX_PROT_RUN_W];
+        for (unsigned c = 0; c < cnt; c++) qcx_polar(thetas[k + c] / 2.0, &cs[c], &ss[c]);
         if (kind[p] == 1) { QCX_TRY(qcx_shard_pauli_rotation(r->amp, r->n, x_masks[k], z_masks[k], cs[0], ss[0], r->stream)); r->rotb_wide++; }
         else QCX_TRY(qcx_shard_pauli_rotation_run(r->amp, r->n, hot[p], cnt, x_masks + k, z_masks + k, cs, ss, r->stream));
         r->rotb_passes++;
-        k += cnt;
-    }
-    return QCX_NO_ERROR;
+        return (int)QCX_NO_ERROR;
+    });
 }
 
 extern "C" int qcx_rotation_batch_last_stats(qcx_register *r, unsigned long *passes, unsigned long *wide_terms)
@@ -2664,7 +2682,7 @@ extern "C" int qcx_diagonal_gate(unsigned first, unsigned num, const double *d, 
 }
 
 // The device form: the caller's table in place.  Where it lies is checked on the host; what it holds, on the device, on the
-// register's stream (k_diag_scan, note_nonfinite's flag word and its one sync) -- before the flush, so a refusal touches nothing.
+// register's stream (k_diag_scan through scan_flag_word: one sync) -- before the flush, so a refusal touches nothing.
 extern "C" int qcx_diagonal_gate_device(unsigned first, unsigned num, const void *d_device, qcx_register *r)
 {
     if (!r || !d_device) return QCX_BAD_ARGUMENTS;
@@ -2696,20 +2714,11 @@ extern "C" int qcx_diagonal_gate_device(unsigned first, unsigned num, const void
     const uintptr_t t0 = (uintptr_t)d_device, t1 = t0 + bytes;
     const auto overlaps = [&](const amp_t *p) { const uintptr_t a0 = (uintptr_t)p, a1 = a0 + (uintptr_t)(r->dim * sizeof(amp_t)); return p && t0 < a1 && a0 < t1; };
     if (overlaps(r->amp) || overlaps(r->scratch)) { set_error("diagonal_gate_device: the table overlaps the register's buffer"); return QCX_BAD_ARGUMENTS; }
-    {
-        Workspace *w;
-        QCX_TRY(workspace(&w));
-        std::lock_guard<std::mutex> use(g_ws_use[w - g_ws]);
-        HIP_TRY(hipMemsetAsync(w->meas_stats, 0, sizeof(unsigned), r->stream));
-        hipLaunchKernelGGL(k_diag_scan, dim3(grid_for(entries, 256 * 8, 65536, 256)), dim3(256), 0, r->stream, (const amp_t *)d_device, entries, w->meas_stats);
-        HIP_TRY(hipGetLastError());
-        const unsigned keep = w->h_meas_stats[0];                // (note_nonfinite's use of the pinned word)
-        HIP_TRY(hipMemcpyAsync(w->h_meas_stats, w->meas_stats, sizeof(unsigned), hipMemcpyDeviceToHost, r->stream));
-        HIP_TRY(hipStreamSynchronize(r->stream));
-        const unsigned bad = w->h_meas_stats[0];
-        w->h_meas_stats[0] = keep;
-        if (bad) { set_error("diagonal_gate_device: the table holds a component that is not finite or exceeds 1 in absolute value"); return QCX_BAD_ARGUMENTS; }
-    }
+    unsigned bad = 0;
+    QCX_TRY(scan_flag_word(r->stream, [&](unsigned *word) {
+        hipLaunchKernelGGL(k_diag_scan, dim3(grid_for(entries, 256 * 8, 65536, 256)), dim3(256), 0, r->stream, (const amp_t *)d_device, entries, word);
+    }, &bad));
+    if (bad) { set_error("diagonal_gate_device: the table holds a component that is not finite or exceeds 1 in absolute value"); return QCX_BAD_ARGUMENTS; }
     return diagonal_run(r, "diagonal_gate_device", first, num, (const amp_t *)d_device);
 }
 
@@ -2761,17 +2770,13 @@ extern "C" int qcx_gate_batch(qcx_register *r, unsigned long ngates, const qcx_g
         }
         return QCX_NO_ERROR;
     }
-    for (unsigned long k = 0; k < ngates;) {
-        const unsigned long p = pass_of[k];
-        unsigned cnt = 0;
-        while (k + cnt < ngates && pass_of[k + cnt] == p) cnt++;
+    return for_each_pass(pass_of, [&](unsigned long k, unsigned cnt, unsigned long p) {
         QCX_TRY(qcx_shard_gate_run(r->amp, r->n, hot[p], cnt, gates + k, r->stream));
         for (unsigned c = 0; c < cnt; c++)
             if (masks[k + c] & 0xFF) r->gateb_lds++;
         r->gateb_passes++;
-        k += cnt;
-    }
-    return QCX_NO_ERROR;
+        return (int)QCX_NO_ERROR;
+    });
 }
 
 extern "C" int qcx_gate_batch_last_stats(qcx_register *r, unsigned long *passes, unsigned long *lds_gates)
@@ -3009,6 +3014,31 @@ static int marg_reserve(qcx_register *r, size_t need)
     return QCX_NO_ERROR;
 }
 
+// the doubles a plan's partials take: every stage but the final one writes 2^out_bits of them at its out_offset
+static size_t stages_scratch(const qcx_marginal_stage *st, unsigned ns)
+{
+    size_t scratch = 0;
+    for (unsigned i = 0; i < ns; i++)
+        if (!st[i].final_stage) scratch = std::max<size_t>(scratch, (size_t)(st[i].out_offset + (((uint64_t)1) << st[i].out_bits)));
+    return scratch;
+}
+
+// Stages [from, ns) of a plan, each a k_marginal<MARG_DBL> launch on r->stream: a stage reads the partials of the stage before it
+// at base + out_offset (stage 0: at base), the final one writes to out.  That kernel never looks at `bad` (MARG_COMPACT's word).
+static int later_stages(qcx_register *r, const qcx_marginal_stage *st, unsigned from, unsigned ns, double *base, double *out, unsigned *bad)
+{
+    for (unsigned i = from; i < ns; i++) {
+        MargParams P;
+        marginal_params(st[i], &P);
+        P.src = i == 0 ? base : base + st[i - 1].out_offset;
+        P.dst = st[i].final_stage ? out : base + st[i].out_offset;
+        P.bad = bad;
+        hipLaunchKernelGGL(k_marginal<MARG_DBL>, dim3((unsigned)std::min<uint64_t>(P.ntiles, 2048)), dim3(256), 0, r->stream, P);
+        HIP_TRY(hipGetLastError());
+    }
+    return QCX_NO_ERROR;
+}
+
 // K10: the marginal of bits [first, first + num) (include/qcx.h, DESIGN s4.5d).  The planned stages run on r->stream: the first
 // reads the state (the register, or the compact form in place), the others only the partials; then one copy of the output.
 static int marginal_launch(qcx_register *r, const void *src, bool compact, unsigned first, unsigned num, double *probs, bool *bad_out)
@@ -3017,22 +3047,19 @@ static int marginal_launch(qcx_register *r, const void *src, bool compact, unsig
     unsigned ns = 0;
     if (compact) QCX_TRY(qcx_marginal_plan_compact(r->n, (unsigned)r->M, first, num, st, &ns));
     else QCX_TRY(qcx_marginal_plan(r->n, first, num, st, &ns));
-    size_t scratch = 0;
-    for (unsigned i = 0; i < ns; i++)
-        if (!st[i].final_stage) scratch = std::max<size_t>(scratch, (size_t)(st[i].out_offset + (((uint64_t)1) << st[i].out_bits)));
-    const size_t nout = (size_t)1 << num;
+    const size_t scratch = stages_scratch(st, ns), nout = (size_t)1 << num;
     QCX_TRY(marg_reserve(r, scratch + nout + 1));
     double *const out = r->marg_buf + scratch;
     unsigned *const bad = (unsigned *)(out + nout);
     if (compact) HIP_TRY(hipMemsetAsync(bad, 0, sizeof(unsigned), r->stream));
-    for (unsigned i = 0; i < ns; i++) {
+    {
         MargParams P;
-        marginal_params(st[i], &P);
-        P.src = i == 0 ? src : (const void *)(r->marg_buf + st[i - 1].out_offset);
-        P.dst = st[i].final_stage ? out : r->marg_buf + st[i].out_offset;
+        marginal_params(st[0], &P);
+        P.src = src;
+        P.dst = st[0].final_stage ? out : r->marg_buf + st[0].out_offset;
         P.bad = bad;
         const unsigned grid = (unsigned)std::min<uint64_t>(P.ntiles, 2048);
-        if (st[i].kind == 2) {
+        if (st[0].kind == 2) {
             // the sparse tree of one block's 2^M leaves: +0 everywhere but at the orbit residues (columns, ascending)
             const unsigned M = (unsigned)r->M;
             std::vector<std::pair<unsigned, unsigned>> nodes;          // (position at this level, slot)
@@ -3056,17 +3083,27 @@ static int marginal_launch(qcx_register *r, const void *src, bool compact, unsig
             }
             P.cb = r->compact_E.cb; P.ncols = r->compact_E.ncols;
             hipLaunchKernelGGL(k_marginal<MARG_COMPACT>, dim3(grid), dim3(256), 0, r->stream, P);
-        } else if (st[i].kind == 0)
+        } else
             hipLaunchKernelGGL(k_marginal<MARG_AMP>, dim3(grid), dim3(256), 0, r->stream, P);
-        else
-            hipLaunchKernelGGL(k_marginal<MARG_DBL>, dim3(grid), dim3(256), 0, r->stream, P);
         HIP_TRY(hipGetLastError());
     }
+    QCX_TRY(later_stages(r, st, 1, ns, r->marg_buf, out, bad));
     unsigned hbad = 0;
     HIP_TRY(hipMemcpyAsync(probs, out, nout * sizeof(double), hipMemcpyDeviceToHost, r->stream));
     if (compact) HIP_TRY(hipMemcpyAsync(&hbad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
     *bad_out = hbad != 0;
+    return QCX_NO_ERROR;
+}
+
+// Behind an observer's checks and its basis shortcut: r->amp holds the state.  A compact result is expanded into the register's
+// buffer (stale while the state is compact) and stays what later calls see; *source then says SRC_EXPANDED.
+static int state_into_register(qcx_register *r, unsigned *source)
+{
+    QCX_TRY(settle_for_read(r));
+    if (!r->compact_pending) return QCX_NO_ERROR;
+    QCX_TRY(launch_expand_compact(r->compact_amp, r->amp, r->n, r->compact_E, r->stream));
+    *source = SRC_EXPANDED;
     return QCX_NO_ERROR;
 }
 
@@ -3076,42 +3113,47 @@ extern "C" int qcx_marginal_probabilities(qcx_register *r, unsigned first, unsig
     if (r->sh) return QCX_UNSUPPORTED;
     if ((uint64_t)first + num > r->n) return QCX_BAD_QUBIT;
     if (num > 30) return QCX_UNSUPPORTED;
-    r->marg_source = 0; r->marg_reads = 0;
+    r->marg = {SRC_REGISTER, 0};
     const uint64_t nout = (uint64_t)1 << num;
     if (basis_only(r)) {
         // 1 at the basis state's range value, +0 everywhere else -- no kernel, the state stays unwritten
         const uint64_t v = (r->basis_index >> first) & (nout - 1u);
         for (uint64_t i = 0; i < nout; i++) probs[i] = i == v ? 1.0 : 0.0;
-        r->marg_source = 2;
+        r->marg.source = SRC_BASIS;
         return QCX_NO_ERROR;
     }
-    QCX_TRY(settle_for_read(r));
     bool bad = false;
-    if (r->compact_pending && first >= (unsigned)r->M) {
-        QCX_TRY(marginal_launch(r, r->compact_amp, true, first, num, probs, &bad));
-        r->marg_source = 1; r->marg_reads = 1;
-        r->compact_measures++;
-        if (!bad) return QCX_NO_ERROR;
-        // a padding column that is not +0: the compact premise broke -- as qcx_measure_state_r, expand (same bits) and read the
-        // register
-        QCX_TRY(expand_pending(r));
-    } else if (r->compact_pending) {
-        // a range inside the M register: the register's buffer (stale while the state is compact) gets the expanded state, and
-        // the compact form stays what later calls see
-        QCX_TRY(launch_expand_compact(r->compact_amp, r->amp, r->n, r->compact_E, r->stream));
-    }
+    if (first >= (unsigned)r->M) {
+        QCX_TRY(settle_for_read(r));
+        if (r->compact_pending) {                         // a range above the M register: the compact form in place
+            QCX_TRY(marginal_launch(r, r->compact_amp, true, first, num, probs, &bad));
+            r->marg = {SRC_COMPACT, 1};
+            r->compact_measures++;
+            if (!bad) return QCX_NO_ERROR;
+            // a padding column that is not +0: the compact premise broke -- as qcx_measure_state_r, expand (same bits) and
+            // read the register
+            QCX_TRY(expand_pending(r));
+        }
+    } else
+        QCX_TRY(state_into_register(r, &r->marg.source));
     QCX_TRY(marginal_launch(r, r->amp, false, first, num, probs, &bad));
-    r->marg_reads += 1;
-    if (r->marg_source == 1 || r->compact_pending) r->marg_source = 3;
+    r->marg.reads += 1;
+    if (r->marg.source == SRC_COMPACT) r->marg.source = SRC_EXPANDED;
+    return QCX_NO_ERROR;
+}
+
+// the body of an observer's *_last_stats getter, on its ReadStats member of the register
+static int last_stats(const qcx_register *r, const ReadStats qcx_register::*which, unsigned *source, unsigned long *state_reads)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (source) *source = (r->*which).source;
+    if (state_reads) *state_reads = (r->*which).reads;
     return QCX_NO_ERROR;
 }
 
 extern "C" int qcx_marginal_last_stats(qcx_register *r, unsigned *source, unsigned long *state_reads)
 {
-    if (!r) return QCX_BAD_ARGUMENTS;
-    if (source) *source = r->marg_source;
-    if (state_reads) *state_reads = r->marg_reads;
-    return QCX_NO_ERROR;
+    return last_stats(r, &qcx_register::marg, source, state_reads);
 }
 
 // K14 / K14b: the stages of a Pauli string's value are those of qcx_marginal_plan(n, 0, 0) -- "sum everything" --, with a Pauli
@@ -3129,24 +3171,7 @@ static int pauli_stages(qcx_register *r, PauliStages *ps)
         set_error("qcx_pauli_expectation: unexpected first stage in the plan of n = %u", r->n);
         return QCX_UNKNOWN_ERROR;
     }
-    ps->row = 0;
-    for (unsigned i = 0; i < ps->ns; i++)
-        if (!st[i].final_stage) ps->row = std::max<size_t>(ps->row, (size_t)(st[i].out_offset + (((uint64_t)1) << st[i].out_bits)));
-    return QCX_NO_ERROR;
-}
-
-// the stages behind the first on one string's partials at `row`: plain k_marginal<MARG_DBL> launches, the value to *out
-static int pauli_later_stages(qcx_register *r, const PauliStages &ps, double *row, double *out)
-{
-    for (unsigned i = 1; i < ps.ns; i++) {
-        MargParams P;
-        marginal_params(ps.st[i], &P);
-        P.src = row + ps.st[i - 1].out_offset;
-        P.dst = ps.st[i].final_stage ? out : row + ps.st[i].out_offset;
-        P.bad = nullptr;
-        hipLaunchKernelGGL(k_marginal<MARG_DBL>, dim3((unsigned)std::min<uint64_t>(P.ntiles, 2048)), dim3(256), 0, r->stream, P);
-        HIP_TRY(hipGetLastError());
-    }
+    ps->row = stages_scratch(st, ps->ns);
     return QCX_NO_ERROR;
 }
 
@@ -3164,7 +3189,7 @@ static int pauli_launch(qcx_register *r, uint64_t x, uint64_t z, double *value)
         hipLaunchKernelGGL((k_pauli_leaves<f.shape, f.full>), dim3((unsigned)std::min<uint64_t>(pu.nunits, 2048)), dim3(256), 0, r->stream, (const amp_t *)r->amp, dst0, pu.nunits, ps.T, x, z, g);
     });
     HIP_TRY(hipGetLastError());
-    QCX_TRY(pauli_later_stages(r, ps, r->marg_buf, out));
+    QCX_TRY(later_stages(r, ps.st, 1, ps.ns, r->marg_buf, out, nullptr));
     HIP_TRY(hipMemcpyAsync(value, out, sizeof(double), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
     return QCX_NO_ERROR;
@@ -3230,7 +3255,7 @@ static int pauli_batch_launch(qcx_register *r, uint64_t x, unsigned K, const uns
         else hipLaunchKernelGGL((k_pauli_leaves_batch<f.shape, f.full, false>), dim3(grid), dim3(256), 0, r->stream, (const amp_t *)r->amp, dst0, stride0, pu.nunits, ps.T, x, K, tm);
     });
     HIP_TRY(hipGetLastError());
-    for (unsigned k = 0; k < K; k++) QCX_TRY(pauli_later_stages(r, ps, r->marg_buf + k * ps.row, out + k));
+    for (unsigned k = 0; k < K; k++) QCX_TRY(later_stages(r, ps.st, 1, ps.ns, r->marg_buf + k * ps.row, out + k, nullptr));
     double got[QCX_PAULI_BATCH_W];
     HIP_TRY(hipMemcpyAsync(got, out, K * sizeof(double), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
@@ -3252,7 +3277,7 @@ static int pauli_batches(qcx_register *r, unsigned long nterms, const uint64_t *
     for (unsigned long p = 0; p < np; p++) {
         const std::vector<unsigned long> &m = members[p];
         QCX_TRY(pauli_batch_launch(r, xs[m[0]], (unsigned)m.size(), m.data(), zs, values, (unsigned)rows));
-        r->exp_reads += 1;
+        r->exp.reads += 1;
     }
     return QCX_NO_ERROR;
 }
@@ -3267,7 +3292,7 @@ static int pauli_terms(qcx_register *r, unsigned long nterms, const uint64_t *xs
                       (unsigned long long)zs[k], r->n);
             return QCX_BAD_QUBIT;
         }
-    r->exp_source = 0; r->exp_reads = 0;
+    r->exp = {SRC_REGISTER, 0};
     if (nterms == 0) return QCX_NO_ERROR;
     if (basis_only(r)) {
         // amplitude 1 at basis_index: a string with an X or a Y has no diagonal entry there, a Z-type one reads the parity
@@ -3275,21 +3300,15 @@ static int pauli_terms(qcx_register *r, unsigned long nterms, const uint64_t *xs
             const double v = xs[k] ? 0.0 : ((__builtin_popcountll(r->basis_index & zs[k]) & 1) ? -1.0 : 1.0);
             if (values) values[k] = v;
         }
-        r->exp_source = 2;
+        r->exp.source = SRC_BASIS;
         return QCX_NO_ERROR;
     }
-    QCX_TRY(settle_for_read(r));
-    if (r->compact_pending) {
-        // as the marginal of a range inside the M register: the register's buffer (stale while the state is compact) gets the
-        // expanded state, and the compact form stays what later calls see
-        QCX_TRY(launch_expand_compact(r->compact_amp, r->amp, r->n, r->compact_E, r->stream));
-        r->exp_source = 3;
-    }
+    QCX_TRY(state_into_register(r, &r->exp.source));
     if (batch) return pauli_batches(r, nterms, xs, zs, values);
     for (unsigned long k = 0; k < nterms; k++) {
         double v = 0.0;
         QCX_TRY(pauli_launch(r, xs[k], zs[k], &v));
-        r->exp_reads += 1;
+        r->exp.reads += 1;
         if (values) values[k] = v;
     }
     return QCX_NO_ERROR;
@@ -3331,10 +3350,7 @@ extern "C" int qcx_pauli_expectation_batch(qcx_register *r, unsigned long nterms
 
 extern "C" int qcx_expectation_last_stats(qcx_register *r, unsigned *source, unsigned long *state_reads)
 {
-    if (!r) return QCX_BAD_ARGUMENTS;
-    if (source) *source = r->exp_source;
-    if (state_reads) *state_reads = r->exp_reads;
-    return QCX_NO_ERROR;
+    return last_stats(r, &qcx_register::exp, source, state_reads);
 }
 
 // ---- K16: the reduced density matrix of bits [first, first + num) (include/qcx.h, DESIGN s4.5j) -----------------------------------
@@ -3372,15 +3388,7 @@ static int rdm_launch(qcx_register *r, unsigned first, unsigned num, double *com
 #undef QCX_RDM_LAUNCH
     }
     HIP_TRY(hipGetLastError());
-    for (unsigned i = 0; i < ns; i++) {
-        MargParams P;
-        marginal_params(st[i], &P);
-        P.src = i == 0 ? r->marg_buf : r->marg_buf + st[i - 1].out_offset;
-        P.dst = st[i].final_stage ? out : r->marg_buf + st[i].out_offset;
-        P.bad = nullptr;
-        hipLaunchKernelGGL(k_marginal<MARG_DBL>, dim3((unsigned)std::min<uint64_t>(P.ntiles, 2048)), dim3(256), 0, r->stream, P);
-        HIP_TRY(hipGetLastError());
-    }
+    QCX_TRY(later_stages(r, st, 0, ns, r->marg_buf, out, nullptr));
     HIP_TRY(hipMemcpyAsync(comps, out, s0.rows * sizeof(double), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
     return QCX_NO_ERROR;
@@ -3392,26 +3400,20 @@ extern "C" int qcx_reduced_density_matrix(qcx_register *r, unsigned first, unsig
     if (r->sh) return QCX_UNSUPPORTED;
     if ((uint64_t)first + num > r->n) return QCX_BAD_QUBIT;
     if (num > QCX_RDM_MAX_QUBITS) return QCX_UNSUPPORTED;
-    r->rdm_source = 0; r->rdm_reads = 0;
+    r->rdm = {SRC_REGISTER, 0};
     const unsigned nv = 1u << num;
     if (basis_only(r)) {
         // amplitude 1 at basis_index: the projector on its range value -- no kernel, the state stays unwritten
         const unsigned v = (unsigned)((r->basis_index >> first) & (nv - 1u));
         for (unsigned i = 0; i < 2u * nv * nv; i++) rho[i] = 0.0;
         rho[2u * (v * nv + v)] = 1.0;
-        r->rdm_source = 2;
+        r->rdm.source = SRC_BASIS;
         return QCX_NO_ERROR;
     }
-    QCX_TRY(settle_for_read(r));
-    if (r->compact_pending) {
-        // as a Pauli string's value: the register's buffer (stale while the state is compact) gets the expanded state, and the
-        // compact form stays what later calls see
-        QCX_TRY(launch_expand_compact(r->compact_amp, r->amp, r->n, r->compact_E, r->stream));
-        r->rdm_source = 3;
-    }
+    QCX_TRY(state_into_register(r, &r->rdm.source));
     double comps[1u << (2 * QCX_RDM_MAX_QUBITS)];
     QCX_TRY(rdm_launch(r, first, num, comps));
-    r->rdm_reads = 1;
+    r->rdm.reads = 1;
     // row v nv + w, v <= w, holds Re rho[v][w], row w nv + v its imaginary part; the lower triangle is the conjugate
     for (unsigned v = 0; v < nv; v++) {
         rho[2u * (v * nv + v)] = comps[v * nv + v];
@@ -3427,10 +3429,7 @@ extern "C" int qcx_reduced_density_matrix(qcx_register *r, unsigned first, unsig
 
 extern "C" int qcx_rdm_last_stats(qcx_register *r, unsigned *source, unsigned long *state_reads)
 {
-    if (!r) return QCX_BAD_ARGUMENTS;
-    if (source) *source = r->rdm_source;
-    if (state_reads) *state_reads = r->rdm_reads;
-    return QCX_NO_ERROR;
+    return last_stats(r, &qcx_register::rdm, source, state_reads);
 }
 
 // K11: measure or post-select the qubits [first, first + num) and collapse the state (include/qcx.h, DESIGN s4.5e).  Two passes:
@@ -3461,12 +3460,12 @@ static int collapse_range(qcx_register *r, unsigned first, unsigned num, double 
         set_error("qcx_postselect_qubits: outcome %lu does not fit %u qubits", *given, num);
         return QCX_BAD_ARGUMENTS;
     }
-    r->coll_source = 0; r->coll_reads = 0; r->coll_writes = 0;
+    r->coll = {SRC_REGISTER, 0}; r->coll_writes = 0;
     const bool was_basis = basis_only(r);
     std::vector<double> P(nout);
     QCX_TRY(qcx_marginal_probabilities(r, first, num, P.data()));
-    r->coll_reads = r->marg_reads;
-    r->coll_source = was_basis ? 2u : (r->marg_source == 1 || r->marg_source == 3) ? 3u : 0u;
+    r->coll.reads = r->marg.reads;
+    r->coll.source = was_basis ? SRC_BASIS : (r->marg.source == SRC_COMPACT || r->marg.source == SRC_EXPANDED) ? SRC_EXPANDED : SRC_REGISTER;
     uint64_t v = nout - 1;                                                  // Q:283 fall-through
     if (given) v = *given;
     else {
@@ -3528,9 +3527,7 @@ extern "C" int qcx_collapse_pass(qcx_register *r, unsigned first, unsigned num, 
 
 extern "C" int qcx_collapse_last_stats(qcx_register *r, unsigned *source, unsigned long *state_reads, unsigned long *state_writes)
 {
-    if (!r) return QCX_BAD_ARGUMENTS;
-    if (source) *source = r->coll_source;
-    if (state_reads) *state_reads = r->coll_reads;
+    QCX_TRY(last_stats(r, &qcx_register::coll, source, state_reads));
     if (state_writes) *state_writes = r->coll_writes;
     return QCX_NO_ERROR;
 }

@@ -4581,22 +4581,6 @@ __global__ __launch_bounds__(64) void k_cu_lines(amp_t *__restrict__ amp, unsign
     }
 }
 
-// K12s  the controlled gate as a STRICT pass (K9's reason: a register that holds non-finite amplitudes): the same rows on the
-// control-set pairs, and every control-clear amplitude rewritten through the reference's identity row q_row((1, 0) * x);
-// `one` and `z` are kernel arguments so that no product is folded.  (The plain gate needs no strict
-// twin: K12a / K12b already multiply every stored triplet out and rewrite every amplitude.)
-__global__ __launch_bounds__(256) void k_strict_cu(amp_t *__restrict__ amp, unsigned n, unsigned q, unsigned c, UMat U, double one, double z)
-{
-    const uint64_t half = (uint64_t)1 << (n - 1);
-    for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < half; p += (uint64_t)gridDim.x * 256u) {
-        const uint64_t i0 = insert_zero(p, q), i1 = i0 | ((uint64_t)1 << q);
-        amp_t a = amp[i0], b = amp[i1];
-        if ((i0 >> c) & 1u) u_butterfly(U, a, b);
-        else { a = q_row(q_mul(one, z, a)); b = q_row(q_mul(one, z, b)); }
-        amp[i0] = a; amp[i1] = b;
-    }
-}
-
 // ---------------------------------------------------------------------------
 // K13  any two-qubit gate, plain or controlled (qcx_two_qubit_gate / qcx_c_two_qubit_gate, DESIGN s4.5g): the 4x4 matrix m on
 // the quads (i, i | 2^lo, i | 2^hi, i | 2^lo | 2^hi), lo < hi, as the reference's mat-vec would apply it from sixteen stored
@@ -4711,25 +4695,6 @@ __global__ __launch_bounds__(64) void k_u2_lines(amp_t *__restrict__ amp, unsign
             if (hit) u4_quad(U, x0, x1, x2, x3);
             if (hit || store_all) { st<NT>(amp + i, x0); st<NT>(amp + (i | lob), x1); st<NT>(amp + (i | hib), x2); st<NT>(amp + (i | lob | hib), x3); }
         }
-    }
-}
-
-// K13s  the controlled gate as a STRICT pass (K9's reason: a register that holds non-finite amplitudes): one plain pass over all
-// 2^(n-2) quads, the defined rows on the control-set quads, and every control-clear amplitude rewritten through the reference's
-// identity row; `one` and `z` are kernel arguments so that no product is folded, as in k_strict_cu.  (The plain gate needs no
-// strict twin: every form of K13 rewrites every amplitude from all sixteen products; the non-finite tests prove it.)
-__global__ __launch_bounds__(256) void k_strict_cu2(amp_t *__restrict__ amp, unsigned n, unsigned lo, unsigned hi, unsigned c, U4Mat U, double one, double z)
-{
-    const uint64_t quads = (uint64_t)1 << (n - 2), lob = (uint64_t)1 << lo, hib = (uint64_t)1 << hi;
-    for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < quads; p += (uint64_t)gridDim.x * 256u) {
-        const uint64_t i = insert_zero(insert_zero(p, lo), hi);
-        amp_t x[4] = {amp[i], amp[i | lob], amp[i | hib], amp[i | lob | hib]};
-        if ((i >> c) & 1u) u4_quad(U, x[0], x[1], x[2], x[3]);
-        else {
-#pragma unroll
-            for (int k = 0; k < 4; k++) x[k] = q_row(q_mul(one, z, x[k]));
-        }
-        amp[i] = x[0]; amp[i | lob] = x[1]; amp[i | hib] = x[2]; amp[i | lob | hib] = x[3];
     }
 }
 
@@ -4853,9 +4818,11 @@ __global__ __launch_bounds__(64) void k_mcu2_lines(amp_t *__restrict__ amp, unsi
     }
 }
 
-// K17s  the strict twins (K9's reason: a register that holds non-finite amplitudes): one plain pass over all pairs / quads, the
-// defined rows where the mask matches and the reference's identity row elsewhere; `one` and `z` are kernel arguments so that
-// no product is folded, as in k_strict_cu.
+// K12s / K13s / K17s  a controlled gate as a STRICT pass (K9's reason: a register that holds non-finite amplitudes), for one
+// control as for any mask: one plain pass over all pairs / quads, the defined rows where (i & cmask) == cvals, and every other
+// amplitude rewritten through the reference's identity row q_row((1, 0) * x); `one` and `z` are kernel arguments so that no
+// product is folded.  (The plain gates need no strict twin: every form of K12 and K13 multiplies every stored triplet out and
+// rewrites every amplitude; the non-finite tests prove it.)
 __global__ __launch_bounds__(256) void k_strict_mcu(amp_t *__restrict__ amp, unsigned n, unsigned q, uint64_t cmask, uint64_t cvals, UMat U,
                                                     double one, double z)
 {

@@ -261,6 +261,40 @@ def test_chain_two_registers_nan_write_between_the_others_measurements(qc, ob, t
     assert run_b(True) == run_b(False)
 
 
+def test_chain_two_registers_device_table_scan_returns_the_borrowed_word(qc, ob, tmp_path):
+    """qcx_diagonal_gate_device checks its table through the flag word that doubles as the last measurement scan's statistics: B's
+    statistics survive A's call, whether the table passes or is refused, and the refusal leaves A's state alone.  B has n = 12:
+    the smallest register whose scan is the parallel one (meas_min_log2), the only scan that writes those statistics -- at
+    n = 10 the record count is 0"""
+    import torch
+    import diagonal_ref as dr
+    with Chain(qc, ob, 8, 4, 0, tmp_path, "b") as b, Chain(qc, ob, 3, 4, 1, tmp_path, "a") as a:
+        b.do("fill", 5)
+        b.do("h", 3)
+        a.do("fill", 1); a.do("h", 2)
+        b.do("sample", 7, 17)
+        before = measure_last_stats(qc)
+        assert before[1] > 0, "B's scan must be the parallel one, which records its blocks"
+        held = a.state()
+        ph = np.linspace(-3.0, 3.0, 1 << 5)
+        t = np.clip(np.cos(ph), -1, 1) + 1j * np.clip(np.sin(ph), -1, 1)
+        dev = torch.from_numpy(t).cuda()
+        torch.cuda.synchronize()
+        qc.diagonal_gate(1, 5, dev, a.reg)
+        assert measure_last_stats(qc) == before, "the scan of A's table changed the statistics of B's last scan"
+        after = a.reg.read()
+        same(after, dr.apply(held, a.n, 1, 5, t), "A behind the table that passed")
+        t[9] = complex(0.5, np.nan)
+        dev = torch.from_numpy(t).cuda()
+        torch.cuda.synchronize()
+        with pytest.raises(qc.QcxError) as e:
+            qc.diagonal_gate(1, 5, dev, a.reg)
+        assert e.value.status == rm.BAD_ARGUMENTS
+        assert measure_last_stats(qc) == before, "the refused table's flag stayed in the statistics of B's last scan"
+        assert np.array_equal(bits(a.reg.read()), bits(after)), "the refusal touched A's state"
+        b.do("sample", 8, 8)                                              # B goes on from the state it had
+
+
 def test_chain_circuit_queued_in_mode_1_sample_then_partial_write(qc, ob, tmp_path, shor_20):
     with Chain(qc, ob, 15, 5, 1, tmp_path) as c:
         k0, m0 = compact_chains(qc, c.reg), compact_measures(qc, c.reg)
@@ -714,6 +748,56 @@ def test_chain_density_matrix_and_batch_behind_the_handed_out_pointer_on_a_calle
         c.do("rdm", 0, 1)
         assert c.reg.rdm_stats() == (2, 0)
         c.do("devptr", 0, c.dim)
+
+
+def last_stats(reg):
+    return {"marginal": reg.marginal_stats(), "expectation": reg.expectation_stats(), "rdm": reg.rdm_stats(), "collapse": reg.collapse_stats()}
+
+
+BATCH_OF_THREE = [(0.5, 0x2011, 0x0013), (-1.25, 0x2011, 0x8100), (2.0, 0, 0x0A05)]       # two x_masks: two reads of the state
+# (op, the getter it answers to): what every state below is asked, in this order
+OBSERVERS = [(("marginal", 8, 3), "marginal"), (("marginal", 1, 2), "marginal"), (("expect", 0x2011, 0x0013), "expectation"),
+             (("expect_batch",), "expectation"), (("rdm", 2, 2), "rdm"), (("measure_qubits", 3, 4, 0.5), "collapse")]
+# (source, state reads[, state writes]) of the callee behind each of OBSERVERS, per state: read off the build before the observers'
+# statistics became one struct and one getter body, not reasoned
+OWN_STATS = {
+    "basis":   [(2, 0), (2, 0), (2, 0), (2, 0), (2, 0), (2, 0, 0)],
+    "compact": [(1, 1), (3, 1), (3, 1), (3, 2), (3, 1), (3, 1, 1)],
+    "filled":  [(0, 1), (0, 1), (0, 1), (0, 2), (0, 1), (0, 1, 1)],
+}
+
+
+def test_chain_one_observers_last_call_statistics_are_its_own(qc, ob, tmp_path):
+    """the four *_last_stats getters behind every observer call, in three states of ONE register: the callee's pair is the
+    documented one, the others keep what they held -- but for measure_qubits, which runs the marginal and sets its pair too.
+    M = 4 and more than 12 qubits (the tiled Pauli and density-matrix kernels); L = 12 and not 9, because a register of 13 qubits
+    cannot hold a compact result: compact_chain wants L + 2 >= 14 for the four residues of C = 15 (register_model.COMPACT_SHAPES)"""
+    with Chain(qc, ob, 12, 4, 0, tmp_path) as c:
+        for state in ("basis", "compact", "filled"):
+            if state == "basis":
+                c.do("reset")
+            elif state == "compact":
+                k0 = compact_chains(qc, c.reg)
+                c.do("reset"); c.do("qcomp", 15, 7)
+                assert compact_chains(qc, c.reg) == k0 + 1
+            else:
+                c.do("fill", 6)
+            for (op, getter), own in zip(OBSERVERS, OWN_STATS[state]):
+                before = last_stats(c.reg)
+                if op[0] == "expect_batch":                               # (Chain's op runs expectation_sum behind the batch)
+                    got = c.reg.expectation_batch([(cf, (x, z)) for cf, x, z in BATCH_OF_THREE])
+                    want = c.m.expectation_batch(BATCH_OF_THREE)
+                    same([got[0]], [want[0]], "the batch's sum"); same(got[1], want[1], "the values of the batch's terms")
+                else:
+                    c.do(*op)
+                after = last_stats(c.reg)
+                assert after[getter] == own, f"{state}: {op!r} left {getter} statistics {after[getter]}"
+                if getter == "collapse":                                  # (a range that begins inside the M register: one source)
+                    assert after["marginal"] == own[:2], f"{state}: measure_qubits runs the marginal: {after['marginal']}"
+                    before["marginal"] = after["marginal"]
+                before[getter] = after[getter]
+                assert after == before, f"{state}: {op!r} moved another call's statistics: {before} -> {after}"
+        c.state()
 
 
 # marginal, density matrix and batch all borrow one scratch area of the register (marg_buf, grown by marg_reserve): sizes that
