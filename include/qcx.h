@@ -293,6 +293,36 @@ int  qcx_diagonal_gate_device(unsigned first_qubit, unsigned num_qubits, const v
 unsigned qcx_diagonal_host_max_qubits(void);     /* a build constant: 20 (a 16-MiB table) */
 /* the last qcx_diagonal_gate(_device) call on this register that passed its checks: form = the plan's, table_entries = 2^num_qubits */
 int  qcx_diagonal_last_stats(qcx_register *reg, unsigned *form, unsigned long *table_entries);
+/* A classical reversible function on the qubit range [first_qubit, first_qubit + num_qubits), |k> -> |perm[k]>, under any set
+ * of controls of either polarity, in ONE pass over the amplitudes that fire (the general form of qcx_c_amodc_gate; the matrix
+ * applied as the reference's mat-vec applies every gate, Q:393-413; tests/permutation_ref.py restates it in numpy and IS the
+ * definition; K19, DESIGN s4.5o).  perm holds 2^num_qubits entries, a bijection of [0, 2^num_qubits); qubit first_qubit is bit 0
+ * of k.  Index i fires when (i & ctrl_mask) == ctrl_values; the operator is the permutation matrix that sends a firing i to i
+ * with its range bits k replaced by perm[k], and the identity on every other index.  Every row holds the one triplet (1, 0):
+ * with x = old[source of the row], every fl() one binary64 rounding, no FMA,
+ *     new.re = fl(0.0 + fl(fl(1.0*x.re) - fl(0.0*x.im))),   new.im = fl(0.0 + fl(fl(1.0*x.im) + fl(0.0*x.re)))
+ *   On a finite state that is pure movement with -0 turned into +0: a register that holds finite amplitudes (its zeros are
+ *   made +0 first, as for every exact gate) has the firing amplitudes moved by one kernel and nothing else touched.  A register
+ *   flagged non-finite takes one strict pass that rewrites EVERY amplitude by the formula (an Inf or NaN poisons the other
+ *   component of its amplitude, as under qcx_mc_one_qubit_gate) and keeps its flag.  The identity table (num_qubits = 0 is one)
+ *   on a finite register launches no kernel.
+ *   So, bit for bit on finite states: (1, 0) on one qubit is X, under controls CNOT and Toffoli; (0, 2, 1, 3) is SWAP, under
+ *   a control Fredkin; k -> a k mod C below C on the low M bits under a control above them is qcx_c_amodc_gate.
+ * The table is inverted on the host and copied into the library's scratch before the call returns, so the caller may reuse
+ * perm at once.  qcx_pauli_rotation's sequence: asynchronous, on the register's stream; flushes queued gates, a pending basis
+ * state and a compact circuit result in every fusion mode; never enters the queue, is not counted by qcx_fusion_stats, stays
+ * exact in mode 2.  qcx_permutation_plan in qcx_plan.h is the launch rule on its own.
+ * Checked in this order, before anything runs and with nothing touched: NULL reg or perm: QCX_BAD_ARGUMENTS; ctrl_values with
+ * bits outside ctrl_mask: QCX_BAD_ARGUMENTS; first_qubit + num_qubits > n: QCX_BAD_QUBIT; a mask bit at or above n or inside
+ * the range: QCX_BAD_QUBIT; num_qubits above qcx_permutation_max_qubits(): QCX_BAD_ARGUMENTS (the message states the maximum);
+ * an entry >= 2^num_qubits or a value that occurs twice: QCX_BAD_ARGUMENTS (the message names the first such entry and its
+ * value); a sharded register: QCX_UNSUPPORTED. */
+int  qcx_permutation_gate(uint64_t ctrl_mask, uint64_t ctrl_values, unsigned first_qubit, unsigned num_qubits,
+                          const uint32_t *perm, qcx_register *reg);
+unsigned qcx_permutation_max_qubits(void);       /* a build constant: 12 (a tile of 2^12 amplitudes holds the range) */
+/* the last qcx_permutation_gate call on this register that passed its checks: form = the plan's (QCX_PERM_* of qcx_plan.h),
+ * moved = the number of k with perm[k] != k */
+int  qcx_permutation_last_stats(qcx_register *reg, unsigned *form, unsigned long *moved);
 int  qcx_swap_states(qcx_register *reg);                                           /* Q:242-249: no-op */
 /* host-side gate schedules */
 int  qcx_inverse_QFT(qcx_register *reg);                                           /* Q:678-690 */

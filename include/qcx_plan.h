@@ -244,6 +244,51 @@ typedef struct {
     char     kernel[48];            /* the instantiation as a kernel trace spells it, e.g. "k_diagonal<2, true, false>" */
 } qcx_diag_plan;
 int  qcx_diagonal_plan(unsigned n, unsigned first, unsigned num, qcx_diag_plan *out);
+
+/* The launch of qcx_permutation_gate (include/qcx.h; K19, DESIGN s4.5o) for the range [first, first + num) of a register of n
+ * qubits under the controls (ctrl_mask, ctrl_values), on a register that holds finite amplitudes, on the host, under the knobs
+ * of the moment; the library launches from this very function.
+ * Controls at bit >= 3 are squeezed out of the work numbering, qcx_mc_gate_plan's rule: `squeezed` is their mask, its ascending
+ * runs are [run_pos[k], run_pos[k] + run_len[k]), k < nruns, and or_const holds the positive ones.  With unsqueezed = n - the
+ * squeezed positions, a tile is 2^T amplitudes, T = min(12, unsqueezed, max(num + 3, the knob perm_tile_log2)) -- the range and
+ * three more bits, no less than the knob asks for (12, so T = min(12, unsqueezed) for every range): tile_mask = the num
+ * range bits and the lowest T - num of the other unsqueezed bits (tile_bits[0 .. T) lists them ascending), so every tile is
+ * closed under any table.  unit_mask =
+ * the unsqueezed bits outside the tile; `units` = 2^(unsqueezed - T) tiles, and workgroup b of `grid` takes the units b, b + grid,
+ * ...  Unit u, tile element e (thread tid of `block` owns e = tid + block j while e < 2^T) is the amplitude
+ *     i = deposit(u, unit_mask) | deposit(e, tile_mask) | or_const,
+ * deposit(v, mask) = v's bits moved, in order, into the set positions of mask.  The range field of e sits at bit range_pos of e:
+ * the element stores tile[e with (e >> range_pos) & (2^num - 1) replaced by the inverse table's entry] to i.
+ * A control below bit 3 is a predicate: elem_mask / elem_values where its bit lies in the tile (tested on i per element),
+ * unit_mask_low / unit_values_low where it does not (tested on deposit(u, unit_mask); a unit that misses is skipped, nothing of it
+ * is read).  store_all: under such a predicate the elements that do not act are stored back as read, so that whole lines leave
+ * (the knob perm_store_all, on by measurement; 0: they are left alone).
+ * form: QCX_PERM_LINES when the tile holds index bits 0-2 (all of them that exist), so that it is made of whole 128-B lines;
+ * QCX_PERM_SHARED when it does not (num >= 10 with first > 0): lines are shared between tiles.
+ * block = 1024 for T = 12, else 256; grid = min(units, the knob perm_grid_cap (0: no cap)), within what HIP takes; lds_bytes =
+ * 16 * 2^T for the tile + 2 * 2^num (rounded up to 16) for the inverse table: at most 64 KiB + 8 KiB.  nt: the knob perm_nt,
+ * nontemporal stores.
+ * NULL out, n = 0 or n > 40: QCX_BAD_ARGUMENTS; then qcx_permutation_gate's refusals, in its order: ctrl_values outside
+ * ctrl_mask: QCX_BAD_ARGUMENTS; first + num > n: QCX_BAD_QUBIT; a mask bit at or above n or inside the range: QCX_BAD_QUBIT;
+ * num > qcx_permutation_max_qubits(): QCX_BAD_ARGUMENTS. */
+#define QCX_PERM_MAX_QUBITS 12
+#define QCX_PERM_MAX_RUNS 20
+enum { QCX_PERM_LINES = 0, QCX_PERM_SHARED = 1 };
+typedef struct {
+    unsigned form, T, first, num;
+    unsigned range_pos;             /* the tile bits below `first` */
+    unsigned char tile_bits[QCX_PERM_MAX_QUBITS];
+    uint64_t tile_mask, unit_mask;
+    uint64_t squeezed, or_const;
+    unsigned nruns;
+    unsigned char run_pos[QCX_PERM_MAX_RUNS], run_len[QCX_PERM_MAX_RUNS];
+    unsigned elem_mask, elem_values, unit_mask_low, unit_values_low;
+    uint64_t units;
+    unsigned grid, block, lds_bytes;
+    unsigned store_all, nt;
+    char     kernel[48];            /* the instantiation as a kernel trace spells it, e.g. "k_perm_tile<false, false>" */
+} qcx_perm_plan;
+int  qcx_permutation_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, unsigned first, unsigned num, qcx_perm_plan *out);
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,10 @@ SIGNATURES = {
     "qcx_diagonal_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
     "qcx_diagonal_plan": (_i, [_u, _u, _u, _p]),
     "qcx_polar_array": (None, [_ul, _p, _p]),
+    "qcx_permutation_gate": (_i, [_u64, _u64, _u, _u, _p, _p]),
+    "qcx_permutation_max_qubits": (_u, []),
+    "qcx_permutation_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
+    "qcx_permutation_plan": (_i, [_u, _u64, _u64, _u, _u, _p]),
     "qcx_swap_states": (_i, [_p]),
     "qcx_inverse_QFT": (_i, [_p]),
     "qcx_quantum_computation": (_i, [_u, _u, _i, _p]),
@@ -313,6 +317,31 @@ def diagonal_plan(n, first, num):
 def diagonal_host_max_qubits():
     """the widest range diagonal_gate takes a host table for (qcx_diagonal_host_max_qubits); wider tables go in device memory"""
     return int(lib().qcx_diagonal_host_max_qubits())
+
+
+PERM_LINES, PERM_SHARED = range(2)                 # QCX_PERM_* (include/qcx_plan.h)
+
+
+class PermPlan(C.Structure):
+    """qcx_perm_plan (include/qcx_plan.h): the launch of a permutation of a qubit range's basis states"""
+    _fields_ = [("form", _u), ("T", _u), ("first", _u), ("num", _u), ("range_pos", _u), ("tile_bits", C.c_ubyte * 12),
+                ("tile_mask", _u64), ("unit_mask", _u64), ("squeezed", _u64), ("or_const", _u64), ("nruns", _u),
+                ("run_pos", C.c_ubyte * 20), ("run_len", C.c_ubyte * 20), ("elem_mask", _u), ("elem_values", _u),
+                ("unit_mask_low", _u), ("unit_values_low", _u), ("units", _u64), ("grid", _u), ("block", _u), ("lds_bytes", _u),
+                ("store_all", _u), ("nt", _u), ("kernel", C.c_char * 48)]
+
+
+def permutation_plan(n, ctrl_mask, ctrl_values, first, num):
+    """What permutation_gate(first, num, ...) under these controls would launch on n qubits that hold finite amplitudes, under
+    the knobs of the moment (host code, no GPU needed; include/qcx_plan.h: qcx_permutation_plan): (status, PermPlan)."""
+    pl = PermPlan()
+    st = lib().qcx_permutation_plan(int(n), int(ctrl_mask), int(ctrl_values), int(first), int(num), C.byref(pl))
+    return st, pl
+
+
+def permutation_max_qubits():
+    """the widest range permutation_gate takes a table for (qcx_permutation_max_qubits)"""
+    return int(lib().qcx_permutation_max_qubits())
 
 
 def pauli_batch_width():

@@ -172,6 +172,10 @@ extern "C" int qcx_set_device(int device) { HIP_TRY(hipSetDevice(device)); retur
     X(prot_grid_cap, 2048)        /* K15 (k_pauli_rot): workgroups, each walks its units (tiles, or pairs of tiles) with this stride; 0 = one unit each */ \
     X(diag_grid_cap, 2048)        /* K18 (k_diagonal): workgroups, each walks its tiles with this stride; 0 = one tile each */ \
     X(diag_lds, 0)                /* K18: 1 = the per-lane form (first < 8) copies a table of first + num <= 12 into LDS once per workgroup; 0 = every lane reads its entry from memory (DESIGN s4.5n has both times) */ \
+    X(perm_grid_cap, 2048)        /* K19 (k_perm_tile): workgroups, each walks its tiles with this stride; 0 = one tile each */ \
+    X(perm_tile_log2, 12)         /* K19: a tile is 2^this amplitudes or the range and three more bits, whichever is more, at most 2^12 (DESIGN s4.5o has the times of 8, 10 and 12) */ \
+    X(perm_store_all, 1)          /* K19: 1 = under a control below bit 3 the elements that do not fire are stored back as read (whole lines leave: 6.19 against 6.45 ms at n = 30) */ \
+    X(perm_nt, 0)                 /* K19: 1 = nontemporal stores */ \
     X(mc_generic, 0)              /* K17 (gates under a control mask): 1 = no control and one positive control run K17's kernels too (0: K12's / K13's launches; the tests compare the two bit for bit) */
 struct Tune {
 #define X(name, value) long name = value;
@@ -898,6 +902,97 @@ extern "C" int qcx_shard_diagonal(void *amp, unsigned n_local, unsigned first, u
     else                                { if (pl.full) QCX_DIAG(2, true, false); else QCX_DIAG(2, false, false); }
 #undef QCX_DIAG
     return launch_status("diagonal gate");
+}
+
+// ---- K19: a permutation of a qubit range's basis states from a table ---------------------------------------------------------------
+// the rule of include/qcx_plan.h, under one snapshot of the knobs.  strict: the pass of a register flagged non-finite -- nothing
+// squeezed, every control a predicate (P->pmask); otherwise P->pmask holds the controls below bit 3
+static int permutation_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t cvals, unsigned first, unsigned num, bool strict,
+                            qcx_perm_plan *out, PermParams *P)
+{
+    if (!out || n == 0 || n > 40) return QCX_BAD_ARGUMENTS;
+    if (cvals & ~cmask) { set_error("permutation_gate: ctrl_values %#llx has bits outside ctrl_mask %#llx", (unsigned long long)cvals, (unsigned long long)cmask); return QCX_BAD_ARGUMENTS; }
+    if (first > n || num > n - first) return QCX_BAD_QUBIT;
+    const uint64_t nmask = (((uint64_t)1) << n) - 1u;
+    const uint64_t range = num >= 64 ? ~(uint64_t)0 : ((((uint64_t)1) << num) - 1u) << first;
+    if ((cmask & ~nmask) != 0 || (cmask & range) != 0) return QCX_BAD_QUBIT;
+    if (num > QCX_PERM_MAX_QUBITS) {
+        set_error("permutation_gate: a table over %u qubits is more than the %u a tile holds", num, (unsigned)QCX_PERM_MAX_QUBITS);
+        return QCX_BAD_ARGUMENTS;
+    }
+    memset(out, 0, sizeof *out);
+    const uint64_t squeezed = strict ? 0 : cmask & ~(uint64_t)7;
+    const unsigned unsq = n - (unsigned)__builtin_popcountll(squeezed);
+    const unsigned want = (unsigned)std::min<long>(12, std::max<long>(0, t.perm_tile_log2));
+    const unsigned T = std::min(std::min(12u, unsq), std::max(num + 3u, want));
+    uint64_t tile = range, others = nmask & ~(squeezed | range);
+    for (unsigned k = num; k < T; k++) { tile |= others & (0 - others); others &= others - 1; }
+    out->T = T; out->first = first; out->num = num;
+    out->tile_mask = tile; out->unit_mask = others;
+    out->range_pos = (unsigned)__builtin_popcountll(tile & ((((uint64_t)1) << first) - 1u));
+    { unsigned k = 0; for (uint64_t m = tile; m; m &= m - 1) out->tile_bits[k++] = (unsigned char)__builtin_ctzll(m); }
+    out->squeezed = squeezed; out->or_const = cvals & squeezed;
+    for (unsigned b = 0; b < n;) {
+        if (!((squeezed >> b) & 1u)) { b++; continue; }
+        unsigned len = 1;
+        while (b + len < n && ((squeezed >> (b + len)) & 1u)) len++;
+        out->run_pos[out->nruns] = (unsigned char)b; out->run_len[out->nruns] = (unsigned char)len; out->nruns++;      // (at most 19 runs above bit 2 of 40 bits)
+        b += len;
+    }
+    const uint64_t pmask = cmask & ~squeezed, pvals = cvals & ~squeezed;
+    if (!strict) {
+        out->elem_mask = (unsigned)(pmask & tile); out->elem_values = (unsigned)(pvals & tile);
+        out->unit_mask_low = (unsigned)(pmask & ~tile); out->unit_values_low = (unsigned)(pvals & ~tile);
+    }
+    out->units = ((uint64_t)1) << (unsq - T);
+    out->form = (tile & 7u & nmask) == (7u & nmask) ? QCX_PERM_LINES : QCX_PERM_SHARED;
+    out->block = T == 12 ? 1024 : 256;
+    out->grid = grid_for(out->units, 1, t.perm_grid_cap, out->block);
+    out->lds_bytes = (16u << T) + (((2u << num) + 15u) & ~15u);
+    out->store_all = (!strict && t.perm_store_all != 0 && pmask != 0) ? 1 : 0;
+    out->nt = (!strict && t.perm_nt != 0) ? 1 : 0;
+    snprintf(out->kernel, sizeof out->kernel, "k_perm_tile<%s, %s>", strict ? "true" : "false", out->nt ? "true" : "false");
+    if (P) {
+        P->tile_mask = tile; P->unit_mask = others; P->orc = out->or_const; P->pmask = pmask; P->pvals = pvals; P->units = out->units;
+        P->T = T; P->pf = out->range_pos; P->num = num; P->store_all = (int)out->store_all;
+    }
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_permutation_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, unsigned first, unsigned num, qcx_perm_plan *out)
+{
+    return permutation_plan(tune_now(), n, ctrl_mask, ctrl_values, first, num, false, out, nullptr);
+}
+
+// The table's check and its inverse, on the host: inv[perm[k]] = k for a bijection of [0, 2^num), num <= QCX_PERM_MAX_QUBITS; the
+// first entry that is out of range or repeats a value is named.  moved = the number of k with perm[k] != k.
+static int permutation_invert(unsigned num, const uint32_t *perm, uint16_t *inv, unsigned long *moved)
+{
+    const uint32_t entries = 1u << num;
+    for (uint32_t k = 0; k < entries; k++) inv[k] = 0xFFFFu;               // (no entry: every value is below 2^12)
+    *moved = 0;
+    for (uint32_t k = 0; k < entries; k++) {
+        const uint32_t v = perm[k];
+        if (v >= entries) { set_error("permutation_gate: entry %u is %u, which is not below 2^%u", k, v, num); return QCX_BAD_ARGUMENTS; }
+        if (inv[v] != 0xFFFFu) { set_error("permutation_gate: entry %u is %u, the value entry %u already has: not a bijection", k, v, (unsigned)inv[v]); return QCX_BAD_ARGUMENTS; }
+        inv[v] = (uint16_t)k;
+        if (v != k) ++*moved;
+    }
+    return QCX_NO_ERROR;
+}
+
+// launches what the plan says; inv_dev: the inverse table in device memory, complete in stream order
+static int permutation_launch(amp_t *a, unsigned n, uint64_t cmask, uint64_t cvals, unsigned first, unsigned num, bool strict,
+                              const uint16_t *inv_dev, hipStream_t st)
+{
+    qcx_perm_plan pl;
+    PermParams P;
+    QCX_TRY(permutation_plan(tune_now(), n, cmask, cvals, first, num, strict, &pl, &P));
+    const dim3 grid(pl.grid), block(pl.block);
+    if (strict)     hipLaunchKernelGGL((k_perm_tile<true, false>), grid, block, pl.lds_bytes, st, a, inv_dev, P, 1.0, 0.0);
+    else if (pl.nt) hipLaunchKernelGGL((k_perm_tile<false, true>), grid, block, pl.lds_bytes, st, a, inv_dev, P, 1.0, 0.0);
+    else            hipLaunchKernelGGL((k_perm_tile<false, false>), grid, block, pl.lds_bytes, st, a, inv_dev, P, 1.0, 0.0);
+    return launch_status("permutation gate");
 }
 
 // ---- K15b: a run of rotations in one pass (qcx_pauli_rotation_batch) -----------------------------------------------------------
@@ -1722,6 +1817,11 @@ struct qcx_register {
     amp_t     *diag_stage;      // each, grown on demand.  diag_ev: the copy out of diag_stage has been passed by the stream
     size_t     diag_cap;        // entries both hold
     hipEvent_t diag_ev;
+    unsigned   perm_form;       // the last permutation_gate call: the plan's form ...
+    unsigned long perm_moved;   // ... and the entries of its table that are not fixed points
+    uint16_t  *perm_tab;        // K19: the inverse table on the device, and the pinned buffer it is copied through: 2^12 entries
+    uint16_t  *perm_stage;      // each, allocated by the first call.  perm_ev: the copy out of perm_stage has been passed by the stream
+    hipEvent_t perm_ev;
     unsigned long gateb_passes, gateb_lds;   // the last gate_batch call: its passes, and the gates in them that exchanged through LDS (K12b / K13b)
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
 };
@@ -1920,6 +2020,9 @@ extern "C" int qcx_register_destroy(qcx_register *r)
     if (r->diag_tab) (void)hipFree(r->diag_tab);
     if (r->diag_stage) (void)hipHostFree(r->diag_stage);
     if (r->diag_ev) (void)hipEventDestroy(r->diag_ev);
+    if (r->perm_tab) (void)hipFree(r->perm_tab);
+    if (r->perm_stage) (void)hipHostFree(r->perm_stage);
+    if (r->perm_ev) (void)hipEventDestroy(r->perm_ev);
     free(r);
     return QCX_NO_ERROR;
 }
@@ -2727,6 +2830,49 @@ extern "C" int qcx_diagonal_last_stats(qcx_register *r, unsigned *form, unsigned
     if (!r) return QCX_BAD_ARGUMENTS;
     if (form) *form = r->diag_form;
     if (table_entries) *table_entries = r->diag_entries;
+    return QCX_NO_ERROR;
+}
+
+// ---- a permutation of a qubit range's basis states from a table (K19) -------------------------------------------------------------
+extern "C" unsigned qcx_permutation_max_qubits(void) { return QCX_PERM_MAX_QUBITS; }
+
+// one_qubit_gate()'s sequence behind the checks of include/qcx.h, in their order.  The inverse table goes through the register's
+// pinned buffer into its device scratch on the register's stream, as qcx_diagonal_gate's table does: the caller's array is free
+// when the call returns, the next call waits for that copy (perm_ev) before it overwrites the pinned buffer, and the device
+// scratch is only ever touched in stream order.
+extern "C" int qcx_permutation_gate(uint64_t cmask, uint64_t cvals, unsigned first, unsigned num, const uint32_t *perm, qcx_register *r)
+{
+    if (!r || !perm) return QCX_BAD_ARGUMENTS;
+    qcx_perm_plan pl;
+    QCX_TRY(qcx_permutation_plan(r->n, cmask, cvals, first, num, &pl));        // (the argument checks, in the header's order)
+    uint16_t inv[1u << QCX_PERM_MAX_QUBITS];
+    unsigned long moved = 0;
+    QCX_TRY(permutation_invert(num, perm, inv, &moved));
+    if (r->sh) { set_error("permutation_gate: not available on a sharded register"); return QCX_UNSUPPORTED; }
+    constexpr size_t cap = sizeof inv;
+    if (!r->perm_ev) HIP_TRY(hipEventCreateWithFlags(&r->perm_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(r->perm_ev));
+    if (!r->perm_tab) {
+        if (hipMalloc(&r->perm_tab, cap) != hipSuccess) { (void)hipGetLastError(); r->perm_tab = nullptr; return QCX_INSUFFICIENT_MEMORY; }
+    }
+    if (!r->perm_stage) {
+        if (hipHostMalloc(&r->perm_stage, cap) != hipSuccess) { (void)hipGetLastError(); r->perm_stage = nullptr; return QCX_INSUFFICIENT_MEMORY; }
+    }
+    QCX_TRY(unqueued_gate(r, "permutation_gate", false));
+    r->perm_form = pl.form; r->perm_moved = moved;
+    if (moved == 0 && !r->nonfinite) return QCX_NO_ERROR;                      // the identity on finite amplitudes whose zeros are +0
+    const size_t bytes = sizeof(uint16_t) << num;
+    memcpy(r->perm_stage, inv, bytes);
+    HIP_TRY(hipMemcpyAsync(r->perm_tab, r->perm_stage, bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipEventRecord(r->perm_ev, r->stream));
+    return permutation_launch(r->amp, r->n, cmask, cvals, first, num, r->nonfinite != 0, r->perm_tab, r->stream);
+}
+
+extern "C" int qcx_permutation_last_stats(qcx_register *r, unsigned *form, unsigned long *moved)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (form) *form = r->perm_form;
+    if (moved) *moved = r->perm_moved;
     return QCX_NO_ERROR;
 }
 

@@ -5537,4 +5537,76 @@ __global__ __launch_bounds__(256) void k_diag_scan(const amp_t *__restrict__ tab
     if (__ballot(bad) && (threadIdx.x & 63u) == 0u) atomicOr(flag, 1u);
 }
 
+// ---------------------------------------------------------------------------
+// K19  a permutation of the basis states of the qubit range [first, first + num), num <= 12, from a table, under any control
+// mask (qcx_permutation_gate, DESIGN s4.5o; tests/permutation_ref.py is the definition): where (i & ctrl_mask) == ctrl_values,
+//     new[i] = old[i with its range field k replaced by inv[k]],   inv = the inverse of the caller's table,
+// in place, k_camodc's way: a tile of 2^T amplitudes that is closed under the table is staged in LDS with coalesced loads, and
+// after the barrier every element fetches its source out of LDS and goes to its OWN address, so the stores are coalesced too
+// and no workgroup reads what another writes.  qcx_permutation_plan (include/qcx_plan.h) is the rule; in the kernel's terms:
+//   tile_mask  the T index bits of a tile: the num range bits and the lowest T - num other bits that are not squeezed; tile
+//              element e stands for the offset deposit(e, tile_mask) -- its low bits are the tile's low bits, so consecutive
+//              threads touch consecutive amplitudes in runs as long as the tile's lowest run of bits
+//   unit_mask  the index bits that number the tiles: base(u) = deposit(u, unit_mask) | orc, orc = the positive squeezed controls
+//              (K17's rule: a control at bit >= 3 is squeezed out, the part of the state where it does not fire is never read)
+//   pmask, pvals  the controls that are NOT squeezed (those below bit 3; STRICT: all of them), a predicate on the index: the
+//              part inside the tile is tested per element, the part outside it per tile -- a tile that misses is skipped
+//   pf         where the range field sits in e: src(e) = e with (e >> pf) & kmask replaced by inv[...]
+// deposit is bit-wise and the block a power of two, so deposit(tid + B j) = deposit(tid) | deposit(B j): the first part is
+// formed once per thread, the second once per workgroup (joff, 128 B of static LDS, read at a uniform address) -- formed per
+// element, the bit loop made the kernel ALU-bound (n = 30: 9.5 ms a pass at every tile size).  The gathered LDS read is a 16-B read per lane: the 16 lanes of a read group
+// take 16 different slots of a bank row whenever pf >= 4 (they differ in e's low four bits alone); with the range lower than
+// that the slots are the table's and some reads serialise.  Elements that do not fire keep their bits: they are not stored, or
+// with store_all stored back as read so that whole lines leave.
+// STRICT is the pass of a register flagged non-finite: nothing squeezed, and EVERY amplitude rewritten through the reference's
+// row q_row((1, 0) * x), firing or not, `one` and `z` being kernel arguments so that no product is folded (k_strict_mcu's rule).
+// ---------------------------------------------------------------------------
+struct PermParams {
+    uint64_t tile_mask, unit_mask, orc, pmask, pvals, units;
+    unsigned T, pf, num;
+    int      store_all;
+};
+
+__device__ __forceinline__ uint64_t perm_deposit(uint64_t v, uint64_t mask)
+{
+    uint64_t r = 0;
+    for (; v != 0 && mask != 0; v >>= 1, mask &= mask - 1)
+        if (v & 1u) r |= mask & (0 - mask);
+    return r;
+}
+
+template <bool STRICT, bool NT>
+__global__ __launch_bounds__(1024) void k_perm_tile(amp_t *__restrict__ amp, const unsigned short *__restrict__ inv_dev, PermParams P,
+                                                    double one, double z)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char qcx_lds_raw[];
+    amp_t *tile = reinterpret_cast<amp_t *>(qcx_lds_raw);
+    const unsigned TS = 1u << P.T, kmask = (1u << P.num) - 1u, B = blockDim.x, tid = threadIdx.x;
+    unsigned short *inv = reinterpret_cast<unsigned short *>(tile + TS);
+    __shared__ uint64_t joff[16];                              // deposit(B j): the part of an element's offset that its round j adds
+    for (unsigned k = tid; k <= kmask; k += B) inv[k] = inv_dev[k];
+    if (tid < 16u) joff[tid] = perm_deposit((uint64_t)tid * B, P.tile_mask);      // (B >= 256 and TS <= 2^12: at most 16 rounds)
+    const uint64_t lane_off = perm_deposit(tid, P.tile_mask);
+    __syncthreads();
+    const uint64_t pe_mask = P.pmask & P.tile_mask, pe_vals = P.pvals & P.tile_mask, pt_mask = P.pmask & ~P.tile_mask, pt_vals = P.pvals & ~P.tile_mask;
+    for (uint64_t u = blockIdx.x; u < P.units; u += gridDim.x) {
+        const uint64_t base = perm_deposit(u, P.unit_mask) | P.orc;
+        const bool tile_fires = (base & pt_mask) == pt_vals;
+        if (!STRICT && !tile_fires) continue;                  // (uniform: the whole workgroup skips the tile and its barriers)
+        amp_t *g = amp + base;
+        for (unsigned e = tid, j = 0; e < TS; e += B, j++) tile[e] = g[lane_off | joff[j]];
+        __syncthreads();
+        for (unsigned e = tid, j = 0; e < TS; e += B, j++) {
+            const uint64_t off = lane_off | joff[j];
+            const bool fires = tile_fires && (off & pe_mask) == pe_vals;
+            unsigned src = e;
+            if (fires) src = (e & ~(kmask << P.pf)) | ((unsigned)inv[(e >> P.pf) & kmask] << P.pf);
+            const amp_t v = tile[src];
+            if constexpr (STRICT) g[off] = q_row(q_mul(one, z, v));
+            else if (fires || P.store_all) st<NT>(g + off, v);
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace qcx

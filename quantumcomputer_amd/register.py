@@ -21,6 +21,7 @@ matrix is ever built.  Everything executes in the HIP library; a missing library
 or GPU raises (see _lib.py).
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -317,6 +318,14 @@ class Register:
         check(lib().qcx_diagonal_last_stats(self._h, C.byref(form), C.byref(entries)), "qcx_diagonal_last_stats")
         return form.value, entries.value
 
+    def permutation_stats(self):
+        """(form, moved) of the last permutation_gate call on this register: the form of its plan (permutation_plan's: PERM_LINES
+        or PERM_SHARED) and the number of table entries with perm[k] != k (0: the identity, which launches no kernel on a
+        register of finite amplitudes)"""
+        form, moved = C.c_uint(0), C.c_ulong(0)
+        check(lib().qcx_permutation_last_stats(self._h, C.byref(form), C.byref(moved)), "qcx_permutation_last_stats")
+        return form.value, moved.value
+
     def gate_batch_stats(self):
         """(passes, low-target gates) of the last gate_batch call on this register: the passes over the state it ran (the plan's:
         gate_batch_plan; the number of gates on a register flagged non-finite), and the gates in them with a target on qubits 0-7,
@@ -607,6 +616,71 @@ def diagonal_phase(first, num, angles, reg):
     """diagonal_gate with the table phase_table(angles): amplitude i takes the phase e^{i angles[k(i)]} -- a QAOA cost layer is
     diagonal_phase(0, n, -gamma * C, reg)"""
     diagonal_gate(first, num, phase_table(angles), reg)
+
+
+def permutation_gate(first, num, perm, reg, controls=None, values=None):
+    """A classical reversible function on the qubits first .. first+num-1: basis state |k> of the range goes to |perm[k]>, qubit
+    `first` being bit 0 of k, on the amplitudes whose control qubits read their `values`, in one pass over those amplitudes
+    (include/qcx.h: qcx_permutation_gate; tests/permutation_ref.py restates it).  perm is anything numpy.asarray turns into
+    2^num integers that form a bijection of [0, 2^num), num <= permutation_max_qubits(); controls and values as for
+    mc_one_qubit_gate (None: no control).  The table is copied before the call returns.  modmul_table, modadd_table,
+    xor_oracle_table and qubit_permutation_table build common tables."""
+    first, num = int(first), int(num)
+    t = np.asarray(perm)
+    if t.dtype.kind not in "iu" or num < 0 or t.size != 1 << num:
+        raise ValueError(f"a permutation of {num} qubits is a table of {1 << max(num, 0)} integers")
+    t = t.reshape(-1)
+    if t.size and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+        raise ValueError("a permutation table holds values in [0, 2^num)")
+    t = np.ascontiguousarray(t, dtype=np.uint32)
+    mask, vals = _control_masks(() if controls is None else controls, values)
+    check(lib().qcx_permutation_gate(mask, vals, first, num, t.ctypes.data_as(C.c_void_p), reg._h), "permutation_gate")
+
+
+def modmul_table(a, C_, num):
+    """k -> a k mod C_ for k < C_ and k -> k above: the table of a modular multiply on num qubits (under a control above them,
+    c_amodc_gate).  gcd(a, C_) must be 1 and C_ <= 2^num."""
+    a, C_, num = int(a), int(C_), int(num)
+    if C_ < 1 or C_ > 1 << num or math.gcd(a, C_) != 1:
+        raise ValueError(f"modmul_table: k -> {a} k mod {C_} is no permutation of {num} qubits' basis states")
+    k = np.arange(1 << num, dtype=np.int64)
+    return np.where(k < C_, (a % C_) * k % C_, k).astype(np.uint32)
+
+
+def modadd_table(c, num, modulus=None):
+    """k -> k + c mod 2^num, or with a modulus <= 2^num: k -> k + c mod modulus below it and k -> k above"""
+    c, num = int(c), int(num)
+    m = 1 << num if modulus is None else int(modulus)
+    if m < 1 or m > 1 << num:
+        raise ValueError(f"modadd_table: a modulus of {m} does not fit {num} qubits")
+    k = np.arange(1 << num, dtype=np.int64)
+    return np.where(k < m, (k + c % m) % m, k).astype(np.uint32)
+
+
+def xor_oracle_table(f_values, nx, ny):
+    """|x>|y> -> |x>|y xor f(x)> on nx + ny qubits, x in the low nx bits of the table's index and y in the ny above them;
+    f_values = f(0), ..., f(2^nx - 1), each below 2^ny"""
+    nx, ny = int(nx), int(ny)
+    f = np.asarray(f_values).reshape(-1)
+    if f.dtype.kind not in "iu" or f.size != 1 << nx or (f.size and (int(f.min()) < 0 or int(f.max()) >= 1 << ny)):
+        raise ValueError(f"xor_oracle_table: f is {1 << nx} integers below 2^{ny}")
+    k = np.arange(1 << (nx + ny), dtype=np.int64)
+    x, y = k & ((1 << nx) - 1), k >> nx
+    return (x | ((y ^ f.astype(np.int64)[x]) << nx)).astype(np.uint32)
+
+
+def qubit_permutation_table(order):
+    """bit j of k moves to bit order[j]: a re-ordering of the range's qubits.  qubit_permutation_table(range(num)[::-1]) is the
+    bit reversal a QFT owes."""
+    order = [int(q) for q in order]
+    num = len(order)
+    if sorted(order) != list(range(num)):
+        raise ValueError(f"qubit_permutation_table: {order!r} is no re-ordering of {num} qubits")
+    k = np.arange(1 << num, dtype=np.int64)
+    out = np.zeros_like(k)
+    for j, q in enumerate(order):
+        out |= ((k >> j) & 1) << q
+    return out.astype(np.uint32)
 
 
 def controlled(U2):
