@@ -323,6 +323,38 @@ unsigned qcx_permutation_max_qubits(void);       /* a build constant: 12 (a tile
 /* the last qcx_permutation_gate call on this register that passed its checks: form = the plan's (QCX_PERM_* of qcx_plan.h),
  * moved = the number of k with perm[k] != k */
 int  qcx_permutation_last_stats(qcx_register *reg, unsigned *form, unsigned long *moved);
+/* A dense 2^k x 2^k matrix on the k = num_targets = 1 .. 5 distinct qubits targets[0 .. k), under any set of controls of either
+ * polarity, in ONE pass over the amplitudes that fire: a circuit block fused into one operator costs one trip through memory
+ * however many gates were multiplied into it (the matrix applied as the reference's mat-vec applies every gate, Q:393-413;
+ * tests/multi_qubit_ref.py restates it in numpy and IS the definition; K20, DESIGN s4.5p).  u holds 2 * 4^k doubles, row-major,
+ * (re, im) per entry; targets[j] is bit j of the matrix index (qcx_two_qubit_gate's convention).  The matrix is first permuted
+ * to m = P u P, so that row and column c of m stand for the c-th amplitude of a group in ascending state index (for k = 2 the
+ * index swap 1 <-> 2 where qubit0 lies above qubit1).  Index i fires when (i & ctrl_mask) == ctrl_values.  For every firing
+ * group (the 2^k indices that differ in the target bits alone), with x_c its amplitudes in ascending index, every fl() one
+ * binary64 rounding, no FMA, the sums started at 0.0 and taken over c ascending, exact zeros multiplied out:
+ *     new_r.re = fl(... fl(fl(0.0 + fl(fl(m_r0.re*x_0.re) - fl(m_r0.im*x_0.im))) + fl(fl(m_r1.re*x_1.re) - fl(m_r1.im*x_1.im))) ...)
+ *     new_r.im = fl(... fl(fl(0.0 + fl(fl(m_r0.re*x_0.im) + fl(m_r0.im*x_0.re))) + fl(fl(m_r1.re*x_1.im) + fl(m_r1.im*x_1.re))) ...)
+ *   Every other amplitude takes the identity row (1, 0): on a register of finite amplitudes (its zeros are made +0 first, as
+ *   for every exact gate) it is not touched; a register flagged non-finite takes one strict pass that rewrites EVERY amplitude
+ *   by the formula and keeps its flag.  So, bit for bit on finite states: k = 1 and 2 are qcx_mc_one_qubit_gate and
+ *   qcx_mc_two_qubit_gate (and ARE those calls, the same kernels and launches, unless the knob multi_generic is set);
+ *   kron(I2, U4) on (t0, t1, t2) is qcx_two_qubit_gate(t0, t1, U4), and the 8x8 controlled(U4) is that gate under a control on
+ *   t2.  The matrix is applied as given: it is not checked for unitarity; every component must be finite with |.| <= 1.
+ * The matrix is permuted on the host and copied into the library's scratch before the call returns, so the caller may reuse
+ * u at once.  qcx_mc_two_qubit_gate's sequence: asynchronous, on the register's stream; flushes queued gates, a pending basis
+ * state and a compact circuit result in every fusion mode; never enters the queue, is not counted by qcx_fusion_stats, stays
+ * exact in mode 2.  qcx_multi_gate_plan in qcx_plan.h is the launch rule on its own.
+ * Checked in this order, before anything runs and with nothing touched: NULL reg, u or targets: QCX_BAD_ARGUMENTS; num_targets
+ * 0 or above qcx_multi_qubit_max_targets(): QCX_BAD_ARGUMENTS (the message states the maximum); a component that is not finite
+ * or exceeds 1 in absolute value: QCX_BAD_ARGUMENTS (the message names it); ctrl_values with bits outside ctrl_mask:
+ * QCX_BAD_ARGUMENTS; a target >= n, two targets equal, or a mask bit at or above n or on a target: QCX_BAD_QUBIT; a sharded
+ * register: QCX_UNSUPPORTED. */
+int  qcx_mc_multi_qubit_gate(uint64_t ctrl_mask, uint64_t ctrl_values, unsigned num_targets, const unsigned *targets, const double *u,
+                             qcx_register *reg);
+unsigned qcx_multi_qubit_max_targets(void);      /* a build constant: 5 */
+/* the last qcx_mc_multi_qubit_gate call on this register that passed its checks: form = the plan's (always QCX_PERM_LINES of
+ * qcx_plan.h), num_targets = its k */
+int  qcx_multi_qubit_last_stats(qcx_register *reg, unsigned *form, unsigned *num_targets);
 int  qcx_swap_states(qcx_register *reg);                                           /* Q:242-249: no-op */
 /* host-side gate schedules */
 int  qcx_inverse_QFT(qcx_register *reg);                                           /* Q:678-690 */

@@ -289,6 +289,45 @@ typedef struct {
     char     kernel[48];            /* the instantiation as a kernel trace spells it, e.g. "k_perm_tile<false, false>" */
 } qcx_perm_plan;
 int  qcx_permutation_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, unsigned first, unsigned num, qcx_perm_plan *out);
+
+/* The launch of qcx_mc_multi_qubit_gate (include/qcx.h; K20, DESIGN s4.5p) for a dense matrix on the num_targets = 3 .. 5 qubits
+ * targets[] (1 and 2 as well: what the knob multi_generic = 1 launches for them) of a register of n qubits under the controls
+ * (ctrl_mask, ctrl_values), on a register that holds finite amplitudes, on the host, under the knobs of the moment; the library
+ * launches from this very function.  The geometry is qcx_permutation_plan's, by the same code, with the target set in place of
+ * the range: controls at bit >= 3 squeezed out (`squeezed`, its runs, or_const), T = min(12, unsqueezed), tile_mask = the target
+ * bits and the lowest T - num_targets other unsqueezed bits (tile_bits[0 .. T) ascending), unit_mask the rest, `units` = 2^(unsqueezed
+ * - T) tiles dealt to `grid` workgroups with that stride, and unit u, tile element e is the amplitude
+ *     i = deposit(u, unit_mask) | deposit(e, tile_mask) | or_const.
+ * target_pos[j] = the bit of e that stands for targets[j] (j as given, not sorted).  A group is the 2^num_targets elements that
+ * differ in those bits alone, so every tile is closed under the operator; member c of a group in ascending index has the
+ * ascending target_pos bits set as c's bits are.  A work item is one group and rows_per_item of its rows (4; 2 for one target);
+ * thread tid of `block` = min(1024, max(64, 2^T / rows_per_item)) takes the items tid, tid + block, ...: item = chunk *
+ * 2^(T - num_targets) + group number, the group number deposited into the element bits that are no target.
+ * A control below bit 3 is a predicate.  A tile holds the lowest 12 - num_targets >= 7 other bits, so bits 0-2 always lie inside
+ * it: the predicate is elem_mask / elem_values, tested per group on i; unit_mask_low / unit_values_low (K19's per-tile
+ * predicate) are always 0 and form is always QCX_PERM_LINES for num_targets <= 5 -- the fields are kept so that one emulation
+ * reads both plans.  store_all: the groups that do not fire are stored back as read (the knob multi_store_all), so that whole
+ * lines leave.  lds_bytes = 16 * 2^T, at most 64 KiB (the matrix is not kept in LDS).  nt: the knob multi_nt.
+ * NULL out or targets, n = 0 or n > 40: QCX_BAD_ARGUMENTS; then qcx_mc_multi_qubit_gate's refusals, in its order: num_targets 0
+ * or above QCX_MULTI_MAX_TARGETS: QCX_BAD_ARGUMENTS; ctrl_values outside ctrl_mask: QCX_BAD_ARGUMENTS; a target >= n, two targets
+ * equal, a mask bit at or above n or on a target: QCX_BAD_QUBIT. */
+#define QCX_MULTI_MAX_TARGETS 5
+typedef struct {
+    unsigned form, T, num_targets;
+    unsigned char targets[QCX_MULTI_MAX_TARGETS], target_pos[QCX_MULTI_MAX_TARGETS];
+    unsigned char tile_bits[QCX_PERM_MAX_QUBITS];
+    uint64_t tile_mask, unit_mask;
+    uint64_t squeezed, or_const;
+    unsigned nruns;
+    unsigned char run_pos[QCX_PERM_MAX_RUNS], run_len[QCX_PERM_MAX_RUNS];
+    unsigned elem_mask, elem_values, unit_mask_low, unit_values_low;
+    uint64_t units;
+    unsigned grid, block, lds_bytes, rows_per_item;
+    unsigned store_all, nt;
+    char     kernel[48];            /* the instantiation as a kernel trace spells it, e.g. "k_multi_tile<5, false>" */
+} qcx_multi_plan;
+int  qcx_multi_gate_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, unsigned num_targets, const unsigned *targets,
+                         qcx_multi_plan *out);
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,10 @@ SIGNATURES = {
     "qcx_permutation_max_qubits": (_u, []),
     "qcx_permutation_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_ul)]),
     "qcx_permutation_plan": (_i, [_u, _u64, _u64, _u, _u, _p]),
+    "qcx_mc_multi_qubit_gate": (_i, [_u64, _u64, _u, _p, _p, _p]),
+    "qcx_multi_qubit_max_targets": (_u, []),
+    "qcx_multi_qubit_last_stats": (_i, [_p, C.POINTER(_u), C.POINTER(_u)]),
+    "qcx_multi_gate_plan": (_i, [_u, _u64, _u64, _u, _p, _p]),
     "qcx_swap_states": (_i, [_p]),
     "qcx_inverse_QFT": (_i, [_p]),
     "qcx_quantum_computation": (_i, [_u, _u, _i, _p]),
@@ -342,6 +346,33 @@ def permutation_plan(n, ctrl_mask, ctrl_values, first, num):
 def permutation_max_qubits():
     """the widest range permutation_gate takes a table for (qcx_permutation_max_qubits)"""
     return int(lib().qcx_permutation_max_qubits())
+
+
+class MultiPlan(C.Structure):
+    """qcx_multi_plan (include/qcx_plan.h): the launch of a dense matrix on 1 .. 5 target qubits"""
+    _fields_ = [("form", _u), ("T", _u), ("num_targets", _u), ("targets", C.c_ubyte * 5), ("target_pos", C.c_ubyte * 5),
+                ("tile_bits", C.c_ubyte * 12), ("tile_mask", _u64), ("unit_mask", _u64), ("squeezed", _u64), ("or_const", _u64),
+                ("nruns", _u), ("run_pos", C.c_ubyte * 20), ("run_len", C.c_ubyte * 20), ("elem_mask", _u), ("elem_values", _u),
+                ("unit_mask_low", _u), ("unit_values_low", _u), ("units", _u64), ("grid", _u), ("block", _u), ("lds_bytes", _u),
+                ("rows_per_item", _u), ("store_all", _u), ("nt", _u), ("kernel", C.c_char * 48)]
+
+
+def multi_gate_plan(n, ctrl_mask, ctrl_values, targets):
+    """What multi_qubit_gate(targets, ...) under these controls would launch on n qubits that hold finite amplitudes, under the
+    knobs of the moment (host code, no GPU needed; include/qcx_plan.h: qcx_multi_gate_plan): (status, MultiPlan).  targets =
+    None passes a NULL pointer (the plan refuses it)."""
+    pl = MultiPlan()
+    if targets is None:
+        return lib().qcx_multi_gate_plan(int(n), int(ctrl_mask), int(ctrl_values), 0, None, C.byref(pl)), pl
+    t = [int(q) for q in targets]
+    arr = (C.c_uint * max(len(t), 1))(*t)
+    st = lib().qcx_multi_gate_plan(int(n), int(ctrl_mask), int(ctrl_values), len(t), C.cast(arr, C.c_void_p), C.byref(pl))
+    return st, pl
+
+
+def multi_qubit_max_targets():
+    """the most targets multi_qubit_gate takes a matrix for (qcx_multi_qubit_max_targets)"""
+    return int(lib().qcx_multi_qubit_max_targets())
 
 
 def pauli_batch_width():

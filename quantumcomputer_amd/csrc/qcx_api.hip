@@ -176,6 +176,10 @@ extern "C" int qcx_set_device(int device) { HIP_TRY(hipSetDevice(device)); retur
     X(perm_tile_log2, 12)         /* K19: a tile is 2^this amplitudes or the range and three more bits, whichever is more, at most 2^12 (DESIGN s4.5o has the times of 8, 10 and 12) */ \
     X(perm_store_all, 1)          /* K19: 1 = under a control below bit 3 the elements that do not fire are stored back as read (whole lines leave: 6.19 against 6.45 ms at n = 30) */ \
     X(perm_nt, 0)                 /* K19: 1 = nontemporal stores */ \
+    X(multi_grid_cap, 2048)       /* K20 (k_multi_tile): workgroups, each walks its tiles with this stride; 0 = one tile each */ \
+    X(multi_store_all, 1)         /* K20: 1 = under a control below bit 3 the groups that do not fire are stored back as read (whole lines leave; K19's measurement) */ \
+    X(multi_nt, 0)                /* K20: 1 = nontemporal stores */ \
+    X(multi_generic, 0)           /* K20 (qcx_mc_multi_qubit_gate): 1 = one and two targets run K20's kernel too (0: mc_gate()'s launches; the tests compare the two bit for bit) */ \
     X(mc_generic, 0)              /* K17 (gates under a control mask): 1 = no control and one positive control run K17's kernels too (0: K12's / K13's launches; the tests compare the two bit for bit) */
 struct Tune {
 #define X(name, value) long name = value;
@@ -904,6 +908,47 @@ extern "C" int qcx_shard_diagonal(void *amp, unsigned n_local, unsigned first, u
     return launch_status("diagonal gate");
 }
 
+// ---- the tile geometry K19 and K20 share ----------------------------------------------------------------------------------------
+// The rule of include/qcx_plan.h (qcx_permutation_plan states it) for an operator on the index bits `opmask` (num of them; the
+// caller has checked them and the controls): controls at bit >= 3 squeezed out (strict: none), a tile of 2^T amplitudes, T =
+// min(12, unsqueezed, want), made of the operator's bits and the lowest T - num other unsqueezed bits, the rest numbering the
+// tiles; the controls that are not squeezed as predicates, per element inside the tile and per tile outside it (strict: the
+// caller takes pmask / pvals whole).
+struct TileGeom {
+    unsigned T, nruns, elem_mask, elem_values, unit_mask_low, unit_values_low;
+    uint64_t tile_mask, unit_mask, squeezed, or_const, pmask, pvals, units;
+    unsigned char tile_bits[QCX_PERM_MAX_QUBITS], run_pos[QCX_PERM_MAX_RUNS], run_len[QCX_PERM_MAX_RUNS];
+    bool lines;                     // the tile holds every index bit below 3 that exists: it is made of whole 128-B lines
+};
+
+static void tile_geometry(unsigned n, uint64_t cmask, uint64_t cvals, uint64_t opmask, unsigned num, bool strict, unsigned want, TileGeom *G)
+{
+    memset(G, 0, sizeof *G);
+    const uint64_t nmask = (((uint64_t)1) << n) - 1u;
+    const uint64_t squeezed = strict ? 0 : cmask & ~(uint64_t)7;
+    const unsigned unsq = n - (unsigned)__builtin_popcountll(squeezed);
+    const unsigned T = std::min(std::min(12u, unsq), want);
+    uint64_t tile = opmask, others = nmask & ~(squeezed | opmask);
+    for (unsigned k = num; k < T; k++) { tile |= others & (0 - others); others &= others - 1; }
+    G->T = T; G->tile_mask = tile; G->unit_mask = others;
+    { unsigned k = 0; for (uint64_t m = tile; m; m &= m - 1) G->tile_bits[k++] = (unsigned char)__builtin_ctzll(m); }
+    G->squeezed = squeezed; G->or_const = cvals & squeezed;
+    for (unsigned b = 0; b < n;) {
+        if (!((squeezed >> b) & 1u)) { b++; continue; }
+        unsigned len = 1;
+        while (b + len < n && ((squeezed >> (b + len)) & 1u)) len++;
+        G->run_pos[G->nruns] = (unsigned char)b; G->run_len[G->nruns] = (unsigned char)len; G->nruns++;            // (at most 19 runs above bit 2 of 40 bits)
+        b += len;
+    }
+    G->pmask = cmask & ~squeezed; G->pvals = cvals & ~squeezed;
+    if (!strict) {
+        G->elem_mask = (unsigned)(G->pmask & tile); G->elem_values = (unsigned)(G->pvals & tile);
+        G->unit_mask_low = (unsigned)(G->pmask & ~tile); G->unit_values_low = (unsigned)(G->pvals & ~tile);
+    }
+    G->units = ((uint64_t)1) << (unsq - T);
+    G->lines = (tile & 7u & nmask) == (7u & nmask);
+}
+
 // ---- K19: a permutation of a qubit range's basis states from a table ---------------------------------------------------------------
 // the rule of include/qcx_plan.h, under one snapshot of the knobs.  strict: the pass of a register flagged non-finite -- nothing
 // squeezed, every control a predicate (P->pmask); otherwise P->pmask holds the controls below bit 3
@@ -921,31 +966,20 @@ static int permutation_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t 
         return QCX_BAD_ARGUMENTS;
     }
     memset(out, 0, sizeof *out);
-    const uint64_t squeezed = strict ? 0 : cmask & ~(uint64_t)7;
-    const unsigned unsq = n - (unsigned)__builtin_popcountll(squeezed);
     const unsigned want = (unsigned)std::min<long>(12, std::max<long>(0, t.perm_tile_log2));
-    const unsigned T = std::min(std::min(12u, unsq), std::max(num + 3u, want));
-    uint64_t tile = range, others = nmask & ~(squeezed | range);
-    for (unsigned k = num; k < T; k++) { tile |= others & (0 - others); others &= others - 1; }
+    TileGeom G;
+    tile_geometry(n, cmask, cvals, range, num, strict, std::max(num + 3u, want), &G);
+    const unsigned T = G.T;
+    const uint64_t tile = G.tile_mask, others = G.unit_mask, pmask = G.pmask, pvals = G.pvals;
     out->T = T; out->first = first; out->num = num;
     out->tile_mask = tile; out->unit_mask = others;
     out->range_pos = (unsigned)__builtin_popcountll(tile & ((((uint64_t)1) << first) - 1u));
-    { unsigned k = 0; for (uint64_t m = tile; m; m &= m - 1) out->tile_bits[k++] = (unsigned char)__builtin_ctzll(m); }
-    out->squeezed = squeezed; out->or_const = cvals & squeezed;
-    for (unsigned b = 0; b < n;) {
-        if (!((squeezed >> b) & 1u)) { b++; continue; }
-        unsigned len = 1;
-        while (b + len < n && ((squeezed >> (b + len)) & 1u)) len++;
-        out->run_pos[out->nruns] = (unsigned char)b; out->run_len[out->nruns] = (unsigned char)len; out->nruns++;      // (at most 19 runs above bit 2 of 40 bits)
-        b += len;
-    }
-    const uint64_t pmask = cmask & ~squeezed, pvals = cvals & ~squeezed;
-    if (!strict) {
-        out->elem_mask = (unsigned)(pmask & tile); out->elem_values = (unsigned)(pvals & tile);
-        out->unit_mask_low = (unsigned)(pmask & ~tile); out->unit_values_low = (unsigned)(pvals & ~tile);
-    }
-    out->units = ((uint64_t)1) << (unsq - T);
-    out->form = (tile & 7u & nmask) == (7u & nmask) ? QCX_PERM_LINES : QCX_PERM_SHARED;
+    memcpy(out->tile_bits, G.tile_bits, sizeof out->tile_bits);
+    out->squeezed = G.squeezed; out->or_const = G.or_const;
+    out->nruns = G.nruns; memcpy(out->run_pos, G.run_pos, sizeof out->run_pos); memcpy(out->run_len, G.run_len, sizeof out->run_len);
+    out->elem_mask = G.elem_mask; out->elem_values = G.elem_values; out->unit_mask_low = G.unit_mask_low; out->unit_values_low = G.unit_values_low;
+    out->units = G.units;
+    out->form = G.lines ? QCX_PERM_LINES : QCX_PERM_SHARED;
     out->block = T == 12 ? 1024 : 256;
     out->grid = grid_for(out->units, 1, t.perm_grid_cap, out->block);
     out->lds_bytes = (16u << T) + (((2u << num) + 15u) & ~15u);
@@ -993,6 +1027,130 @@ static int permutation_launch(amp_t *a, unsigned n, uint64_t cmask, uint64_t cva
     else if (pl.nt) hipLaunchKernelGGL((k_perm_tile<false, true>), grid, block, pl.lds_bytes, st, a, inv_dev, P, 1.0, 0.0);
     else            hipLaunchKernelGGL((k_perm_tile<false, false>), grid, block, pl.lds_bytes, st, a, inv_dev, P, 1.0, 0.0);
     return launch_status("permutation gate");
+}
+
+// ---- K20: a dense matrix on 1 .. 5 target qubits --------------------------------------------------------------------------------
+// the rule of include/qcx_plan.h, under one snapshot of the knobs: K19's geometry (tile_geometry) with the target set as the
+// operator's bits.  (A register flagged non-finite does not come here: its strict pass has no tiles.)
+static int multi_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t cvals, unsigned k, const unsigned *targets, qcx_multi_plan *out,
+                      MultiParams *P)
+{
+    if (!out || !targets || n == 0 || n > 40) return QCX_BAD_ARGUMENTS;
+    if (k == 0 || k > QCX_MULTI_MAX_TARGETS) {
+        set_error("mc_multi_qubit_gate: %u targets; a matrix acts on 1 to %u qubits", k, (unsigned)QCX_MULTI_MAX_TARGETS);
+        return QCX_BAD_ARGUMENTS;
+    }
+    if (cvals & ~cmask) { set_error("mc_multi_qubit_gate: ctrl_values %#llx has bits outside ctrl_mask %#llx", (unsigned long long)cvals, (unsigned long long)cmask); return QCX_BAD_ARGUMENTS; }
+    uint64_t tmask = 0;
+    for (unsigned j = 0; j < k; j++) {
+        if (targets[j] >= n || ((tmask >> targets[j]) & 1u)) return QCX_BAD_QUBIT;
+        tmask |= (uint64_t)1 << targets[j];
+    }
+    const uint64_t nmask = (((uint64_t)1) << n) - 1u;
+    if ((cmask & ~nmask) != 0 || (cmask & tmask) != 0) return QCX_BAD_QUBIT;
+    memset(out, 0, sizeof *out);
+    TileGeom G;
+    tile_geometry(n, cmask, cvals, tmask, k, false, 12, &G);
+    out->T = G.T; out->num_targets = k;
+    unsigned emask = 0;
+    for (unsigned j = 0; j < k; j++) {
+        out->targets[j] = (unsigned char)targets[j];
+        out->target_pos[j] = (unsigned char)__builtin_popcountll(G.tile_mask & ((((uint64_t)1) << targets[j]) - 1u));
+        emask |= 1u << out->target_pos[j];
+    }
+    memcpy(out->tile_bits, G.tile_bits, sizeof out->tile_bits);
+    out->tile_mask = G.tile_mask; out->unit_mask = G.unit_mask;
+    out->squeezed = G.squeezed; out->or_const = G.or_const;
+    out->nruns = G.nruns; memcpy(out->run_pos, G.run_pos, sizeof out->run_pos); memcpy(out->run_len, G.run_len, sizeof out->run_len);
+    out->elem_mask = G.elem_mask; out->elem_values = G.elem_values; out->unit_mask_low = G.unit_mask_low; out->unit_values_low = G.unit_values_low;
+    out->units = G.units;
+    out->form = G.lines ? QCX_PERM_LINES : QCX_PERM_SHARED;
+    out->rows_per_item = k == 1 ? 2 : 4;
+    out->block = std::min(1024u, std::max(64u, (1u << G.T) / out->rows_per_item));
+    out->grid = grid_for(out->units, 1, t.multi_grid_cap, out->block);
+    out->lds_bytes = 16u << G.T;
+    out->store_all = (t.multi_store_all != 0 && G.pmask != 0) ? 1 : 0;
+    out->nt = t.multi_nt != 0 ? 1 : 0;
+    snprintf(out->kernel, sizeof out->kernel, "k_multi_tile<%u, %s>", k, out->nt ? "true" : "false");
+    if (P) {
+        P->tile_mask = G.tile_mask; P->unit_mask = G.unit_mask; P->orc = G.or_const; P->units = G.units;
+        P->pe_mask = G.elem_mask; P->pe_vals = G.elem_values; P->T = G.T; P->emask = emask; P->store_all = (int)out->store_all;
+    }
+    return QCX_NO_ERROR;
+}
+
+extern "C" int qcx_multi_gate_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, unsigned num_targets, const unsigned *targets,
+                                   qcx_multi_plan *out)
+{
+    return multi_plan(tune_now(), n, ctrl_mask, ctrl_values, num_targets, targets, out, nullptr);
+}
+
+// The matrix as the kernels take it: m = P u P, row and column c the c-th amplitude of a group in ascending state index, laid out
+// column-major, mt[2 (c 2^k + r)] = m[r][c] (re, im).  rank[j] = how many targets lie below targets[j]: bit j of the caller's
+// index is bit rank[j] of the ascending one.  sorted: the targets ascending.
+static void multi_ascending(unsigned k, const unsigned *targets, const double *u, double *mt, unsigned char *sorted)
+{
+    unsigned rank[QCX_MULTI_MAX_TARGETS], given[1u << QCX_MULTI_MAX_TARGETS];
+    for (unsigned j = 0; j < k; j++) {
+        rank[j] = 0;
+        for (unsigned i = 0; i < k; i++) rank[j] += targets[i] < targets[j];
+        sorted[rank[j]] = (unsigned char)targets[j];
+    }
+    const unsigned d = 1u << k;
+    for (unsigned c = 0; c < d; c++) {
+        given[c] = 0;
+        for (unsigned j = 0; j < k; j++) given[c] |= ((c >> rank[j]) & 1u) << j;
+    }
+    for (unsigned r = 0; r < d; r++)
+        for (unsigned c = 0; c < d; c++) {
+            const double *e = u + 2u * (given[r] * d + given[c]);
+            mt[2u * (c * d + r)] = e[0]; mt[2u * (c * d + r) + 1u] = e[1];
+        }
+}
+
+template <unsigned K>
+static void multi_launch_k(const qcx_multi_plan &pl, const MultiParams &P, amp_t *a, const double *mt_dev, hipStream_t st)
+{
+    const dim3 grid(pl.grid), block(pl.block);
+    if (pl.nt) hipLaunchKernelGGL((k_multi_tile<K, true>), grid, block, pl.lds_bytes, st, a, mt_dev, P);
+    else       hipLaunchKernelGGL((k_multi_tile<K, false>), grid, block, pl.lds_bytes, st, a, mt_dev, P);
+}
+
+template <unsigned K>
+static void multi_strict_k(amp_t *a, unsigned n, uint64_t dim, const MultiTargets &tq, uint64_t cmask, uint64_t cvals, const double *mt_dev, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_strict_multi<K>), dim3(grid_for(dim >> K, 256, 65536, 256)), dim3(256), 0, st, a, n, tq, cmask, cvals, mt_dev, 1.0, 0.0);
+}
+
+// launches what the plan says (strict: the one pass over every group of a register flagged non-finite); mt_dev: multi_ascending's
+// matrix in device memory, complete in stream order; sorted: the targets ascending
+static int multi_launch(amp_t *a, unsigned n, uint64_t cmask, uint64_t cvals, unsigned k, const unsigned *targets, const unsigned char *sorted,
+                        bool strict, const double *mt_dev, hipStream_t st)
+{
+    if (strict) {
+        MultiTargets tq; memset(&tq, 0, sizeof tq);
+        for (unsigned j = 0; j < k; j++) tq.q[j] = sorted[j];
+        const uint64_t dim = (uint64_t)1 << n;
+        switch (k) {
+        case 1: multi_strict_k<1>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
+        case 2: multi_strict_k<2>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
+        case 3: multi_strict_k<3>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
+        case 4: multi_strict_k<4>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
+        default: multi_strict_k<5>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
+        }
+        return launch_status("multi-qubit gate");
+    }
+    qcx_multi_plan pl;
+    MultiParams P;
+    QCX_TRY(multi_plan(tune_now(), n, cmask, cvals, k, targets, &pl, &P));
+    switch (k) {
+    case 1: multi_launch_k<1>(pl, P, a, mt_dev, st); break;
+    case 2: multi_launch_k<2>(pl, P, a, mt_dev, st); break;
+    case 3: multi_launch_k<3>(pl, P, a, mt_dev, st); break;
+    case 4: multi_launch_k<4>(pl, P, a, mt_dev, st); break;
+    default: multi_launch_k<5>(pl, P, a, mt_dev, st); break;
+    }
+    return launch_status("multi-qubit gate");
 }
 
 // ---- K15b: a run of rotations in one pass (qcx_pauli_rotation_batch) -----------------------------------------------------------
@@ -1822,6 +1980,11 @@ struct qcx_register {
     uint16_t  *perm_tab;        // K19: the inverse table on the device, and the pinned buffer it is copied through: 2^12 entries
     uint16_t  *perm_stage;      // each, allocated by the first call.  perm_ev: the copy out of perm_stage has been passed by the stream
     hipEvent_t perm_ev;
+    unsigned   multi_form;      // the last mc_multi_qubit_gate call: the plan's form ...
+    unsigned   multi_k;         // ... and its number of targets
+    double    *multi_mat;       // K20: the ascending matrix on the device, and the pinned buffer it is copied through: 2 * 4^5 doubles
+    double    *multi_stage;     // each, allocated by the first call.  multi_ev: the copy out of multi_stage has been passed by the stream
+    hipEvent_t multi_ev;
     unsigned long gateb_passes, gateb_lds;   // the last gate_batch call: its passes, and the gates in them that exchanged through LDS (K12b / K13b)
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
 };
@@ -2023,6 +2186,9 @@ extern "C" int qcx_register_destroy(qcx_register *r)
     if (r->perm_tab) (void)hipFree(r->perm_tab);
     if (r->perm_stage) (void)hipHostFree(r->perm_stage);
     if (r->perm_ev) (void)hipEventDestroy(r->perm_ev);
+    if (r->multi_mat) (void)hipFree(r->multi_mat);
+    if (r->multi_stage) (void)hipHostFree(r->multi_stage);
+    if (r->multi_ev) (void)hipEventDestroy(r->multi_ev);
     free(r);
     return QCX_NO_ERROR;
 }
@@ -2873,6 +3039,56 @@ extern "C" int qcx_permutation_last_stats(qcx_register *r, unsigned *form, unsig
     if (!r) return QCX_BAD_ARGUMENTS;
     if (form) *form = r->perm_form;
     if (moved) *moved = r->perm_moved;
+    return QCX_NO_ERROR;
+}
+
+// ---- a dense matrix on 1 .. 5 target qubits under a control mask (K20) ---------------------------------------------------------------
+extern "C" unsigned qcx_multi_qubit_max_targets(void) { return QCX_MULTI_MAX_TARGETS; }
+
+// mc_gate()'s sequence behind the checks of include/qcx.h, in their order.  One and two targets ARE mc_gate() -- the same kernels
+// and launches -- unless multi_generic is set.  The ascending matrix goes through the register's pinned buffer into its device
+// scratch on the register's stream, as qcx_permutation_gate's table does: the caller's array is free when the call returns, the
+// next call waits for that copy (multi_ev) before it overwrites the pinned buffer, and the device scratch is only ever touched
+// in stream order.
+extern "C" int qcx_mc_multi_qubit_gate(uint64_t cmask, uint64_t cvals, unsigned k, const unsigned *targets, const double *u, qcx_register *r)
+{
+    const char *who = "mc_multi_qubit_gate";
+    if (!r || !u || !targets) return QCX_BAD_ARGUMENTS;
+    if (k == 0 || k > QCX_MULTI_MAX_TARGETS) {
+        set_error("%s: %u targets; a matrix acts on 1 to %u qubits", who, k, (unsigned)QCX_MULTI_MAX_TARGETS);
+        return QCX_BAD_ARGUMENTS;
+    }
+    QCX_TRY(check_matrix(who, u, 2 << (2 * k)));
+    qcx_multi_plan pl;
+    QCX_TRY(qcx_multi_gate_plan(r->n, cmask, cvals, k, targets, &pl));         // (the other argument checks, in the header's order)
+    if (r->sh) { set_error("%s: not available on a sharded register", who); return QCX_UNSUPPORTED; }
+    if (k <= 2 && tune_now().multi_generic == 0) {
+        r->multi_form = pl.form; r->multi_k = k;
+        return mc_gate(cmask, cvals, k, targets[0], k == 2 ? targets[1] : 0, u, r, who);
+    }
+    constexpr size_t cap = sizeof(double) * (2u << (2 * QCX_MULTI_MAX_TARGETS));
+    if (!r->multi_ev) HIP_TRY(hipEventCreateWithFlags(&r->multi_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(r->multi_ev));
+    if (!r->multi_mat) {
+        if (hipMalloc(&r->multi_mat, cap) != hipSuccess) { (void)hipGetLastError(); r->multi_mat = nullptr; return QCX_INSUFFICIENT_MEMORY; }
+    }
+    if (!r->multi_stage) {
+        if (hipHostMalloc(&r->multi_stage, cap) != hipSuccess) { (void)hipGetLastError(); r->multi_stage = nullptr; return QCX_INSUFFICIENT_MEMORY; }
+    }
+    QCX_TRY(unqueued_gate(r, who, false));
+    r->multi_form = pl.form; r->multi_k = k;
+    unsigned char sorted[QCX_MULTI_MAX_TARGETS];
+    multi_ascending(k, targets, u, r->multi_stage, sorted);
+    HIP_TRY(hipMemcpyAsync(r->multi_mat, r->multi_stage, sizeof(double) * (2u << (2 * k)), hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipEventRecord(r->multi_ev, r->stream));
+    return multi_launch(r->amp, r->n, cmask, cvals, k, targets, sorted, r->nonfinite != 0, r->multi_mat, r->stream);
+}
+
+extern "C" int qcx_multi_qubit_last_stats(qcx_register *r, unsigned *form, unsigned *num_targets)
+{
+    if (!r) return QCX_BAD_ARGUMENTS;
+    if (form) *form = r->multi_form;
+    if (num_targets) *num_targets = r->multi_k;
     return QCX_NO_ERROR;
 }
 

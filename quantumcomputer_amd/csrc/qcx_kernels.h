@@ -5609,4 +5609,164 @@ __global__ __launch_bounds__(1024) void k_perm_tile(amp_t *__restrict__ amp, con
     }
 }
 
+// ---------------------------------------------------------------------------
+// K20  a dense 2^K x 2^K matrix on K = 1 .. 5 target qubits under any control mask (qcx_mc_multi_qubit_gate, DESIGN s4.5p;
+// tests/multi_qubit_ref.py is the definition): where (i & ctrl_mask) == ctrl_values, the 2^K amplitudes x_c of i's group (c
+// ascending with the state index) become
+//     new_r = q_row(m[r][0] * x_0, m[r][1] * x_1, ...),   products by q_mul (the pinned arithmetic), as a loop,
+// m = the caller's matrix permuted to ascending order on the host.  The geometry is K19's with the target set in place of the
+// range: a tile of 2^T amplitudes chosen by tile_mask holds every target bit, so it is closed under the operator; it is staged
+// in LDS with coalesced loads, computed on, and stored from LDS with every element going to its own address.
+//   work       a work item is one group and R = 4 of its rows (2 for K = 1): item = chunk * 2^(T-K) + group, so that the lanes of
+//              a wave hold consecutive groups and ONE chunk whenever a tile has 64 groups or more.  The item reads the group's
+//              x_c out of LDS in ascending c, once for its R rows, and runs R accumulator chains side by side.
+//   matrix     mt[2 (c 2^K + r)] = m[r][c] (re, im), column-major, in device memory: the R entries of a column that an item
+//              needs are 16 R contiguous bytes at an address that is uniform over the item's lanes.  The lanes are taken chunk
+//              by chunk (readfirstlane; one round where the wave holds one chunk), so the address is provably uniform and the
+//              entries come as scalar loads into SGPRs -- no per-lane gather, no LDS for the matrix, and the VGPRs hold the
+//              2 R sums, one x and addresses only.
+//   in place   the rows stay in registers until every item of the workgroup has read its inputs (a barrier), go to the
+//              outputs' slots in LDS, and after a second barrier the tile leaves as it came.
+//   slots      element e lives in slot e ^ ((e >> 4) & 15), a permutation inside each 256-B bank row of sixteen 16-B slots:
+//              staging and storing stay conflict-free, and the group reads of targets below element bit 4 (lanes 128 B
+//              apart for targets 0-2) spread over the row's slots, not over two of them.
+//   controls   at bit >= 3 they are squeezed out of the tile numbering (orc holds the positive ones); below bit 3 they lie inside
+//              every tile (a tile holds the lowest 12 - K >= 7 other bits) and are a predicate per group, pe_mask / pe_vals on
+//              the element's offset.  Groups that do not fire keep their bits: not stored, or with store_all stored as read.
+// ---------------------------------------------------------------------------
+struct MultiParams {
+    uint64_t tile_mask, unit_mask, orc, units;
+    unsigned pe_mask, pe_vals;         // the controls below bit 3, as bits of the state index
+    unsigned T;
+    unsigned emask;                    // the K target bits of a tile element
+    int      store_all;
+};
+
+__device__ __forceinline__ unsigned multi_slot(unsigned e) { return e ^ ((e >> 4) & 15u); }
+
+// R rows of one group: out[k] = row R chunk + k.  chunk is uniform over the active lanes (the caller sees to it).
+template <unsigned K, unsigned R>
+__device__ __forceinline__ void multi_rows(const amp_t *tile, const unsigned *tdep, const double *__restrict__ mt, unsigned chunk, unsigned eb,
+                                           amp_t (&out)[R])
+{
+    constexpr unsigned D = 1u << K;
+    // (the constant address space: with a uniform address the entries are scalar loads even though the kernel stores to amp)
+    typedef const double __attribute__((address_space(4))) *const_doubles;
+    const uint64_t at = (uint64_t)(mt + 2u * R * chunk);       // (made uniform HERE: the compiler puts the lanes' own chunk in the caller's place)
+    const unsigned at_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(at >> 32)), at_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)at);
+    const const_doubles mc = (const_doubles)(((uint64_t)at_hi << 32) | (uint64_t)at_lo);      // (unsigned halves: the builtin returns an int)
+#pragma unroll
+    for (unsigned k = 0; k < R; k++) { out[k].x = 0.0; out[k].y = 0.0; }
+#pragma unroll 8
+    for (unsigned c = 0; c < D; c++) {
+        const amp_t x = tile[multi_slot(eb | tdep[c])];
+        const const_doubles m = mc + 2u * D * c;
+#pragma unroll
+        for (unsigned k = 0; k < R; k++) {
+            const q_mul p(m[2u * k], m[2u * k + 1u], x);
+            out[k].x = out[k].x + p.re();
+            out[k].y = out[k].y + p.im();
+        }
+    }
+}
+
+template <unsigned K, bool NT>
+__global__ __launch_bounds__(1024) void k_multi_tile(amp_t *__restrict__ amp, const double *__restrict__ mt, MultiParams P)
+{
+    constexpr unsigned D = 1u << K, R = K == 1 ? 2 : 4, NI = K == 1 ? 2 : 1;      // (K = 1: 2^11 items of a 2^12 tile, two per thread)
+    extern __shared__ __attribute__((aligned(16))) unsigned char qcx_lds_raw[];
+    amp_t *tile = reinterpret_cast<amp_t *>(qcx_lds_raw);
+    __shared__ uint64_t joff[16];                              // deposit(B j), k_perm_tile's
+    __shared__ unsigned tdep[D];                               // deposit(c, emask): member c of a group, as element bits
+    const unsigned TS = 1u << P.T, B = blockDim.x, tid = threadIdx.x;
+    if (tid < 16u) joff[tid] = perm_deposit((uint64_t)tid * B, P.tile_mask);
+    if (tid < D) tdep[tid] = (unsigned)perm_deposit(tid, P.emask);
+    const uint64_t lane_off = perm_deposit(tid, P.tile_mask);
+    const unsigned glog = P.T - K, items = TS / R;
+    unsigned eb[NI], chunk[NI];
+    bool fires[NI];
+#pragma unroll
+    for (unsigned j = 0; j < NI; j++) {
+        const unsigned it = tid + B * j;
+        chunk[j] = it >> glog;
+        eb[j] = (unsigned)perm_deposit(it & ((1u << glog) - 1u), (TS - 1u) & ~P.emask);
+        fires[j] = it < items && ((unsigned)perm_deposit(eb[j], P.tile_mask) & P.pe_mask) == P.pe_vals;
+    }
+    __syncthreads();
+    for (uint64_t u = blockIdx.x; u < P.units; u += gridDim.x) {
+        amp_t *g = amp + (perm_deposit(u, P.unit_mask) | P.orc);
+        for (unsigned e = tid, j = 0; e < TS; e += B, j++) tile[multi_slot(e)] = g[lane_off | joff[j]];
+        __syncthreads();
+        amp_t out[NI][R];
+#pragma unroll
+        for (unsigned j = 0; j < NI; j++) {
+            if (!fires[j]) continue;
+            for (;;) {                                         // the lanes of one chunk at a time: its rows' entries are scalar loads
+                const unsigned cu = __builtin_amdgcn_readfirstlane(chunk[j]);
+                if (cu == chunk[j]) { multi_rows<K, R>(tile, tdep, mt, cu, eb[j], out[j]); break; }
+            }
+        }
+        __syncthreads();                                       // (every input has been read)
+#pragma unroll
+        for (unsigned j = 0; j < NI; j++) {
+            if (!fires[j]) continue;
+#pragma unroll
+            for (unsigned k = 0; k < R; k++) tile[multi_slot(eb[j] | tdep[R * chunk[j] + k])] = out[j][k];
+        }
+        __syncthreads();
+        for (unsigned e = tid, j = 0; e < TS; e += B, j++) {
+            const uint64_t off = lane_off | joff[j];
+            if (P.store_all || ((unsigned)off & P.pe_mask) == P.pe_vals) st<NT>(g + off, tile[multi_slot(e)]);
+        }
+        __syncthreads();
+    }
+}
+
+// K20s  the same operator as a STRICT pass (K9's reason: a register that holds non-finite amplitudes): nothing squeezed, one
+// thread per group with the group's inputs in registers, the defined rows where (i & cmask) == cvals and every other amplitude
+// rewritten through the reference's identity row q_row((1, 0) * x); `one` and `z` are kernel arguments so that no product is
+// folded (k_strict_mcu's rule).  tq: the targets in ascending order.
+struct MultiTargets { unsigned char q[5]; };
+
+template <unsigned K>
+__global__ __launch_bounds__(256) void k_strict_multi(amp_t *__restrict__ amp, unsigned n, MultiTargets tq, uint64_t cmask, uint64_t cvals,
+                                                      const double *__restrict__ mt, double one, double z)
+{
+    constexpr unsigned D = 1u << K;
+    const uint64_t groups = (uint64_t)1 << (n - K);
+    for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < groups; p += (uint64_t)gridDim.x * 256u) {
+        uint64_t i = p;
+#pragma unroll
+        for (unsigned j = 0; j < K; j++) i = insert_zero(i, tq.q[j]);
+        uint64_t bit[K];
+#pragma unroll
+        for (unsigned j = 0; j < K; j++) bit[j] = (uint64_t)1 << tq.q[j];
+        const auto dep = [&](unsigned c) {                     // member c of the group (c is a constant of the unrolled loops)
+            uint64_t d = 0;
+#pragma unroll
+            for (unsigned j = 0; j < K; j++) if ((c >> j) & 1u) d |= bit[j];
+            return d;
+        };
+        amp_t x[D];
+#pragma unroll
+        for (unsigned c = 0; c < D; c++) x[c] = amp[i | dep(c)];
+        if ((i & cmask) == cvals) {
+#pragma unroll
+            for (unsigned r = 0; r < D; r++) {
+                amp_t acc = q_row();
+#pragma unroll
+                for (unsigned c = 0; c < D; c++) {
+                    const q_mul pr(mt[2u * (c * D + r)], mt[2u * (c * D + r) + 1u], x[c]);
+                    acc.x = acc.x + pr.re();
+                    acc.y = acc.y + pr.im();
+                }
+                amp[i | dep(r)] = acc;
+            }
+        } else {
+#pragma unroll
+            for (unsigned c = 0; c < D; c++) amp[i | dep(c)] = q_row(q_mul(one, z, x[c]));
+        }
+    }
+}
+
 }  // namespace qcx

@@ -326,6 +326,13 @@ class Register:
         check(lib().qcx_permutation_last_stats(self._h, C.byref(form), C.byref(moved)), "qcx_permutation_last_stats")
         return form.value, moved.value
 
+    def multi_qubit_stats(self):
+        """(form, num_targets) of the last multi_qubit_gate call on this register that passed its checks: the form of its plan
+        (multi_gate_plan's; always PERM_LINES) and the number of its targets"""
+        form, k = C.c_uint(0), C.c_uint(0)
+        check(lib().qcx_multi_qubit_last_stats(self._h, C.byref(form), C.byref(k)), "qcx_multi_qubit_last_stats")
+        return form.value, k.value
+
     def gate_batch_stats(self):
         """(passes, low-target gates) of the last gate_batch call on this register: the passes over the state it ran (the plan's:
         gate_batch_plan; the number of gates on a register flagged non-finite), and the gates in them with a target on qubits 0-7,
@@ -681,6 +688,74 @@ def qubit_permutation_table(order):
     for j, q in enumerate(order):
         out |= ((k >> j) & 1) << q
     return out.astype(np.uint32)
+
+
+def _matrix_multi(U, k):
+    """U as the 2 * 4^k doubles qcx_mc_multi_qubit_gate takes: row-major (re, im); U is a 2^k x 2^k matrix or those doubles"""
+    d = 1 << k
+    m = np.asarray(U)
+    if m.shape == (2 * d * d,) and not np.iscomplexobj(m):
+        return np.ascontiguousarray(m, dtype=np.float64)
+    m = np.asarray(U, dtype=complex)
+    if m.shape != (d, d):
+        raise ValueError(f"a gate on {k} qubits is a {d}x{d} matrix, not shape {m.shape}")
+    return np.ascontiguousarray(m.reshape(d * d)).view(np.float64)
+
+
+def multi_qubit_gate(targets, U, reg, controls=None, values=None):
+    """Apply the dense 2^k x 2^k matrix U to the k = 1 .. 5 distinct qubits `targets`, on the amplitudes whose control qubits
+    read their `values`, in one pass over those amplitudes, with the reference's mat-vec arithmetic (include/qcx.h:
+    qcx_mc_multi_qubit_gate; tests/multi_qubit_ref.py restates it).  targets[j] is bit j of the matrix index, two_qubit_gate's
+    convention: "A on targets[0], B on targets[1], C on targets[2]" is numpy.kron(C, numpy.kron(B, A)).  U is anything
+    numpy.asarray(U, complex) turns into shape (2^k, 2^k), or the 2 * 4^k doubles; it is applied as given, not checked for
+    unitarity, and copied before the call returns.  controls and values as for mc_one_qubit_gate (None: no control).
+    fused_matrix turns a list of one- and two-qubit gates into such a block."""
+    t = [int(q) for q in (targets if np.ndim(targets) else (targets,))]
+    if any(not 0 <= q < 2 ** 31 for q in t):
+        raise ValueError(f"{targets!r} are not qubits")
+    if not 1 <= len(t) <= _lib.multi_qubit_max_targets():
+        raise ValueError(f"a matrix acts on 1 to {_lib.multi_qubit_max_targets()} qubits, not {len(t)}")
+    u = _matrix_multi(U, len(t))
+    mask, vals = _control_masks(() if controls is None else controls, values)
+    arr = (C.c_uint * len(t))(*t)
+    check(lib().qcx_mc_multi_qubit_gate(mask, vals, len(t), C.cast(arr, C.c_void_p), u.ctypes.data_as(C.c_void_p), reg._h), "multi_qubit_gate")
+
+
+def fused_matrix(gates, targets):
+    """The product of gates = [(U, targets) or (U, targets, control), ...] (gate_batch's form, applied in order) as ONE
+    2^k x 2^k matrix on the k qubits `targets`, in multi_qubit_gate's index convention (targets[j] is bit j), in plain numpy:
+    multi_qubit_gate(targets, fused_matrix(layer, targets), reg) is the layer as one block.  Every qubit a gate names, its
+    control included, must lie in `targets`.  The product is rounded as numpy rounds a matrix product, so the block equals
+    the gate-by-gate calls to rounding error, not bit for bit."""
+    tq = [int(q) for q in targets]
+    if len(set(tq)) != len(tq):
+        raise ValueError(f"fused_matrix: the targets {targets!r} are not distinct")
+    k = len(tq)
+    where = {q: j for j, q in enumerate(tq)}
+    idx = np.arange(1 << k)
+    out = np.eye(1 << k, dtype=complex)
+    for g in gates:
+        t, c = _lib.gate_targets(g)
+        for q in t + (() if c is None else (c,)):
+            if q not in where:
+                raise ValueError(f"fused_matrix: qubit {q} of a gate is not among the targets {tq}")
+        d = 1 << len(t)
+        u = np.asarray(g[0])
+        u = u.astype(np.float64).view(np.complex128).reshape(d, d) if u.shape == (2 * d * d,) and not np.iscomplexobj(u) else np.asarray(g[0], dtype=complex)
+        if u.shape != (d, d):
+            raise ValueError(f"fused_matrix: a gate on {len(t)} qubits is a {d}x{d} matrix, not shape {u.shape}")
+        local = sum(((idx >> where[q]) & 1) << l for l, q in enumerate(t))      # the gate's own index of every block index
+        tmask = sum(1 << where[q] for q in t)
+        fires = np.ones(1 << k, dtype=bool) if c is None else ((idx >> where[c]) & 1).astype(bool)
+        G = np.zeros((1 << k, 1 << k), dtype=complex)
+        for r in idx:
+            if not fires[r]:
+                G[r, r] = 1.0
+                continue
+            for col in range(d):
+                G[r, (r & ~tmask) | sum(((col >> l) & 1) << where[q] for l, q in enumerate(t))] = u[local[r], col]
+        out = G @ out
+    return out
 
 
 def controlled(U2):
