@@ -245,38 +245,26 @@ typedef struct {
 } qcx_diag_plan;
 int  qcx_diagonal_plan(unsigned n, unsigned first, unsigned num, qcx_diag_plan *out);
 
-/* The launch of qcx_permutation_gate (include/qcx.h; K19, DESIGN s4.5o) for the range [first, first + num) of a register of n
- * qubits under the controls (ctrl_mask, ctrl_values), on a register that holds finite amplitudes, on the host, under the knobs
- * of the moment; the library launches from this very function.
+/* The tile geometry qcx_permutation_plan and qcx_multi_gate_plan share (one function of the library fills it), for an operator
+ * on `num` index bits -- the range [first, first + num), or the target set -- of a register of n qubits under the controls
+ * (ctrl_mask, ctrl_values), and a tile of at most 2^want amplitudes.
  * Controls at bit >= 3 are squeezed out of the work numbering, qcx_mc_gate_plan's rule: `squeezed` is their mask, its ascending
  * runs are [run_pos[k], run_pos[k] + run_len[k]), k < nruns, and or_const holds the positive ones.  With unsqueezed = n - the
- * squeezed positions, a tile is 2^T amplitudes, T = min(12, unsqueezed, max(num + 3, the knob perm_tile_log2)) -- the range and
- * three more bits, no less than the knob asks for (12, so T = min(12, unsqueezed) for every range): tile_mask = the num
- * range bits and the lowest T - num of the other unsqueezed bits (tile_bits[0 .. T) lists them ascending), so every tile is
- * closed under any table.  unit_mask =
- * the unsqueezed bits outside the tile; `units` = 2^(unsqueezed - T) tiles, and workgroup b of `grid` takes the units b, b + grid,
- * ...  Unit u, tile element e (thread tid of `block` owns e = tid + block j while e < 2^T) is the amplitude
+ * squeezed positions, a tile is 2^T amplitudes, T = min(12, unsqueezed, want): tile_mask = the operator's bits and the lowest
+ * T - num of the other unsqueezed bits (tile_bits[0 .. T) lists them ascending), so every tile is closed under any operator on
+ * those bits.  unit_mask = the unsqueezed bits outside the tile; `units` = 2^(unsqueezed - T) tiles, and workgroup b of the
+ * plan's `grid` takes the units b, b + grid, ...  Unit u, tile element e is the amplitude
  *     i = deposit(u, unit_mask) | deposit(e, tile_mask) | or_const,
- * deposit(v, mask) = v's bits moved, in order, into the set positions of mask.  The range field of e sits at bit range_pos of e:
- * the element stores tile[e with (e >> range_pos) & (2^num - 1) replaced by the inverse table's entry] to i.
- * A control below bit 3 is a predicate: elem_mask / elem_values where its bit lies in the tile (tested on i per element),
- * unit_mask_low / unit_values_low where it does not (tested on deposit(u, unit_mask); a unit that misses is skipped, nothing of it
- * is read).  store_all: under such a predicate the elements that do not act are stored back as read, so that whole lines leave
- * (the knob perm_store_all, on by measurement; 0: they are left alone).
+ * deposit(v, mask) = v's bits moved, in order, into the set positions of mask.
+ * A control below bit 3 is a predicate: elem_mask / elem_values where its bit lies in the tile (tested on i), unit_mask_low /
+ * unit_values_low where it does not (tested on deposit(u, unit_mask); a unit that misses is skipped, nothing of it is read).
  * form: QCX_PERM_LINES when the tile holds index bits 0-2 (all of them that exist), so that it is made of whole 128-B lines;
- * QCX_PERM_SHARED when it does not (num >= 10 with first > 0): lines are shared between tiles.
- * block = 1024 for T = 12, else 256; grid = min(units, the knob perm_grid_cap (0: no cap)), within what HIP takes; lds_bytes =
- * 16 * 2^T for the tile + 2 * 2^num (rounded up to 16) for the inverse table: at most 64 KiB + 8 KiB.  nt: the knob perm_nt,
- * nontemporal stores.
- * NULL out, n = 0 or n > 40: QCX_BAD_ARGUMENTS; then qcx_permutation_gate's refusals, in its order: ctrl_values outside
- * ctrl_mask: QCX_BAD_ARGUMENTS; first + num > n: QCX_BAD_QUBIT; a mask bit at or above n or inside the range: QCX_BAD_QUBIT;
- * num > qcx_permutation_max_qubits(): QCX_BAD_ARGUMENTS. */
+ * QCX_PERM_SHARED when it does not: lines are shared between tiles. */
 #define QCX_PERM_MAX_QUBITS 12
 #define QCX_PERM_MAX_RUNS 20
 enum { QCX_PERM_LINES = 0, QCX_PERM_SHARED = 1 };
 typedef struct {
-    unsigned form, T, first, num;
-    unsigned range_pos;             /* the tile bits below `first` */
+    unsigned form, T;
     unsigned char tile_bits[QCX_PERM_MAX_QUBITS];
     uint64_t tile_mask, unit_mask;
     uint64_t squeezed, or_const;
@@ -284,6 +272,27 @@ typedef struct {
     unsigned char run_pos[QCX_PERM_MAX_RUNS], run_len[QCX_PERM_MAX_RUNS];
     unsigned elem_mask, elem_values, unit_mask_low, unit_values_low;
     uint64_t units;
+} qcx_tile_geom;
+
+/* The launch of qcx_permutation_gate (include/qcx.h; K19, DESIGN s4.5o) for the range [first, first + num) of a register of n
+ * qubits under the controls (ctrl_mask, ctrl_values), on a register that holds finite amplitudes, on the host, under the knobs
+ * of the moment; the library launches from this very function.
+ * geom: the geometry above for the range, with want = max(num + 3, the knob perm_tile_log2) -- the range and three more bits, no
+ * less than the knob asks for (12, so T = min(12, unsqueezed) for every range); QCX_PERM_SHARED occurs for num >= 10 with
+ * first > 0.  Thread tid of `block` owns the tile elements e = tid + block j while e < 2^T.  The range field of e sits at bit
+ * range_pos of e: the element stores tile[e with (e >> range_pos) & (2^num - 1) replaced by the inverse table's entry] to i.
+ * The predicates are tested per element and per unit.  store_all: under a predicate the elements that do not act are stored
+ * back as read, so that whole lines leave (the knob perm_store_all, on by measurement; 0: they are left alone).
+ * block = 1024 for T = 12, else 256; grid = min(units, the knob perm_grid_cap (0: no cap)), within what HIP takes; lds_bytes =
+ * 16 * 2^T for the tile + 2 * 2^num (rounded up to 16) for the inverse table: at most 64 KiB + 8 KiB.  nt: the knob perm_nt,
+ * nontemporal stores.
+ * NULL out, n = 0 or n > 40: QCX_BAD_ARGUMENTS; then qcx_permutation_gate's refusals, in its order: ctrl_values outside
+ * ctrl_mask: QCX_BAD_ARGUMENTS; first + num > n: QCX_BAD_QUBIT; a mask bit at or above n or inside the range: QCX_BAD_QUBIT;
+ * num > qcx_permutation_max_qubits(): QCX_BAD_ARGUMENTS. */
+typedef struct {
+    qcx_tile_geom geom;
+    unsigned first, num;
+    unsigned range_pos;             /* the tile bits below `first` */
     unsigned grid, block, lds_bytes;
     unsigned store_all, nt;
     char     kernel[48];            /* the instantiation as a kernel trace spells it, e.g. "k_perm_tile<false, false>" */
@@ -293,35 +302,25 @@ int  qcx_permutation_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, 
 /* The launch of qcx_mc_multi_qubit_gate (include/qcx.h; K20, DESIGN s4.5p) for a dense matrix on the num_targets = 3 .. 5 qubits
  * targets[] (1 and 2 as well: what the knob multi_generic = 1 launches for them) of a register of n qubits under the controls
  * (ctrl_mask, ctrl_values), on a register that holds finite amplitudes, on the host, under the knobs of the moment; the library
- * launches from this very function.  The geometry is qcx_permutation_plan's, by the same code, with the target set in place of
- * the range: controls at bit >= 3 squeezed out (`squeezed`, its runs, or_const), T = min(12, unsqueezed), tile_mask = the target
- * bits and the lowest T - num_targets other unsqueezed bits (tile_bits[0 .. T) ascending), unit_mask the rest, `units` = 2^(unsqueezed
- * - T) tiles dealt to `grid` workgroups with that stride, and unit u, tile element e is the amplitude
- *     i = deposit(u, unit_mask) | deposit(e, tile_mask) | or_const.
- * target_pos[j] = the bit of e that stands for targets[j] (j as given, not sorted).  A group is the 2^num_targets elements that
- * differ in those bits alone, so every tile is closed under the operator; member c of a group in ascending index has the
- * ascending target_pos bits set as c's bits are.  A work item is one group and rows_per_item of its rows (4; 2 for one target);
- * thread tid of `block` = min(1024, max(64, 2^T / rows_per_item)) takes the items tid, tid + block, ...: item = chunk *
- * 2^(T - num_targets) + group number, the group number deposited into the element bits that are no target.
- * A control below bit 3 is a predicate.  A tile holds the lowest 12 - num_targets >= 7 other bits, so bits 0-2 always lie inside
- * it: the predicate is elem_mask / elem_values, tested per group on i; unit_mask_low / unit_values_low (K19's per-tile
- * predicate) are always 0 and form is always QCX_PERM_LINES for num_targets <= 5 -- the fields are kept so that one emulation
- * reads both plans.  store_all: the groups that do not fire are stored back as read (the knob multi_store_all), so that whole
- * lines leave.  lds_bytes = 16 * 2^T, at most 64 KiB (the matrix is not kept in LDS).  nt: the knob multi_nt.
+ * launches from this very function.
+ * geom: the geometry above for the target set, with want = 12.  target_pos[j] = the bit of e that stands for targets[j] (j as
+ * given, not sorted).  A group is the 2^num_targets elements that differ in those bits alone, so every tile is closed under the
+ * operator; member c of a group in ascending index has the ascending target_pos bits set as c's bits are.  A work item is one
+ * group and rows_per_item of its rows (4; 2 for one target); thread tid of `block` = min(1024, max(64, 2^T / rows_per_item))
+ * takes the items tid, tid + block, ...: item = chunk * 2^(T - num_targets) + group number, the group number deposited into the
+ * element bits that are no target.
+ * A tile holds the lowest 12 - num_targets >= 7 other bits, so bits 0-2 always lie inside it: the predicate is elem_mask /
+ * elem_values, tested per group on i; geom.unit_mask_low / unit_values_low are always 0 and geom.form is always QCX_PERM_LINES
+ * for num_targets <= 5.  store_all: the groups that do not fire are stored back as read (the knob multi_store_all), so that
+ * whole lines leave.  lds_bytes = 16 * 2^T, at most 64 KiB (the matrix is not kept in LDS).  nt: the knob multi_nt.
  * NULL out or targets, n = 0 or n > 40: QCX_BAD_ARGUMENTS; then qcx_mc_multi_qubit_gate's refusals, in its order: num_targets 0
  * or above QCX_MULTI_MAX_TARGETS: QCX_BAD_ARGUMENTS; ctrl_values outside ctrl_mask: QCX_BAD_ARGUMENTS; a target >= n, two targets
  * equal, a mask bit at or above n or on a target: QCX_BAD_QUBIT. */
 #define QCX_MULTI_MAX_TARGETS 5
 typedef struct {
-    unsigned form, T, num_targets;
+    qcx_tile_geom geom;
+    unsigned num_targets;
     unsigned char targets[QCX_MULTI_MAX_TARGETS], target_pos[QCX_MULTI_MAX_TARGETS];
-    unsigned char tile_bits[QCX_PERM_MAX_QUBITS];
-    uint64_t tile_mask, unit_mask;
-    uint64_t squeezed, or_const;
-    unsigned nruns;
-    unsigned char run_pos[QCX_PERM_MAX_RUNS], run_len[QCX_PERM_MAX_RUNS];
-    unsigned elem_mask, elem_values, unit_mask_low, unit_values_low;
-    uint64_t units;
     unsigned grid, block, lds_bytes, rows_per_item;
     unsigned store_all, nt;
     char     kernel[48];            /* the instantiation as a kernel trace spells it, e.g. "k_multi_tile<5, false>" */

@@ -326,12 +326,17 @@ def diagonal_host_max_qubits():
 PERM_LINES, PERM_SHARED = range(2)                 # QCX_PERM_* (include/qcx_plan.h)
 
 
+class TileGeom(C.Structure):
+    """qcx_tile_geom (include/qcx_plan.h): the tile geometry PermPlan and MultiPlan embed; its fields read as theirs"""
+    _fields_ = [("form", _u), ("T", _u), ("tile_bits", C.c_ubyte * 12), ("tile_mask", _u64), ("unit_mask", _u64),
+                ("squeezed", _u64), ("or_const", _u64), ("nruns", _u), ("run_pos", C.c_ubyte * 20), ("run_len", C.c_ubyte * 20),
+                ("elem_mask", _u), ("elem_values", _u), ("unit_mask_low", _u), ("unit_values_low", _u), ("units", _u64)]
+
+
 class PermPlan(C.Structure):
     """qcx_perm_plan (include/qcx_plan.h): the launch of a permutation of a qubit range's basis states"""
-    _fields_ = [("form", _u), ("T", _u), ("first", _u), ("num", _u), ("range_pos", _u), ("tile_bits", C.c_ubyte * 12),
-                ("tile_mask", _u64), ("unit_mask", _u64), ("squeezed", _u64), ("or_const", _u64), ("nruns", _u),
-                ("run_pos", C.c_ubyte * 20), ("run_len", C.c_ubyte * 20), ("elem_mask", _u), ("elem_values", _u),
-                ("unit_mask_low", _u), ("unit_values_low", _u), ("units", _u64), ("grid", _u), ("block", _u), ("lds_bytes", _u),
+    _anonymous_ = ("geom",)
+    _fields_ = [("geom", TileGeom), ("first", _u), ("num", _u), ("range_pos", _u), ("grid", _u), ("block", _u), ("lds_bytes", _u),
                 ("store_all", _u), ("nt", _u), ("kernel", C.c_char * 48)]
 
 
@@ -350,11 +355,10 @@ def permutation_max_qubits():
 
 class MultiPlan(C.Structure):
     """qcx_multi_plan (include/qcx_plan.h): the launch of a dense matrix on 1 .. 5 target qubits"""
-    _fields_ = [("form", _u), ("T", _u), ("num_targets", _u), ("targets", C.c_ubyte * 5), ("target_pos", C.c_ubyte * 5),
-                ("tile_bits", C.c_ubyte * 12), ("tile_mask", _u64), ("unit_mask", _u64), ("squeezed", _u64), ("or_const", _u64),
-                ("nruns", _u), ("run_pos", C.c_ubyte * 20), ("run_len", C.c_ubyte * 20), ("elem_mask", _u), ("elem_values", _u),
-                ("unit_mask_low", _u), ("unit_values_low", _u), ("units", _u64), ("grid", _u), ("block", _u), ("lds_bytes", _u),
-                ("rows_per_item", _u), ("store_all", _u), ("nt", _u), ("kernel", C.c_char * 48)]
+    _anonymous_ = ("geom",)
+    _fields_ = [("geom", TileGeom), ("num_targets", _u), ("targets", C.c_ubyte * 5), ("target_pos", C.c_ubyte * 5),
+                ("grid", _u), ("block", _u), ("lds_bytes", _u), ("rows_per_item", _u), ("store_all", _u), ("nt", _u),
+                ("kernel", C.c_char * 48)]
 
 
 def multi_gate_plan(n, ctrl_mask, ctrl_values, targets):

@@ -17,6 +17,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -646,6 +647,15 @@ extern "C" int qcx_shard_one_qubit(void *amp, unsigned n_local, unsigned q, int 
     return launch_status("one-qubit gate");
 }
 
+// A runtime flag, and a number of targets, as a template argument -- pauli_dispatch's pattern (below): launch(tag), a generic
+// lambda that reads decltype(tag)::value.
+template <class Launch> static void flag_dispatch(bool flag, Launch launch) { if (flag) launch(std::true_type()); else launch(std::false_type()); }
+template <unsigned K = 1, class Launch> static void targets_dispatch(unsigned k, Launch launch)         // k = 1 .. 5 (above: as 5)
+{
+    if constexpr (K < QCX_MULTI_MAX_TARGETS) { if (k != K) return targets_dispatch<K + 1>(k, launch); }
+    launch(std::integral_constant<unsigned, K>());
+}
+
 // ---- K13: any two-qubit gate, plain or controlled --------------------------------------------------------------------------
 template <bool NT, bool CTL>
 static void launch_u2_quad(amp_t *a, unsigned lo, unsigned hi, unsigned c, const U4Mat &U, uint64_t count, long want_slog, hipStream_t st)
@@ -707,11 +717,12 @@ extern "C" int qcx_shard_two_qubit(void *amp, unsigned n_local, unsigned q0, uns
         const unsigned grid = grid_for(count, 64, 0, 64);
         unsigned glog, slog;
         stream_map(grid, (uint64_t)grid * 64, count, want, &glog, &slog);
-#define QCX_U2_LINES(NS, NT) hipLaunchKernelGGL((k_u2_lines<NS, NT>), dim3(grid), dim3(64), 0, st, a, lo, hi, mlo, mhi, nsq, s[0], s[1], cset, clow, store_all, U, count, glog, slog)
-        if (ns == 2)      { if (nt) QCX_U2_LINES(2, true); else QCX_U2_LINES(2, false); }
-        else if (ns == 1) { if (nt) QCX_U2_LINES(1, true); else QCX_U2_LINES(1, false); }
-        else              { if (nt) QCX_U2_LINES(0, true); else QCX_U2_LINES(0, false); }
-#undef QCX_U2_LINES
+        const auto lines = [&](auto nsv) { flag_dispatch(nt, [&](auto ntv) {
+            hipLaunchKernelGGL((k_u2_lines<decltype(nsv)::value, decltype(ntv)::value>), dim3(grid), dim3(64), 0, st, a, lo, hi, mlo, mhi, nsq, s[0], s[1], cset, clow, store_all, U, count, glog, slog);
+        }); };
+        if (ns == 2)      lines(std::integral_constant<int, 2>());
+        else if (ns == 1) lines(std::integral_constant<int, 1>());
+        else              lines(std::integral_constant<int, 0>());
     } else {
         const bool ntq = nt && lowest >= 3;                    // nontemporal only where a wave instruction covers whole 128-B lines
         if (ctl < 0) { if (ntq) launch_u2_quad<true, false>(a, lo, hi, 0, U, namps >> 2, want, st); else launch_u2_quad<false, false>(a, lo, hi, 0, U, namps >> 2, want, st); }
@@ -720,15 +731,63 @@ extern "C" int qcx_shard_two_qubit(void *amp, unsigned n_local, unsigned q0, uns
     return launch_status("two-qubit gate");
 }
 
-// ---- K17: a one- or two-qubit gate under a control mask (include/qcx_plan.h states the rule, DESIGN s4.5m) ------------------------
-// The ONE place that decides the form, the numbering and the launch geometry; mc_launch() below launches what it returns.
-static int mc_gate_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q0, unsigned q1, qcx_mc_plan *out)
+// ---- the argument checks the masked and the table gates share ------------------------------------------------------------------------
+// Each caller runs them in the order its header documents, on n <= 40 qubits.  Only the first writes a text (`who` names the
+// caller in it): the QCX_BAD_QUBIT refusals leave qcx_last_error() as it stands.
+static int check_ctrl_values(const char *who, uint64_t cmask, uint64_t cvals)
 {
-    if (!out || (ntargets != 1 && ntargets != 2) || n == 0 || n > 40) return QCX_BAD_ARGUMENTS;
-    if (cvals & ~cmask) { set_error("mc gate: ctrl_values %#llx has bits outside ctrl_mask %#llx", (unsigned long long)cvals, (unsigned long long)cmask); return QCX_BAD_ARGUMENTS; }
-    if (q0 >= n || (ntargets == 2 && (q1 >= n || q1 == q0))) return QCX_BAD_QUBIT;
+    if (cvals & ~cmask) { set_error("%s: ctrl_values %#llx has bits outside ctrl_mask %#llx", who, (unsigned long long)cvals, (unsigned long long)cmask); return QCX_BAD_ARGUMENTS; }
+    return QCX_NO_ERROR;
+}
+static int check_targets(unsigned n, unsigned k, const unsigned *targets, uint64_t *tmask)       // k distinct qubits below n; *tmask: their bits
+{
+    *tmask = 0;
+    for (unsigned j = 0; j < k; j++) {
+        if (targets[j] >= n || ((*tmask >> targets[j]) & 1u)) return QCX_BAD_QUBIT;
+        *tmask |= (uint64_t)1 << targets[j];
+    }
+    return QCX_NO_ERROR;
+}
+static int check_range(unsigned n, unsigned first, unsigned num, uint64_t *range)                // [first, first + num) inside n qubits; *range (if asked for): its bits
+{
+    if (first > n || num > n - first) return QCX_BAD_QUBIT;
+    if (range) *range = ((((uint64_t)1) << num) - 1u) << first;
+    return QCX_NO_ERROR;
+}
+static int check_ctrl_mask(unsigned n, uint64_t cmask, uint64_t opmask)                          // no control at or above n or on a bit the operator acts on
+{
+    return ((cmask >> n) != 0 || (cmask & opmask) != 0) ? QCX_BAD_QUBIT : QCX_NO_ERROR;
+}
+
+// The ascending runs of set bits of `mask`, [run_pos[k], run_pos[k] + run_len[k]), k < *nruns.  false: more than `cap` of them
+// (the first `cap` are listed).
+static bool mask_runs(uint64_t mask, unsigned char *run_pos, unsigned char *run_len, unsigned cap, unsigned *nruns)
+{
+    for (*nruns = 0; mask != 0; ++*nruns) {
+        const unsigned b = (unsigned)__builtin_ctzll(mask), len = (unsigned)__builtin_ctzll(~(mask >> b));
+        if (*nruns == cap) return false;
+        run_pos[*nruns] = (unsigned char)b; run_len[*nruns] = (unsigned char)len;
+        mask &= ~(((((uint64_t)1) << len) - 1u) << b);
+    }
+    return true;
+}
+
+// ---- K17: a one- or two-qubit gate under a control mask (include/qcx_plan.h states the rule, DESIGN s4.5m) ------------------------
+// the checks of the plan and of the gate calls, in the header's order
+static int mc_check(const char *who, unsigned n, uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q0, unsigned q1)
+{
+    const unsigned targets[2] = {q0, q1};
+    uint64_t tmask;
+    QCX_TRY(check_ctrl_values(who, cmask, cvals));
+    QCX_TRY(check_targets(n, ntargets, targets, &tmask));
+    return check_ctrl_mask(n, cmask, tmask);
+}
+
+// The ONE place that decides the form, the numbering and the launch geometry, for arguments that passed mc_check(); mc_launch()
+// below launches what it returns.
+static int mc_gate_rule(const Tune &t, unsigned n, uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q0, unsigned q1, qcx_mc_plan *out)
+{
     const uint64_t tmask = ((uint64_t)1 << q0) | (ntargets == 2 ? (uint64_t)1 << q1 : 0);
-    if ((cmask >> n) != 0 || (cmask & tmask) != 0) return QCX_BAD_QUBIT;
     memset(out, 0, sizeof *out);
     const unsigned lo = ntargets == 2 && q1 < q0 ? q1 : q0, hi = ntargets == 2 ? (q0 < q1 ? q1 : q0) : q0;
     const uint64_t high = cmask & ~(uint64_t)7;
@@ -761,14 +820,7 @@ static int mc_gate_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t cval
     }
     out->form = form; out->ns = ns;
     out->count = (uint64_t)1 << (n - (unsigned)__builtin_popcountll(squeezed));
-    for (unsigned b = 0; b < n;) {
-        if (!((squeezed >> b) & 1u)) { b++; continue; }
-        unsigned len = 1;
-        while (b + len < n && ((squeezed >> (b + len)) & 1u)) len++;
-        if (out->nruns == QCX_MC_MAX_RUNS) { set_error("mc gate: more than %d runs of squeezed positions", QCX_MC_MAX_RUNS); return QCX_UNSUPPORTED; }
-        out->run_pos[out->nruns] = (unsigned char)b; out->run_len[out->nruns] = (unsigned char)len; out->nruns++;
-        b += len;
-    }
+    if (!mask_runs(squeezed, out->run_pos, out->run_len, QCX_MC_MAX_RUNS, &out->nruns)) { set_error("mc gate: more than %d runs of squeezed positions", QCX_MC_MAX_RUNS); return QCX_UNSUPPORTED; }
     out->or_const = cvals & squeezed;
     if (lines) { out->low_mask = low; out->low_values = (unsigned)cvals & 7u; out->store_all = (low & 3u) ? 1 : 0; }
     if (form == QCX_MC_LINES2 && ns >= 1) out->shfl_lo = 1u << plo;
@@ -791,14 +843,16 @@ static int mc_gate_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t cval
 extern "C" int qcx_mc_gate_plan(unsigned n, uint64_t ctrl_mask, uint64_t ctrl_values, unsigned ntargets, unsigned qubit0, unsigned qubit1,
                                 qcx_mc_plan *out)
 {
-    return mc_gate_plan(tune_now(), n, ctrl_mask, ctrl_values, ntargets, qubit0, qubit1, out);
+    if (!out || (ntargets != 1 && ntargets != 2) || n == 0 || n > 40) return QCX_BAD_ARGUMENTS;
+    QCX_TRY(mc_check("mc gate", n, ctrl_mask, ctrl_values, ntargets, qubit0, qubit1));
+    return mc_gate_rule(tune_now(), n, ctrl_mask, ctrl_values, ntargets, qubit0, qubit1, out);
 }
 
 // launches what the plan says (u: the caller's 8 or 32 doubles)
 static int mc_launch(amp_t *a, unsigned n, uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q0, unsigned q1, const double *u, hipStream_t st)
 {
     qcx_mc_plan pl;
-    QCX_TRY(mc_gate_plan(tune_now(), n, cmask, cvals, ntargets, q0, q1, &pl));
+    QCX_TRY(mc_gate_rule(tune_now(), n, cmask, cvals, ntargets, q0, q1, &pl));
     static_assert(MC_MAP_RUNS == QCX_MC_MAX_RUNS, "McMap holds the runs of a qcx_mc_plan");
     McMap M; memset(&M, 0, sizeof M);
     M.nruns = pl.nruns; M.orc = pl.or_const;
@@ -807,19 +861,21 @@ static int mc_launch(amp_t *a, unsigned n, uint64_t cmask, uint64_t cvals, unsig
     const int sa = (int)pl.store_all;
     if (ntargets == 1) {
         const UMat U = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]};
-#define QCX_MC1(K) do { if (pl.nt) hipLaunchKernelGGL((K<true>), grid, block, 0, st, a, q0, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog); \
-                        else       hipLaunchKernelGGL((K<false>), grid, block, 0, st, a, q0, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog); } while (0)
-        if (pl.form == QCX_MC_LINE_SHFL) QCX_MC1(k_mcu_shfl); else QCX_MC1(k_mcu_pair);
-#undef QCX_MC1
+        flag_dispatch(pl.nt != 0, [&](auto nt) {
+            if (pl.form == QCX_MC_LINE_SHFL) hipLaunchKernelGGL((k_mcu_shfl<decltype(nt)::value>), grid, block, 0, st, a, q0, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog);
+            else                             hipLaunchKernelGGL((k_mcu_pair<decltype(nt)::value>), grid, block, 0, st, a, q0, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog);
+        });
     } else {
         const U4Mat U = u4_ascending(q0, q1, u);
         const unsigned lo = q0 < q1 ? q0 : q1, hi = q0 < q1 ? q1 : q0;
-#define QCX_MC2(NS, NT) hipLaunchKernelGGL((k_mcu2_lines<NS, NT>), grid, block, 0, st, a, lo, hi, pl.shfl_lo, pl.shfl_hi, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog)
-        if (pl.form == QCX_MC_LINES2 && pl.ns == 2)      { if (pl.nt) QCX_MC2(2, true); else QCX_MC2(2, false); }
-        else if (pl.form == QCX_MC_LINES2 && pl.ns == 1) { if (pl.nt) QCX_MC2(1, true); else QCX_MC2(1, false); }
-        else if (pl.nt) hipLaunchKernelGGL((k_mcu2_quad<true>), grid, block, 0, st, a, lo, hi, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog);
-        else            hipLaunchKernelGGL((k_mcu2_quad<false>), grid, block, 0, st, a, lo, hi, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog);
-#undef QCX_MC2
+        flag_dispatch(pl.nt != 0, [&](auto nt) {
+            auto lines = [&](auto ns) {
+                hipLaunchKernelGGL((k_mcu2_lines<decltype(ns)::value, decltype(nt)::value>), grid, block, 0, st, a, lo, hi, pl.shfl_lo, pl.shfl_hi, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog);
+            };
+            if (pl.form == QCX_MC_LINES2 && pl.ns == 2)      lines(std::integral_constant<int, 2>());
+            else if (pl.form == QCX_MC_LINES2 && pl.ns == 1) lines(std::integral_constant<int, 1>());
+            else hipLaunchKernelGGL((k_mcu2_quad<decltype(nt)::value>), grid, block, 0, st, a, lo, hi, M, pl.low_mask, pl.low_values, sa, U, pl.count, pl.glog, pl.slog);
+        });
     }
     return launch_status("mc gate");
 }
@@ -869,7 +925,7 @@ extern "C" int qcx_shard_pauli_rotation(void *amp, unsigned n_local, uint64_t x_
 static int diagonal_plan(const Tune &t, unsigned n, unsigned first, unsigned num, qcx_diag_plan *out)
 {
     if (!out || n == 0 || n > 40) return QCX_BAD_ARGUMENTS;
-    if (first > n || num > n - first) return QCX_BAD_QUBIT;
+    QCX_TRY(check_range(n, first, num, nullptr));
     memset(out, 0, sizeof *out);
     const unsigned T = std::min(n, 12u);
     out->T = T; out->first = first; out->num = num;
@@ -898,30 +954,23 @@ extern "C" int qcx_shard_diagonal(void *amp, unsigned n_local, unsigned first, u
     qcx_diag_plan pl;
     QCX_TRY(diagonal_plan(tune_now(), n_local, first, num, &pl));
     const dim3 grid(pl.grid), block(pl.block);
-#define QCX_DIAG(FORM, FULL, LDS) hipLaunchKernelGGL((k_diagonal<FORM, FULL, LDS>), grid, block, pl.lds_bytes, (hipStream_t)stream, \
-                                                     (amp_t *)amp, (const amp_t *)table_dev, pl.units, pl.T, pl.first, pl.kmask)
-    if (pl.form == QCX_DIAG_TILE)       { if (pl.full) QCX_DIAG(0, true, false); else QCX_DIAG(0, false, false); }
-    else if (pl.form == QCX_DIAG_GROUP) { if (pl.full) QCX_DIAG(1, true, false); else QCX_DIAG(1, false, false); }
-    else if (pl.lds)                    { if (pl.full) QCX_DIAG(2, true, true);  else QCX_DIAG(2, false, true); }
-    else                                { if (pl.full) QCX_DIAG(2, true, false); else QCX_DIAG(2, false, false); }
-#undef QCX_DIAG
+    // the (FORM, LDS) pairs the kernel is built in are written out below: only the lane form has an LDS variant
+    const auto launch = [&](auto form, auto lds) { flag_dispatch(pl.full != 0, [&](auto full) {
+        hipLaunchKernelGGL((k_diagonal<decltype(form)::value, decltype(full)::value, decltype(lds)::value>), grid, block, pl.lds_bytes,
+                           (hipStream_t)stream, (amp_t *)amp, (const amp_t *)table_dev, pl.units, pl.T, pl.first, pl.kmask);
+    }); };
+    if (pl.form == QCX_DIAG_TILE)       launch(std::integral_constant<int, 0>(), std::false_type());
+    else if (pl.form == QCX_DIAG_GROUP) launch(std::integral_constant<int, 1>(), std::false_type());
+    else if (pl.lds)                    launch(std::integral_constant<int, 2>(), std::true_type());
+    else                                launch(std::integral_constant<int, 2>(), std::false_type());
     return launch_status("diagonal gate");
 }
 
 // ---- the tile geometry K19 and K20 share ----------------------------------------------------------------------------------------
-// The rule of include/qcx_plan.h (qcx_permutation_plan states it) for an operator on the index bits `opmask` (num of them; the
-// caller has checked them and the controls): controls at bit >= 3 squeezed out (strict: none), a tile of 2^T amplitudes, T =
-// min(12, unsqueezed, want), made of the operator's bits and the lowest T - num other unsqueezed bits, the rest numbering the
-// tiles; the controls that are not squeezed as predicates, per element inside the tile and per tile outside it (strict: the
-// caller takes pmask / pvals whole).
-struct TileGeom {
-    unsigned T, nruns, elem_mask, elem_values, unit_mask_low, unit_values_low;
-    uint64_t tile_mask, unit_mask, squeezed, or_const, pmask, pvals, units;
-    unsigned char tile_bits[QCX_PERM_MAX_QUBITS], run_pos[QCX_PERM_MAX_RUNS], run_len[QCX_PERM_MAX_RUNS];
-    bool lines;                     // the tile holds every index bit below 3 that exists: it is made of whole 128-B lines
-};
-
-static void tile_geometry(unsigned n, uint64_t cmask, uint64_t cvals, uint64_t opmask, unsigned num, bool strict, unsigned want, TileGeom *G)
+// Fills a plan's qcx_tile_geom in place by the rule include/qcx_plan.h states there, for an operator on the index bits `opmask`
+// (num of them; the caller has checked them and the controls) and a tile of at most 2^want amplitudes.  strict: nothing is
+// squeezed and no predicate is split; the caller takes the controls whole.
+static void tile_geometry(unsigned n, uint64_t cmask, uint64_t cvals, uint64_t opmask, unsigned num, bool strict, unsigned want, qcx_tile_geom *G)
 {
     memset(G, 0, sizeof *G);
     const uint64_t nmask = (((uint64_t)1) << n) - 1u;
@@ -933,63 +982,51 @@ static void tile_geometry(unsigned n, uint64_t cmask, uint64_t cvals, uint64_t o
     G->T = T; G->tile_mask = tile; G->unit_mask = others;
     { unsigned k = 0; for (uint64_t m = tile; m; m &= m - 1) G->tile_bits[k++] = (unsigned char)__builtin_ctzll(m); }
     G->squeezed = squeezed; G->or_const = cvals & squeezed;
-    for (unsigned b = 0; b < n;) {
-        if (!((squeezed >> b) & 1u)) { b++; continue; }
-        unsigned len = 1;
-        while (b + len < n && ((squeezed >> (b + len)) & 1u)) len++;
-        G->run_pos[G->nruns] = (unsigned char)b; G->run_len[G->nruns] = (unsigned char)len; G->nruns++;            // (at most 19 runs above bit 2 of 40 bits)
-        b += len;
-    }
-    G->pmask = cmask & ~squeezed; G->pvals = cvals & ~squeezed;
+    (void)mask_runs(squeezed, G->run_pos, G->run_len, QCX_PERM_MAX_RUNS, &G->nruns);         // (at most 19 runs above bit 2 of 40 bits)
     if (!strict) {
-        G->elem_mask = (unsigned)(G->pmask & tile); G->elem_values = (unsigned)(G->pvals & tile);
-        G->unit_mask_low = (unsigned)(G->pmask & ~tile); G->unit_values_low = (unsigned)(G->pvals & ~tile);
+        const uint64_t pmask = cmask & ~squeezed, pvals = cvals & ~squeezed;
+        G->elem_mask = (unsigned)(pmask & tile); G->elem_values = (unsigned)(pvals & tile);
+        G->unit_mask_low = (unsigned)(pmask & ~tile); G->unit_values_low = (unsigned)(pvals & ~tile);
     }
     G->units = ((uint64_t)1) << (unsq - T);
-    G->lines = (tile & 7u & nmask) == (7u & nmask);
+    G->form = (tile & 7u & nmask) == (7u & nmask) ? QCX_PERM_LINES : QCX_PERM_SHARED;
 }
 
 // ---- K19: a permutation of a qubit range's basis states from a table ---------------------------------------------------------------
+static PermParams perm_params(const qcx_perm_plan &pl, uint64_t pmask, uint64_t pvals)        // pmask / pvals: the controls that are predicates
+{
+    const qcx_tile_geom &G = pl.geom;
+    return {G.tile_mask, G.unit_mask, G.or_const, pmask, pvals, G.units, G.T, pl.range_pos, pl.num, (int)pl.store_all};
+}
+
 // the rule of include/qcx_plan.h, under one snapshot of the knobs.  strict: the pass of a register flagged non-finite -- nothing
 // squeezed, every control a predicate (P->pmask); otherwise P->pmask holds the controls below bit 3
 static int permutation_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t cvals, unsigned first, unsigned num, bool strict,
                             qcx_perm_plan *out, PermParams *P)
 {
     if (!out || n == 0 || n > 40) return QCX_BAD_ARGUMENTS;
-    if (cvals & ~cmask) { set_error("permutation_gate: ctrl_values %#llx has bits outside ctrl_mask %#llx", (unsigned long long)cvals, (unsigned long long)cmask); return QCX_BAD_ARGUMENTS; }
-    if (first > n || num > n - first) return QCX_BAD_QUBIT;
-    const uint64_t nmask = (((uint64_t)1) << n) - 1u;
-    const uint64_t range = num >= 64 ? ~(uint64_t)0 : ((((uint64_t)1) << num) - 1u) << first;
-    if ((cmask & ~nmask) != 0 || (cmask & range) != 0) return QCX_BAD_QUBIT;
+    uint64_t range;
+    QCX_TRY(check_ctrl_values("permutation_gate", cmask, cvals));
+    QCX_TRY(check_range(n, first, num, &range));
+    QCX_TRY(check_ctrl_mask(n, cmask, range));
     if (num > QCX_PERM_MAX_QUBITS) {
         set_error("permutation_gate: a table over %u qubits is more than the %u a tile holds", num, (unsigned)QCX_PERM_MAX_QUBITS);
         return QCX_BAD_ARGUMENTS;
     }
     memset(out, 0, sizeof *out);
     const unsigned want = (unsigned)std::min<long>(12, std::max<long>(0, t.perm_tile_log2));
-    TileGeom G;
+    qcx_tile_geom &G = out->geom;
     tile_geometry(n, cmask, cvals, range, num, strict, std::max(num + 3u, want), &G);
-    const unsigned T = G.T;
-    const uint64_t tile = G.tile_mask, others = G.unit_mask, pmask = G.pmask, pvals = G.pvals;
-    out->T = T; out->first = first; out->num = num;
-    out->tile_mask = tile; out->unit_mask = others;
-    out->range_pos = (unsigned)__builtin_popcountll(tile & ((((uint64_t)1) << first) - 1u));
-    memcpy(out->tile_bits, G.tile_bits, sizeof out->tile_bits);
-    out->squeezed = G.squeezed; out->or_const = G.or_const;
-    out->nruns = G.nruns; memcpy(out->run_pos, G.run_pos, sizeof out->run_pos); memcpy(out->run_len, G.run_len, sizeof out->run_len);
-    out->elem_mask = G.elem_mask; out->elem_values = G.elem_values; out->unit_mask_low = G.unit_mask_low; out->unit_values_low = G.unit_values_low;
-    out->units = G.units;
-    out->form = G.lines ? QCX_PERM_LINES : QCX_PERM_SHARED;
-    out->block = T == 12 ? 1024 : 256;
-    out->grid = grid_for(out->units, 1, t.perm_grid_cap, out->block);
-    out->lds_bytes = (16u << T) + (((2u << num) + 15u) & ~15u);
+    const uint64_t pmask = cmask & ~G.squeezed, pvals = cvals & ~G.squeezed;
+    out->first = first; out->num = num;
+    out->range_pos = (unsigned)__builtin_popcountll(G.tile_mask & ((((uint64_t)1) << first) - 1u));
+    out->block = G.T == 12 ? 1024 : 256;
+    out->grid = grid_for(G.units, 1, t.perm_grid_cap, out->block);
+    out->lds_bytes = (16u << G.T) + (((2u << num) + 15u) & ~15u);
     out->store_all = (!strict && t.perm_store_all != 0 && pmask != 0) ? 1 : 0;
     out->nt = (!strict && t.perm_nt != 0) ? 1 : 0;
     snprintf(out->kernel, sizeof out->kernel, "k_perm_tile<%s, %s>", strict ? "true" : "false", out->nt ? "true" : "false");
-    if (P) {
-        P->tile_mask = tile; P->unit_mask = others; P->orc = out->or_const; P->pmask = pmask; P->pvals = pvals; P->units = out->units;
-        P->T = T; P->pf = out->range_pos; P->num = num; P->store_all = (int)out->store_all;
-    }
+    if (P) *P = perm_params(*out, pmask, pvals);
     return QCX_NO_ERROR;
 }
 
@@ -1030,6 +1067,14 @@ static int permutation_launch(amp_t *a, unsigned n, uint64_t cmask, uint64_t cva
 }
 
 // ---- K20: a dense matrix on 1 .. 5 target qubits --------------------------------------------------------------------------------
+static MultiParams multi_params(const qcx_multi_plan &pl)
+{
+    const qcx_tile_geom &G = pl.geom;
+    unsigned emask = 0;
+    for (unsigned j = 0; j < pl.num_targets; j++) emask |= 1u << pl.target_pos[j];
+    return {G.tile_mask, G.unit_mask, G.or_const, G.units, G.elem_mask, G.elem_values, G.T, emask, (int)pl.store_all};
+}
+
 // the rule of include/qcx_plan.h, under one snapshot of the knobs: K19's geometry (tile_geometry) with the target set as the
 // operator's bits.  (A register flagged non-finite does not come here: its strict pass has no tiles.)
 static int multi_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t cvals, unsigned k, const unsigned *targets, qcx_multi_plan *out,
@@ -1040,42 +1085,26 @@ static int multi_plan(const Tune &t, unsigned n, uint64_t cmask, uint64_t cvals,
         set_error("mc_multi_qubit_gate: %u targets; a matrix acts on 1 to %u qubits", k, (unsigned)QCX_MULTI_MAX_TARGETS);
         return QCX_BAD_ARGUMENTS;
     }
-    if (cvals & ~cmask) { set_error("mc_multi_qubit_gate: ctrl_values %#llx has bits outside ctrl_mask %#llx", (unsigned long long)cvals, (unsigned long long)cmask); return QCX_BAD_ARGUMENTS; }
-    uint64_t tmask = 0;
-    for (unsigned j = 0; j < k; j++) {
-        if (targets[j] >= n || ((tmask >> targets[j]) & 1u)) return QCX_BAD_QUBIT;
-        tmask |= (uint64_t)1 << targets[j];
-    }
-    const uint64_t nmask = (((uint64_t)1) << n) - 1u;
-    if ((cmask & ~nmask) != 0 || (cmask & tmask) != 0) return QCX_BAD_QUBIT;
+    uint64_t tmask;
+    QCX_TRY(check_ctrl_values("mc_multi_qubit_gate", cmask, cvals));
+    QCX_TRY(check_targets(n, k, targets, &tmask));
+    QCX_TRY(check_ctrl_mask(n, cmask, tmask));
     memset(out, 0, sizeof *out);
-    TileGeom G;
+    qcx_tile_geom &G = out->geom;
     tile_geometry(n, cmask, cvals, tmask, k, false, 12, &G);
-    out->T = G.T; out->num_targets = k;
-    unsigned emask = 0;
+    out->num_targets = k;
     for (unsigned j = 0; j < k; j++) {
         out->targets[j] = (unsigned char)targets[j];
         out->target_pos[j] = (unsigned char)__builtin_popcountll(G.tile_mask & ((((uint64_t)1) << targets[j]) - 1u));
-        emask |= 1u << out->target_pos[j];
     }
-    memcpy(out->tile_bits, G.tile_bits, sizeof out->tile_bits);
-    out->tile_mask = G.tile_mask; out->unit_mask = G.unit_mask;
-    out->squeezed = G.squeezed; out->or_const = G.or_const;
-    out->nruns = G.nruns; memcpy(out->run_pos, G.run_pos, sizeof out->run_pos); memcpy(out->run_len, G.run_len, sizeof out->run_len);
-    out->elem_mask = G.elem_mask; out->elem_values = G.elem_values; out->unit_mask_low = G.unit_mask_low; out->unit_values_low = G.unit_values_low;
-    out->units = G.units;
-    out->form = G.lines ? QCX_PERM_LINES : QCX_PERM_SHARED;
     out->rows_per_item = k == 1 ? 2 : 4;
     out->block = std::min(1024u, std::max(64u, (1u << G.T) / out->rows_per_item));
-    out->grid = grid_for(out->units, 1, t.multi_grid_cap, out->block);
+    out->grid = grid_for(G.units, 1, t.multi_grid_cap, out->block);
     out->lds_bytes = 16u << G.T;
-    out->store_all = (t.multi_store_all != 0 && G.pmask != 0) ? 1 : 0;
+    out->store_all = (t.multi_store_all != 0 && (cmask & ~G.squeezed) != 0) ? 1 : 0;
     out->nt = t.multi_nt != 0 ? 1 : 0;
     snprintf(out->kernel, sizeof out->kernel, "k_multi_tile<%u, %s>", k, out->nt ? "true" : "false");
-    if (P) {
-        P->tile_mask = G.tile_mask; P->unit_mask = G.unit_mask; P->orc = G.or_const; P->units = G.units;
-        P->pe_mask = G.elem_mask; P->pe_vals = G.elem_values; P->T = G.T; P->emask = emask; P->store_all = (int)out->store_all;
-    }
+    if (P) *P = multi_params(*out);
     return QCX_NO_ERROR;
 }
 
@@ -1108,20 +1137,6 @@ static void multi_ascending(unsigned k, const unsigned *targets, const double *u
         }
 }
 
-template <unsigned K>
-static void multi_launch_k(const qcx_multi_plan &pl, const MultiParams &P, amp_t *a, const double *mt_dev, hipStream_t st)
-{
-    const dim3 grid(pl.grid), block(pl.block);
-    if (pl.nt) hipLaunchKernelGGL((k_multi_tile<K, true>), grid, block, pl.lds_bytes, st, a, mt_dev, P);
-    else       hipLaunchKernelGGL((k_multi_tile<K, false>), grid, block, pl.lds_bytes, st, a, mt_dev, P);
-}
-
-template <unsigned K>
-static void multi_strict_k(amp_t *a, unsigned n, uint64_t dim, const MultiTargets &tq, uint64_t cmask, uint64_t cvals, const double *mt_dev, hipStream_t st)
-{
-    hipLaunchKernelGGL((k_strict_multi<K>), dim3(grid_for(dim >> K, 256, 65536, 256)), dim3(256), 0, st, a, n, tq, cmask, cvals, mt_dev, 1.0, 0.0);
-}
-
 // launches what the plan says (strict: the one pass over every group of a register flagged non-finite); mt_dev: multi_ascending's
 // matrix in device memory, complete in stream order; sorted: the targets ascending
 static int multi_launch(amp_t *a, unsigned n, uint64_t cmask, uint64_t cvals, unsigned k, const unsigned *targets, const unsigned char *sorted,
@@ -1131,25 +1146,18 @@ static int multi_launch(amp_t *a, unsigned n, uint64_t cmask, uint64_t cvals, un
         MultiTargets tq; memset(&tq, 0, sizeof tq);
         for (unsigned j = 0; j < k; j++) tq.q[j] = sorted[j];
         const uint64_t dim = (uint64_t)1 << n;
-        switch (k) {
-        case 1: multi_strict_k<1>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
-        case 2: multi_strict_k<2>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
-        case 3: multi_strict_k<3>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
-        case 4: multi_strict_k<4>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
-        default: multi_strict_k<5>(a, n, dim, tq, cmask, cvals, mt_dev, st); break;
-        }
+        targets_dispatch(k, [&](auto kk) {
+            hipLaunchKernelGGL((k_strict_multi<decltype(kk)::value>), dim3(grid_for(dim >> k, 256, 65536, 256)), dim3(256), 0, st, a, n, tq, cmask, cvals, mt_dev, 1.0, 0.0);
+        });
         return launch_status("multi-qubit gate");
     }
     qcx_multi_plan pl;
     MultiParams P;
     QCX_TRY(multi_plan(tune_now(), n, cmask, cvals, k, targets, &pl, &P));
-    switch (k) {
-    case 1: multi_launch_k<1>(pl, P, a, mt_dev, st); break;
-    case 2: multi_launch_k<2>(pl, P, a, mt_dev, st); break;
-    case 3: multi_launch_k<3>(pl, P, a, mt_dev, st); break;
-    case 4: multi_launch_k<4>(pl, P, a, mt_dev, st); break;
-    default: multi_launch_k<5>(pl, P, a, mt_dev, st); break;
-    }
+    const dim3 grid(pl.grid), block(pl.block);
+    targets_dispatch(k, [&](auto kk) { flag_dispatch(pl.nt != 0, [&](auto nt) {
+        hipLaunchKernelGGL((k_multi_tile<decltype(kk)::value, decltype(nt)::value>), grid, block, pl.lds_bytes, st, a, mt_dev, P);
+    }); });
     return launch_status("multi-qubit gate");
 }
 
@@ -1933,6 +1941,47 @@ extern "C" int qcx_measure_last_stats(unsigned *slow_blocks, unsigned *blocks)
 enum { SRC_REGISTER = 0, SRC_COMPACT = 1, SRC_BASIS = 2 /* no kernel */, SRC_EXPANDED = 3 };
 struct ReadStats { unsigned source; unsigned long reads; };
 
+// A small host array on its way to the device (K18's table, K19's inverse table, K20's matrix): through a pinned buffer into a
+// device buffer, on the register's stream, so the caller's array is free when the call returns and the kernel finds the data
+// behind the copy.  The next call waits for that copy (ev) before it overwrites the pinned buffer; the device buffer is only
+// ever touched in stream order.  All zero: empty.
+struct StagedUpload {
+    void      *dev, *pinned;
+    size_t     cap;             // bytes each holds
+    hipEvent_t ev;              // the copy out of `pinned` has been passed by the stream
+
+    // `pinned` free to take `bytes`: both buffers grown to a power-of-two multiple of min_bytes if need be.  A failed allocation
+    // is QCX_INSUFFICIENT_MEMORY and leaves the member empty.
+    int reserve(size_t bytes, size_t min_bytes, hipStream_t stream)
+    {
+        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        else HIP_TRY(hipEventSynchronize(ev));
+        if (cap >= bytes) return QCX_NO_ERROR;
+        if (cap) {
+            HIP_TRY(hipStreamSynchronize(stream));                // (a kernel may still be reading the old buffer)
+            (void)hipFree(dev); (void)hipHostFree(pinned);
+            dev = pinned = nullptr; cap = 0;
+        }
+        size_t want = min_bytes;
+        while (want < bytes) want <<= 1;
+        if (hipMalloc(&dev, want) != hipSuccess) { (void)hipGetLastError(); dev = nullptr; return QCX_INSUFFICIENT_MEMORY; }
+        if (hipHostMalloc(&pinned, want) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(dev); dev = pinned = nullptr; return QCX_INSUFFICIENT_MEMORY; }
+        cap = want;
+        return QCX_NO_ERROR;
+    }
+    int send(size_t bytes, hipStream_t stream)
+    {
+        HIP_TRY(hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(ev, stream));
+        return QCX_NO_ERROR;
+    }
+    void release()
+    {
+        if (cap) { (void)hipFree(dev); (void)hipHostFree(pinned); }
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
 struct qcx_register {
     int        L, M;
     unsigned   n;
@@ -1971,20 +2020,13 @@ struct qcx_register {
     unsigned long rotb_passes, rotb_wide;    // the last pauli_rotation_batch call: its passes, and those of them that are one wide term (K15)
     unsigned   diag_form;       // the last diagonal_gate call: the plan's form ...
     unsigned long diag_entries; // ... and its table's entries
-    amp_t     *diag_tab;        // K18, host form: the table on the device, and the pinned buffer it is copied through; one allocation
-    amp_t     *diag_stage;      // each, grown on demand.  diag_ev: the copy out of diag_stage has been passed by the stream
-    size_t     diag_cap;        // entries both hold
-    hipEvent_t diag_ev;
+    StagedUpload diag_up;       // K18, host form: the table, 2^12 entries or more
     unsigned   perm_form;       // the last permutation_gate call: the plan's form ...
     unsigned long perm_moved;   // ... and the entries of its table that are not fixed points
-    uint16_t  *perm_tab;        // K19: the inverse table on the device, and the pinned buffer it is copied through: 2^12 entries
-    uint16_t  *perm_stage;      // each, allocated by the first call.  perm_ev: the copy out of perm_stage has been passed by the stream
-    hipEvent_t perm_ev;
+    StagedUpload perm_up;       // K19: the inverse table, 2^12 entries
     unsigned   multi_form;      // the last mc_multi_qubit_gate call: the plan's form ...
     unsigned   multi_k;         // ... and its number of targets
-    double    *multi_mat;       // K20: the ascending matrix on the device, and the pinned buffer it is copied through: 2 * 4^5 doubles
-    double    *multi_stage;     // each, allocated by the first call.  multi_ev: the copy out of multi_stage has been passed by the stream
-    hipEvent_t multi_ev;
+    StagedUpload multi_up;      // K20: the ascending matrix, 2 * 4^5 doubles
     unsigned long gateb_passes, gateb_lds;   // the last gate_batch call: its passes, and the gates in them that exchanged through LDS (K12b / K13b)
     struct ShardSet *sh;     // non-null: the register is sharded over several GPUs by this process (qcx_sharded.inc.h)
 };
@@ -2180,15 +2222,7 @@ extern "C" int qcx_register_destroy(qcx_register *r)
     (void)hipFree(r->amp);
     if (r->scratch) (void)hipFree(r->scratch);
     if (r->marg_buf) (void)hipFree(r->marg_buf);
-    if (r->diag_tab) (void)hipFree(r->diag_tab);
-    if (r->diag_stage) (void)hipHostFree(r->diag_stage);
-    if (r->diag_ev) (void)hipEventDestroy(r->diag_ev);
-    if (r->perm_tab) (void)hipFree(r->perm_tab);
-    if (r->perm_stage) (void)hipHostFree(r->perm_stage);
-    if (r->perm_ev) (void)hipEventDestroy(r->perm_ev);
-    if (r->multi_mat) (void)hipFree(r->multi_mat);
-    if (r->multi_stage) (void)hipHostFree(r->multi_stage);
-    if (r->multi_ev) (void)hipEventDestroy(r->multi_ev);
+    r->diag_up.release(); r->perm_up.release(); r->multi_up.release();
     free(r);
     return QCX_NO_ERROR;
 }
@@ -2796,10 +2830,7 @@ static int mc_gate(uint64_t cmask, uint64_t cvals, unsigned ntargets, unsigned q
 {
     if (!r || !u) return QCX_BAD_ARGUMENTS;
     QCX_TRY(check_matrix(who, u, ntargets == 1 ? 8 : 32));
-    if (cvals & ~cmask) { set_error("%s: ctrl_values %#llx has bits outside ctrl_mask %#llx", who, (unsigned long long)cvals, (unsigned long long)cmask); return QCX_BAD_ARGUMENTS; }
-    if (q0 >= r->n || (ntargets == 2 && (q1 >= r->n || q1 == q0))) return QCX_BAD_QUBIT;
-    const uint64_t tmask = ((uint64_t)1 << q0) | (ntargets == 2 ? (uint64_t)1 << q1 : 0);
-    if ((r->n < 64 && (cmask >> r->n) != 0) || (cmask & tmask) != 0) return QCX_BAD_QUBIT;
+    QCX_TRY(mc_check(who, r->n, cmask, cvals, ntargets, q0, q1));          // (mc_launch() plans without repeating them)
     if (tune_now().mc_generic == 0 && (cmask == 0 || (cmask == cvals && (cmask & (cmask - 1)) == 0))) {
         const int ctl = cmask ? (int)__builtin_ctzll(cmask) : -1;
         return ntargets == 1 ? one_qubit_gate(ctl, q0, u, r, who) : two_qubit_gate(ctl, q0, q1, u, r, who);
@@ -2911,13 +2942,11 @@ static int diagonal_run(qcx_register *r, const char *who, unsigned first, unsign
     return qcx_shard_diagonal(r->amp, r->n, first, num, tab_dev, r->stream);
 }
 
-// The host form: the table goes through the register's pinned buffer into its device scratch, on the register's stream, so the
-// caller's array is free when the call returns and the kernel finds the table behind the copy.  The next call waits for that
-// copy (diag_ev) before it overwrites the pinned buffer; the device scratch is only ever touched in stream order.
+// The host form: the table goes to the device as a StagedUpload (r->diag_up, grown on demand), sent before the flush.
 extern "C" int qcx_diagonal_gate(unsigned first, unsigned num, const double *d, qcx_register *r)
 {
     if (!r || !d) return QCX_BAD_ARGUMENTS;
-    if (first > r->n || num > r->n - first) return QCX_BAD_QUBIT;
+    QCX_TRY(check_range(r->n, first, num, nullptr));
     if (num > QCX_DIAG_HOST_MAX) {
         set_error("diagonal_gate: a table over %u qubits is more than the host form takes (%u); build it on the device and call qcx_diagonal_gate_device", num, QCX_DIAG_HOST_MAX);
         return QCX_BAD_ARGUMENTS;
@@ -2929,25 +2958,10 @@ extern "C" int qcx_diagonal_gate(unsigned first, unsigned num, const double *d, 
             return QCX_BAD_ARGUMENTS;
         }
     if (r->sh) { set_error("diagonal_gate: not available on a sharded register"); return QCX_UNSUPPORTED; }
-    if (!r->diag_ev) HIP_TRY(hipEventCreateWithFlags(&r->diag_ev, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(r->diag_ev));
-    if (r->diag_cap < entries) {
-        HIP_TRY(hipStreamSynchronize(r->stream));                 // (a kernel may still be reading the old table)
-        if (r->diag_tab) (void)hipFree(r->diag_tab);
-        if (r->diag_stage) (void)hipHostFree(r->diag_stage);
-        r->diag_tab = nullptr; r->diag_stage = nullptr; r->diag_cap = 0;
-        size_t cap = 4096;
-        while (cap < entries) cap <<= 1;
-        if (hipMalloc(&r->diag_tab, cap * sizeof(amp_t)) != hipSuccess) { (void)hipGetLastError(); r->diag_tab = nullptr; return QCX_INSUFFICIENT_MEMORY; }
-        if (hipHostMalloc(&r->diag_stage, cap * sizeof(amp_t)) != hipSuccess) {
-            (void)hipGetLastError(); (void)hipFree(r->diag_tab); r->diag_tab = nullptr; r->diag_stage = nullptr; return QCX_INSUFFICIENT_MEMORY;
-        }
-        r->diag_cap = cap;
-    }
-    memcpy(r->diag_stage, d, entries * sizeof(amp_t));
-    HIP_TRY(hipMemcpyAsync(r->diag_tab, r->diag_stage, entries * sizeof(amp_t), hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipEventRecord(r->diag_ev, r->stream));
-    return diagonal_run(r, "diagonal_gate", first, num, r->diag_tab);
+    QCX_TRY(r->diag_up.reserve(entries * sizeof(amp_t), 4096 * sizeof(amp_t), r->stream));
+    memcpy(r->diag_up.pinned, d, entries * sizeof(amp_t));
+    QCX_TRY(r->diag_up.send(entries * sizeof(amp_t), r->stream));
+    return diagonal_run(r, "diagonal_gate", first, num, (const amp_t *)r->diag_up.dev);
 }
 
 // The device form: the caller's table in place.  Where it lies is checked on the host; what it holds, on the device, on the
@@ -2955,7 +2969,7 @@ extern "C" int qcx_diagonal_gate(unsigned first, unsigned num, const double *d, 
 extern "C" int qcx_diagonal_gate_device(unsigned first, unsigned num, const void *d_device, qcx_register *r)
 {
     if (!r || !d_device) return QCX_BAD_ARGUMENTS;
-    if (first > r->n || num > r->n - first) return QCX_BAD_QUBIT;
+    QCX_TRY(check_range(r->n, first, num, nullptr));
     const uint64_t entries = ((uint64_t)1) << num, bytes = entries * sizeof(amp_t);
     hipPointerAttribute_t at;
     memset(&at, 0, sizeof at);
@@ -3002,10 +3016,8 @@ extern "C" int qcx_diagonal_last_stats(qcx_register *r, unsigned *form, unsigned
 // ---- a permutation of a qubit range's basis states from a table (K19) -------------------------------------------------------------
 extern "C" unsigned qcx_permutation_max_qubits(void) { return QCX_PERM_MAX_QUBITS; }
 
-// one_qubit_gate()'s sequence behind the checks of include/qcx.h, in their order.  The inverse table goes through the register's
-// pinned buffer into its device scratch on the register's stream, as qcx_diagonal_gate's table does: the caller's array is free
-// when the call returns, the next call waits for that copy (perm_ev) before it overwrites the pinned buffer, and the device
-// scratch is only ever touched in stream order.
+// one_qubit_gate()'s sequence behind the checks of include/qcx.h, in their order.  The inverse table goes to the device as a
+// StagedUpload (r->perm_up), reserved before the flush and sent behind it; the identity sends nothing.
 extern "C" int qcx_permutation_gate(uint64_t cmask, uint64_t cvals, unsigned first, unsigned num, const uint32_t *perm, qcx_register *r)
 {
     if (!r || !perm) return QCX_BAD_ARGUMENTS;
@@ -3015,23 +3027,14 @@ extern "C" int qcx_permutation_gate(uint64_t cmask, uint64_t cvals, unsigned fir
     unsigned long moved = 0;
     QCX_TRY(permutation_invert(num, perm, inv, &moved));
     if (r->sh) { set_error("permutation_gate: not available on a sharded register"); return QCX_UNSUPPORTED; }
-    constexpr size_t cap = sizeof inv;
-    if (!r->perm_ev) HIP_TRY(hipEventCreateWithFlags(&r->perm_ev, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(r->perm_ev));
-    if (!r->perm_tab) {
-        if (hipMalloc(&r->perm_tab, cap) != hipSuccess) { (void)hipGetLastError(); r->perm_tab = nullptr; return QCX_INSUFFICIENT_MEMORY; }
-    }
-    if (!r->perm_stage) {
-        if (hipHostMalloc(&r->perm_stage, cap) != hipSuccess) { (void)hipGetLastError(); r->perm_stage = nullptr; return QCX_INSUFFICIENT_MEMORY; }
-    }
+    QCX_TRY(r->perm_up.reserve(sizeof inv, sizeof inv, r->stream));
     QCX_TRY(unqueued_gate(r, "permutation_gate", false));
-    r->perm_form = pl.form; r->perm_moved = moved;
+    r->perm_form = pl.geom.form; r->perm_moved = moved;
     if (moved == 0 && !r->nonfinite) return QCX_NO_ERROR;                      // the identity on finite amplitudes whose zeros are +0
     const size_t bytes = sizeof(uint16_t) << num;
-    memcpy(r->perm_stage, inv, bytes);
-    HIP_TRY(hipMemcpyAsync(r->perm_tab, r->perm_stage, bytes, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipEventRecord(r->perm_ev, r->stream));
-    return permutation_launch(r->amp, r->n, cmask, cvals, first, num, r->nonfinite != 0, r->perm_tab, r->stream);
+    memcpy(r->perm_up.pinned, inv, bytes);
+    QCX_TRY(r->perm_up.send(bytes, r->stream));
+    return permutation_launch(r->amp, r->n, cmask, cvals, first, num, r->nonfinite != 0, (const uint16_t *)r->perm_up.dev, r->stream);
 }
 
 extern "C" int qcx_permutation_last_stats(qcx_register *r, unsigned *form, unsigned long *moved)
@@ -3046,10 +3049,8 @@ extern "C" int qcx_permutation_last_stats(qcx_register *r, unsigned *form, unsig
 extern "C" unsigned qcx_multi_qubit_max_targets(void) { return QCX_MULTI_MAX_TARGETS; }
 
 // mc_gate()'s sequence behind the checks of include/qcx.h, in their order.  One and two targets ARE mc_gate() -- the same kernels
-// and launches -- unless multi_generic is set.  The ascending matrix goes through the register's pinned buffer into its device
-// scratch on the register's stream, as qcx_permutation_gate's table does: the caller's array is free when the call returns, the
-// next call waits for that copy (multi_ev) before it overwrites the pinned buffer, and the device scratch is only ever touched
-// in stream order.
+// and launches -- unless multi_generic is set.  The ascending matrix is written straight into the pinned buffer of a
+// StagedUpload (r->multi_up), reserved before the flush and sent behind it.
 extern "C" int qcx_mc_multi_qubit_gate(uint64_t cmask, uint64_t cvals, unsigned k, const unsigned *targets, const double *u, qcx_register *r)
 {
     const char *who = "mc_multi_qubit_gate";
@@ -3063,25 +3064,17 @@ extern "C" int qcx_mc_multi_qubit_gate(uint64_t cmask, uint64_t cvals, unsigned 
     QCX_TRY(qcx_multi_gate_plan(r->n, cmask, cvals, k, targets, &pl));         // (the other argument checks, in the header's order)
     if (r->sh) { set_error("%s: not available on a sharded register", who); return QCX_UNSUPPORTED; }
     if (k <= 2 && tune_now().multi_generic == 0) {
-        r->multi_form = pl.form; r->multi_k = k;
+        r->multi_form = pl.geom.form; r->multi_k = k;
         return mc_gate(cmask, cvals, k, targets[0], k == 2 ? targets[1] : 0, u, r, who);
     }
     constexpr size_t cap = sizeof(double) * (2u << (2 * QCX_MULTI_MAX_TARGETS));
-    if (!r->multi_ev) HIP_TRY(hipEventCreateWithFlags(&r->multi_ev, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(r->multi_ev));
-    if (!r->multi_mat) {
-        if (hipMalloc(&r->multi_mat, cap) != hipSuccess) { (void)hipGetLastError(); r->multi_mat = nullptr; return QCX_INSUFFICIENT_MEMORY; }
-    }
-    if (!r->multi_stage) {
-        if (hipHostMalloc(&r->multi_stage, cap) != hipSuccess) { (void)hipGetLastError(); r->multi_stage = nullptr; return QCX_INSUFFICIENT_MEMORY; }
-    }
+    QCX_TRY(r->multi_up.reserve(cap, cap, r->stream));
     QCX_TRY(unqueued_gate(r, who, false));
-    r->multi_form = pl.form; r->multi_k = k;
+    r->multi_form = pl.geom.form; r->multi_k = k;
     unsigned char sorted[QCX_MULTI_MAX_TARGETS];
-    multi_ascending(k, targets, u, r->multi_stage, sorted);
-    HIP_TRY(hipMemcpyAsync(r->multi_mat, r->multi_stage, sizeof(double) * (2u << (2 * k)), hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipEventRecord(r->multi_ev, r->stream));
-    return multi_launch(r->amp, r->n, cmask, cvals, k, targets, sorted, r->nonfinite != 0, r->multi_mat, r->stream);
+    multi_ascending(k, targets, u, (double *)r->multi_up.pinned, sorted);
+    QCX_TRY(r->multi_up.send(sizeof(double) * (2u << (2 * k)), r->stream));
+    return multi_launch(r->amp, r->n, cmask, cvals, k, targets, sorted, r->nonfinite != 0, (const double *)r->multi_up.dev, r->stream);
 }
 
 extern "C" int qcx_multi_qubit_last_stats(qcx_register *r, unsigned *form, unsigned *num_targets)

@@ -21,19 +21,19 @@ static int check_plan(unsigned n, uint64_t cm, uint64_t cv, unsigned k, const un
     MultiParams P;
     const int st = multi_plan(tune_now(), n, cm, cv, k, targets, &pl, &P);
     if (st != QCX_NO_ERROR) { g_refused++; return 0; }
-    const uint64_t nmask = (((uint64_t)1) << n) - 1u, sq = pl.squeezed;
+    const uint64_t nmask = (((uint64_t)1) << n) - 1u, sq = pl.geom.squeezed;
     uint64_t tmask = 0;
     for (unsigned j = 0; j < k; j++) tmask |= (uint64_t)1 << targets[j];
-    bool bad = (pl.tile_mask | pl.unit_mask | sq) != nmask || (pl.tile_mask & pl.unit_mask) != 0 || ((pl.tile_mask | pl.unit_mask) & sq) != 0;
-    bad = bad || (unsigned)__builtin_popcountll(pl.tile_mask) != pl.T || pl.T > 12 || pl.T < k || (pl.tile_mask & tmask) != tmask;
-    bad = bad || (pl.units << pl.T) != (((uint64_t)1) << (n - (unsigned)__builtin_popcountll(sq))) || pl.grid < 1 || pl.grid > pl.units;
-    bad = bad || pl.lds_bytes > 65536 || pl.block < 64 || pl.block > 1024 || (pl.block & (pl.block - 1)) != 0 || !strchr(pl.kernel, '<') || pl.nruns > QCX_PERM_MAX_RUNS;
-    bad = bad || (uint64_t)pl.block * pl.rows_per_item * (k == 1 ? 2 : 1) < (((uint64_t)1) << pl.T);
-    bad = bad || pl.unit_mask_low != 0 || pl.form != QCX_PERM_LINES;
-    bad = bad || P.tile_mask != pl.tile_mask || P.unit_mask != pl.unit_mask || P.units != pl.units || P.T != pl.T || P.pe_mask != pl.elem_mask || P.pe_vals != pl.elem_values;
-    bad = bad || (P.orc & ~sq) != 0 || (unsigned)__builtin_popcount(P.emask) != k || P.emask >= (1u << pl.T);
-    for (unsigned j = 0; j < pl.T; j++) bad = bad || !((pl.tile_mask >> pl.tile_bits[j]) & 1u);
-    for (unsigned j = 0; j < k; j++) bad = bad || pl.tile_bits[pl.target_pos[j]] != targets[j] || !((P.emask >> pl.target_pos[j]) & 1u);
+    bool bad = (pl.geom.tile_mask | pl.geom.unit_mask | sq) != nmask || (pl.geom.tile_mask & pl.geom.unit_mask) != 0 || ((pl.geom.tile_mask | pl.geom.unit_mask) & sq) != 0;
+    bad = bad || (unsigned)__builtin_popcountll(pl.geom.tile_mask) != pl.geom.T || pl.geom.T > 12 || pl.geom.T < k || (pl.geom.tile_mask & tmask) != tmask;
+    bad = bad || (pl.geom.units << pl.geom.T) != (((uint64_t)1) << (n - (unsigned)__builtin_popcountll(sq))) || pl.grid < 1 || pl.grid > pl.geom.units;
+    bad = bad || pl.lds_bytes > 65536 || pl.block < 64 || pl.block > 1024 || (pl.block & (pl.block - 1)) != 0 || !strchr(pl.kernel, '<') || pl.geom.nruns > QCX_PERM_MAX_RUNS;
+    bad = bad || (uint64_t)pl.block * pl.rows_per_item * (k == 1 ? 2 : 1) < (((uint64_t)1) << pl.geom.T);
+    bad = bad || pl.geom.unit_mask_low != 0 || pl.geom.form != QCX_PERM_LINES;
+    bad = bad || P.tile_mask != pl.geom.tile_mask || P.unit_mask != pl.geom.unit_mask || P.units != pl.geom.units || P.T != pl.geom.T || P.pe_mask != pl.geom.elem_mask || P.pe_vals != pl.geom.elem_values;
+    bad = bad || (P.orc & ~sq) != 0 || (unsigned)__builtin_popcount(P.emask) != k || P.emask >= (1u << pl.geom.T);
+    for (unsigned j = 0; j < pl.geom.T; j++) bad = bad || !((pl.geom.tile_mask >> pl.geom.tile_bits[j]) & 1u);
+    for (unsigned j = 0; j < k; j++) bad = bad || pl.geom.tile_bits[pl.target_pos[j]] != targets[j] || !((P.emask >> pl.target_pos[j]) & 1u);
     if (bad) { fprintf(stderr, "bad plan: n %u mask %#llx values %#llx k %u first target %u\n", n, (unsigned long long)cm, (unsigned long long)cv, k, targets[0]); return 1; }
     g_plans++;
     return 0;

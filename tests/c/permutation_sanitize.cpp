@@ -22,14 +22,14 @@ static int check_plan(unsigned n, uint64_t cm, uint64_t cv, unsigned first, unsi
     const int st = permutation_plan(tune_now(), n, cm, cv, first, num, strict, &pl, &P);
     if (st != QCX_NO_ERROR) { g_refused++; return 0; }
     const uint64_t nmask = (((uint64_t)1) << n) - 1u;
-    const uint64_t sq = strict ? 0 : pl.squeezed;
-    bool bad = (pl.tile_mask | pl.unit_mask | sq) != nmask || (pl.tile_mask & pl.unit_mask) != 0 || ((pl.tile_mask | pl.unit_mask) & sq) != 0;
-    bad = bad || (unsigned)__builtin_popcountll(pl.tile_mask) != pl.T || pl.T > 12 || pl.range_pos + num > pl.T;
-    bad = bad || (pl.units << pl.T) != (((uint64_t)1) << (n - (unsigned)__builtin_popcountll(sq))) || pl.grid < 1 || pl.grid > pl.units;
-    bad = bad || pl.lds_bytes > 73728 || (pl.block != 256 && pl.block != 1024) || !strchr(pl.kernel, '<') || pl.nruns > QCX_PERM_MAX_RUNS;
-    bad = bad || P.tile_mask != pl.tile_mask || P.unit_mask != pl.unit_mask || P.units != pl.units || P.T != pl.T || P.pf != pl.range_pos;
+    const uint64_t sq = strict ? 0 : pl.geom.squeezed;
+    bool bad = (pl.geom.tile_mask | pl.geom.unit_mask | sq) != nmask || (pl.geom.tile_mask & pl.geom.unit_mask) != 0 || ((pl.geom.tile_mask | pl.geom.unit_mask) & sq) != 0;
+    bad = bad || (unsigned)__builtin_popcountll(pl.geom.tile_mask) != pl.geom.T || pl.geom.T > 12 || pl.range_pos + num > pl.geom.T;
+    bad = bad || (pl.geom.units << pl.geom.T) != (((uint64_t)1) << (n - (unsigned)__builtin_popcountll(sq))) || pl.grid < 1 || pl.grid > pl.geom.units;
+    bad = bad || pl.lds_bytes > 73728 || (pl.block != 256 && pl.block != 1024) || !strchr(pl.kernel, '<') || pl.geom.nruns > QCX_PERM_MAX_RUNS;
+    bad = bad || P.tile_mask != pl.geom.tile_mask || P.unit_mask != pl.geom.unit_mask || P.units != pl.geom.units || P.T != pl.geom.T || P.pf != pl.range_pos;
     bad = bad || (P.pmask & sq) != 0 || (P.pvals & ~P.pmask) != 0 || (P.orc & ~sq) != 0;
-    for (unsigned k = 0; k < pl.T; k++) bad = bad || !((pl.tile_mask >> pl.tile_bits[k]) & 1u);
+    for (unsigned k = 0; k < pl.geom.T; k++) bad = bad || !((pl.geom.tile_mask >> pl.geom.tile_bits[k]) & 1u);
     if (bad) { fprintf(stderr, "bad plan: n %u mask %#llx values %#llx first %u num %u strict %d\n", n, (unsigned long long)cm, (unsigned long long)cv, first, num, (int)strict); return 1; }
     g_plans++;
     return 0;
